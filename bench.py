@@ -2,7 +2,19 @@
 """bench.py -- Mrays/s of the Whitted hot path, one process per GPU.
 
     python bench.py --gpus 1 --steps K --warmup W                        (BASELINE config 2, the headline)
+    python bench.py --gpus 1 --steps K --warmup W --full                 (the same, plus every check and extra figure)
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR     (also writes the last step's outputs)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times --steps steps, writes its outputs when --dump-outputs is given and prints the
+line: metric, value, unit, higher_is_better, dtype, ms_per_step (one timed step), ms_per_frame, config, env.  Everything
+else below -- ms_per_frame_latency, config.frame_checksum, config.cull_never_hit, config.image_mean, gather_verified,
+roofline, cpu_baseline, frame_matches_reference / frame_check -- takes work of its own and is measured with --full only.
+
+--dump-outputs DIR: what the timed path computed in its last step, as float32 DIR/<name>.npy (64 MB at most): the
+frames of the step (rgb8 values; rank 0's gathered frames at N > 1), or the path tracer's linear sums.  An array too
+large to be written whole is written as a fixed, seeded sample of its values (<name>_sample.npy) plus the flat indices
+sampled (<name>_sample_index.npy, float64).  Inputs are fixed by the arguments, so two builds compare value for value.
 
 Workloads (--workload):
   config2    mount_low.p3f 1920x1080 depth 4 BVH -- the configuration BASELINE.json's metric is quoted on.
@@ -25,7 +37,7 @@ set).  torch.distributed (gloo) only carries the 128-byte communicator id, the b
 value = rays of all frames / max-over-ranks wall time; a ray is one closest-hit or one shadow query,
 counted by the counting build of the same kernels on the same frame.
 
-The line checks what it timed:
+With --full the line checks what it timed:
   "frame_matches_reference"  the LAST TIMED FRAME (device buffer, downloaded after the timed region) equals the
                  frame the cpu_baseline leg rendered -- by the reference's own object code where that renders the
                  same frame (config 2), else by the oracle port on all cores at full size, with the reference's
@@ -34,7 +46,7 @@ The line checks what it timed:
                  Details in "frame_check".
   "gather_verified"  (N > 1) the gathered, de-interleaved frame on rank 0 equals a one-GPU render of the same frame.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (all but "env" with --full only):
   "roofline"     for the ray kernel with the most device time (from the rocprofv3 kernel stats and PMC summaries
                  committed under profiles/, see profiles/current.json).  bound "valu_issue" for scenes served from
                  LDS (config 2 / 4: HBM is not what binds a 12-primitive scene): achieved = SQ_INSTS_VALU per launch
@@ -84,6 +96,32 @@ WORKLOADS = {
     "synthetic": dict(scene=None, res=(1920, 1080), depth=4, spp=0, frames=12, name=None),
 }
 HBM_SCENE_WORKLOADS = ("config3", "synthetic")      # scenes the kernels read from HBM / L2, not from an LDS copy
+
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs writes at most this much in all
+DUMP_WHOLE_BYTES = 32 << 20      # an output larger than this as float32 is written as a sample
+DUMP_SAMPLES = 1 << 21           # values in such a sample (8 MB, plus 16 MB of float64 indices)
+DUMP_SEED = 20261015
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: {name: host array} as float32 <out_dir>/<name>.npy; an array over DUMP_WHOLE_BYTES as float32 is
+    written as DUMP_SAMPLES values at fixed, seeded flat indices (<name>_sample.npy) plus those indices
+    (<name>_sample_index.npy, float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    files = []
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.size * 4 <= DUMP_WHOLE_BYTES:
+            files.append((name, a.astype(np.float32)))
+        else:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, DUMP_SAMPLES, replace=False))
+            files.append((name + "_sample", a.reshape(-1)[idx].astype(np.float32)))
+            files.append((name + "_sample_index", idx.astype(np.float64)))
+    total = sum(v.nbytes for _, v in files)
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    for fn, v in files:
+        np.save(os.path.join(out_dir, fn + ".npy"), v)
 
 
 # what the kernels are compiled from (host-side files do not make a profile stale)
@@ -437,7 +475,8 @@ def bench_pathtracer(args, torch, dist, P, rank, world, local_rank, dev, comm):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     dt_max = float(tt.item())
     if rank == 0:
-        img = torch.nan_to_num(lin / spp).clamp(0, None).pow(1 / 2.2)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"linear_sum": lin.cpu().numpy()})
         line = {
             "metric": "Msamples/s (paths) + ms/image @1920x1080 %d spp" % spp,
             "value": W * H * spp * args.steps / dt_max / 1e6, "unit": "Msamples/s",
@@ -446,18 +485,20 @@ def bench_pathtracer(args, torch, dist, P, rank, world, local_rank, dev, comm):
             "vs_baseline": None, "dtype": "f32",
             "data": "synthetic: the procedural scene of GPU_PathTracer_template/P3D_RT.glsl (no mouse, iTime = k/60)",
             "config": {"workload": "P3D_RT.glsl path tracer 1920x1080 %d spp (BASELINE config 5)" % spp,
-                       "parallelism": "1 GPU" if world == 1 else "%d GPUs: samples split, one ncclReduce(sum) to rank 0 through the C-ABI" % world,
-                       "image_mean": float(img.mean().item())},
-            "roofline": None,
+                       "parallelism": "1 GPU" if world == 1 else "%d GPUs: samples split, one ncclReduce(sum) to rank 0 through the C-ABI" % world},
         }
-        if world == 1 and spp == 256:
+        if args.full:
+            img = torch.nan_to_num(lin / spp).clamp(0, None).pow(1 / 2.2)
+            line["config"]["image_mean"] = float(img.mean().item())
+            line["roofline"] = None
+        if args.full and world == 1 and spp == 256:
             # one launch per step: the step IS the kernel (HIP-event bracket = the barrier-to-barrier time of the timed region)
             rl = roofline_from_profiles("pathtracer", {"kernel": "p3dpt::pt_frames_kernel", "kernel_ms": dt_max / args.steps * 1e3,
                                                        "frame_ms": dt_max / args.steps * 1e3})
             rl["algorithmic"] = {"note": "the path tracer's scene is procedural (hashed per ray, PT/P3D_RT.glsl:88-178): there is no scene data to read; "
                                          "HBM sees the running sums only (12 B per pixel per launch)"}
             line["roofline"] = rl
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             from oracle import oracle_py as O
             w, h, n = 240, 135, 4
             t = time.perf_counter()
@@ -496,13 +537,18 @@ def main():
                     help="replay the frames of a step as ONE captured HIP graph (auto = off: measured slower than eager launches)")
     ap.add_argument("--gather", choices=["pipelined", "sync"], default="pipelined",
                     help="N > 1: two tile-buffer sets, so that a step's gather overlaps the next step's rendering, or one")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU leg (and with it frame_matches_reference)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU leg (and with it frame_matches_reference)")
     ap.add_argument("--prims", type=int, default=1000000, help="synthetic workload: number of primitives")
     ap.add_argument("--schedule", choices=["default", "wavefront", "tree", "tile"], default="default",
                     help="force a kernel schedule (default: the library's measured choice)")
     ap.add_argument("--tune", choices=["on", "off"], default="on",
                     help="scenes read from HBM: let the library rank its schedules with the bench's frames in flight (p3d_tune_schedule)")
     ap.add_argument("--spp", type=int, default=256, help="pathtracer workload: samples (frames) per step")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: single-frame latency, roofline, CPU baseline "
+                         "and frame check, config 3's cull_never_hit build, the N > 1 gather check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as float32 DIR/<name>.npy (64 MB at most)")
     args = ap.parse_args()
 
     # stdout carries ONE line, the JSON: anything the libraries print on the way (the host loader echoes the camera like
@@ -735,15 +781,23 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
 
-    # single-frame latency (one frame in flight) and the dominant kernel's duration: HIP events on the launch stream
-    nl = max(min(args.steps * B, 200), 8)
-    frame_ms_sum = kern_ms_sum = 0.0
-    for _ in range(nl):
-        ds.render_device(cam, rgb8_ptr=tile_sets[0][0].data_ptr(), profile=True, **sched, **kw)
-        f_ms, k_ms = ds.profile()
-        frame_ms_sum += f_ms
-        kern_ms_sum += k_ms
-    frame_dev_ms, kern_ms = frame_ms_sum / nl, kern_ms_sum / nl
+    # the B frames of the last timed step (rank 0's gathered frames at N > 1), before anything renders into the buffers again
+    last_step = (frames if world > 1 else tile_sets[(state["next"] - 1) % nbuf][:, :H]) if rank == 0 else None
+    if args.dump_outputs and rank == 0:
+        host = last_step.cpu().numpy()
+        dump_outputs(args.dump_outputs, dict({"rgb8_last_frame": host[B - 1]}, **({"rgb8_step_frames": host} if B > 1 else {})))
+        del host
+
+    if args.full:
+        # single-frame latency (one frame in flight) and the dominant kernel's duration: HIP events on the launch stream
+        nl = max(min(args.steps * B, 200), 8)
+        frame_ms_sum = kern_ms_sum = 0.0
+        for _ in range(nl):
+            ds.render_device(cam, rgb8_ptr=tile_sets[0][0].data_ptr(), profile=True, **sched, **kw)
+            f_ms, k_ms = ds.profile()
+            frame_ms_sum += f_ms
+            kern_ms_sum += k_ms
+        frame_dev_ms, kern_ms = frame_ms_sum / nl, kern_ms_sum / nl
     chosen = ds.last_schedule()
 
     tt = torch.tensor([dt], dtype=torch.float64)
@@ -755,20 +809,7 @@ def main():
     rays_frame = float(rr.item())
 
     if rank == 0:
-        final = (frames[B - 1] if world > 1 else tile_sets[(state["next"] - 1) % nbuf][B - 1][:H]).cpu().numpy()
         total_rays = rays_frame * B * args.steps
-        dominant = {"tree": "p3d::whitted_tree_kernel", "tile": "p3d::wf_tile_kernel", "wavefront": "p3d::wf_primary_kernel"}[chosen]
-        live = {"kernel": dominant, "schedule": chosen, "kernel_ms": kern_ms, "frame_ms": frame_dev_ms, "alg_bytes": int(alg_bytes),
-                "alg_gbps": alg_bytes / (frame_dev_ms * 1e-3) / 1e9, "frames_in_flight": F,
-                "frame_ms_in_flight": dt_max / args.steps / B * 1e3 if world == 1 else None}
-        gather_verified = None
-        if world > 1:
-            # the gathered, de-interleaved frame against a one-GPU render of the same frame on this rank
-            whole = torch.zeros((H, W, 3), dtype=torch.uint8, device=dev)
-            kw1 = dict(kw, rank=0, world=1)
-            ds.render_device(cam, rgb8_ptr=whole.data_ptr(), **sched, **kw1)
-            ds.sync()
-            gather_verified = bool(np.array_equal(final, whole.cpu().numpy()))
         if synthetic:
             data = "synthetic: %d random spheres+triangles (SURVEY 8d scaling scene, seed 2024), mount_low camera" % args.prims
         else:
@@ -782,7 +823,6 @@ def main():
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": dt_max / args.steps * 1e3,
             "ms_per_frame": dt_max / args.steps / B * 1e3,
-            "ms_per_frame_latency": frame_dev_ms,
             "higher_is_better": True,
             "scaling": "strong",
             "vs_baseline": None,
@@ -800,13 +840,25 @@ def main():
                                   % ("two buffer sets (overlaps the next step)" if nbuf == 2 else "one buffer set")),
                        "rays_per_frame": int(rays_frame),
                        "row_block": ROW_BLOCK,
-                       "parallelism": "1 GPU" if world == 1 else "%d GPUs: interleaved 16-row blocks + one RCCL gather to rank 0 through the C-ABI" % world,
-                       "frame_checksum": int(final.astype(np.uint64).sum())},
-            "roofline": roofline_from_profiles(args.workload, live, "synthetic_%d" % args.prims if synthetic else None),
+                       "parallelism": "1 GPU" if world == 1 else "%d GPUs: interleaved 16-row blocks + one RCCL gather to rank 0 through the C-ABI" % world},
             "env": {"lib": os.path.relpath(P.api.LIB_PATH, REPO), "P3D": {k: v for k, v in sorted(os.environ.items()) if k.startswith("P3D_")}},
         }
+    if rank == 0 and args.full:
+        final = last_step[B - 1].cpu().numpy()
+        dominant = {"tree": "p3d::whitted_tree_kernel", "tile": "p3d::wf_tile_kernel", "wavefront": "p3d::wf_primary_kernel"}[chosen]
+        live = {"kernel": dominant, "schedule": chosen, "kernel_ms": kern_ms, "frame_ms": frame_dev_ms, "alg_bytes": int(alg_bytes),
+                "alg_gbps": alg_bytes / (frame_dev_ms * 1e-3) / 1e9, "frames_in_flight": F,
+                "frame_ms_in_flight": dt_max / args.steps / B * 1e3 if world == 1 else None}
+        line["ms_per_frame_latency"] = frame_dev_ms
+        line["config"]["frame_checksum"] = int(final.astype(np.uint64).sum())
+        line["roofline"] = roofline_from_profiles(args.workload, live, "synthetic_%d" % args.prims if synthetic else None)
         if world > 1:
-            line["gather_verified"] = gather_verified
+            # the gathered, de-interleaved frame against a one-GPU render of the same frame on this rank
+            whole = torch.zeros((H, W, 3), dtype=torch.uint8, device=dev)
+            kw1 = dict(kw, rank=0, world=1)
+            ds.render_device(cam, rgb8_ptr=whole.data_ptr(), **sched, **kw1)
+            ds.sync()
+            line["gather_verified"] = bool(np.array_equal(final, whole.cpu().numpy()))
         if args.workload == "config3" and world == 1:
             # the exact shortcut of DESIGN.md 12 as a SECOND figure: triangles no ray can hit left out of the BVH
             hc = P.DeviceScene.from_host(hs, device=local_rank, cull_never_hit=True)
@@ -849,6 +901,7 @@ def main():
             else:
                 line["frame_matches_reference"] = None
                 line["frame_check"] = {"note": "no CPU frame for this size of the synthetic scene"}
+    if rank == 0:
         emit_line(line)
     if world > 1:
         dist.barrier()
