@@ -135,6 +135,13 @@ typedef struct p3d_render_params {
  * The lookup itself is bit-exact against the reference's object code (tests/test_oracle_vs_ref.py).  Like the other
  * features it needs the tile or the wavefront schedule. */
 #define P3D_FEATURE_SKYBOX 4u
+/* SCHLICK_APPROX of RT/main.cpp:99 (false there): the Fresnel weight of a transmissive hit becomes Schlick's
+ * approximation KR = rI + (1 - rI) * pow(1 - cos_theta_i, 5), rI = ((ior_1 - newIor) / (ior_1 + newIor))^2
+ * (RT/main.cpp:699-702), instead of the default 1 / 2 * (R0 + R1) -- an integer 1 / 2, so 0: with the switch
+ * glass shows its reflection.  Under total internal reflection KR stays 0 (RT/main.cpp:710).  No random draws: the
+ * frames equal the reference's in every float bit -- the device runs glibc's double pow algorithm (csrc/p3d_pow.h) and
+ * g++'s operation order -- on all three schedules, and combine with every other switch, samples and sharding. */
+#define P3D_FEATURE_SCHLICK 8u
 
 #define P3D_FLAG_COUNTERS 1u     /* accumulate p3d_counters on the device (slower kernels)  */
 /* Kernel schedules: three ways to run the same per-node code, bit-identical frames.  Which one p3d_render() uses
@@ -355,6 +362,12 @@ int p3d_debug_intersect(int device, uint32_t n, const uint32_t* type, const floa
  * powf(x[i], y[i]) (the Blinn-Phong exponent, RT/main.cpp:520; csrc/p3d_powf.h). Host arrays of n floats.
  * The parity tests compare it bit for bit with the box's own libm. */
 int p3d_debug_powf(int device, uint32_t n, const float* x, const float* y, float* out);
+
+/* Unit-level probes of P3D_FEATURE_SCHLICK: out[i] = the device's restatement of the host C library's pow(x[i], y[i])
+ * (csrc/p3d_pow.h; n doubles each), and out[i] = the KR expression of RT/main.cpp:700-701 as the shading evaluates it on
+ * (ior_1[i], new_ior[i], cos_theta_i[i]) (n floats each). The parity tests compare both bit for bit with the host. */
+int p3d_debug_pow(int device, uint32_t n, const double* x, const double* y, double* out);
+int p3d_debug_schlick_kr(int device, uint32_t n, const float* ior_1, const float* new_ior, const float* cos_theta_i, float* out);
 
 /* Exhaustive check of the device's 3-instruction reciprocal (csrc/p3d_device_math.h: frcp) against the correctly rounded
  * division 1.0f / x it replaces in normalize() and Triangle::intercepts: the bit patterns first_bits .. first_bits +

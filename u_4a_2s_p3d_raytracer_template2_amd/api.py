@@ -21,6 +21,7 @@ FLAG_TILE_KERNEL = 64
 FLAG_DEVICE_SAMPLES = 128
 FLAG_PACKET_WALK = 256
 FEATURE_SOFT_SHADOW, FEATURE_FUZZY_REFLECTION, FEATURE_SKYBOX = 1, 2, 4
+FEATURE_SCHLICK = 8          # the reference's SCHLICK_APPROX (RT/main.cpp:99), bit-exact
 
 
 class P3DError(RuntimeError):
@@ -82,7 +83,7 @@ class SceneStats(C.Structure):
 C_ABI_SYMBOLS = ["p3d_abi_version", "p3d_last_error", "p3d_device_count", "p3d_scene_create",
                  "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_local_rows", "p3d_render", "p3d_sync",
                  "p3d_get_counters", "p3d_get_profile", "p3d_last_schedule", "p3d_set_tuning", "p3d_set_stream", "p3d_timer_begin", "p3d_timer_end", "p3d_deinterleave_frames",
-                 "p3d_deinterleave", "p3d_debug_intersect", "p3d_debug_powf", "p3d_debug_check_rcp", "p3d_tune_schedule", "p3d_debug_set_stamps", "p3d_debug_set_stamp_level",
+                 "p3d_deinterleave", "p3d_debug_intersect", "p3d_debug_powf", "p3d_debug_pow", "p3d_debug_schlick_kr", "p3d_debug_check_rcp", "p3d_tune_schedule", "p3d_debug_set_stamps", "p3d_debug_set_stamp_level",
                  "p3d_comm_unique_id", "p3d_comm_create", "p3d_comm_create_all", "p3d_comm_destroy", "p3d_comm_info",
                  "p3d_gather", "p3d_gather_all", "p3d_device_alloc", "p3d_device_free", "p3d_upload", "p3d_download"]
 
@@ -151,6 +152,8 @@ def lib():
     L.p3d_pt_reduce_sum.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
     L.p3d_debug_intersect.argtypes = [C.c_int, C.c_uint32] + [C.c_void_p] * 7
     L.p3d_debug_powf.argtypes = [C.c_int, C.c_uint32] + [C.c_void_p] * 3
+    L.p3d_debug_pow.argtypes = [C.c_int, C.c_uint32] + [C.c_void_p] * 3
+    L.p3d_debug_schlick_kr.argtypes = [C.c_int, C.c_uint32] + [C.c_void_p] * 4
     L.p3d_debug_check_rcp.argtypes = [C.c_int, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
     L.p3d_tune_schedule.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     # host shim
@@ -382,20 +385,20 @@ class DeviceScene:
         _check(lib().p3d_get_counters(self.h, C.byref(c)), "p3d_get_counters")
         return c.as_dict()
 
-    def _params(self, max_depth, accel, spp, samples, rank, world, row_block, counters, tree=False, no_lds=False, profile=False, wavefront=False, soft_shadow=False, fuzzy_reflection=False, seed=0, tile=False, samples_ptr=0, packet=False, private_walk=False, skybox=False):
+    def _params(self, max_depth, accel, spp, samples, rank, world, row_block, counters, tree=False, no_lds=False, profile=False, wavefront=False, soft_shadow=False, fuzzy_reflection=False, seed=0, tile=False, samples_ptr=0, packet=False, private_walk=False, skybox=False, schlick=False):
         p = RenderParams()
         p.max_depth, p.accel, p.spp = int(max_depth), int(accel), int(spp)
         p.samples = samples.ctypes.data_as(C.POINTER(C.c_float)) if samples is not None else None
         if samples_ptr:                      # sample array already on the device (uploaded once by the caller)
             p.samples = C.cast(C.c_void_p(int(samples_ptr)), C.POINTER(C.c_float))
         p.row_block, p.rank, p.world = int(row_block), int(rank), int(world)
-        p.features = (FEATURE_SOFT_SHADOW if soft_shadow else 0) | (FEATURE_FUZZY_REFLECTION if fuzzy_reflection else 0) | (FEATURE_SKYBOX if skybox else 0)
+        p.features = (FEATURE_SOFT_SHADOW if soft_shadow else 0) | (FEATURE_FUZZY_REFLECTION if fuzzy_reflection else 0) | (FEATURE_SKYBOX if skybox else 0) | (FEATURE_SCHLICK if schlick else 0)
         p.seed = int(seed) & 0xFFFFFFFF
         p.flags = (FLAG_COUNTERS if counters else 0) | (FLAG_TREE_KERNEL if tree else 0) | (FLAG_NO_LDS_SCENE if no_lds else 0) | (FLAG_PROFILE if profile else 0) | (FLAG_WAVEFRONT if wavefront else 0) | (FLAG_TILE_KERNEL if tile else 0) | (FLAG_DEVICE_SAMPLES if samples_ptr else 0) | (FLAG_PACKET_WALK if packet else 0) | (FLAG_PRIVATE_WALK if private_walk else 0)
         return p
 
     def render(self, cam, max_depth=4, accel=ACCEL_BVH, spp=0, samples=None, rank=0, world=1, row_block=16,
-               want_f32=True, want_hit=True, counters=False, tree=False, no_lds=False, profile=False, wavefront=False, soft_shadow=False, fuzzy_reflection=False, seed=0, tile=False, packet=False, private_walk=False, skybox=False):
+               want_f32=True, want_hit=True, counters=False, tree=False, no_lds=False, profile=False, wavefront=False, soft_shadow=False, fuzzy_reflection=False, seed=0, tile=False, packet=False, private_walk=False, skybox=False, schlick=False):
         """Render into host numpy arrays (rows: res_y for world==1, local_rows otherwise)."""
         rows = cam.res_y if world == 1 else local_rows(cam.res_y, row_block, world)
         rgb8 = np.zeros((rows, cam.res_x, 3), np.uint8)
@@ -403,7 +406,7 @@ class DeviceScene:
         hid = np.full((rows, cam.res_x), -2, np.int32) if want_hit else None
         if samples is not None:
             samples = np.ascontiguousarray(samples, np.float32)
-        p = self._params(max_depth, accel, spp, samples, rank, world, row_block, counters, tree, no_lds, profile, wavefront, soft_shadow, fuzzy_reflection, seed, tile, 0, packet, private_walk, skybox)
+        p = self._params(max_depth, accel, spp, samples, rank, world, row_block, counters, tree, no_lds, profile, wavefront, soft_shadow, fuzzy_reflection, seed, tile, 0, packet, private_walk, skybox, schlick)
         o = Outputs(rgb8.ctypes.data, f32.ctypes.data if want_f32 else None,
                     hid.ctypes.data if want_hit else None, 0)
         _check(lib().p3d_render(self.h, C.byref(cam), C.byref(p), C.byref(o)), "p3d_render")
@@ -413,10 +416,10 @@ class DeviceScene:
         return out
 
     def render_device(self, cam, rgb8_ptr=0, rgb32f_ptr=0, hit_ptr=0, max_depth=4, accel=ACCEL_BVH, spp=0,
-                      samples=None, rank=0, world=1, row_block=16, counters=False, tree=False, no_lds=False, profile=False, wavefront=False, soft_shadow=False, fuzzy_reflection=False, seed=0, tile=False, samples_ptr=0, packet=False, private_walk=False, skybox=False):
+                      samples=None, rank=0, world=1, row_block=16, counters=False, tree=False, no_lds=False, profile=False, wavefront=False, soft_shadow=False, fuzzy_reflection=False, seed=0, tile=False, samples_ptr=0, packet=False, private_walk=False, skybox=False, schlick=False):
         """Enqueue one frame into caller-owned DEVICE buffers (raw pointers); asynchronous.  samples_ptr: the
         spp > 0 sample array as a device pointer (uploaded once by the caller) instead of `samples`."""
-        p = self._params(max_depth, accel, spp, samples, rank, world, row_block, counters, tree, no_lds, profile, wavefront, soft_shadow, fuzzy_reflection, seed, tile, samples_ptr, packet, private_walk, skybox)
+        p = self._params(max_depth, accel, spp, samples, rank, world, row_block, counters, tree, no_lds, profile, wavefront, soft_shadow, fuzzy_reflection, seed, tile, samples_ptr, packet, private_walk, skybox, schlick)
         o = Outputs(rgb8_ptr or None, rgb32f_ptr or None, hit_ptr or None, 1)
         _check(lib().p3d_render(self.h, C.byref(cam), C.byref(p), C.byref(o)), "p3d_render")
 
@@ -442,11 +445,11 @@ def tune_schedule(handles, cam, rgb8_ptrs, frames=3, **kw):
     assert n >= 1 and len(rgb8_ptrs) == n
     k = dict(max_depth=4, accel=ACCEL_BVH, spp=0, samples=None, rank=0, world=1, row_block=16, counters=False, tree=False,
              no_lds=False, profile=False, wavefront=False, soft_shadow=False, fuzzy_reflection=False, seed=0, tile=False,
-             samples_ptr=0, packet=False, private_walk=False, skybox=False)
+             samples_ptr=0, packet=False, private_walk=False, skybox=False, schlick=False)
     k.update(kw)
     p = handles[0]._params(k["max_depth"], k["accel"], k["spp"], k["samples"], k["rank"], k["world"], k["row_block"], k["counters"],
                            k["tree"], k["no_lds"], k["profile"], k["wavefront"], k["soft_shadow"], k["fuzzy_reflection"], k["seed"],
-                           k["tile"], k["samples_ptr"], k["packet"], k["private_walk"], k["skybox"])
+                           k["tile"], k["samples_ptr"], k["packet"], k["private_walk"], k["skybox"], k["schlick"])
     hs = (C.c_void_p * n)(*[h.h.value if isinstance(h.h, C.c_void_p) else h.h for h in handles])
     outs = (Outputs * n)(*[Outputs(int(q) or None, None, None, 1) for q in rgb8_ptrs])
     ms = (C.c_float * 6)()
@@ -545,6 +548,28 @@ def debug_powf(x, y, device=0):
     assert x.shape == y.shape
     out = np.zeros_like(x)
     _check(lib().p3d_debug_powf(int(device), len(x), x.ctypes.data, y.ctypes.data, out.ctypes.data), "p3d_debug_powf")
+    return out
+
+
+def debug_pow(x, y, device=0):
+    """The device's restatement of the host libm's pow(double, double) (csrc/p3d_pow.h) on n argument pairs."""
+    x = np.ascontiguousarray(x, np.float64).ravel()
+    y = np.ascontiguousarray(y, np.float64).ravel()
+    assert x.shape == y.shape
+    out = np.zeros_like(x)
+    _check(lib().p3d_debug_pow(int(device), len(x), x.ctypes.data, y.ctypes.data, out.ctypes.data), "p3d_debug_pow")
+    return out
+
+
+def debug_schlick_kr(ior_1, new_ior, cos_theta_i, device=0):
+    """The shading's SCHLICK_APPROX weight KR (RT/main.cpp:700-701) on the device for n (ior_1, newIor, cos_theta_i)."""
+    a = np.ascontiguousarray(ior_1, np.float32).ravel()
+    b = np.ascontiguousarray(new_ior, np.float32).ravel()
+    c = np.ascontiguousarray(cos_theta_i, np.float32).ravel()
+    assert a.shape == b.shape == c.shape
+    out = np.zeros_like(c)
+    _check(lib().p3d_debug_schlick_kr(int(device), len(c), a.ctypes.data, b.ctypes.data, c.ctypes.data, out.ctypes.data),
+           "p3d_debug_schlick_kr")
     return out
 
 

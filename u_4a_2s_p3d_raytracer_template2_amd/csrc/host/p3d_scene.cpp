@@ -470,7 +470,8 @@ int renderScene(const Scene& scene, const RenderOptions& opt, bool want_colors, 
     prm.spp = opt.spp < 0 ? (int)scene.GetSamplesPerPixel() : opt.spp;
     prm.world = 1; prm.rank = 0; prm.row_block = 16;
     prm.flags = opt.counters ? P3D_FLAG_COUNTERS : 0;
-    prm.features = (opt.SOFT_SHADOW ? P3D_FEATURE_SOFT_SHADOW : 0u) | (opt.FUZZY_REFLECTION ? P3D_FEATURE_FUZZY_REFLECTION : 0u);
+    prm.features = (opt.SOFT_SHADOW ? P3D_FEATURE_SOFT_SHADOW : 0u) | (opt.FUZZY_REFLECTION ? P3D_FEATURE_FUZZY_REFLECTION : 0u) |
+                   (opt.SCHLICK_APPROX ? P3D_FEATURE_SCHLICK : 0u);
     if (opt.SKYBOX) {
         if (!scene.HasSkybox()) { if (err) *err = "RenderOptions::SKYBOX without Scene::SetSkybox()"; return P3D_ERR_STATE; }
         if (opt.gpus > 1) { if (err) *err = "the skybox switch is served on one GPU"; return P3D_ERR_ARG; }

@@ -225,6 +225,8 @@ struct RenderOptions {
     // DEPTH_OF_FIELD follow spp > 0 as in RT/main.cpp:943-944
     bool SOFT_SHADOW = false;
     bool FUZZY_REFLECTION = false;
+    // the reference's SCHLICK_APPROX (RT/main.cpp:99): Schlick's Fresnel weight at transmissive hits, bit-exact
+    bool SCHLICK_APPROX = false;
     // misses return Scene::GetSkyboxColor(ray) (RT/scene.cpp:383-461; never called by the reference) when the
     // scene carries a cube map (Scene::SetSkybox): off by default, like in the reference's rayTracing()
     bool SKYBOX = false;

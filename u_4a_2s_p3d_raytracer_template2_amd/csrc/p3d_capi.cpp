@@ -48,6 +48,9 @@ hipError_t sort_tiles_by_cost(const uint32_t* cost, uint32_t* cost_sorted, uint3
 bool kernels_have_stamps();
 hipError_t launch_debug_check_rcp(uint32_t first, uint64_t count, unsigned long long* n_bad, uint32_t* first_bad, hipStream_t stream);
 hipError_t launch_debug_powf(uint32_t n, const float* x, const float* y, float* out, hipStream_t stream);
+hipError_t launch_debug_pow(uint32_t n, const double* x, const double* y, double* out, hipStream_t stream);
+hipError_t launch_debug_schlick_kr(uint32_t n, const float* ior_1, const float* new_ior, const float* cos_theta_i, float* out,
+                                   hipStream_t stream);
 hipError_t launch_debug_intersect(uint32_t n, const uint32_t* type, const float* prim12, const float* origin,
                                   const float* dir, int32_t* hit, float* t, float* normal, hipStream_t stream);
 }  // namespace p3d
@@ -543,12 +546,13 @@ int run_wavefront_pass(p3d_scene* s, p3d_scene::Workspace& ws, hipStream_t strea
     P.wf_level = 1;
     P.wf_rays_in = nullptr; P.wf_count_in = nullptr; P.wf_cap_in = 0;
     P.wf_rays_out = rays(2); P.wf_count_out = qcount(2); P.wf_cap_out = cap(2);
-    auto rng = [&](int l) { return (P.features && l >= 2 && l <= D) ? (uint32_t*)ws.rng[l].p : nullptr; };
+    auto rng = [&](int l) { return (feat_stochastic(P.features) && l >= 2 && l <= D) ? (uint32_t*)ws.rng[l].p : nullptr; };
     P.wf_rng_in = nullptr; P.wf_rng_out = rng(2);
     P.wf_nodes_parent = nullptr; P.wf_ncap_parent = 0;
     P.wf_nodes_self = nodes(1); P.wf_ncount_self = ncount(1); P.wf_ncap_self = cap(1);
     {   // persistent grids: as many waves as can be resident (cached occupancy queries)
-        const uint32_t okey = (count ? 1u : 0u) | (lds ? 2u : 0u) | ((uint32_t)walk << 2) | (P.features ? 16u : 0u) | ((uint32_t)occ << 5);
+        const uint32_t okey = (count ? 1u : 0u) | (lds ? 2u : 0u) | ((uint32_t)walk << 2) | (feat_stochastic(P.features) ? 16u : 0u) |
+                              ((uint32_t)occ << 5) | (feat_schlick(P.features) ? 256u : 0u);
         if (s->wf_occ.key != okey || s->wf_occ.stack != P.trav_stack_dwords) {
             HIP_TRY(wf_resident_waves(P, false, count, lds, walk, occ, &s->wf_occ.waves));
             s->wf_occ.key = okey; s->wf_occ.stack = P.trav_stack_dwords;
@@ -738,7 +742,7 @@ int p3d_render(p3d_scene* s, const p3d_camera* cam, const p3d_render_params* prm
     P.wf_min_width = lds_scene ? 64 : 8;
 
     // distribution-ray-tracing switches (RT/main.cpp:40-45)
-    if (prm->features & ~(P3D_FEATURE_SOFT_SHADOW | P3D_FEATURE_FUZZY_REFLECTION | P3D_FEATURE_SKYBOX)) return fail(P3D_ERR_ARG, "unknown feature bit");
+    if (prm->features & ~(P3D_FEATURE_SOFT_SHADOW | P3D_FEATURE_FUZZY_REFLECTION | P3D_FEATURE_SKYBOX | P3D_FEATURE_SCHLICK)) return fail(P3D_ERR_ARG, "unknown feature bit");
     if (prm->features & P3D_FEATURE_SKYBOX) {
         if (!s->sky.p || s->sky_w[0] == 0) return fail(P3D_ERR_STATE, "P3D_FEATURE_SKYBOX needs p3d_scene_set_skybox() first");
         P.features |= kFeatSky;
@@ -774,6 +778,9 @@ int p3d_render(p3d_scene* s, const p3d_camera* cam, const p3d_render_params* prm
     if (prm->features & P3D_FEATURE_FUZZY_REFLECTION) P.features |= kFeatFuzzy;
     P.seed = prm->seed;
     const bool stochastic = P.features != 0;
+    // SCHLICK_APPROX (RT/main.cpp:699-702, :710): deterministic, picks the kernels built with it -- no random-stream
+    // workspace, every schedule (the tree included), measured like any other configuration (prm->features is in the keys)
+    if (prm->features & P3D_FEATURE_SCHLICK) P.features |= kFeatSchlick;
     const bool count = (prm->flags & P3D_FLAG_COUNTERS) != 0;
 
     // ---- schedule.  Three ways to run the same per-node code, bit-identical frames:
@@ -819,7 +826,8 @@ int p3d_render(p3d_scene* s, const p3d_camera* cam, const p3d_render_params* prm
         tile_blocks = 0;
         tile_ok = tile_kernel_lds_bytes(PT, lds_scene) <= kMaxLdsBytes && D <= 16;
         if (!tile_ok) return P3D_OK;
-        const uint32_t okey = (count ? 1u : 0u) | (lds_scene ? 2u : 0u) | ((uint32_t)walk << 2) | (stochastic ? 16u : 0u) | ((uint32_t)tile_occ << 5);
+        const uint32_t okey = (count ? 1u : 0u) | (lds_scene ? 2u : 0u) | ((uint32_t)walk << 2) | (stochastic ? 16u : 0u) | ((uint32_t)tile_occ << 5) |
+                              (feat_schlick(P.features) ? 256u : 0u);
         const size_t olds = tile_kernel_lds_bytes(PT, lds_scene);
         auto* slot = &s->tile_occ[walk == 3 ? 1 : 0];
         if (slot->key != okey || slot->lds != olds) {
@@ -1330,6 +1338,43 @@ int p3d_debug_powf(int device, uint32_t n, const float* x, const float* y, float
     if (e == hipSuccess) e = hipMemcpy(out, d + 2 * (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost);
     (void)hipFree(d);
     if (e != hipSuccess) return fail(P3D_ERR_HIP, std::string("p3d_debug_powf: ") + hipGetErrorString(e));
+    return P3D_OK;
+}
+
+int p3d_debug_pow(int device, uint32_t n, const double* x, const double* y, double* out) {
+    if (!x || !y || !out) return fail(P3D_ERR_ARG, "NULL argument");
+    if (n == 0) return P3D_OK;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(P3D_ERR_NO_DEVICE, "no HIP device visible");
+    HIP_TRY(hipSetDevice(device));
+    double* d = nullptr;                                  // x | y | out
+    HIP_TRY(hipMalloc((void**)&d, (size_t)n * 24));
+    hipError_t e = hipMemcpy(d, x, (size_t)n * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d + n, y, (size_t)n * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = launch_debug_pow(n, d, d + n, d + 2 * (size_t)n, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out, d + 2 * (size_t)n, (size_t)n * 8, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (e != hipSuccess) return fail(P3D_ERR_HIP, std::string("p3d_debug_pow: ") + hipGetErrorString(e));
+    return P3D_OK;
+}
+
+int p3d_debug_schlick_kr(int device, uint32_t n, const float* ior_1, const float* new_ior, const float* cos_theta_i, float* out) {
+    if (!ior_1 || !new_ior || !cos_theta_i || !out) return fail(P3D_ERR_ARG, "NULL argument");
+    if (n == 0) return P3D_OK;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(P3D_ERR_NO_DEVICE, "no HIP device visible");
+    HIP_TRY(hipSetDevice(device));
+    float* d = nullptr;                                   // ior_1 | new_ior | cos_theta_i | out
+    HIP_TRY(hipMalloc((void**)&d, (size_t)n * 16));
+    hipError_t e = hipMemcpy(d, ior_1, (size_t)n * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d + n, new_ior, (size_t)n * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d + 2 * (size_t)n, cos_theta_i, (size_t)n * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = launch_debug_schlick_kr(n, d, d + n, d + 2 * (size_t)n, d + 3 * (size_t)n, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out, d + 3 * (size_t)n, (size_t)n * 4, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (e != hipSuccess) return fail(P3D_ERR_HIP, std::string("p3d_debug_schlick_kr: ") + hipGetErrorString(e));
     return P3D_OK;
 }
 

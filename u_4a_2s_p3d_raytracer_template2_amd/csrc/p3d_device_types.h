@@ -82,6 +82,10 @@ struct DeviceCounters {
 
 constexpr uint32_t kWfShards = 64;           // queue shards of the wavefront schedule (LaunchParams::wf_shards); == the wave size
 constexpr uint32_t kFeatSoftJitter = 1u, kFeatFuzzy = 2u, kFeatSky = 4u;   // LaunchParams::features
+// SCHLICK_APPROX: no random draws and no run-time test -- it selects the kernels built with it (p3d_kernels.hip)
+constexpr uint32_t kFeatSchlick = 8u;
+P3D_HD inline bool feat_stochastic(uint32_t f) { return (f & ~kFeatSchlick) != 0u; }   // needs random-stream keys
+P3D_HD inline bool feat_schlick(uint32_t f) { return (f & kFeatSchlick) != 0u; }
 constexpr uint32_t kShareDwords = 384;      // per-wave LDS of the work-sharing walk (p3d_traverse.h), behind the wave's stack slots
 
 // Everything a render launch needs, passed by value (lands in SGPRs / kernarg segment).

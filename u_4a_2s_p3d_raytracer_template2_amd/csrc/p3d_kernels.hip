@@ -349,7 +349,7 @@ __device__ __forceinline__ void stamp_wave(const LaunchParams& P, uint32_t wave_
 // (Measured and dropped in round 3, profiles/r03_exp03_sharing_wg_levers.txt / r03_exp04_tiles_lpt_bound.txt: 8- and 16-wave
 //  workgroups -- level 1 of config 2 46 -> 51 -> 54 us -- and 2-4 tiles per workgroup one after the other: the waves of
 //  this launch start at ~830 per microsecond whatever the workgroup shape, and the loop's registers cost occupancy.)
-template <bool COUNT, bool LDS, int WALK, int OCC, bool STOCH = false>
+template <bool COUNT, bool LDS, int WALK, int OCC, bool STOCH = false, bool SCHLICK = false>
 __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void wf_primary_kernel(const LaunchParams P) {
     const uint32_t par = P.wf_ctrl[0] & 1u;                     // this pass's counter set (LaunchParams::wf_alt)
     if (blockIdx.x == 0 && blockIdx.y == 0) {
@@ -377,7 +377,7 @@ __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void wf_primary_kernel
     // the random stream of a pixel sample is keyed by the pixel's place in the FULL frame, so a frame
     // sharded over several GPUs draws the same numbers as on one
     const uint32_t rng = STOCH ? rng_mix(rng_mix(P.seed, (uint32_t)(y * P.res_x + x)), (uint32_t)P.wf_sample) : 0u;
-    const NodeOut o = shade_hit<COUNT, WALK, typename View<LDS>::type, STOCH>(P, sv, ray, h, valid, 1, 1.0f, tc, ctr, rng);
+    const NodeOut o = shade_hit<COUNT, WALK, typename View<LDS>::type, STOCH, SCHLICK>(P, sv, ray, h, valid, 1, 1.0f, tc, ctr, rng);
     stamp(P, tile, 3);
     emit(P, sh, 1, valid, (uint32_t)p, 1.0f, o);
     stamp(P, tile, 4);
@@ -401,7 +401,7 @@ __device__ __forceinline__ uint32_t wave_width(uint32_t count, uint32_t waves_pe
 }
 
 // level >= 2: one queued ray per lane, persistent waves striding over the queue
-template <bool COUNT, bool LDS, int WALK, int OCC, bool STOCH = false>
+template <bool COUNT, bool LDS, int WALK, int OCC, bool STOCH = false, bool SCHLICK = false>
 __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void wf_secondary_kernel(const LaunchParams P) {
     constexpr uint32_t S = kWfShards;
     const uint32_t wave_id = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
@@ -447,7 +447,7 @@ __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void wf_secondary_kern
             if (stamps_on(P) && st1) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stamp_wave(P, wave_id, 1); }
             const Hit h = find_closest<COUNT, WALK>(P, sv, ray, live, tc, ctr);
             stamp_wave(P, wave_id, 2, st1);
-            const NodeOut o = shade_hit<COUNT, WALK, typename View<LDS>::type, STOCH>(P, sv, ray, h, live, P.wf_level, ior_1, tc,
+            const NodeOut o = shade_hit<COUNT, WALK, typename View<LDS>::type, STOCH, SCHLICK>(P, sv, ray, h, live, P.wf_level, ior_1, tc,
                                                                                     ctr, rng);
             stamp_wave(P, wave_id, 3, st1);
             if (P.wf_pair_in) combine_pair(P, sh, live, link, o);
@@ -494,7 +494,7 @@ __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void wf_secondary_kern
         const bool live = valid && link != kPairEmpty;
         const Hit h = find_closest<COUNT, WALK>(P, sv, ray, live, tc, ctr);
         stamp_wave(P, wave_id, 2, st1);
-        const NodeOut o = shade_hit<COUNT, WALK, typename View<LDS>::type, STOCH>(P, sv, ray, h, live, P.wf_level, ior_1, tc,
+        const NodeOut o = shade_hit<COUNT, WALK, typename View<LDS>::type, STOCH, SCHLICK>(P, sv, ray, h, live, P.wf_level, ior_1, tc,
                                                                                 ctr, rng);
         stamp_wave(P, wave_id, 3, st1);
         if (P.wf_pair_in) combine_pair(P, sh, live, link, o);
@@ -651,7 +651,7 @@ __device__ __forceinline__ void tile_emit(const LaunchParams& P, const TileCtx& 
     }
 }
 
-template <bool COUNT, bool LDS, int WALK, int OCC, bool STOCH = false>
+template <bool COUNT, bool LDS, int WALK, int OCC, bool STOCH = false, bool SCHLICK = false>
 __global__ __launch_bounds__(256) P3D_OCC(OCC) void wf_tile_kernel(const LaunchParams P) {
     const typename View<LDS>::type sv = View<LDS>::make_shading(P);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -731,7 +731,7 @@ __global__ __launch_bounds__(256) P3D_OCC(OCC) void wf_tile_kernel(const LaunchP
                     }
                     const Hit h = find_closest<COUNT, WALK>(P, sv, ray, valid, tc, ctr);
                     if (l == 1 && smp == 0 && inside && P.hit_id) P.hit_id[p] = (h.ref == 0xFFFFFFFFu) ? -1 : (int32_t)h.sid;
-                    const NodeOut o = shade_hit<COUNT, WALK, typename View<LDS>::type, STOCH>(P, sv, ray, h, valid, l, ior_1, tc,
+                    const NodeOut o = shade_hit<COUNT, WALK, typename View<LDS>::type, STOCH, SCHLICK>(P, sv, ray, h, valid, l, ior_1, tc,
                                                                                               ctr, rng, smp);
                     tile_emit(P, X, l, valid, link, ior_1, o);
                 }
@@ -791,7 +791,7 @@ enum { FR_C = 0, FR_KR = 3, FR_META = 4, FR_A = 5, FR_RD = 8, FR_IOR = 11 };
 #define FR_WAIT_REFR 0x80000000u
 
 // One primary ray's whole tree: rayTracing(ray, 1, 1.0) of RT/main.cpp:530-721, iterative.
-template <bool COUNT, bool GRID, class SV, class FR>
+template <bool COUNT, bool GRID, class SV, class FR, bool SCHLICK = false>
 __device__ __forceinline__ V3 trace_tree(const LaunchParams& P, const SV& sv, Ray ray, const TravCtx& tc, FR fr,
                                          int32_t& primary_hit, Ctr& ctr) {
     int fsp = 0;              // frames on the stack == depth - 1
@@ -802,7 +802,7 @@ __device__ __forceinline__ V3 trace_tree(const LaunchParams& P, const SV& sv, Ra
     for (;;) {
         Hit h = find_closest<COUNT, GRID ? WALK_GRID : WALK_LANE>(P, sv, ray, true, tc, ctr);
         if (first) { primary_hit = (h.ref == 0xFFFFFFFFu) ? -1 : (int32_t)h.sid; first = false; }
-        NodeOut o = shade_hit<COUNT, GRID ? WALK_GRID : WALK_LANE>(P, sv, ray, h, true, fsp + 1, ior_1, tc, ctr);
+        NodeOut o = shade_hit<COUNT, GRID ? WALK_GRID : WALK_LANE, SV, false, SCHLICK>(P, sv, ray, h, true, fsp + 1, ior_1, tc, ctr);
         if (!o.terminal) {
             fr.put3(fsp, FR_C, o.color);
             fr.f(fsp, FR_KR) = __float_as_uint(o.KR);
@@ -855,7 +855,7 @@ __device__ __forceinline__ V3 trace_tree(const LaunchParams& P, const SV& sv, Ra
 // The same trees with the wave's lanes in ONE loop (work-sharing walk, WALK_SHARED): every iteration all 64 lanes reach
 // find_closest() / shade_hit() together -- a lane whose pixel is finished (or outside the image) comes along as a helper
 // of the others' walks -- and a lane that finishes a sample's tree starts its next sample at once.
-template <bool COUNT, class SV, class FR>
+template <bool COUNT, class SV, class FR, bool SCHLICK = false>
 __device__ __forceinline__ void trace_trees_shared(const LaunchParams& P, const SV& sv, int x, int y, bool valid, const TravCtx& tc, FR fr,
                                                    V3& color, int32_t& hid, Ctr& ctr) {
     const int ns = P.spp > 0 ? P.spp * P.spp : 1;
@@ -869,7 +869,7 @@ __device__ __forceinline__ void trace_trees_shared(const LaunchParams& P, const 
     while (__ballot(alive) != 0) {
         const Hit h = find_closest<COUNT, WALK_SHARED>(P, sv, ray, alive, tc, ctr);
         if (alive && first) { if (smp == 0) hid = (h.ref == 0xFFFFFFFFu) ? -1 : (int32_t)h.sid; first = false; }
-        const NodeOut o = shade_hit<COUNT, WALK_SHARED>(P, sv, ray, h, alive, fsp + 1, ior_1, tc, ctr);
+        const NodeOut o = shade_hit<COUNT, WALK_SHARED, SV, false, SCHLICK>(P, sv, ray, h, alive, fsp + 1, ior_1, tc, ctr);
         if (!alive) continue;
         if (!o.terminal) {
             fr.put3(fsp, FR_C, o.color);
@@ -926,7 +926,7 @@ __device__ __forceinline__ void trace_trees_shared(const LaunchParams& P, const 
 }
 
 // PRIV = dwords of private memory for the frames (12 per level below the first), 0 = frames in LDS
-template <bool COUNT, bool LDS, int OCC, bool GRID = false, int PRIV = 0, bool SHARED = false>
+template <bool COUNT, bool LDS, int OCC, bool GRID = false, int PRIV = 0, bool SHARED = false, bool SCHLICK = false>
 __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void whitted_tree_kernel(const LaunchParams P) {
     const typename View<LDS>::type sv = View<LDS>::make_shading(P);
     const int lane = threadIdx.x & 63;
@@ -946,7 +946,7 @@ __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void whitted_tree_kern
     V3 color = mk(0.0f, 0.0f, 0.0f);
     int32_t hid = -1;
     if constexpr (SHARED) {
-        trace_trees_shared<COUNT>(P, sv, x, y, in_image, st, fr, color, hid, ctr);
+        trace_trees_shared<COUNT, typename View<LDS>::type, decltype(fr), SCHLICK>(P, sv, x, y, in_image, st, fr, color, hid, ctr);
         if (in_image) {
             const size_t p = (size_t)row * P.res_x + x;
             write_pixel(P, p, color);
@@ -958,12 +958,12 @@ __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void whitted_tree_kern
         return;
     }
     if (P.spp == 0) {                                    // RT/main.cpp:756-775
-        color = clampc(trace_tree<COUNT, GRID>(P, sv, camera_ray(P, x, y, 0), st, fr, hid, ctr));
+        color = clampc(trace_tree<COUNT, GRID, typename View<LDS>::type, decltype(fr), SCHLICK>(P, sv, camera_ray(P, x, y, 0), st, fr, hid, ctr));
     } else {                                             // RT/main.cpp:776-801
         const int ns = P.spp * P.spp;
         for (int s = 0; s < ns; s++) {
             int32_t h2 = -1;
-            V3 c = clampc(trace_tree<COUNT, GRID>(P, sv, camera_ray(P, x, y, s), st, fr, h2, ctr));
+            V3 c = clampc(trace_tree<COUNT, GRID, typename View<LDS>::type, decltype(fr), SCHLICK>(P, sv, camera_ray(P, x, y, s), st, fr, h2, ctr));
             color = add(color, c);
             if (s == 0) hid = h2;
         }
@@ -1071,9 +1071,19 @@ size_t wavefront_lds_bytes(const LaunchParams& P, bool lds) {
 // Kernel variants are picked through function pointers: {count} x {scene in LDS} x {walk: lane / packet / grid}
 // x {register budget: only for the timed non-grid builds} x {random draws}.  Counting, grid and stochastic
 // builds always use the default register budget.
+// Schlick builds (P3D_FEATURE_SCHLICK) exist for every walk, scene placement, counting and random-draw combination the
+// dispatcher can pick, all with the default register budget.
 template <class F> static const void* fn_ptr(F f) { return reinterpret_cast<const void*>(f); }
 #define P3D_DEFINE_SELECTOR(NAME, KERNEL)                                                                         \
-    static const void* NAME(bool count, bool lds, int walk, int occ, bool stoch) {                                \
+    template <bool C, bool S> static const void* NAME##_schlick(bool lds, int walk) {                             \
+        if (!lds) return walk == 3 ? fn_ptr(KERNEL<C, false, 3, 1, S, true>) : walk == 2 ? fn_ptr(KERNEL<C, false, 2, 1, S, true>)         \
+                       : walk == 1 ? fn_ptr(KERNEL<C, false, 1, 1, S, true>) : fn_ptr(KERNEL<C, false, 0, 1, S, true>);                   \
+        return walk == 2 ? fn_ptr(KERNEL<C, true, 2, 1, S, true>) : walk == 1 ? fn_ptr(KERNEL<C, true, 1, 1, S, true>)                     \
+                         : fn_ptr(KERNEL<C, true, 0, 1, S, true>);                                                \
+    }                                                                                                             \
+    static const void* NAME(bool count, bool lds, int walk, int occ, bool stoch, bool schlick) {                  \
+        if (schlick) return count ? (stoch ? NAME##_schlick<true, true>(lds, walk) : NAME##_schlick<true, false>(lds, walk))             \
+                                  : (stoch ? NAME##_schlick<false, true>(lds, walk) : NAME##_schlick<false, false>(lds, walk));          \
         if (walk == WALK_GRID || count || stoch) occ = 1;                                                         \
         if (walk == WALK_SHARED && !lds) {                                                                        \
             if (stoch) return count ? fn_ptr(KERNEL<true, false, 3, 1, true>) : fn_ptr(KERNEL<false, false, 3, 1, true>);                                                                  \
@@ -1102,7 +1112,16 @@ P3D_DEFINE_SELECTOR(wf_secondary_fn, wf_secondary_kernel)
 P3D_DEFINE_SELECTOR(wf_tile_fn, wf_tile_kernel)
 #undef P3D_DEFINE_SELECTOR
 
-static const void* tree_fn(bool count, bool lds, int occ, bool grid, int priv = 0, bool shared = false) {
+template <bool C> static const void* tree_schlick_fn(bool lds, bool grid, int priv, bool shared) {
+    if (grid) return lds ? fn_ptr(whitted_tree_kernel<C, true, 1, true, 0, false, true>) : fn_ptr(whitted_tree_kernel<C, false, 1, true, 0, false, true>);
+    if (lds) return fn_ptr(whitted_tree_kernel<C, true, 1, false, 0, false, true>);
+    if (shared) return priv == 36 ? fn_ptr(whitted_tree_kernel<C, false, 1, false, 36, true, true>)
+                     : priv == 84 ? fn_ptr(whitted_tree_kernel<C, false, 1, false, 84, true, true>) : fn_ptr(whitted_tree_kernel<C, false, 1, false, 0, true, true>);
+    return priv == 36 ? fn_ptr(whitted_tree_kernel<C, false, 1, false, 36, false, true>)
+         : priv == 84 ? fn_ptr(whitted_tree_kernel<C, false, 1, false, 84, false, true>) : fn_ptr(whitted_tree_kernel<C, false, 1, false, 0, false, true>);
+}
+static const void* tree_fn(bool count, bool lds, int occ, bool grid, int priv = 0, bool shared = false, bool schlick = false) {
+    if (schlick) return count ? tree_schlick_fn<true>(lds, grid, priv, shared) : tree_schlick_fn<false>(lds, grid, priv, shared);
     if (shared && !lds && !grid && priv == 36) {
         if (count) return fn_ptr(whitted_tree_kernel<true, false, 1, false, 36, true>);
         return occ == 5 ? fn_ptr(whitted_tree_kernel<false, false, 5, false, 36, true>) : occ == 6 ? fn_ptr(whitted_tree_kernel<false, false, 6, false, 36, true>)
@@ -1141,7 +1160,7 @@ static hipError_t launch_by_pointer(const void* fn, const LaunchParams& P, dim3 
 }
 
 hipError_t launch_tree(const LaunchParams& P, bool count, bool lds, int occ, bool shared, hipStream_t stream) {
-    return launch_by_pointer(tree_fn(count, lds, occ, P.accel == 1, tree_private_dwords(P, lds), shared), P, dim3((unsigned)P.grid_blocks),
+    return launch_by_pointer(tree_fn(count, lds, occ, P.accel == 1, tree_private_dwords(P, lds), shared, feat_schlick(P.features)), P, dim3((unsigned)P.grid_blocks),
                              dim3(64 * P.wg_waves), tree_kernel_lds_bytes(P, lds), stream);
 }
 hipError_t launch_wf_primary(const LaunchParams& P, bool count, bool lds, int walk, int occ, hipStream_t stream) {
@@ -1149,17 +1168,17 @@ hipError_t launch_wf_primary(const LaunchParams& P, bool count, bool lds, int wa
     // (LDS scenes only: the kernels of scenes read from HBM number their tiles through the learned order)
     const bool grid2d = lds && P.xcd_chunk == 1 && P.wf_tile_rows > 1 && P.tiles_x * P.wf_tile_rows == P.n_tiles;
     const dim3 grid = grid2d ? dim3((unsigned)P.tiles_x, (unsigned)P.wf_tile_rows) : dim3((unsigned)P.grid_blocks);
-    return launch_by_pointer(wf_primary_fn(count, lds, walk, occ, P.features != 0), P, grid,
+    return launch_by_pointer(wf_primary_fn(count, lds, walk, occ, feat_stochastic(P.features), feat_schlick(P.features)), P, grid,
                              dim3(64 * P.wg_waves), wavefront_lds_bytes(P, lds), stream);
 }
 hipError_t launch_wf_secondary(const LaunchParams& P, bool count, bool lds, int walk, int occ, unsigned waves,
                                hipStream_t stream) {
-    return launch_by_pointer(wf_secondary_fn(count, lds, walk, occ, P.features != 0), P, dim3((waves + P.wg_waves - 1) / P.wg_waves),
+    return launch_by_pointer(wf_secondary_fn(count, lds, walk, occ, feat_stochastic(P.features), feat_schlick(P.features)), P, dim3((waves + P.wg_waves - 1) / P.wg_waves),
                              dim3(64 * P.wg_waves), wavefront_lds_bytes(P, lds), stream);
 }
 // waves of the deeper-level kernel that can be resident on the device at once (LDS-scene variants: 256-thread workgroups)
 hipError_t wf_resident_waves(const LaunchParams& P, bool primary, bool count, bool lds, int walk, int occ, unsigned* waves) {
-    const void* fn = primary ? wf_primary_fn(count, lds, walk, occ, P.features != 0) : wf_secondary_fn(count, lds, walk, occ, P.features != 0);
+    const void* fn = primary ? wf_primary_fn(count, lds, walk, occ, feat_stochastic(P.features), feat_schlick(P.features)) : wf_secondary_fn(count, lds, walk, occ, feat_stochastic(P.features), feat_schlick(P.features));
     int per_cu = 0, dev = 0, cus = 0;
     hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * P.wg_waves, wavefront_lds_bytes(P, lds));
     if (e != hipSuccess) return e;
@@ -1174,7 +1193,7 @@ size_t tile_kernel_lds_bytes(const LaunchParams& P, bool lds) {
 }
 // workgroups of this variant that can be resident on the whole device (persistent grid size)
 hipError_t tile_kernel_resident_blocks(const LaunchParams& P, bool count, bool lds, int walk, int occ, int* blocks) {
-    const void* fn = wf_tile_fn(count, lds, walk, occ, P.features != 0);
+    const void* fn = wf_tile_fn(count, lds, walk, occ, feat_stochastic(P.features), feat_schlick(P.features));
     const size_t shmem = tile_kernel_lds_bytes(P, lds);
     if (shmem > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
@@ -1189,7 +1208,7 @@ hipError_t tile_kernel_resident_blocks(const LaunchParams& P, bool count, bool l
     return hipSuccess;
 }
 hipError_t launch_wf_tile(const LaunchParams& P, bool count, bool lds, int walk, int occ, unsigned blocks, hipStream_t stream) {
-    return launch_by_pointer(wf_tile_fn(count, lds, walk, occ, P.features != 0), P, dim3(blocks), dim3(256),
+    return launch_by_pointer(wf_tile_fn(count, lds, walk, occ, feat_stochastic(P.features), feat_schlick(P.features)), P, dim3(blocks), dim3(256),
                              tile_kernel_lds_bytes(P, lds), stream);
 }
 
@@ -1221,7 +1240,10 @@ hipError_t prepare_kernels(size_t max_lds) {
     // only the tree kernel without an LDS scene copy can need more than the 64 KiB default
     const void* fns[] = {tree_fn(true, false, 1, false), tree_fn(false, false, 1, false), tree_fn(false, false, 5, false),
                          tree_fn(false, false, 6, false), tree_fn(true, false, 1, true), tree_fn(false, false, 1, true),
-                         tree_fn(true, false, 1, false, 0, true), tree_fn(false, false, 1, false, 0, true)};
+                         tree_fn(true, false, 1, false, 0, true), tree_fn(false, false, 1, false, 0, true),
+                         tree_fn(true, false, 1, false, 0, false, true), tree_fn(false, false, 1, false, 0, false, true),
+                         tree_fn(true, false, 1, true, 0, false, true), tree_fn(false, false, 1, true, 0, false, true),
+                         tree_fn(true, false, 1, false, 0, true, true), tree_fn(false, false, 1, false, 0, true, true)};
     for (const void* f : fns) {
         hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds);
         if (e != hipSuccess) return e;
@@ -1273,6 +1295,25 @@ __global__ void debug_powf_kernel(uint32_t n, const float* x, const float* y, fl
 }
 hipError_t launch_debug_powf(uint32_t n, const float* x, const float* y, float* out, hipStream_t stream) {
     hipLaunchKernelGGL(debug_powf_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, x, y, out);
+    return hipGetLastError();
+}
+
+__global__ void debug_pow_kernel(uint32_t n, const double* x, const double* y, double* out) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = p3d_pow(x[i], y[i]);
+}
+hipError_t launch_debug_pow(uint32_t n, const double* x, const double* y, double* out, hipStream_t stream) {
+    hipLaunchKernelGGL(debug_pow_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, x, y, out);
+    return hipGetLastError();
+}
+// the KR expression of shade_hit<..., SCHLICK = true> on (ior_1, newIor, cos_theta_i) triples
+__global__ void debug_schlick_kr_kernel(uint32_t n, const float* ior_1, const float* new_ior, const float* cos_theta_i, float* out) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = p3d_schlick_kr(ior_1[i], new_ior[i], cos_theta_i[i], PowTab());
+}
+hipError_t launch_debug_schlick_kr(uint32_t n, const float* ior_1, const float* new_ior, const float* cos_theta_i, float* out,
+                                   hipStream_t stream) {
+    hipLaunchKernelGGL(debug_schlick_kr_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, ior_1, new_ior, cos_theta_i, out);
     return hipGetLastError();
 }
 

@@ -8,6 +8,7 @@
 
 #include "p3d_traverse.h"
 #include "p3d_powf.h"
+#include "p3d_pow.h"
 
 namespace p3d {
 
@@ -205,7 +206,9 @@ __device__ __forceinline__ V3 combine_node(V3 color, float KR, V3 spec, V3 refl_
 // the shadow queries sit in wave-uniform control flow (the packet walk needs every lane of the
 // wave to arrive together): lanes without a ray or without a hit carry live == false /
 // hit == false through the light loop instead of leaving early.
-template <bool COUNT, int WALK, class SV, bool STOCH = false>
+// SCHLICK: the reference's SCHLICK_APPROX switch (P3D_FEATURE_SCHLICK) as a compile-time parameter: kernels without it
+// are the code they were before the switch existed.
+template <bool COUNT, int WALK, class SV, bool STOCH = false, bool SCHLICK = false>
 __device__ __forceinline__ NodeOut shade_hit(const LaunchParams& P, const SV& sv, const Ray& ray, const Hit& h,
                                              bool live, int depth, float ior_1, const TravCtx& tc, Ctr& ctr,
                                              uint32_t rng = 0u, int sample_override = -1) {
@@ -310,13 +313,19 @@ __device__ __forceinline__ NodeOut shade_hit(const LaunchParams& P, const SV& sv
             o.refr.d = rfr;
             o.newIor = inside ? 1.0f : M.ior;
             o.has_refr = true;
-            float den = ior_1 * cos_i + o.newIor * cos_t;
-            float q0 = fabsf(fdiv(ior_1 * cos_i - o.newIor * cos_t, den));
-            float q1 = fabsf(fdiv(ior_1 * cos_t - o.newIor * cos_i, den));
-            R0 = (float)((double)q0 * (double)q0);
-            R1 = (float)((double)q1 * (double)q1);
+            if constexpr (SCHLICK) {                                     // RT/main.cpp:699-702 (p3d_pow.h)
+                KR = p3d_schlick_kr(ior_1, o.newIor, cos_i, PowTab());
+            } else {
+                float den = ior_1 * cos_i + o.newIor * cos_t;
+                float q0 = fabsf(fdiv(ior_1 * cos_i - o.newIor * cos_t, den));
+                float q1 = fabsf(fdiv(ior_1 * cos_t - o.newIor * cos_i, den));
+                R0 = (float)((double)q0 * (double)q0);
+                R1 = (float)((double)q1 * (double)q1);
+            }
         }
-        KR = 0.0f * (R0 + R1);                                           // 1 / 2 * (R0 + R1), SURVEY Q5
+        // 1 / 2 * (R0 + R1), SURVEY Q5 -- with SCHLICK_APPROX only under total internal reflection (RT/main.cpp:710; a NaN
+        // insqrt, which leaves the reference's KR unset, gets the same 0 here)
+        if (!SCHLICK || !(insqrt >= 0.0f)) KR = 0.0f * (R0 + R1);
     } else {
         KR = M.ks;
     }
