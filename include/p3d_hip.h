@@ -241,6 +241,26 @@ int p3d_local_rows(int32_t res_y, int32_t row_block, int32_t world);
  * processLight() and every intercepts() beneath them. */
 int p3d_render(p3d_scene* scene, const p3d_camera* cam, const p3d_render_params* params,
                const p3d_outputs* out);
+/* Renders n frames of one configuration, frame f seen through cams[f], in the same launches.  Frame f equals what
+ * p3d_render(scene, &cams[f], params', out_f) would produce, in every bit, where params' = *params except
+ * seed = params->seed + f and samples = frame f's sample array.
+ *  - cams: a HOST array of n >= 1 cameras sharing res_x and res_y (else P3D_ERR_ARG); eye, basis, w / h, plane_dist,
+ *    aperture and focal_ratio may differ per frame.
+ *  - outputs: every plane holds the n frames back to back, frame f starting f * rows * res_x pixels in, where rows is
+ *    what p3d_render uses: res_y when world == 1, p3d_local_rows() when world > 1.  Host or device memory as in
+ *    p3d_render; NULL planes are allowed.  Sharded batches stitch with p3d_deinterleave_frames (tile_stride_bytes =
+ *    rows * res_x * bpp).
+ *  - samples (spp > 0): n sample arrays back to back, on the host or (P3D_FLAG_DEVICE_SAMPLES) on the device.
+ *  - random streams: frame f is keyed with seed + f.
+ *  - every feature, flag, accel mode, rank / world and row_block of p3d_render is accepted.  Counters are the sum over
+ *    the batch; the profile brackets the whole batch.  Batches keep their own measured schedule choice and tile order
+ *    (keyed on n), so alternating with p3d_render on one handle re-measures neither.
+ *  - a batch whose stacked pixel count n * p3d_local_rows() * res_x does not fit 31 bits is refused with P3D_ERR_LIMIT
+ *    before anything is allocated.
+ *  - under a stream capture it behaves like p3d_render: the per-frame cameras are written by launches of the captured
+ *    stream itself, so a replay renders the cameras it was captured with. */
+int p3d_render_frames(p3d_scene* scene, const p3d_camera* cams, int32_t n, const p3d_render_params* params,
+                      const p3d_outputs* out);
 int p3d_sync(p3d_scene* scene);
 /* counters of the most recent render made with P3D_FLAG_COUNTERS (waits for it) */
 int p3d_get_counters(p3d_scene* scene, p3d_counters* out);

@@ -81,7 +81,7 @@ class SceneStats(C.Structure):
 
 # every symbol include/p3d_hip.h declares (tests check that the library exports them all)
 C_ABI_SYMBOLS = ["p3d_abi_version", "p3d_last_error", "p3d_device_count", "p3d_scene_create",
-                 "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_local_rows", "p3d_render", "p3d_sync",
+                 "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_sync",
                  "p3d_get_counters", "p3d_get_profile", "p3d_last_schedule", "p3d_set_tuning", "p3d_set_stream", "p3d_timer_begin", "p3d_timer_end", "p3d_deinterleave_frames",
                  "p3d_deinterleave", "p3d_debug_intersect", "p3d_debug_powf", "p3d_debug_pow", "p3d_debug_schlick_kr", "p3d_debug_check_rcp", "p3d_tune_schedule", "p3d_debug_set_stamps", "p3d_debug_set_stamp_level",
                  "p3d_comm_unique_id", "p3d_comm_create", "p3d_comm_create_all", "p3d_comm_destroy", "p3d_comm_info",
@@ -125,6 +125,7 @@ def lib():
     L.p3d_scene_get_stats.argtypes = [C.c_void_p, C.POINTER(SceneStats)]
     L.p3d_local_rows.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     L.p3d_render.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(Outputs)]
+    L.p3d_render_frames.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.POINTER(RenderParams), C.POINTER(Outputs)]
     L.p3d_sync.argtypes = [C.c_void_p]
     L.p3d_get_counters.argtypes = [C.c_void_p, C.POINTER(Counters)]
     L.p3d_set_stream.argtypes = [C.c_void_p, C.c_void_p]
@@ -163,6 +164,8 @@ def lib():
     L.p3dh_scene_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     L.p3dh_scene_set_resolution.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
     L.p3dh_scene_set_eye.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_float]
+    L.p3dh_orbit_eyes.argtypes = [C.c_float, C.c_float, C.c_float, C.c_int32, C.c_float, C.c_float, C.c_void_p]
+    L.p3dh_scene_orbit_cameras.argtypes = [C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_void_p]
     L.p3dh_scene_desc.argtypes = [C.c_void_p, C.POINTER(SceneDesc)]
     L.p3dh_scene_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
     L.p3dh_primary_ray.argtypes = [C.c_void_p, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float)]
@@ -248,6 +251,13 @@ class HostScene:
     def set_eye(self, x, y, z):
         lib().p3dh_scene_set_eye(self.h, float(x), float(y), float(z))
 
+    def orbit_cameras(self, n, step_deg, d_beta_deg=0.0):
+        """n cameras of the reference's mouse orbit around this scene's eye (orbit_eyes; Camera::SetEye on a copy of the
+        camera per eye, so the scene's own camera is unchanged)."""
+        out = (Camera * int(n))()
+        lib().p3dh_scene_orbit_cameras(self.h, int(n), float(step_deg), float(d_beta_deg), out)
+        return list(out)
+
     def desc(self):
         d = SceneDesc()
         lib().p3dh_scene_desc(self.h, C.byref(d))
@@ -281,6 +291,14 @@ class HostScene:
         lib().p3dh_generate_samples(int(seed), self.res_x, self.res_y, int(spp), cam.aperture,
                                     out.ctypes.data_as(C.c_void_p))
         return out
+
+
+def orbit_eyes(eye, n, step_deg, d_beta_deg=0.0):
+    """(n, 3) float32: the host layer's orbit_eyes, the reference's mouse orbit (RT/main.cpp:339-341, 419-421)."""
+    out = np.zeros((int(n), 3), np.float32)
+    lib().p3dh_orbit_eyes(float(eye[0]), float(eye[1]), float(eye[2]), int(n), float(step_deg), float(d_beta_deg),
+                          out.ctypes.data_as(C.c_void_p))
+    return out
 
 
 def make_desc(ptype, data12, material, materials12, lights6, bg):
@@ -423,6 +441,40 @@ class DeviceScene:
         o = Outputs(rgb8_ptr or None, rgb32f_ptr or None, hit_ptr or None, 1)
         _check(lib().p3d_render(self.h, C.byref(cam), C.byref(p), C.byref(o)), "p3d_render")
 
+    def render_frames(self, cams, max_depth=4, accel=ACCEL_BVH, spp=0, samples=None, rank=0, world=1, row_block=16,
+                      want_f32=True, want_hit=True, counters=False, tree=False, no_lds=False, profile=False, wavefront=False,
+                      soft_shadow=False, fuzzy_reflection=False, seed=0, tile=False, packet=False, private_walk=False, skybox=False,
+                      schlick=False):
+        """n frames of one configuration in one p3d_render_frames call, frame f seen through cams[f] with seed + f.
+        samples (spp > 0): (n, res_y, res_x, spp*spp, 4), one sample array per frame.  Returns rgb8 (n, rows, W, 3),
+        rgb32f (n, rows, W, 3) and hit_id (n, rows, W); rows = res_y for world == 1, local_rows otherwise."""
+        arr, n = _camera_array(cams)
+        c0 = arr[0]
+        rows = c0.res_y if world == 1 else local_rows(c0.res_y, row_block, world)
+        rgb8 = np.zeros((n, rows, c0.res_x, 3), np.uint8)
+        f32 = np.zeros((n, rows, c0.res_x, 3), np.float32) if want_f32 else None
+        hid = np.full((n, rows, c0.res_x), -2, np.int32) if want_hit else None
+        if samples is not None:
+            samples = np.ascontiguousarray(samples, np.float32)
+        p = self._params(max_depth, accel, spp, samples, rank, world, row_block, counters, tree, no_lds, profile, wavefront, soft_shadow, fuzzy_reflection, seed, tile, 0, packet, private_walk, skybox, schlick)
+        o = Outputs(rgb8.ctypes.data if rgb8.size else None, f32.ctypes.data if want_f32 and f32.size else None,
+                    hid.ctypes.data if want_hit and hid.size else None, 0)
+        _check(lib().p3d_render_frames(self.h, arr, n, C.byref(p), C.byref(o)), "p3d_render_frames")
+        out = {"rgb8": rgb8, "rgb32f": f32, "hit_id": hid}
+        if counters:
+            out["counters"] = self.counters()
+        return out
+
+    def render_frames_device(self, cams, rgb8_ptr=0, rgb32f_ptr=0, hit_ptr=0, max_depth=4, accel=ACCEL_BVH, spp=0,
+                             samples=None, rank=0, world=1, row_block=16, counters=False, tree=False, no_lds=False, profile=False,
+                             wavefront=False, soft_shadow=False, fuzzy_reflection=False, seed=0, tile=False, samples_ptr=0, packet=False,
+                             private_walk=False, skybox=False, schlick=False):
+        """Enqueue a batch into caller-owned DEVICE buffers holding n frames back to back (raw pointers); asynchronous."""
+        arr, n = _camera_array(cams)
+        p = self._params(max_depth, accel, spp, samples, rank, world, row_block, counters, tree, no_lds, profile, wavefront, soft_shadow, fuzzy_reflection, seed, tile, samples_ptr, packet, private_walk, skybox, schlick)
+        o = Outputs(rgb8_ptr or None, rgb32f_ptr or None, hit_ptr or None, 1)
+        _check(lib().p3d_render_frames(self.h, arr, n, C.byref(p), C.byref(o)), "p3d_render_frames")
+
     def deinterleave_frames(self, gathered_ptr, frames_ptr, res_x, res_y, row_block, world, bpp, n_frames,
                             rank_stride_bytes=0, tile_stride_bytes=0, frame_stride_bytes=0):
         L = lib()
@@ -435,6 +487,12 @@ class DeviceScene:
     def deinterleave(self, gathered_ptr, frame_ptr, res_x, res_y, row_block, world, bpp, rank_stride_bytes=0):
         _check(lib().p3d_deinterleave(self.h, C.c_void_p(gathered_ptr), C.c_void_p(frame_ptr), res_x, res_y,
                                       row_block, world, bpp, int(rank_stride_bytes)), "p3d_deinterleave")
+
+
+def _camera_array(cams):
+    """A sequence of Camera structs -> (ctypes Camera array, n).  n == 0 is passed on: the library refuses it."""
+    cams = list(cams)
+    return (Camera * max(len(cams), 1))(*cams), len(cams)
 
 
 def tune_schedule(handles, cam, rgb8_ptrs, frames=3, **kw):

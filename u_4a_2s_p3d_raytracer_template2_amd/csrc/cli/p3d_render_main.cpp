@@ -3,6 +3,8 @@
 //   p3d_render <scene.p3f> [--res W H] [--accel 0|1|2] [--depth D] [--spp N] [--seed S]
 //              [--device K | --gpus N] [--out image.png|image.ppm] [--counters] [--soft-shadow] [--fuzzy-reflection]
 // --gpus N: devices 0..N-1 each render every N-th block of 16 rows, one RCCL gather to device 0.
+// --orbit N STEP_DEG: N frames of the reference's mouse orbit (alpha advancing by STEP_DEG per frame, RT/main.cpp:339-341,
+// 419-421) in ONE p3d_render_frames call; --out then takes a %d pattern (e.g. frame_%03d.png) for the frame number.
 // Defaults are the reference's: resolution / accel / spp from the file, MAX_DEPTH 4.
 #include <chrono>
 #include <cstdio>
@@ -27,11 +29,12 @@ static int save_ppm(const char* path, const std::vector<uint8_t>& img, int w, in
 int main(int argc, char** argv) {
     if (argc < 2) {
         fprintf(stderr, "usage: %s scene.p3f [--res W H] [--accel A] [--depth D] [--spp N] [--seed S] "
-                        "[--device K | --gpus N] [--out file.ppm] [--counters] [--soft-shadow] [--fuzzy-reflection] [--schlick]\n", argv[0]);
+                        "[--device K | --gpus N] [--out file.ppm] [--orbit N STEP_DEG] [--counters] [--soft-shadow] [--fuzzy-reflection] [--schlick]\n", argv[0]);
         return 2;
     }
     RenderOptions opt;
-    int rw = 0, rh = 0;
+    int rw = 0, rh = 0, orbit_n = 0;
+    float orbit_step = 0.0f;
     std::string out = "RT_Output.png";                       // the reference's file name, RT/main.cpp:968
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i];
@@ -44,6 +47,7 @@ int main(int argc, char** argv) {
         else if (a == "--device") { need(1); opt.device = atoi(argv[++i]); }
         else if (a == "--gpus") { need(1); opt.gpus = atoi(argv[++i]); }
         else if (a == "--out") { need(1); out = argv[++i]; }
+        else if (a == "--orbit") { need(2); orbit_n = atoi(argv[++i]); orbit_step = (float)atof(argv[++i]); if (orbit_n < 1) { fprintf(stderr, "--orbit needs N >= 1\n"); return 2; } }
         else if (a == "--counters") opt.counters = true;
         else if (a == "--soft-shadow") opt.SOFT_SHADOW = true;
         else if (a == "--fuzzy-reflection") opt.FUZZY_REFLECTION = true;
@@ -55,6 +59,35 @@ int main(int argc, char** argv) {
     if (rw > 0 && rh > 0) scene.GetCamera()->SetResolution(rw, rh);
     printf("Scene loaded: %d objects, %d lights, %dx%d\n", scene.getNumObjects(), scene.getNumLights(),
            scene.GetCamera()->GetResX(), scene.GetCamera()->GetResY());
+    const int W = scene.GetCamera()->GetResX(), H = scene.GetCamera()->GetResY();
+    auto save = [&](const std::string& path, const uint8_t* img) {
+        const bool ppm = path.size() > 4 && path.compare(path.size() - 4, 4, ".ppm") == 0;
+        if (ppm) { std::vector<uint8_t> v(img, img + (size_t)W * H * 3); return save_ppm(path.c_str(), v, W, H); }
+        return save_png(path.c_str(), img, W, H);
+    };
+    if (orbit_n > 0) {
+        {   // exactly one conversion, %d or %0Nd: the pattern is handed to snprintf
+            const size_t pc = out.find('%');
+            size_t e = pc == std::string::npos ? pc : out.find_first_not_of("0123456789", pc + 1);
+            if (pc == std::string::npos || e == std::string::npos || out[e] != 'd' || out.find('%', pc + 1) != std::string::npos) {
+                fprintf(stderr, "--orbit needs an --out pattern with one %%d (e.g. frame_%%03d.png)\n");
+                return 2;
+            }
+        }
+        const std::vector<Vector> eyes = orbit_eyes(scene.GetCamera()->GetEye(), orbit_n, orbit_step, 0.0f);
+        RenderResult res;
+        std::string err;
+        int rc = renderFrames(scene, opt, eyes, false, false, res, &err);
+        if (rc) { fprintf(stderr, "render failed (%d): %s\n", rc, err.c_str()); return 1; }
+        printf("Done: %d frames, %.4f ms per frame on the device stream\n", orbit_n, res.kernel_ms / orbit_n);
+        for (int f = 0; f < orbit_n; f++) {
+            char path[4096];
+            snprintf(path, sizeof path, out.c_str(), f);
+            if (save(path, res.img_Data.data() + (size_t)f * W * H * 3)) { fprintf(stderr, "Error saving Image file\n"); return 1; }
+            printf("Image file created: %s\n", path);
+        }
+        return 0;
+    }
     RenderResult res;
     std::string err;
     auto t0 = std::chrono::high_resolution_clock::now();
@@ -70,9 +103,7 @@ int main(int argc, char** argv) {
                (unsigned long long)res.counters.box_tests, (unsigned long long)res.counters.sphere_tests,
                (unsigned long long)res.counters.tri_tests);
     }
-    const int W = scene.GetCamera()->GetResX(), H = scene.GetCamera()->GetResY();
-    const bool ppm = out.size() > 4 && out.compare(out.size() - 4, 4, ".ppm") == 0;
-    if (ppm ? save_ppm(out.c_str(), res.img_Data, W, H) : save_png(out.c_str(), res.img_Data.data(), W, H)) {
+    if (save(out, res.img_Data.data())) {
         fprintf(stderr, "Error saving Image file\n");
         return 1;
     }

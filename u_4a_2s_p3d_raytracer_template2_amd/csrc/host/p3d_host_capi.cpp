@@ -47,6 +47,17 @@ void p3dh_primary_ray(const p3dh_scene* h, float px, float py, float* o3, float*
     o3[0] = r.origin.x; o3[1] = r.origin.y; o3[2] = r.origin.z;
     d3[0] = r.direction.x; d3[1] = r.direction.y; d3[2] = r.direction.z;
 }
+// Camera::SetEye on a COPY of the scene's camera per eye of the reference's orbit (orbit_eyes): n cameras, the scene's own
+// camera unchanged.  eyes3 (optional): the n eyes.
+void p3dh_orbit_eyes(float ex, float ey, float ez, int32_t n, float step_deg, float d_beta_deg, float* eyes3) {
+    std::vector<Vector> e = orbit_eyes(Vector(ex, ey, ez), n, step_deg, d_beta_deg);
+    for (int i = 0; i < n; i++) { eyes3[3 * i] = e[i].x; eyes3[3 * i + 1] = e[i].y; eyes3[3 * i + 2] = e[i].z; }
+}
+void p3dh_scene_orbit_cameras(const p3dh_scene* h, int32_t n, float step_deg, float d_beta_deg, p3d_camera* out) {
+    Camera cam = *h->scene.GetCamera();
+    std::vector<Vector> e = orbit_eyes(cam.GetEye(), n, step_deg, d_beta_deg);
+    for (int i = 0; i < n; i++) { cam.SetEye(e[i]); cam.describe(&out[i]); }
+}
 void p3dh_generate_samples(uint32_t seed, int32_t res_x, int32_t res_y, int32_t spp, float aperture, float* out) {
     generate_samples(seed, res_x, res_y, spp, aperture, out);
 }

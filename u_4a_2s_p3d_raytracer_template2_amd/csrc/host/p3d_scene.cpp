@@ -508,4 +508,74 @@ int renderScene(const Scene& scene, const RenderOptions& opt, bool want_colors, 
     return P3D_OK;
 }
 
+std::vector<Vector> orbit_eyes(Vector eye, int n, float step_deg, float d_beta_deg) {
+    const float r = eye.length();
+    const float beta = asinf(eye.y / r) * 180.0f / 3.14f;          // RT/main.cpp:340-341
+    const float alpha = atanf(eye.x / eye.z) * 180.0f / 3.14f;
+    std::vector<Vector> out;
+    for (int k = 0; k < n; k++) {
+        const float a = alpha + (float)k * step_deg;
+        float b = beta + d_beta_deg;
+        if (b > 85.0f) b = 85.0f; else if (b < -85.0f) b = -85.0f;  // RT/main.cpp:403-406
+        const float x = r * std::sin(a * 3.14f / 180.0f) * std::cos(b * 3.14f / 180.0f);   // RT/main.cpp:419-421
+        const float z = r * std::cos(a * 3.14f / 180.0f) * std::cos(b * 3.14f / 180.0f);
+        const float y = r * std::sin(b * 3.14f / 180.0f);
+        out.push_back(Vector(x, y, z));
+    }
+    return out;
+}
+
+int renderFrames(const Scene& scene, const RenderOptions& opt, const std::vector<Vector>& eyes, bool want_colors, bool want_hit,
+                 RenderResult& out, std::string* err) {
+    auto bad = [&](int rc) { if (err) *err = p3d_last_error(); return rc; };
+    if (!scene.GetCamera()) { if (err) *err = "scene has no camera"; return P3D_ERR_ARG; }
+    if (opt.gpus != 1) { if (err) *err = "renderFrames renders on one device (gpus must be 1)"; return P3D_ERR_ARG; }
+    if (eyes.empty()) { if (err) *err = "no eyes"; return P3D_ERR_ARG; }
+    const int n = (int)eyes.size();
+    std::vector<p3d_camera> cams((size_t)n);
+    Camera cam = *scene.GetCamera();
+    for (int f = 0; f < n; f++) { cam.SetEye(eyes[f]); cam.describe(&cams[f]); }
+    Scene::Flat flat;
+    scene.flatten(flat);
+    p3d_render_params prm;
+    memset(&prm, 0, sizeof prm);
+    prm.max_depth = opt.max_depth;
+    prm.accel = opt.accel < 0 ? (int)scene.GetAccelStruct() : opt.accel;
+    prm.spp = opt.spp < 0 ? (int)scene.GetSamplesPerPixel() : opt.spp;
+    prm.world = 1; prm.rank = 0; prm.row_block = 16;
+    prm.flags = opt.counters ? P3D_FLAG_COUNTERS : 0;
+    prm.features = (opt.SOFT_SHADOW ? P3D_FEATURE_SOFT_SHADOW : 0u) | (opt.FUZZY_REFLECTION ? P3D_FEATURE_FUZZY_REFLECTION : 0u) |
+                   (opt.SCHLICK_APPROX ? P3D_FEATURE_SCHLICK : 0u);
+    if (opt.SKYBOX) {
+        if (!scene.HasSkybox()) { if (err) *err = "RenderOptions::SKYBOX without Scene::SetSkybox()"; return P3D_ERR_STATE; }
+        prm.features |= P3D_FEATURE_SKYBOX;
+    }
+    prm.seed = opt.seed;
+    const size_t npx = (size_t)cams[0].res_x * cams[0].res_y;
+    std::vector<float> samples;
+    if (prm.spp > 0) {                 // the reference draws new rand() samples per frame: frame f from seed + f
+        const size_t per = npx * prm.spp * prm.spp * 4;
+        samples.resize(per * n);
+        for (int f = 0; f < n; f++) generate_samples(opt.seed + (unsigned)f, cams[0].res_x, cams[0].res_y, prm.spp, cams[f].aperture, samples.data() + per * f);
+        prm.samples = samples.data();
+    }
+    p3d_scene* dev = nullptr;
+    int rc = p3d_scene_create(&flat.desc, nullptr, opt.device, &dev);
+    if (rc) return bad(rc);
+    if (opt.SKYBOX && (rc = upload_skybox(scene, dev)) != 0) { p3d_scene_destroy(dev); return bad(rc); }
+    out.img_Data.assign(npx * 3 * n, 0);
+    if (want_colors) out.colors.assign(npx * 3 * n, 0.0f);
+    if (want_hit) out.hit_id.assign(npx * n, -1);
+    p3d_outputs o;
+    o.rgb8 = out.img_Data.data(); o.rgb32f = want_colors ? out.colors.data() : nullptr;
+    o.hit_id = want_hit ? out.hit_id.data() : nullptr; o.memory = 0;
+    rc = p3d_timer_begin(dev);
+    if (!rc) rc = p3d_render_frames(dev, cams.data(), n, &prm, &o);
+    if (!rc) rc = p3d_timer_end(dev, &out.kernel_ms);
+    if (!rc && opt.counters) rc = p3d_get_counters(dev, &out.counters);
+    if (rc) { bad(rc); p3d_scene_destroy(dev); return rc; }
+    p3d_scene_destroy(dev);
+    return P3D_OK;
+}
+
 }  // namespace p3d_host

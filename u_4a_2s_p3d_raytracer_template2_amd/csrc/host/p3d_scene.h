@@ -246,5 +246,15 @@ int save_png(const char* path, const uint8_t* img_Data, int width, int height);
 int renderScene(const Scene& scene, const RenderOptions& opt, bool want_colors, bool want_hit, RenderResult& out,
                 std::string* err);
 
+// The reference's mouse orbit (RT/main.cpp:339-341 spherical coordinates of the eye, :419-421 back to Cartesian, with its
+// 3.14f and float sin / cos): n eyes, alpha advancing by step_deg per frame, beta offset by d_beta_deg (clamped to +-85 like
+// the mouse motion), r = |eye|.
+std::vector<Vector> orbit_eyes(Vector eye, int n, float step_deg, float d_beta_deg);
+// The render-again loop with the eyes known ahead: Camera::SetEye(eyes[f]) per frame (RT/main.cpp:740 semantics, the
+// basis is not renormalised; the scene's own camera is left as it was) and ONE p3d_render_frames call.  out holds the n
+// frames back to back (img_Data: n * res_x * res_y * 3); frame f keyed with opt.seed + f.  One device (opt.gpus must be 1).
+int renderFrames(const Scene& scene, const RenderOptions& opt, const std::vector<Vector>& eyes, bool want_colors, bool want_hit,
+                 RenderResult& out, std::string* err);
+
 }  // namespace p3d_host
 #endif

@@ -89,6 +89,15 @@ P3D_HD inline bool feat_schlick(uint32_t f) { return (f & kFeatSchlick) != 0u; }
 constexpr uint32_t kShareDwords = 384;      // per-wave LDS of the work-sharing walk (p3d_traverse.h), behind the wave's stack slots
 
 // Everything a render launch needs, passed by value (lands in SGPRs / kernarg segment).
+// One frame's camera in a batch: the camera fields of LaunchParams under the same names (RT/camera.h), and the products
+// the host forms for Camera::PrimaryRay (uw = u*w, vh = v*h, vz = n*(-plane_dist)).  128 bytes.
+struct FrameCam {
+    float eye[3], u[3], v[3], n[3];
+    float w, h, plane_dist, aperture, focal_ratio;
+    float uw[3], vh[3], vz[3];
+    float pad[6];
+};
+
 struct LaunchParams {
     // scene: one blob of 16-byte quads holding every per-lane-indexed array (nodes, leaf records,
     // spheres, sphere meta, triangles, boxes, materials; section offsets in quads), so that a
@@ -176,6 +185,12 @@ struct LaunchParams {
     // the k-th tile a workgroup draws is tile_order[k] (nullptr: k); tile_cost[tile] = how long the tile took, in 10 ns
     // ticks, for the next ordering (bvh_device.hip: sort_tiles_by_cost).  Scenes read from HBM only.
     const uint32_t* tile_order; uint32_t* tile_cost;
+    // ---- frame batches (p3d_render_frames): n_frames frames of frame_rows compact rows each, stacked into one tall image
+    // of local_rows = n_frames * frame_rows rows.  Frame f is seen through frame_cams[f], keys its random streams with
+    // seed + f, reads sample array f and writes its pixels out_rows rows apart (res_y when world == 1, else frame_rows).
+    // n_frames <= 1: one frame, whose camera is the fields above (frame_cams unused).
+    int32_t n_frames, frame_rows, out_rows;
+    const FrameCam* frame_cams;
 };
 
 // Every level of a pass for the fused resolve launch (small frames / shards, wf_resolve_fused_kernel): level l's

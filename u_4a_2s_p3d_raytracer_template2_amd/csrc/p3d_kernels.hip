@@ -22,6 +22,7 @@
 #include <stdint.h>
 
 #include <algorithm>
+#include <cstring>
 
 #include "p3d_device_types.h"
 #include "p3d_shade.h"
@@ -77,12 +78,14 @@ __device__ __forceinline__ int image_row(const LaunchParams& P, int row) {
 
 // "color += rayTracing(...).clamp()" over the samples in order, then "color / (4 * 4)"
 // (RT/main.cpp:797-800), for the rows [row0, row0 + rows) of the compact buffer
+template <bool BATCH>
 __global__ __launch_bounds__(256) void sum_samples_kernel(const LaunchParams P, size_t first_px, size_t n_px) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_px; i += (size_t)gridDim.x * blockDim.x) {
         const size_t p = first_px + i;
         // rows past the image (the compact buffer is padded to whole row blocks) are never written:
         // a caller's device plane only holds res_y rows when world == 1 (include/p3d_hip.h)
-        const int row = (int)(p / (size_t)P.res_x);
+        int row = (int)(p / (size_t)P.res_x);
+        if (BATCH) row %= P.out_rows;                    // (a batch: p counts out_rows rows per frame)
         if (image_row(P, row) >= P.res_y) continue;
         V3 acc = mk(0.0f, 0.0f, 0.0f);
         for (int smp = 0; smp < P.wf_nsamples; smp++) {
@@ -93,11 +96,26 @@ __global__ __launch_bounds__(256) void sum_samples_kernel(const LaunchParams P, 
     }
 }
 
-// tile -> pixel.  Returns false for lanes outside the image.
-template <bool ORDERED = false>
-__device__ __forceinline__ bool tile_pixel(const LaunchParams& P, int& x, int& y, int& row, int* tile_out = nullptr) {
+// Frame batches (LaunchParams::n_frames) are compiled into their own kernel instantiations (BATCH = true); BATCH = false
+// is the one-frame code unchanged.
+// Frame of a batch that the tile row starting at stacked compact row `row0` belongs to (0 for one frame).  row0 is
+// wave-uniform: the division runs once per wave, on the scalar unit.
+template <bool BATCH>
+__device__ __forceinline__ int batch_frame(const LaunchParams& P, int row0) {
+    return BATCH ? __builtin_amdgcn_readfirstlane(row0 / P.frame_rows) : 0;
+}
+// stacked compact row of frame f -> row of the caller's planes (frame f starts out_rows rows in)
+template <bool BATCH>
+__device__ __forceinline__ int out_row(const LaunchParams& P, int f, int row) {
+    return BATCH ? row + f * (P.out_rows - P.frame_rows) : row;
+}
+
+// tile -> pixel.  Returns false for lanes outside the image.  row = the stacked compact row; f = the batch frame;
+// y = the image row inside frame f.
+template <bool ORDERED = false, bool BATCH = false>
+__device__ __forceinline__ bool tile_pixel(const LaunchParams& P, int& x, int& y, int& row, int& f, int* tile_out = nullptr) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    x = 0; y = 0; row = 0;
+    x = 0; y = 0; row = 0; f = 0;
     int tx, ty, tile;
     if (!ORDERED && gridDim.y > 1) {
         // 2-D launch (identity tile map, xcd_chunk == 1): blockIdx.x / .y ARE the tile's column and row -- no division by
@@ -123,16 +141,26 @@ __device__ __forceinline__ bool tile_pixel(const LaunchParams& P, int& x, int& y
         tx = tile % P.tiles_x; ty = P.wf_tile_row0 + tile / P.tiles_x;
     }
     x = tx * 16 + (lane & 15);
-    row = ty * (P.wg_waves * 4) + (lane >> 4) + wave * 4;         // row in the compact local buffer
-    y = image_row(P, row);
+    const int row0 = ty * (P.wg_waves * 4);
+    row = row0 + (lane >> 4) + wave * 4;                          // row in the compact local buffer
+    f = batch_frame<BATCH>(P, row0);
+    y = image_row(P, BATCH ? row - f * P.frame_rows : row);
     return x < P.res_x && y < P.res_y;
 }
 
-__device__ __forceinline__ Ray camera_ray(const LaunchParams& P, int x, int y, int sample) {
-    if (P.spp == 0) return primary_ray_tab(P, x, y);                                  // RT/main.cpp:756-772
+// camera ray of pixel (x, y) of batch frame f: frame f's camera and sample array (wave-uniform branch and loads)
+template <bool BATCH = false>
+__device__ __forceinline__ Ray camera_ray(const LaunchParams& P, int x, int y, int sample, int f) {
     const int ns = P.spp * P.spp;                                                     // RT/main.cpp:776-795
+    if (BATCH) {
+        const FrameCam& C = P.frame_cams[f];
+        if (P.spp == 0) return primary_ray_tab(P, C, x, y);
+        const float4 sm = reinterpret_cast<const float4*>(P.samples)[(((size_t)f * P.res_y + y) * P.res_x + x) * ns + sample];
+        return primary_ray_lens(P, C, sm.z, sm.w, sm.x, sm.y);
+    }
+    if (P.spp == 0) return primary_ray_tab(P, P, x, y);                               // RT/main.cpp:756-772
     const float4 sm = reinterpret_cast<const float4*>(P.samples)[((size_t)y * P.res_x + x) * ns + sample];
-    return primary_ray_lens(P, sm.z, sm.w, sm.x, sm.y);
+    return primary_ray_lens(P, P, sm.z, sm.w, sm.x, sm.y);
 }
 
 // ------------------------------------------------------------------ WAVEFRONT schedule
@@ -349,7 +377,7 @@ __device__ __forceinline__ void stamp_wave(const LaunchParams& P, uint32_t wave_
 // (Measured and dropped in round 3, profiles/r03_exp03_sharing_wg_levers.txt / r03_exp04_tiles_lpt_bound.txt: 8- and 16-wave
 //  workgroups -- level 1 of config 2 46 -> 51 -> 54 us -- and 2-4 tiles per workgroup one after the other: the waves of
 //  this launch start at ~830 per microsecond whatever the workgroup shape, and the loop's registers cost occupancy.)
-template <bool COUNT, bool LDS, int WALK, int OCC, bool STOCH = false, bool SCHLICK = false>
+template <bool COUNT, bool LDS, int WALK, int OCC, bool STOCH = false, bool SCHLICK = false, bool BATCH = false>
 __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void wf_primary_kernel(const LaunchParams P) {
     const uint32_t par = P.wf_ctrl[0] & 1u;                     // this pass's counter set (LaunchParams::wf_alt)
     if (blockIdx.x == 0 && blockIdx.y == 0) {
@@ -359,24 +387,24 @@ __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void wf_primary_kernel
         for (uint32_t i = threadIdx.x; i < 2u * kWfShards; i += blockDim.x) other[i] = 0u;
     }
     const typename View<LDS>::type sv = View<LDS>::make_shading(P);
-    int x, y, row, tile;
-    const bool valid = tile_pixel<!LDS>(P, x, y, row, &tile);
+    int x, y, row, f, tile;
+    const bool valid = tile_pixel<!LDS, BATCH>(P, x, y, row, f, &tile);
     if (__ballot(valid) == 0) return;
     const Shard sh = shard_of(P, (uint32_t)tile % kWfShards, par);
     const TravCtx tc = wave_stack<LDS>(P, 0);
     Ctr ctr = {0, 0, 0, 0, 0, 0, 0};
-    const size_t p = (size_t)row * P.res_x + x;
+    const size_t p = (size_t)out_row<BATCH>(P, f, row) * P.res_x + x;
     const unsigned long long t_tile = (!LDS && P.tile_cost) ? __builtin_amdgcn_s_memrealtime() : 0ull;
     stamp(P, tile, 0);
     Ray ray; ray.o = mk(0.0f, 0.0f, 0.0f); ray.d = mk(1.0f, 0.0f, 0.0f);
-    if (valid) ray = camera_ray(P, x, y, P.wf_sample);
+    if (valid) ray = camera_ray<BATCH>(P, x, y, P.wf_sample, f);
     stamp(P, tile, 1);
     const Hit h = find_closest<COUNT, WALK>(P, sv, ray, valid, tc, ctr);
     stamp(P, tile, 2);
     if (valid && P.hit_id && P.wf_sample == 0) P.hit_id[p] = (h.ref == 0xFFFFFFFFu) ? -1 : (int32_t)h.sid;
     // the random stream of a pixel sample is keyed by the pixel's place in the FULL frame, so a frame
-    // sharded over several GPUs draws the same numbers as on one
-    const uint32_t rng = STOCH ? rng_mix(rng_mix(P.seed, (uint32_t)(y * P.res_x + x)), (uint32_t)P.wf_sample) : 0u;
+    // sharded over several GPUs draws the same numbers as on one (frame f of a batch: seed + f)
+    const uint32_t rng = STOCH ? rng_mix(rng_mix(BATCH ? P.seed + (uint32_t)f : P.seed, (uint32_t)(y * P.res_x + x)), (uint32_t)P.wf_sample) : 0u;
     const NodeOut o = shade_hit<COUNT, WALK, typename View<LDS>::type, STOCH, SCHLICK>(P, sv, ray, h, valid, 1, 1.0f, tc, ctr, rng);
     stamp(P, tile, 3);
     emit(P, sh, 1, valid, (uint32_t)p, 1.0f, o);
@@ -586,20 +614,23 @@ struct TileCtx {
     }
     RayRec* rays; NodeRec* nodes; uint32_t* keys;     // this workgroup's slot
     int tx, ty;                           // tile coordinates
+    int oy;                               // batches only: row of the caller's planes that the tile's top row goes to
     __device__ __forceinline__ TileLds* lds() const { return reinterpret_cast<TileLds*>(p3d_lds + lds_off); }
 };
 
 // compact pixel index of tile-local pixel `link` (= the thread id that traced it)
+template <bool BATCH>
 __device__ __forceinline__ size_t tile_pixel_index(const LaunchParams& P, const TileCtx& X, uint32_t link) {
     const int x = X.tx * 16 + (int)(link & 15u);
-    const int row = X.ty * 16 + (int)(link >> 6) * 4 + (int)((link >> 4) & 3u);
+    const int row = (BATCH ? X.oy : X.ty * 16) + (int)(link >> 6) * 4 + (int)((link >> 4) & 3u);
     return (size_t)row * P.res_x + x;
 }
 
+template <bool BATCH>
 __device__ __forceinline__ void tile_deliver(const LaunchParams& P, const TileCtx& X, int level, uint32_t link, V3 ret) {
     if (level == 1) {                                            // "rayTracing(...).clamp()" of a pixel sample
         const V3 c = clampc(ret);
-        if (P.spp == 0) { write_pixel(P, tile_pixel_index(P, X, link), c); return; }
+        if (P.spp == 0) { write_pixel(P, tile_pixel_index<BATCH>(P, X, link), c); return; }
         float* a = X.lds()->acc + 3 * link;                      // color += ... in sample order (RT/main.cpp:797)
         a[0] = a[0] + c.x; a[1] = a[1] + c.y; a[2] = a[2] + c.z;
         return;
@@ -610,10 +641,11 @@ __device__ __forceinline__ void tile_deliver(const LaunchParams& P, const TileCt
 }
 
 // like emit(): must be reached by all lanes of the wave together
+template <bool BATCH>
 __device__ __forceinline__ void tile_emit(const LaunchParams& P, const TileCtx& X, int level, bool valid, uint32_t link,
                                           float ior_1, const NodeOut& o) {
     const int lane = threadIdx.x & 63;
-    if (valid && o.terminal) tile_deliver(P, X, level, link, o.ret);
+    if (valid && o.terminal) tile_deliver<BATCH>(P, X, level, link, o.ret);
     const bool parks = valid && !o.terminal;
     const uint64_t m_node = __ballot(parks);
     if (m_node == 0) return;                                   // wave-uniform
@@ -651,7 +683,7 @@ __device__ __forceinline__ void tile_emit(const LaunchParams& P, const TileCtx& 
     }
 }
 
-template <bool COUNT, bool LDS, int WALK, int OCC, bool STOCH = false, bool SCHLICK = false>
+template <bool COUNT, bool LDS, int WALK, int OCC, bool STOCH = false, bool SCHLICK = false, bool BATCH = false>
 __global__ __launch_bounds__(256) P3D_OCC(OCC) void wf_tile_kernel(const LaunchParams P) {
     const typename View<LDS>::type sv = View<LDS>::make_shading(P);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -689,11 +721,13 @@ __global__ __launch_bounds__(256) P3D_OCC(OCC) void wf_tile_kernel(const LaunchP
         }
         prev_tile = tile;
         X.tx = tile % P.tiles_x; X.ty = tile / P.tiles_x;
+        const int f = batch_frame<BATCH>(P, X.ty * 16);          // (batches: the frame, and its rows in the planes)
+        if (BATCH) X.oy = out_row<BATCH>(P, f, X.ty * 16);
         const int x = X.tx * 16 + (lane & 15);
         const int row = X.ty * 16 + wave * 4 + (lane >> 4);      // row in the compact local buffer
-        const int y = image_row(P, row);
+        const int y = image_row(P, BATCH ? row - f * P.frame_rows : row);
         const bool inside = x < P.res_x && y < P.res_y;
-        const size_t p = (size_t)row * P.res_x + x;
+        const size_t p = (size_t)(BATCH ? X.oy + wave * 4 + (lane >> 4) : row) * P.res_x + x;
         if (P.spp > 0) { T->acc[3 * tid] = 0.0f; T->acc[3 * tid + 1] = 0.0f; T->acc[3 * tid + 2] = 0.0f; }
         for (int smp = 0; smp < ns; smp++) {
             if (tid < 2 * kMaxTileLevels) T->n_rays[tid] = 0u;   // n_rays and n_nodes are contiguous
@@ -717,8 +751,8 @@ __global__ __launch_bounds__(256) P3D_OCC(OCC) void wf_tile_kernel(const LaunchP
                     Ray ray; ray.o = mk(0.0f, 0.0f, 0.0f); ray.d = mk(1.0f, 0.0f, 0.0f);
                     if (l == 1) {
                         valid = inside;
-                        if (inside) ray = camera_ray(P, x, y, smp);
-                        if (STOCH) rng = rng_mix(rng_mix(P.seed, (uint32_t)(y * P.res_x + x)), (uint32_t)smp);
+                        if (inside) ray = camera_ray<BATCH>(P, x, y, smp, f);
+                        if (STOCH) rng = rng_mix(rng_mix(BATCH ? P.seed + (uint32_t)f : P.seed, (uint32_t)(y * P.res_x + x)), (uint32_t)smp);
                     } else {
                         valid = in_batch && i < n;
                         if (valid) {
@@ -733,7 +767,7 @@ __global__ __launch_bounds__(256) P3D_OCC(OCC) void wf_tile_kernel(const LaunchP
                     if (l == 1 && smp == 0 && inside && P.hit_id) P.hit_id[p] = (h.ref == 0xFFFFFFFFu) ? -1 : (int32_t)h.sid;
                     const NodeOut o = shade_hit<COUNT, WALK, typename View<LDS>::type, STOCH, SCHLICK>(P, sv, ray, h, valid, l, ior_1, tc,
                                                                                               ctr, rng, smp);
-                    tile_emit(P, X, l, valid, link, ior_1, o);
+                    tile_emit<BATCH>(P, X, l, valid, link, ior_1, o);
                 }
                 __syncthreads();
             }
@@ -744,7 +778,7 @@ __global__ __launch_bounds__(256) P3D_OCC(OCC) void wf_tile_kernel(const LaunchP
                     const float4 a = nd[0], b = nd[1], c = nd[2];
                     const Mtl M = load_material(sv, __float_as_uint(b.w));
                     const V3 ret = combine_node(mk(a.x, a.y, a.z), a.w, M.spec, mk(b.x, b.y, b.z), mk(c.x, c.y, c.z));
-                    tile_deliver(P, X, l, __float_as_uint(c.w), ret);
+                    tile_deliver<BATCH>(P, X, l, __float_as_uint(c.w), ret);
                 }
                 __syncthreads();
             }
@@ -855,8 +889,8 @@ __device__ __forceinline__ V3 trace_tree(const LaunchParams& P, const SV& sv, Ra
 // The same trees with the wave's lanes in ONE loop (work-sharing walk, WALK_SHARED): every iteration all 64 lanes reach
 // find_closest() / shade_hit() together -- a lane whose pixel is finished (or outside the image) comes along as a helper
 // of the others' walks -- and a lane that finishes a sample's tree starts its next sample at once.
-template <bool COUNT, class SV, class FR, bool SCHLICK = false>
-__device__ __forceinline__ void trace_trees_shared(const LaunchParams& P, const SV& sv, int x, int y, bool valid, const TravCtx& tc, FR fr,
+template <bool COUNT, class SV, class FR, bool SCHLICK = false, bool BATCH = false>
+__device__ __forceinline__ void trace_trees_shared(const LaunchParams& P, const SV& sv, int x, int y, int f, bool valid, const TravCtx& tc, FR fr,
                                                    V3& color, int32_t& hid, Ctr& ctr) {
     const int ns = P.spp > 0 ? P.spp * P.spp : 1;
     const V3 zero = mk(0.0f, 0.0f, 0.0f);
@@ -865,7 +899,7 @@ __device__ __forceinline__ void trace_trees_shared(const LaunchParams& P, const 
     bool alive = valid, first = true;
     V3 acc = zero;
     Ray ray; ray.o = zero; ray.d = mk(1.0f, 0.0f, 0.0f);
-    if (alive) ray = camera_ray(P, x, y, 0);
+    if (alive) ray = camera_ray<BATCH>(P, x, y, 0, f);
     while (__ballot(alive) != 0) {
         const Hit h = find_closest<COUNT, WALK_SHARED>(P, sv, ray, alive, tc, ctr);
         if (alive && first) { if (smp == 0) hid = (h.ref == 0xFFFFFFFFu) ? -1 : (int32_t)h.sid; first = false; }
@@ -920,18 +954,18 @@ __device__ __forceinline__ void trace_trees_shared(const LaunchParams& P, const 
         if (P.spp == 0) { color = c; alive = false; continue; }
         acc = add(acc, c);                                       // RT/main.cpp:797, in sample order
         smp++;
-        if (smp < ns) { ray = camera_ray(P, x, y, smp); fsp = 0; ior_1 = 1.0f; }
+        if (smp < ns) { ray = camera_ray<BATCH>(P, x, y, smp, f); fsp = 0; ior_1 = 1.0f; }
         else { color = mk(fdiv(acc.x, 16.0f), fdiv(acc.y, 16.0f), fdiv(acc.z, 16.0f)); alive = false; }
     }
 }
 
 // PRIV = dwords of private memory for the frames (12 per level below the first), 0 = frames in LDS
-template <bool COUNT, bool LDS, int OCC, bool GRID = false, int PRIV = 0, bool SHARED = false, bool SCHLICK = false>
+template <bool COUNT, bool LDS, int OCC, bool GRID = false, int PRIV = 0, bool SHARED = false, bool SCHLICK = false, bool BATCH = false>
 __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void whitted_tree_kernel(const LaunchParams P) {
     const typename View<LDS>::type sv = View<LDS>::make_shading(P);
     const int lane = threadIdx.x & 63;
-    int x, y, row, tile;
-    const bool in_image = tile_pixel<!LDS>(P, x, y, row, &tile);
+    int x, y, row, f, tile;
+    const bool in_image = tile_pixel<!LDS, BATCH>(P, x, y, row, f, &tile);
     if (SHARED ? __ballot(in_image) == 0 : !in_image) return;   // no barriers below: early exit is safe
     const unsigned long long t_tile = (!LDS && P.tile_cost) ? __builtin_amdgcn_s_memrealtime() : 0ull;
     stamp(P, tile, 0);
@@ -946,9 +980,9 @@ __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void whitted_tree_kern
     V3 color = mk(0.0f, 0.0f, 0.0f);
     int32_t hid = -1;
     if constexpr (SHARED) {
-        trace_trees_shared<COUNT, typename View<LDS>::type, decltype(fr), SCHLICK>(P, sv, x, y, in_image, st, fr, color, hid, ctr);
+        trace_trees_shared<COUNT, typename View<LDS>::type, decltype(fr), SCHLICK, BATCH>(P, sv, x, y, f, in_image, st, fr, color, hid, ctr);
         if (in_image) {
-            const size_t p = (size_t)row * P.res_x + x;
+            const size_t p = (size_t)out_row<BATCH>(P, f, row) * P.res_x + x;
             write_pixel(P, p, color);
             if (P.hit_id) P.hit_id[p] = hid;
             flush_counters<COUNT>(P, ctr, 1u);
@@ -958,18 +992,18 @@ __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void whitted_tree_kern
         return;
     }
     if (P.spp == 0) {                                    // RT/main.cpp:756-775
-        color = clampc(trace_tree<COUNT, GRID, typename View<LDS>::type, decltype(fr), SCHLICK>(P, sv, camera_ray(P, x, y, 0), st, fr, hid, ctr));
+        color = clampc(trace_tree<COUNT, GRID, typename View<LDS>::type, decltype(fr), SCHLICK>(P, sv, camera_ray<BATCH>(P, x, y, 0, f), st, fr, hid, ctr));
     } else {                                             // RT/main.cpp:776-801
         const int ns = P.spp * P.spp;
         for (int s = 0; s < ns; s++) {
             int32_t h2 = -1;
-            V3 c = clampc(trace_tree<COUNT, GRID, typename View<LDS>::type, decltype(fr), SCHLICK>(P, sv, camera_ray(P, x, y, s), st, fr, h2, ctr));
+            V3 c = clampc(trace_tree<COUNT, GRID, typename View<LDS>::type, decltype(fr), SCHLICK>(P, sv, camera_ray<BATCH>(P, x, y, s, f), st, fr, h2, ctr));
             color = add(color, c);
             if (s == 0) hid = h2;
         }
         color = mk(fdiv(color.x, 16.0f), fdiv(color.y, 16.0f), fdiv(color.z, 16.0f));
     }
-    const size_t p = (size_t)row * P.res_x + x;
+    const size_t p = (size_t)out_row<BATCH>(P, f, row) * P.res_x + x;
     write_pixel(P, p, color);
     if (P.hit_id) P.hit_id[p] = hid;
     flush_counters<COUNT>(P, ctr, 1u);
@@ -1112,6 +1146,34 @@ P3D_DEFINE_SELECTOR(wf_secondary_fn, wf_secondary_kernel)
 P3D_DEFINE_SELECTOR(wf_tile_fn, wf_tile_kernel)
 #undef P3D_DEFINE_SELECTOR
 
+// Frame batches (BATCH = true): the kernels that make camera rays, for every walk, scene placement, counting, random-draw
+// and Schlick combination, all with the default register budget (the deeper levels and the resolves are shared).
+#define P3D_DEFINE_BATCH_SELECTOR(NAME, KERNEL)                                                                   \
+    template <bool C, bool S, bool K> static const void* NAME##_b(bool lds, int walk) {                          \
+        if (!lds) return walk == 3 ? fn_ptr(KERNEL<C, false, 3, 1, S, K, true>) : walk == 2 ? fn_ptr(KERNEL<C, false, 2, 1, S, K, true>)   \
+                       : walk == 1 ? fn_ptr(KERNEL<C, false, 1, 1, S, K, true>) : fn_ptr(KERNEL<C, false, 0, 1, S, K, true>);             \
+        return walk == 2 ? fn_ptr(KERNEL<C, true, 2, 1, S, K, true>) : walk == 1 ? fn_ptr(KERNEL<C, true, 1, 1, S, K, true>)               \
+                         : fn_ptr(KERNEL<C, true, 0, 1, S, K, true>);                                            \
+    }                                                                                                             \
+    static const void* NAME(bool count, bool lds, int walk, bool stoch, bool schlick) {                          \
+        if (lds && walk == WALK_SHARED) walk = WALK_LANE;                                                         \
+        if (count) return stoch ? (schlick ? NAME##_b<true, true, true>(lds, walk) : NAME##_b<true, true, false>(lds, walk))           \
+                                : (schlick ? NAME##_b<true, false, true>(lds, walk) : NAME##_b<true, false, false>(lds, walk));        \
+        return stoch ? (schlick ? NAME##_b<false, true, true>(lds, walk) : NAME##_b<false, true, false>(lds, walk))                    \
+                     : (schlick ? NAME##_b<false, false, true>(lds, walk) : NAME##_b<false, false, false>(lds, walk));                 \
+    }
+P3D_DEFINE_BATCH_SELECTOR(wf_primary_batch_fn, wf_primary_kernel)
+P3D_DEFINE_BATCH_SELECTOR(wf_tile_batch_fn, wf_tile_kernel)
+#undef P3D_DEFINE_BATCH_SELECTOR
+static const void* wf_primary_pick(const LaunchParams& P, bool count, bool lds, int walk, int occ) {
+    return P.n_frames > 1 ? wf_primary_batch_fn(count, lds, walk, feat_stochastic(P.features), feat_schlick(P.features))
+                          : wf_primary_fn(count, lds, walk, occ, feat_stochastic(P.features), feat_schlick(P.features));
+}
+static const void* wf_tile_pick(const LaunchParams& P, bool count, bool lds, int walk, int occ) {
+    return P.n_frames > 1 ? wf_tile_batch_fn(count, lds, walk, feat_stochastic(P.features), feat_schlick(P.features))
+                          : wf_tile_fn(count, lds, walk, occ, feat_stochastic(P.features), feat_schlick(P.features));
+}
+
 template <bool C> static const void* tree_schlick_fn(bool lds, bool grid, int priv, bool shared) {
     if (grid) return lds ? fn_ptr(whitted_tree_kernel<C, true, 1, true, 0, false, true>) : fn_ptr(whitted_tree_kernel<C, false, 1, true, 0, false, true>);
     if (lds) return fn_ptr(whitted_tree_kernel<C, true, 1, false, 0, false, true>);
@@ -1120,7 +1182,17 @@ template <bool C> static const void* tree_schlick_fn(bool lds, bool grid, int pr
     return priv == 36 ? fn_ptr(whitted_tree_kernel<C, false, 1, false, 36, false, true>)
          : priv == 84 ? fn_ptr(whitted_tree_kernel<C, false, 1, false, 84, false, true>) : fn_ptr(whitted_tree_kernel<C, false, 1, false, 0, false, true>);
 }
-static const void* tree_fn(bool count, bool lds, int occ, bool grid, int priv = 0, bool shared = false, bool schlick = false) {
+template <bool C, bool K> static const void* tree_batch_fn(bool lds, bool grid, int priv, bool shared) {
+    if (grid) return lds ? fn_ptr(whitted_tree_kernel<C, true, 1, true, 0, false, K, true>) : fn_ptr(whitted_tree_kernel<C, false, 1, true, 0, false, K, true>);
+    if (lds) return fn_ptr(whitted_tree_kernel<C, true, 1, false, 0, false, K, true>);
+    if (shared) return priv == 36 ? fn_ptr(whitted_tree_kernel<C, false, 1, false, 36, true, K, true>)
+                     : priv == 84 ? fn_ptr(whitted_tree_kernel<C, false, 1, false, 84, true, K, true>) : fn_ptr(whitted_tree_kernel<C, false, 1, false, 0, true, K, true>);
+    return priv == 36 ? fn_ptr(whitted_tree_kernel<C, false, 1, false, 36, false, K, true>)
+         : priv == 84 ? fn_ptr(whitted_tree_kernel<C, false, 1, false, 84, false, K, true>) : fn_ptr(whitted_tree_kernel<C, false, 1, false, 0, false, K, true>);
+}
+static const void* tree_fn(bool count, bool lds, int occ, bool grid, int priv = 0, bool shared = false, bool schlick = false, bool batch = false) {
+    if (batch) return count ? (schlick ? tree_batch_fn<true, true>(lds, grid, priv, shared) : tree_batch_fn<true, false>(lds, grid, priv, shared))
+                            : (schlick ? tree_batch_fn<false, true>(lds, grid, priv, shared) : tree_batch_fn<false, false>(lds, grid, priv, shared));
     if (schlick) return count ? tree_schlick_fn<true>(lds, grid, priv, shared) : tree_schlick_fn<false>(lds, grid, priv, shared);
     if (shared && !lds && !grid && priv == 36) {
         if (count) return fn_ptr(whitted_tree_kernel<true, false, 1, false, 36, true>);
@@ -1160,7 +1232,7 @@ static hipError_t launch_by_pointer(const void* fn, const LaunchParams& P, dim3 
 }
 
 hipError_t launch_tree(const LaunchParams& P, bool count, bool lds, int occ, bool shared, hipStream_t stream) {
-    return launch_by_pointer(tree_fn(count, lds, occ, P.accel == 1, tree_private_dwords(P, lds), shared, feat_schlick(P.features)), P, dim3((unsigned)P.grid_blocks),
+    return launch_by_pointer(tree_fn(count, lds, occ, P.accel == 1, tree_private_dwords(P, lds), shared, feat_schlick(P.features), P.n_frames > 1), P, dim3((unsigned)P.grid_blocks),
                              dim3(64 * P.wg_waves), tree_kernel_lds_bytes(P, lds), stream);
 }
 hipError_t launch_wf_primary(const LaunchParams& P, bool count, bool lds, int walk, int occ, hipStream_t stream) {
@@ -1168,7 +1240,7 @@ hipError_t launch_wf_primary(const LaunchParams& P, bool count, bool lds, int wa
     // (LDS scenes only: the kernels of scenes read from HBM number their tiles through the learned order)
     const bool grid2d = lds && P.xcd_chunk == 1 && P.wf_tile_rows > 1 && P.tiles_x * P.wf_tile_rows == P.n_tiles;
     const dim3 grid = grid2d ? dim3((unsigned)P.tiles_x, (unsigned)P.wf_tile_rows) : dim3((unsigned)P.grid_blocks);
-    return launch_by_pointer(wf_primary_fn(count, lds, walk, occ, feat_stochastic(P.features), feat_schlick(P.features)), P, grid,
+    return launch_by_pointer(wf_primary_pick(P, count, lds, walk, occ), P, grid,
                              dim3(64 * P.wg_waves), wavefront_lds_bytes(P, lds), stream);
 }
 hipError_t launch_wf_secondary(const LaunchParams& P, bool count, bool lds, int walk, int occ, unsigned waves,
@@ -1178,7 +1250,7 @@ hipError_t launch_wf_secondary(const LaunchParams& P, bool count, bool lds, int 
 }
 // waves of the deeper-level kernel that can be resident on the device at once (LDS-scene variants: 256-thread workgroups)
 hipError_t wf_resident_waves(const LaunchParams& P, bool primary, bool count, bool lds, int walk, int occ, unsigned* waves) {
-    const void* fn = primary ? wf_primary_fn(count, lds, walk, occ, feat_stochastic(P.features), feat_schlick(P.features)) : wf_secondary_fn(count, lds, walk, occ, feat_stochastic(P.features), feat_schlick(P.features));
+    const void* fn = primary ? wf_primary_pick(P, count, lds, walk, occ) : wf_secondary_fn(count, lds, walk, occ, feat_stochastic(P.features), feat_schlick(P.features));
     int per_cu = 0, dev = 0, cus = 0;
     hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * P.wg_waves, wavefront_lds_bytes(P, lds));
     if (e != hipSuccess) return e;
@@ -1193,7 +1265,7 @@ size_t tile_kernel_lds_bytes(const LaunchParams& P, bool lds) {
 }
 // workgroups of this variant that can be resident on the whole device (persistent grid size)
 hipError_t tile_kernel_resident_blocks(const LaunchParams& P, bool count, bool lds, int walk, int occ, int* blocks) {
-    const void* fn = wf_tile_fn(count, lds, walk, occ, feat_stochastic(P.features), feat_schlick(P.features));
+    const void* fn = wf_tile_pick(P, count, lds, walk, occ);
     const size_t shmem = tile_kernel_lds_bytes(P, lds);
     if (shmem > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
@@ -1208,7 +1280,7 @@ hipError_t tile_kernel_resident_blocks(const LaunchParams& P, bool count, bool l
     return hipSuccess;
 }
 hipError_t launch_wf_tile(const LaunchParams& P, bool count, bool lds, int walk, int occ, unsigned blocks, hipStream_t stream) {
-    return launch_by_pointer(wf_tile_fn(count, lds, walk, occ, feat_stochastic(P.features), feat_schlick(P.features)), P, dim3(blocks), dim3(256),
+    return launch_by_pointer(wf_tile_pick(P, count, lds, walk, occ), P, dim3(blocks), dim3(256),
                              tile_kernel_lds_bytes(P, lds), stream);
 }
 
@@ -1225,6 +1297,28 @@ hipError_t launch_wf_resolve(const LaunchParams& P, unsigned blocks, hipStream_t
 __global__ void clear_words_kernel(uint32_t* p, uint32_t n) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) p[i] = 0u;
 }
+// Per-frame cameras of a batch, carried by the launch's own arguments (kFrameCamsPerLaunch records, 2 KiB): a stream capture
+// bakes them into the graph, so a replay writes the cameras it was captured with, and no host buffer has to outlive the call.
+constexpr int kFrameCamsPerLaunch = 16;
+struct FrameCamChunk { FrameCam cam[kFrameCamsPerLaunch]; };
+__global__ __launch_bounds__(256) void frame_cams_kernel(const FrameCamChunk c, FrameCam* dst, uint32_t n_floats) {
+    for (uint32_t i = threadIdx.x; i < n_floats; i += blockDim.x)
+        reinterpret_cast<float*>(dst)[i] = reinterpret_cast<const float*>(c.cam)[i];
+}
+hipError_t launch_frame_cams(FrameCam* dst, const FrameCam* cams, int n, hipStream_t stream) {
+    for (int f0 = 0; f0 < n; f0 += kFrameCamsPerLaunch) {
+        const int k = n - f0 < kFrameCamsPerLaunch ? n - f0 : kFrameCamsPerLaunch;
+        FrameCamChunk c;
+        memset(&c, 0, sizeof c);
+        memcpy(c.cam, cams + f0, (size_t)k * sizeof(FrameCam));
+        hipLaunchKernelGGL(frame_cams_kernel, dim3(1), dim3(256), 0, stream, c, dst + f0,
+                           (uint32_t)(k * (sizeof(FrameCam) / sizeof(float))));
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 hipError_t launch_clear_words(uint32_t* p, uint32_t n, hipStream_t stream) {
     hipLaunchKernelGGL(clear_words_kernel, dim3((n + 255) / 256 < 64 ? (n + 255) / 256 : 64), dim3(256), 0, stream, p, n);
     return hipGetLastError();
@@ -1232,7 +1326,8 @@ hipError_t launch_clear_words(uint32_t* p, uint32_t n, hipStream_t stream) {
 
 hipError_t launch_sum_samples(const LaunchParams& P, size_t first_px, size_t n_px, hipStream_t stream) {
     const unsigned blocks = (unsigned)std::min<size_t>((n_px + 255) / 256, 256 * 32);
-    hipLaunchKernelGGL(sum_samples_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, stream, P, first_px, n_px);
+    if (P.n_frames > 1) hipLaunchKernelGGL(sum_samples_kernel<true>, dim3(blocks ? blocks : 1), dim3(256), 0, stream, P, first_px, n_px);
+    else hipLaunchKernelGGL(sum_samples_kernel<false>, dim3(blocks ? blocks : 1), dim3(256), 0, stream, P, first_px, n_px);
     return hipGetLastError();
 }
 
@@ -1246,6 +1341,12 @@ hipError_t prepare_kernels(size_t max_lds) {
                          tree_fn(true, false, 1, false, 0, true, true), tree_fn(false, false, 1, false, 0, true, true)};
     for (const void* f : fns) {
         hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds);
+        if (e != hipSuccess) return e;
+    }
+    for (int k = 0; k < 16; k++) {           // ... and their batch builds (count x grid x shared x schlick)
+        if ((k & 2) && (k & 4)) continue;    // (GRID mode has no shared walk)
+        hipError_t e = hipFuncSetAttribute(tree_fn(k & 1, false, 1, (k & 2) != 0, 0, (k & 4) != 0, (k & 8) != 0, true),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;

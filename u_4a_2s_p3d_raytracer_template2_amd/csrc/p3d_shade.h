@@ -342,12 +342,14 @@ __device__ __forceinline__ NodeOut shade_hit(const LaunchParams& P, const SV& sv
 // Camera::PrimaryRay, RT/camera.h:91-108
 // the same ray from the frame constants: fx = px/res_x - 0.5f, fy = py/res_y - 0.5f come from
 // the per-column / per-row tables, uw = u*w, vh = v*h, vz = n*(-plane_dist) from the host
-__device__ __forceinline__ Ray primary_ray_tab(const LaunchParams& P, int x, int y) {
+// C: the camera -- LaunchParams itself, or a batch frame's FrameCam (the same field names)
+template <class C>
+__device__ __forceinline__ Ray primary_ray_tab(const LaunchParams& P, const C& cam, int x, int y) {
     const float fx = P.ray_fx[x], fy = P.ray_fy[y];
-    V3 vX = mul(mk(P.uw[0], P.uw[1], P.uw[2]), fx);
-    V3 vY = mul(mk(P.vh[0], P.vh[1], P.vh[2]), fy);
-    Ray r; r.o = mk(P.eye[0], P.eye[1], P.eye[2]);
-    r.d = normalized(add(add(vX, vY), mk(P.vz[0], P.vz[1], P.vz[2])));
+    V3 vX = mul(mk(cam.uw[0], cam.uw[1], cam.uw[2]), fx);
+    V3 vY = mul(mk(cam.vh[0], cam.vh[1], cam.vh[2]), fy);
+    Ray r; r.o = mk(cam.eye[0], cam.eye[1], cam.eye[2]);
+    r.d = normalized(add(add(vX, vY), mk(cam.vz[0], cam.vz[1], cam.vz[2])));
     return r;
 }
 __device__ __forceinline__ Ray primary_ray(const LaunchParams& P, float px, float py) {
@@ -360,14 +362,15 @@ __device__ __forceinline__ Ray primary_ray(const LaunchParams& P, float px, floa
     return r;
 }
 // Camera::PrimaryRay(lens, pixel), RT/camera.h:110-127
-__device__ __forceinline__ Ray primary_ray_lens(const LaunchParams& P, float lx, float ly, float px, float py) {
-    V3 u = mk(P.u[0], P.u[1], P.u[2]), v = mk(P.v[0], P.v[1], P.v[2]), n = mk(P.n[0], P.n[1], P.n[2]);
-    float ppx = P.w * (fdiv(px, (float)P.res_x) - 0.5f) * P.focal_ratio;
-    float ppy = P.h * (fdiv(py, (float)P.res_y) - 0.5f) * P.focal_ratio;
-    V3 dir = add(add(mul(u, ppx - lx), mul(v, ppy - ly)), mul(n, -P.focal_ratio * P.plane_dist));
+template <class C>
+__device__ __forceinline__ Ray primary_ray_lens(const LaunchParams& P, const C& cam, float lx, float ly, float px, float py) {
+    V3 u = mk(cam.u[0], cam.u[1], cam.u[2]), v = mk(cam.v[0], cam.v[1], cam.v[2]), n = mk(cam.n[0], cam.n[1], cam.n[2]);
+    float ppx = cam.w * (fdiv(px, (float)P.res_x) - 0.5f) * cam.focal_ratio;
+    float ppy = cam.h * (fdiv(py, (float)P.res_y) - 0.5f) * cam.focal_ratio;
+    V3 dir = add(add(mul(u, ppx - lx), mul(v, ppy - ly)), mul(n, -cam.focal_ratio * cam.plane_dist));
     Ray r;
     r.d = normalized(dir);
-    r.o = add(add(mk(P.eye[0], P.eye[1], P.eye[2]), mul(u, lx)), mul(v, ly));
+    r.o = add(add(mk(cam.eye[0], cam.eye[1], cam.eye[2]), mul(u, lx)), mul(v, ly));
     return r;
 }
 
