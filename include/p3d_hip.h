@@ -393,6 +393,9 @@ int p3d_debug_schlick_kr(int device, uint32_t n, const float* ior_1, const float
  * division 1.0f / x it replaces in normalize() and Triangle::intercepts: the bit patterns first_bits .. first_bits +
  * count - 1 (count <= 2^32: all floats). n_bad = patterns whose results differ (NaN = NaN), first_bad = the lowest. */
 int p3d_debug_check_rcp(int device, uint32_t first_bits, uint64_t count, uint64_t* n_bad, uint32_t* first_bad);
+/* The same check for rcp_len(x) (csrc/p3d_device_math.h), the branch-free reciprocal that normalize() applies to a
+ * square root's output. */
+int p3d_debug_check_rcp_len(int device, uint32_t first_bits, uint64_t count, uint64_t* n_bad, uint32_t* first_bad);
 
 #ifdef __cplusplus
 }

@@ -48,6 +48,7 @@ hipError_t sort_tiles_by_cost(const uint32_t* cost, uint32_t* cost_sorted, uint3
                               void* temp, size_t& temp_bytes, hipStream_t stream);
 bool kernels_have_stamps();
 hipError_t launch_debug_check_rcp(uint32_t first, uint64_t count, unsigned long long* n_bad, uint32_t* first_bad, hipStream_t stream);
+hipError_t launch_debug_check_rcp_len(uint32_t first, uint64_t count, unsigned long long* n_bad, uint32_t* first_bad, hipStream_t stream);
 hipError_t launch_debug_powf(uint32_t n, const float* x, const float* y, float* out, hipStream_t stream);
 hipError_t launch_debug_pow(uint32_t n, const double* x, const double* y, double* out, hipStream_t stream);
 hipError_t launch_debug_schlick_kr(uint32_t n, const float* ior_1, const float* new_ior, const float* cos_theta_i, float* out,
@@ -1366,7 +1367,9 @@ int p3d_tune_schedule(p3d_scene** scenes, int32_t n, const p3d_camera* cam, cons
     return P3D_OK;
 }
 
-int p3d_debug_check_rcp(int device, uint32_t first_bits, uint64_t count, uint64_t* n_bad, uint32_t* first_bad) {
+typedef hipError_t (*RcpCheckLaunch)(uint32_t, uint64_t, unsigned long long*, uint32_t*, hipStream_t);
+static int debug_check_reciprocal(const char* what, RcpCheckLaunch launch, int device, uint32_t first_bits, uint64_t count,
+                                  uint64_t* n_bad, uint32_t* first_bad) {
     if (!n_bad || !first_bad) return fail(P3D_ERR_ARG, "NULL argument");
     *n_bad = 0; *first_bad = 0xFFFFFFFFu;
     if (count == 0) return P3D_OK;
@@ -1378,14 +1381,20 @@ int p3d_debug_check_rcp(int device, uint32_t first_bits, uint64_t count, uint64_
     HIP_TRY(hipMalloc((void**)&d, 16));
     const unsigned long long init[2] = {0ull, 0xFFFFFFFFull};
     hipError_t e = hipMemcpy(d, init, 16, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = launch_debug_check_rcp(first_bits, count, d, (uint32_t*)(d + 1), nullptr);
+    if (e == hipSuccess) e = launch(first_bits, count, d, (uint32_t*)(d + 1), nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     unsigned long long out[2] = {0, 0};
     if (e == hipSuccess) e = hipMemcpy(out, d, 16, hipMemcpyDeviceToHost);
     (void)hipFree(d);
-    if (e != hipSuccess) return fail(P3D_ERR_HIP, std::string("p3d_debug_check_rcp: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(P3D_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
     *n_bad = out[0]; *first_bad = (uint32_t)out[1];
     return P3D_OK;
+}
+int p3d_debug_check_rcp(int device, uint32_t first_bits, uint64_t count, uint64_t* n_bad, uint32_t* first_bad) {
+    return debug_check_reciprocal("p3d_debug_check_rcp", launch_debug_check_rcp, device, first_bits, count, n_bad, first_bad);
+}
+int p3d_debug_check_rcp_len(int device, uint32_t first_bits, uint64_t count, uint64_t* n_bad, uint32_t* first_bad) {
+    return debug_check_reciprocal("p3d_debug_check_rcp_len", launch_debug_check_rcp_len, device, first_bits, count, n_bad, first_bad);
 }
 
 int p3d_debug_powf(int device, uint32_t n, const float* x, const float* y, float* out) {

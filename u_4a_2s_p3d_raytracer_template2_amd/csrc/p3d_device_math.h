@@ -44,9 +44,24 @@ __device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y 
 __device__ __forceinline__ V3 cross(V3 u, V3 v) {                       // RT/vector.cpp:85-100
     return mk(u.y * v.z - u.z * v.y, u.z * v.x - u.x * v.z, u.x * v.y - u.y * v.x);
 }
+// 1.0f / x for a length, x = fsqrt(s): +0, +inf, NaN or a normal float >= 2^-75, in 7 vector instructions, no scalar ones
+// and no branch, where the compiler's division takes 11.  The hardware reciprocal flushes subnormal results, so x > 2^126
+// is reciprocated as x * 2^-64 and v_div_fmas scales its Newton step back by 2^-64 with one rounding; the Newton step in FMA
+// arithmetic makes the reciprocal exact; v_div_fixup returns the IEEE results for +0, +inf and NaN.  Equal to 1.0f / x
+// for every non-negative float except the subnormals -- checked over all of them on the device (p3d_debug_check_rcp_len,
+// tests/test_gpu_exact_rcp_len.py).
+// UNREACHABLE: subnormal x (v_rcp_f32 flushes them, and the result is wrong).  fsqrt never returns one: the square root of
+// the smallest positive float, 2^-149, is 2^-74.5.  Do not call rcp_len on anything but a square root's output.
+__device__ __forceinline__ float rcp_len(float x) {
+    const bool big = x > 0x1p126f;
+    const float xs = x * (big ? 0x1p-64f : 1.0f);
+    const float r0 = __builtin_amdgcn_rcpf(xs);
+    const float e = __builtin_fmaf(-xs, r0, 1.0f);
+    return __builtin_amdgcn_div_fixupf(__builtin_amdgcn_div_fmasf(e, r0, r0, big), x, 1.0f);
+}
 __device__ __forceinline__ float vlen(V3 a) { return fsqrt(a.x * a.x + a.y * a.y + a.z * a.z); }
 __device__ __forceinline__ V3 normalized(V3 a) {                        // RT/vector.cpp:66-71
-    float l = fdiv(1.0f, vlen(a));
+    float l = rcp_len(vlen(a));
     return mk(a.x * l, a.y * l, a.z * l);
 }
 __device__ __forceinline__ float clamp01(float v) { return (v < 0.0f) ? 0.0f : ((v > 1.0f) ? 1.0f : v); }

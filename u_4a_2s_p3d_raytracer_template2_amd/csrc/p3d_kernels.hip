@@ -1384,9 +1384,23 @@ __global__ void debug_check_rcp_kernel(uint32_t first, uint64_t count, unsigned 
         if (!same) { atomicAdd(n_bad, 1ull); atomicMin(first_bad, bits); }
     }
 }
+// the same for rcp_len(x), the reciprocal of a square root's output
+__global__ void debug_check_rcp_len_kernel(uint32_t first, uint64_t count, unsigned long long* n_bad, uint32_t* first_bad) {
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t bits = first + (uint32_t)i;
+        const float x = __uint_as_float(bits);
+        const float a = rcp_len(x), b = 1.0f / x;
+        const bool same = __float_as_uint(a) == __float_as_uint(b) || (a != a && b != b);
+        if (!same) { atomicAdd(n_bad, 1ull); atomicMin(first_bad, bits); }
+    }
+}
 bool kernels_have_stamps() { return kStamps; }
 hipError_t launch_debug_check_rcp(uint32_t first, uint64_t count, unsigned long long* n_bad, uint32_t* first_bad, hipStream_t stream) {
     hipLaunchKernelGGL(debug_check_rcp_kernel, dim3(256 * 16), dim3(256), 0, stream, first, count, n_bad, first_bad);
+    return hipGetLastError();
+}
+hipError_t launch_debug_check_rcp_len(uint32_t first, uint64_t count, unsigned long long* n_bad, uint32_t* first_bad, hipStream_t stream) {
+    hipLaunchKernelGGL(debug_check_rcp_len_kernel, dim3(256 * 16), dim3(256), 0, stream, first, count, n_bad, first_bad);
     return hipGetLastError();
 }
 

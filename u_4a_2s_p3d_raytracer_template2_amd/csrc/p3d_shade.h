@@ -84,15 +84,14 @@ __device__ __forceinline__ Hit find_closest(const LaunchParams& P, const SV& sv,
 }
 
 // Shadow query of processLight() (RT/main.cpp:476-510).  `need` = this lane builds a shadow
-// ray (L.N > 0).  NONE: un-normalised direction, no distance bound; BVH/GRID: normalised
-// direction and t < |L| (BVH::Traverse(Ray&), RT/bvh.cpp:351-352).
+// ray (L.N > 0).  NONE: un-normalised direction L, no distance bound; BVH/GRID: normalised
+// direction Ln and t < len = |L| (BVH::Traverse(Ray&), RT/bvh.cpp:351-352).
 template <bool COUNT, int WALK, class SV>
-__device__ __forceinline__ bool light_occluded(const LaunchParams& P, const SV& sv, V3 L, V3 precise, bool need,
+__device__ __forceinline__ bool light_occluded(const LaunchParams& P, const SV& sv, V3 L, V3 Ln, float len, V3 precise, bool need,
                                                const TravCtx& tc, Ctr& ctr) {
-    Ray sr; sr.o = precise; sr.d = L;
-    float length = 0.0f;
     const bool bounded = WALK == WALK_GRID || P.accel != 0;
-    if (bounded && need) { length = vlen(sr.d); sr.d = normalized(sr.d); }
+    Ray sr; sr.o = precise; sr.d = bounded ? Ln : L;
+    const float length = bounded ? len : 0.0f;
     if (WALK == WALK_PACKET) return any_hit_packet<COUNT>(P, sv, sr, need, bounded, length, tc.wave, ctr);
     if (WALK == WALK_SHARED) return any_shared<COUNT>(P, sv, sr, need, bounded, length, tc, ctr);
     if (WALK == WALK_GRID) return need ? grid_any<COUNT>(P, sv, sr, length, ctr) : false;   // Grid::Traverse(Ray&), RT/grid.cpp:313
@@ -102,22 +101,22 @@ __device__ __forceinline__ bool light_occluded(const LaunchParams& P, const SV& 
 __device__ __forceinline__ PowTabLds pow_tab(const LdsScene&) { return PowTabLds(); }
 __device__ __forceinline__ PowTabGlobal pow_tab(const GlobalScene& g) { return PowTabGlobal(g.q); }
 
-// Blinn-Phong term of one unoccluded light, RT/main.cpp:512-525
+// Blinn-Phong term of one unoccluded light, RT/main.cpp:512-525; L = normalized(light - hit point), the value the
+// shadow query was given
 template <class SV>
 __device__ __forceinline__ void light_term(const SV& sv, V3 L, V3 lcol, V3& color, const Mtl& M, const Ray& ray, V3 normal) {
-    L = normalized(L);        // (the same value light_occluded() formed for a bounded shadow ray: CSE'd when inlined)
-    V3 H = normalized(add(L, mul(ray.d, -1.0f)));
-    float VdotN = dot(H, normal);
     float d1 = dot(normal, L);
     float max1 = (0.0f < d1) ? d1 : 0.0f;                // std::max(0.0f, x)
-    float max2 = (0.0f < VdotN) ? VdotN : 0.0f;
     V3 diff = mul(cmul(lcol, M.diff), max1);
     if (M.ks == 0.0f && M.shine >= 0.0f) {
         // spec * Ks * 0.4 is (finite * 0) * 0.4 = 0: the sum is unchanged (up to the sign of a zero),
-        // and powf is the most expensive call of the whole term
+        // and powf is the most expensive call of the whole term -- so is the half vector, formed below only
         color = add(color, mul(diff, M.kd));
         return;
     }
+    V3 H = normalized(add(L, mul(ray.d, -1.0f)));
+    float VdotN = dot(H, normal);
+    float max2 = (0.0f < VdotN) ? VdotN : 0.0f;
     // the host libm's powf, bit for bit (p3d_powf.h); max2 is +0 or positive
     V3 spec = mul(cmul(lcol, M.spec), p3d_powf_nonneg(max2, M.shine, pow_tab(sv)));
     color = add(color, add(mul(diff, M.kd), mul(mul(spec, M.ks), 0.4f)));
@@ -238,30 +237,24 @@ __device__ __forceinline__ NodeOut shade_hit(const LaunchParams& P, const SV& sv
         if ((h.ref >> kRefKindShift) == 0u) normal = prim_normal(P, sv, h.ref, ray, precise);
     }
     V3 color = mk(0.0f, 0.0f, 0.0f);
-    // lights in groups of 64: first every shadow query of the group (bit i = light i occluded),
-    // then the shading terms in light order -- same sums, same order as the reference's loop
-    for (uint32_t l0 = 0; l0 < P.n_lights; l0 += 64) {
-        const uint32_t ln = (P.n_lights - l0 < 64u) ? (P.n_lights - l0) : 64u;
-        uint64_t occluded = 0;
-        for (uint32_t i = 0; i < ln; i++) {
-            const float4 lpos = reinterpret_cast<const float4*>(P.lights + l0 + i)[0];
-            V3 L = sub(light_position<STOCH>(P, lpos, l0 + i, rng, sample), hit_point);
+    // one pass per light, in light order (the reference's loop): L, |L| and L / |L| once, the shadow query -- reached by
+    // the whole wave, lanes without a hit included --, then the term of an unoccluded light.  The material is read after
+    // the query: its twelve registers live across the walk cost the LDS kernels their occupancy.
+    for (uint32_t i = 0; i < P.n_lights; i++) {
+        const float4* lp = reinterpret_cast<const float4*>(P.lights + i);
+        const float4 lpos = lp[0];
+        const V3 L = sub(light_position<STOCH>(P, lpos, i, rng, sample), hit_point);
+        const float len = vlen(L);
+        const V3 Ln = mul(L, rcp_len(len));                               // normalized(L)
 #ifdef P3D_DEBUG_SKIP
-            const bool need = hit && dot(L, normal) > 0.0f && P.dbg_skip != 2u;
+        const bool need = hit && dot(L, normal) > 0.0f && P.dbg_skip != 2u;
 #else
-            const bool need = hit && dot(L, normal) > 0.0f;              // RT/main.cpp:476
+        const bool need = hit && dot(L, normal) > 0.0f;                  // RT/main.cpp:476
 #endif
-            if (light_occluded<COUNT, WALK>(P, sv, L, precise, need, tc, ctr)) occluded |= (1ull << i);
-        }
-        if (hit) {
-            Mtl Ml = load_material(sv, h.mat);
-            for (uint32_t i = 0; i < ln; i++) {
-                if (occluded & (1ull << i)) continue;
-                const float4* lp = reinterpret_cast<const float4*>(P.lights + l0 + i);
-                float4 lpos = lp[0], lcol = lp[1];
-                V3 L = sub(light_position<STOCH>(P, lpos, l0 + i, rng, sample), hit_point);
-                light_term(sv, L, mk(lcol.x, lcol.y, lcol.z), color, Ml, ray, normal);
-            }
+        const bool occluded = light_occluded<COUNT, WALK>(P, sv, L, Ln, len, precise, need, tc, ctr);
+        if (hit && !occluded) {
+            const float4 lcol = lp[1];
+            light_term(sv, Ln, mk(lcol.x, lcol.y, lcol.z), color, load_material(sv, h.mat), ray, normal);
         }
     }
     if (!hit) {
