@@ -26,6 +26,7 @@
 
 #include "bvh_builder.h"
 #include "p3d_device_types.h"
+#include "p3d_launch.h"
 
 namespace p3d {
 

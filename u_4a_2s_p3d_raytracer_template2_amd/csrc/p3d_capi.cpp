@@ -17,45 +17,10 @@
 #include "bvh_builder.h"
 #include "grid_builder.h"
 #include "p3d_device_types.h"
+#include "p3d_launch.h"
 #include "scene_flatten.h"
 #define P3D_POWF_TABLES_ONLY
 #include "p3d_powf.h"
-
-namespace p3d {
-size_t tree_kernel_lds_bytes(const LaunchParams& P, bool lds);
-size_t wavefront_lds_bytes(const LaunchParams& P, bool lds);
-hipError_t launch_tree(const LaunchParams& P, bool count, bool lds, int occ, bool shared, hipStream_t stream);
-hipError_t launch_wf_primary(const LaunchParams& P, bool count, bool lds, int walk, int occ, hipStream_t stream);
-hipError_t launch_wf_secondary(const LaunchParams& P, bool count, bool lds, int walk, int occ, unsigned waves,
-                               hipStream_t stream);
-hipError_t launch_wf_resolve(const LaunchParams& P, unsigned blocks, hipStream_t stream);
-hipError_t launch_wf_resolve_fused(const LaunchParams& P, const ResolveLevels& R, unsigned shards, hipStream_t stream);
-hipError_t launch_clear_words(uint32_t* p, uint32_t n, hipStream_t stream);
-hipError_t launch_frame_cams(FrameCam* dst, const FrameCam* cams, int n, hipStream_t stream);
-hipError_t wf_resident_waves(const LaunchParams& P, bool primary, bool count, bool lds, int walk, int occ, unsigned* waves);
-size_t tile_kernel_lds_bytes(const LaunchParams& P, bool lds);
-hipError_t tile_kernel_resident_blocks(const LaunchParams& P, bool count, bool lds, int walk, int occ, int* blocks);
-hipError_t launch_wf_tile(const LaunchParams& P, bool count, bool lds, int walk, int occ, unsigned blocks, hipStream_t stream);
-hipError_t launch_raygen_table(float* fx, float* fy, int res_x, int res_y, hipStream_t stream);
-hipError_t prepare_kernels(size_t max_lds);
-hipError_t launch_sum_samples(const LaunchParams& P, size_t first_px, size_t n_px, hipStream_t stream);
-hipError_t launch_deinterleave(const void* gathered, void* frames, int res_x, int res_y, int row_block,
-                               int world, size_t rank_stride, int bpp, int n_frames, size_t in_stride,
-                               size_t out_stride, hipStream_t stream);
-hipError_t build_lbvh_device(const std::vector<BuildPrim>& prims, const BvhOptions& opt, NodePair* d_nodes,
-                             uint32_t* d_refs, BvhStats& stats, hipStream_t stream);
-hipError_t sort_tiles_by_cost(const uint32_t* cost, uint32_t* cost_sorted, uint32_t* iota, uint32_t* order, uint32_t n,
-                              void* temp, size_t& temp_bytes, hipStream_t stream);
-bool kernels_have_stamps();
-hipError_t launch_debug_check_rcp(uint32_t first, uint64_t count, unsigned long long* n_bad, uint32_t* first_bad, hipStream_t stream);
-hipError_t launch_debug_check_rcp_len(uint32_t first, uint64_t count, unsigned long long* n_bad, uint32_t* first_bad, hipStream_t stream);
-hipError_t launch_debug_powf(uint32_t n, const float* x, const float* y, float* out, hipStream_t stream);
-hipError_t launch_debug_pow(uint32_t n, const double* x, const double* y, double* out, hipStream_t stream);
-hipError_t launch_debug_schlick_kr(uint32_t n, const float* ior_1, const float* new_ior, const float* cos_theta_i, float* out,
-                                   hipStream_t stream);
-hipError_t launch_debug_intersect(uint32_t n, const uint32_t* type, const float* prim12, const float* origin,
-                                  const float* dir, int32_t* hit, float* t, float* normal, hipStream_t stream);
-}  // namespace p3d
 
 using namespace p3d;
 
@@ -64,6 +29,8 @@ namespace {
 thread_local std::string g_err;
 
 int fail(int code, const std::string& msg) { g_err = msg; return code; }
+
+KernelVariant with_budget(KernelVariant v, int occ) { v.occ = occ; return v; }   // v at a register budget (waves per SIMD)
 
 #define HIP_TRY(expr)                                                                      \
     do {                                                                                   \
@@ -180,8 +147,9 @@ struct p3d_scene {
     } tile_lpt, wave_lpt;            // 16x16 tiles of the tile schedule / 16x4 wave tiles of the tree and wavefront level-1 launches
     TileOrder tile_lpt_batch, wave_lpt_batch;   // ... of frame batches (p3d_render_frames), keyed on n and the tile count too
     bool tile_lpt_enabled = true;
-    struct { uint32_t key = 0xFFFFFFFFu; size_t lds = 0; int blocks = 0; } tile_occ[2];   // cached occupancy queries (private / shared walk)
-    struct { uint32_t key = 0xFFFFFFFFu; uint32_t stack = 0; unsigned waves = 0, primary_waves = 0; } wf_occ;                 // ... of the deeper-level kernel
+    // cached occupancy queries (private / shared walk), keyed by the build they were made for (walk -1: none yet)
+    struct { KernelVariant v = {false, false, -1}; size_t lds = 0; int blocks = 0; } tile_occ[2];
+    struct { KernelVariant v = {false, false, -1}; uint32_t stack = 0; unsigned waves = 0; } wf_occ;   // ... of the deeper-level kernel
     hipStream_t lane_stream[kLanes] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[kLanes] = {nullptr, nullptr, nullptr, nullptr};
     // upper limit of the workspace one frame may allocate (wavefront schedule: worst-case level queues of a band
@@ -528,15 +496,15 @@ constexpr size_t kCountBufferWords = kCountWords + 4 * kShards + 64;
 // One sample pass over one band of tile rows, level by level (see p3d_kernels.hip).
 // shard_px = pixels a shard can own in this band (worst case), so level l holds at most
 // shard_px << (l-1) rays / nodes per shard.
-int run_wavefront_pass(p3d_scene* s, p3d_scene::Workspace& ws, hipStream_t stream, LaunchParams P, bool count, bool lds,
-                       int walk, size_t shard_px, bool profile) {
+int run_wavefront_pass(p3d_scene* s, p3d_scene::Workspace& ws, hipStream_t stream, LaunchParams P, KernelVariant v,
+                       size_t shard_px, bool profile) {
     const int D = P.max_depth;
     // scenes read from HBM wait on fetches most of the time: a register budget of 6 waves per SIMD measured 3 %
     // faster than the compiler's default there (10^6 primitives 3.19 -> 3.08 ms); LDS scenes keep the default
     // ... and since round 3 the LDS scenes' level kernels run at 6 too: the deeper-level kernel needs 82 VGPRs by default
     // (5 waves per SIMD), 78 under that budget without a spill -- config 2 0.0720 -> 0.0692 ms/frame, config 4 on this
     // schedule 5.30 -> 5.05 ms (profiles/r03_exp10_register_budgets.txt)
-    const int occ = s->occupancy ? s->occupancy : 6;
+    v = with_budget(v, s->occupancy ? s->occupancy : 6);
     const size_t n_counts = kCountWords;
     uint32_t* counts = (uint32_t*)ws.counts.p;                              // [level][shard] ray counts, then node counts
     // No clearing launch and nothing about a frame in host state (a captured frame can be replayed any number of
@@ -558,11 +526,10 @@ int run_wavefront_pass(p3d_scene* s, p3d_scene::Workspace& ws, hipStream_t strea
     P.wf_nodes_parent = nullptr; P.wf_ncap_parent = 0;
     P.wf_nodes_self = nodes(1); P.wf_ncount_self = ncount(1); P.wf_ncap_self = cap(1);
     {   // persistent grids: as many waves as can be resident (cached occupancy queries)
-        const uint32_t okey = (count ? 1u : 0u) | (lds ? 2u : 0u) | ((uint32_t)walk << 2) | (feat_stochastic(P.features) ? 16u : 0u) |
-                              ((uint32_t)occ << 5) | (feat_schlick(P.features) ? 256u : 0u);
-        if (s->wf_occ.key != okey || s->wf_occ.stack != P.trav_stack_dwords) {
-            HIP_TRY(wf_resident_waves(P, false, count, lds, walk, occ, &s->wf_occ.waves));
-            s->wf_occ.key = okey; s->wf_occ.stack = P.trav_stack_dwords;
+        const KernelVariant deeper = level_variant(v, false);
+        if (!(s->wf_occ.v == deeper) || s->wf_occ.stack != P.trav_stack_dwords) {
+            HIP_TRY(wf_resident_waves(P, deeper, &s->wf_occ.waves));
+            s->wf_occ.v = deeper; s->wf_occ.stack = P.trav_stack_dwords;
         }
     }
     const unsigned resident_waves = s->wf_occ.waves;
@@ -572,7 +539,7 @@ int run_wavefront_pass(p3d_scene* s, p3d_scene::Workspace& ws, hipStream_t strea
     P.wf_pair_in = 0; P.wf_pair_out = (pair_mode && D == 2) ? 1 : 0;
     P.wf_nodes_grand = nullptr; P.wf_ncap_grand = 0;
     if (profile) HIP_TRY(hipEventRecord(s->ev_prof[2], stream));
-    HIP_TRY(launch_wf_primary(P, count, lds, walk, occ, stream));
+    HIP_TRY(launch_wf_primary(P, v, stream));
     if (profile) HIP_TRY(hipEventRecord(s->ev_prof[3], stream));
     for (int l = 2; l <= D; l++) {
         P.wf_level = l;
@@ -586,9 +553,9 @@ int run_wavefront_pass(p3d_scene* s, p3d_scene::Workspace& ws, hipStream_t strea
         P.wf_nodes_grand = l >= 3 ? nodes(l - 2) : nullptr; P.wf_ncap_grand = l >= 3 ? cap(l - 2) : 0;
         size_t total = (size_t)cap(l) * kShards;
         // LDS scenes: as many waves as can be resident (the kernel numbers its batches through all shards)
-        unsigned waves = (unsigned)std::min<size_t>((total + 63) / 64, lds ? resident_waves : kPersistentWavesNarrow);
+        unsigned waves = (unsigned)std::min<size_t>((total + 63) / 64, v.lds ? resident_waves : kPersistentWavesNarrow);
         waves = std::max<unsigned>(kShards * 4, (waves / (kShards * 4)) * (kShards * 4));   // whole workgroups per shard
-        HIP_TRY(launch_wf_secondary(P, count, lds, walk, occ, waves, stream));
+        HIP_TRY(launch_wf_secondary(P, v, waves, stream));
     }
     P.wf_pair_in = P.wf_pair_out = 0;
     const int top = pair_mode ? D - 2 : D - 1;            // highest level that still has to be resolved by a launch
@@ -703,7 +670,6 @@ int render_batch(p3d_scene* s, const p3d_camera* cams, int32_t n_frames, const p
     const bool can_share = !lds_scene && prm->accel != P3D_ACCEL_GRID && !packet && s->share_min_idle > 0 && s->share_min_idle <= 64 &&
                            !(prm->flags & P3D_FLAG_PRIVATE_WALK);
     bool shared_walk = can_share;
-    int walk = prm->accel == P3D_ACCEL_GRID ? 2 : (packet ? 1 : (shared_walk ? 3 : 0));
     if (prm->accel == P3D_ACCEL_GRID) {
         if (s->unit_rays_only) return fail(P3D_ERR_STATE, "scene was built with cull_never_hit: GRID mode walks the reference's grid over ALL primitives; use accel BVH");
         if (!s->grid_ready) {
@@ -807,6 +773,9 @@ int render_batch(p3d_scene* s, const p3d_camera* cams, int32_t n_frames, const p
     // workspace, every schedule (the tree included), measured like any other configuration (prm->features is in the keys)
     if (prm->features & P3D_FEATURE_SCHLICK) P.features |= kFeatSchlick;
     const bool count = (prm->flags & P3D_FLAG_COUNTERS) != 0;
+    KernelVariant kv;      // the kernel builds this frame asks for; every schedule sets its own register budget
+    kv.count = count; kv.lds = lds_scene; kv.walk = prm->accel == P3D_ACCEL_GRID ? 2 : (packet ? 1 : (shared_walk ? 3 : 0));
+    kv.stoch = stochastic; kv.schlick = feat_schlick(P.features); kv.batch = batch;
 
     // ---- schedule.  Three ways to run the same per-node code, bit-identical frames:
     //   TILE       one launch; a workgroup keeps a 16x16 tile's whole tree to itself (default)
@@ -851,13 +820,12 @@ int render_batch(p3d_scene* s, const p3d_camera* cams, int32_t n_frames, const p
         tile_blocks = 0;
         tile_ok = tile_kernel_lds_bytes(PT, lds_scene) <= kMaxLdsBytes && D <= 16;
         if (!tile_ok) return P3D_OK;
-        const uint32_t okey = (count ? 1u : 0u) | (lds_scene ? 2u : 0u) | ((uint32_t)walk << 2) | (stochastic ? 16u : 0u) | ((uint32_t)tile_occ << 5) |
-                              (feat_schlick(P.features) ? 256u : 0u) | (batch ? 512u : 0u);
+        const KernelVariant served = level_variant(with_budget(kv, tile_occ), true);
         const size_t olds = tile_kernel_lds_bytes(PT, lds_scene);
-        auto* slot = &s->tile_occ[walk == 3 ? 1 : 0];
-        if (slot->key != okey || slot->lds != olds) {
-            HIP_TRY(tile_kernel_resident_blocks(PT, count, lds_scene, walk, tile_occ, &slot->blocks));
-            slot->key = okey; slot->lds = olds;
+        auto* slot = &s->tile_occ[shared_walk ? 1 : 0];
+        if (!(slot->v == served) || slot->lds != olds) {
+            HIP_TRY(tile_kernel_resident_blocks(PT, served, &slot->blocks));
+            slot->v = served; slot->lds = olds;
         }
         tile_blocks = std::min(slot->blocks, PT.n_tiles);
         tile_blocks = (int)std::min<size_t>((size_t)tile_blocks, budget / slot_bytes);
@@ -868,7 +836,7 @@ int render_batch(p3d_scene* s, const p3d_camera* cams, int32_t n_frames, const p
     auto apply_walk = [&](bool share) -> int {            // private <-> shared walks for this frame (scenes read from HBM)
         if (share == shared_walk) return P3D_OK;
         shared_walk = share;
-        walk = shared_walk ? 3 : 0;
+        kv.walk = shared_walk ? 3 : 0;
         P.trav_stack_dwords = P.trav_stack_entries * kHbmStackDwordsPerEntry + (shared_walk ? kShareDwords : 0u);
         PT.trav_stack_dwords = P.trav_stack_dwords;
         return tile_query();
@@ -1061,8 +1029,8 @@ int render_batch(p3d_scene* s, const p3d_camera* cams, int32_t n_frames, const p
         }
         if (s->verbose)
             fprintf(stderr, "p3d: tile schedule: %d workgroups (occupancy query: %d on the device), %zu B LDS each, %zu B workspace slot, %d tiles\n",
-                    tile_blocks, s->tile_occ[walk == 3 ? 1 : 0].blocks, tile_kernel_lds_bytes(PT, lds_scene), slot_bytes, PT.n_tiles);
-        HIP_TRY(launch_wf_tile(PT, count, lds_scene, walk, tile_occ, (unsigned)tile_blocks, s->stream));
+                    tile_blocks, s->tile_occ[shared_walk ? 1 : 0].blocks, tile_kernel_lds_bytes(PT, lds_scene), slot_bytes, PT.n_tiles);
+        HIP_TRY(launch_wf_tile(PT, with_budget(kv, tile_occ), (unsigned)tile_blocks, s->stream));
         if (profile) HIP_TRY(hipEventRecord(s->ev_prof[3], s->stream));
         if (PT.tile_cost) { int rc = tile_order_end(s, tile_lpt, (uint32_t)PT.n_tiles, lpt_sort); if (rc) return rc; }
     } else if (use_tree) {
@@ -1077,7 +1045,7 @@ int render_batch(p3d_scene* s, const p3d_camera* cams, int32_t n_frames, const p
         }
         if (profile) HIP_TRY(hipEventRecord(s->ev_prof[2], s->stream));
         // scenes read from HBM: a register budget of 6 waves per SIMD (dragon with the flat walk loop: 1.285 ms at 5, 1.239 at 6)
-        HIP_TRY(launch_tree(P, count, lds_scene, s->occupancy ? s->occupancy : (lds_scene ? 0 : 6), shared_walk, s->stream));
+        HIP_TRY(launch_tree(P, with_budget(kv, s->occupancy ? s->occupancy : (lds_scene ? 0 : 6)), s->stream));
         if (profile) HIP_TRY(hipEventRecord(s->ev_prof[3], s->stream));
         if (P.tile_cost) { int rc = tile_order_end(s, wave_lpt, (uint32_t)P.n_tiles, lpt_sort); if (rc) return rc; }
     } else {
@@ -1126,8 +1094,7 @@ int render_batch(p3d_scene* s, const p3d_camera* cams, int32_t n_frames, const p
                 B.n_tiles = B.tiles_x * B.wf_tile_rows;
                 int chunks = (B.n_tiles + B.xcd_chunk - 1) / B.xcd_chunk;
                 B.grid_blocks = ((chunks + 7) / 8) * 8 * B.xcd_chunk;
-                int rc = run_wavefront_pass(s, s->ws[ln], lane_stream, B, count, lds_scene, walk, shard_px,
-                                            profile && smp == 0 && r0 == 0);
+                int rc = run_wavefront_pass(s, s->ws[ln], lane_stream, B, kv, shard_px, profile && smp == 0 && r0 == 0);
                 if (rc) return rc;
             }
         }

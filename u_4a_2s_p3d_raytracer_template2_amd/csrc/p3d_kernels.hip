@@ -23,8 +23,10 @@
 
 #include <algorithm>
 #include <cstring>
+#include <utility>
 
 #include "p3d_device_types.h"
+#include "p3d_launch.h"
 #include "p3d_shade.h"
 
 namespace p3d {
@@ -1102,186 +1104,173 @@ size_t wavefront_lds_bytes(const LaunchParams& P, bool lds) {
     return scene_lds_bytes(P, lds) + (size_t)P.trav_stack_dwords * 4 * P.wg_waves;
 }
 
-// Kernel variants are picked through function pointers: {count} x {scene in LDS} x {walk: lane / packet / grid}
-// x {register budget: only for the timed non-grid builds} x {random draws}.  Counting, grid and stochastic
-// builds always use the default register budget.
-// Schlick builds (P3D_FEATURE_SCHLICK) exist for every walk, scene placement, counting and random-draw combination the
-// dispatcher can pick, all with the default register budget.
-template <class F> static const void* fn_ptr(F f) { return reinterpret_cast<const void*>(f); }
-#define P3D_DEFINE_SELECTOR(NAME, KERNEL)                                                                         \
-    template <bool C, bool S> static const void* NAME##_schlick(bool lds, int walk) {                             \
-        if (!lds) return walk == 3 ? fn_ptr(KERNEL<C, false, 3, 1, S, true>) : walk == 2 ? fn_ptr(KERNEL<C, false, 2, 1, S, true>)         \
-                       : walk == 1 ? fn_ptr(KERNEL<C, false, 1, 1, S, true>) : fn_ptr(KERNEL<C, false, 0, 1, S, true>);                   \
-        return walk == 2 ? fn_ptr(KERNEL<C, true, 2, 1, S, true>) : walk == 1 ? fn_ptr(KERNEL<C, true, 1, 1, S, true>)                     \
-                         : fn_ptr(KERNEL<C, true, 0, 1, S, true>);                                                \
-    }                                                                                                             \
-    static const void* NAME(bool count, bool lds, int walk, int occ, bool stoch, bool schlick) {                  \
-        if (schlick) return count ? (stoch ? NAME##_schlick<true, true>(lds, walk) : NAME##_schlick<true, false>(lds, walk))             \
-                                  : (stoch ? NAME##_schlick<false, true>(lds, walk) : NAME##_schlick<false, false>(lds, walk));          \
-        if (walk == WALK_GRID || count || stoch) occ = 1;                                                         \
-        if (walk == WALK_SHARED && !lds) {                                                                        \
-            if (stoch) return count ? fn_ptr(KERNEL<true, false, 3, 1, true>) : fn_ptr(KERNEL<false, false, 3, 1, true>);                                                                  \
-            if (count) return fn_ptr(KERNEL<true, false, 3, 1, false>);                                           \
-            return occ == 5 ? fn_ptr(KERNEL<false, false, 3, 5, false>) : occ == 6 ? fn_ptr(KERNEL<false, false, 3, 6, false>) : fn_ptr(KERNEL<false, false, 3, 1, false>);               \
-        }                                                                                                         \
-        if (walk == WALK_SHARED) walk = WALK_LANE;                                                                \
-        if (stoch) {                                                                                              \
-            if (count) return lds ? (walk == 2 ? fn_ptr(KERNEL<true, true, 2, 1, true>) : walk == 1 ? fn_ptr(KERNEL<true, true, 1, 1, true>) : fn_ptr(KERNEL<true, true, 0, 1, true>))       \
-                                  : (walk == 2 ? fn_ptr(KERNEL<true, false, 2, 1, true>) : walk == 1 ? fn_ptr(KERNEL<true, false, 1, 1, true>) : fn_ptr(KERNEL<true, false, 0, 1, true>));   \
-            return lds ? (walk == 2 ? fn_ptr(KERNEL<false, true, 2, 1, true>) : walk == 1 ? fn_ptr(KERNEL<false, true, 1, 1, true>) : fn_ptr(KERNEL<false, true, 0, 1, true>))              \
-                       : (walk == 2 ? fn_ptr(KERNEL<false, false, 2, 1, true>) : walk == 1 ? fn_ptr(KERNEL<false, false, 1, 1, true>) : fn_ptr(KERNEL<false, false, 0, 1, true>));          \
-        }                                                                                                         \
-        if (count) return lds ? (walk == 2 ? fn_ptr(KERNEL<true, true, 2, 1, false>) : walk == 1 ? fn_ptr(KERNEL<true, true, 1, 1, false>) : fn_ptr(KERNEL<true, true, 0, 1, false>))      \
-                              : (walk == 2 ? fn_ptr(KERNEL<true, false, 2, 1, false>) : walk == 1 ? fn_ptr(KERNEL<true, false, 1, 1, false>) : fn_ptr(KERNEL<true, false, 0, 1, false>));  \
-        if (walk == 2) return lds ? fn_ptr(KERNEL<false, true, 2, 1, false>) : fn_ptr(KERNEL<false, false, 2, 1, false>);                                                                  \
-        if (occ == 5) return lds ? (walk == 1 ? fn_ptr(KERNEL<false, true, 1, 5, false>) : fn_ptr(KERNEL<false, true, 0, 5, false>))                                                        \
-                                 : (walk == 1 ? fn_ptr(KERNEL<false, false, 1, 5, false>) : fn_ptr(KERNEL<false, false, 0, 5, false>));                                                     \
-        if (occ == 6) return lds ? (walk == 1 ? fn_ptr(KERNEL<false, true, 1, 6, false>) : fn_ptr(KERNEL<false, true, 0, 6, false>))                                                        \
-                                 : (walk == 1 ? fn_ptr(KERNEL<false, false, 1, 6, false>) : fn_ptr(KERNEL<false, false, 0, 6, false>));                                                     \
-        return lds ? (walk == 1 ? fn_ptr(KERNEL<false, true, 1, 1, false>) : fn_ptr(KERNEL<false, true, 0, 1, false>))                                                                      \
-                   : (walk == 1 ? fn_ptr(KERNEL<false, false, 1, 1, false>) : fn_ptr(KERNEL<false, false, 0, 1, false>));                                                                   \
-    }
-P3D_DEFINE_SELECTOR(wf_primary_fn, wf_primary_kernel)
-P3D_DEFINE_SELECTOR(wf_secondary_fn, wf_secondary_kernel)
-P3D_DEFINE_SELECTOR(wf_tile_fn, wf_tile_kernel)
-#undef P3D_DEFINE_SELECTOR
+// Kernel variants.  The host asks with a KernelVariant (p3d_launch.h); not every combination of its switches is built.
+// Per kernel family: canonical_*() maps a request to the build that serves it, built_*() is the one statement of which
+// builds exist, and a table over all combinations holds the kernels' pointers -- nullptr where nothing is built.
+using KernelFn = void (*)(const LaunchParams);
+constexpr int kOccs[3] = {1, 5, 6};               // register budgets: the compiler's default, 5 and 6 waves per SIMD
+constexpr int kPrivs[3] = {0, 36, 84};            // tree kernel: dwords of private frames (0: frames in LDS)
+constexpr int kLevelVariants = 2 * 2 * 4 * 3 * 2 * 2 * 2, kTreeVariants = kLevelVariants * 3;
 
-// Frame batches (BATCH = true): the kernels that make camera rays, for every walk, scene placement, counting, random-draw
-// and Schlick combination, all with the default register budget (the deeper levels and the resolves are shared).
-#define P3D_DEFINE_BATCH_SELECTOR(NAME, KERNEL)                                                                   \
-    template <bool C, bool S, bool K> static const void* NAME##_b(bool lds, int walk) {                          \
-        if (!lds) return walk == 3 ? fn_ptr(KERNEL<C, false, 3, 1, S, K, true>) : walk == 2 ? fn_ptr(KERNEL<C, false, 2, 1, S, K, true>)   \
-                       : walk == 1 ? fn_ptr(KERNEL<C, false, 1, 1, S, K, true>) : fn_ptr(KERNEL<C, false, 0, 1, S, K, true>);             \
-        return walk == 2 ? fn_ptr(KERNEL<C, true, 2, 1, S, K, true>) : walk == 1 ? fn_ptr(KERNEL<C, true, 1, 1, S, K, true>)               \
-                         : fn_ptr(KERNEL<C, true, 0, 1, S, K, true>);                                            \
-    }                                                                                                             \
-    static const void* NAME(bool count, bool lds, int walk, bool stoch, bool schlick) {                          \
-        if (lds && walk == WALK_SHARED) walk = WALK_LANE;                                                         \
-        if (count) return stoch ? (schlick ? NAME##_b<true, true, true>(lds, walk) : NAME##_b<true, true, false>(lds, walk))           \
-                                : (schlick ? NAME##_b<true, false, true>(lds, walk) : NAME##_b<true, false, false>(lds, walk));        \
-        return stoch ? (schlick ? NAME##_b<false, true, true>(lds, walk) : NAME##_b<false, true, false>(lds, walk))                    \
-                     : (schlick ? NAME##_b<false, false, true>(lds, walk) : NAME##_b<false, false, false>(lds, walk));                 \
-    }
-P3D_DEFINE_BATCH_SELECTOR(wf_primary_batch_fn, wf_primary_kernel)
-P3D_DEFINE_BATCH_SELECTOR(wf_tile_batch_fn, wf_tile_kernel)
-#undef P3D_DEFINE_BATCH_SELECTOR
-static const void* wf_primary_pick(const LaunchParams& P, bool count, bool lds, int walk, int occ) {
-    return P.n_frames > 1 ? wf_primary_batch_fn(count, lds, walk, feat_stochastic(P.features), feat_schlick(P.features))
-                          : wf_primary_fn(count, lds, walk, occ, feat_stochastic(P.features), feat_schlick(P.features));
+// position of a canonical variant (occ is 1, 5 or 6) in a family's table, and the variant at a position.  A walk that is
+// none of the four has no position, so the launch fails with hipErrorInvalidDeviceFunction; no caller passes one.
+constexpr int variant_index(const KernelVariant& v) {
+    if (v.walk < WALK_LANE || v.walk > WALK_SHARED) return -1;
+    return (((((v.count * 2 + v.lds) * 4 + v.walk) * 3 + (v.occ == 5 ? 1 : v.occ == 6 ? 2 : 0)) * 2 + v.stoch) * 2 + v.schlick) * 2 + v.batch;
 }
-static const void* wf_tile_pick(const LaunchParams& P, bool count, bool lds, int walk, int occ) {
-    return P.n_frames > 1 ? wf_tile_batch_fn(count, lds, walk, feat_stochastic(P.features), feat_schlick(P.features))
-                          : wf_tile_fn(count, lds, walk, occ, feat_stochastic(P.features), feat_schlick(P.features));
+constexpr KernelVariant variant_at(int i) {
+    KernelVariant v;
+    v.batch = i % 2; i /= 2; v.schlick = i % 2; i /= 2; v.stoch = i % 2; i /= 2;
+    v.occ = kOccs[i % 3]; i /= 3; v.walk = i % 4; i /= 4; v.lds = i % 2; v.count = i / 2;
+    return v;
 }
 
-template <bool C> static const void* tree_schlick_fn(bool lds, bool grid, int priv, bool shared) {
-    if (grid) return lds ? fn_ptr(whitted_tree_kernel<C, true, 1, true, 0, false, true>) : fn_ptr(whitted_tree_kernel<C, false, 1, true, 0, false, true>);
-    if (lds) return fn_ptr(whitted_tree_kernel<C, true, 1, false, 0, false, true>);
-    if (shared) return priv == 36 ? fn_ptr(whitted_tree_kernel<C, false, 1, false, 36, true, true>)
-                     : priv == 84 ? fn_ptr(whitted_tree_kernel<C, false, 1, false, 84, true, true>) : fn_ptr(whitted_tree_kernel<C, false, 1, false, 0, true, true>);
-    return priv == 36 ? fn_ptr(whitted_tree_kernel<C, false, 1, false, 36, false, true>)
-         : priv == 84 ? fn_ptr(whitted_tree_kernel<C, false, 1, false, 84, false, true>) : fn_ptr(whitted_tree_kernel<C, false, 1, false, 0, false, true>);
+// The level kernels (wf_primary_kernel, wf_tile_kernel; wf_secondary_kernel has no BATCH: the deeper levels are shared).
+constexpr KernelVariant canonical_level(KernelVariant v, bool has_batch) {
+    if (!has_batch) v.batch = false;
+    if (v.walk == WALK_SHARED && v.lds) v.walk = WALK_LANE;        // LDS scenes have no shared walk
+    // a register budget only for the timed builds of the BVH walks: grid, counting, stochastic, Schlick and batch builds use the default
+    if ((v.occ != 5 && v.occ != 6) || v.walk == WALK_GRID || v.count || v.stoch || v.schlick || v.batch) v.occ = 1;
+    return v;
 }
-template <bool C, bool K> static const void* tree_batch_fn(bool lds, bool grid, int priv, bool shared) {
-    if (grid) return lds ? fn_ptr(whitted_tree_kernel<C, true, 1, true, 0, false, K, true>) : fn_ptr(whitted_tree_kernel<C, false, 1, true, 0, false, K, true>);
-    if (lds) return fn_ptr(whitted_tree_kernel<C, true, 1, false, 0, false, K, true>);
-    if (shared) return priv == 36 ? fn_ptr(whitted_tree_kernel<C, false, 1, false, 36, true, K, true>)
-                     : priv == 84 ? fn_ptr(whitted_tree_kernel<C, false, 1, false, 84, true, K, true>) : fn_ptr(whitted_tree_kernel<C, false, 1, false, 0, true, K, true>);
-    return priv == 36 ? fn_ptr(whitted_tree_kernel<C, false, 1, false, 36, false, K, true>)
-         : priv == 84 ? fn_ptr(whitted_tree_kernel<C, false, 1, false, 84, false, K, true>) : fn_ptr(whitted_tree_kernel<C, false, 1, false, 0, false, K, true>);
+constexpr bool built_level(const KernelVariant& v, bool has_batch) {
+    if (v.batch && !has_batch) return false;
+    if (v.walk == WALK_SHARED && v.lds) return false;
+    if (v.occ == 1) return true;
+    return v.walk != WALK_GRID && !v.count && !v.stoch && !v.schlick && !v.batch;
 }
-static const void* tree_fn(bool count, bool lds, int occ, bool grid, int priv = 0, bool shared = false, bool schlick = false, bool batch = false) {
-    if (batch) return count ? (schlick ? tree_batch_fn<true, true>(lds, grid, priv, shared) : tree_batch_fn<true, false>(lds, grid, priv, shared))
-                            : (schlick ? tree_batch_fn<false, true>(lds, grid, priv, shared) : tree_batch_fn<false, false>(lds, grid, priv, shared));
-    if (schlick) return count ? tree_schlick_fn<true>(lds, grid, priv, shared) : tree_schlick_fn<false>(lds, grid, priv, shared);
-    if (shared && !lds && !grid && priv == 36) {
-        if (count) return fn_ptr(whitted_tree_kernel<true, false, 1, false, 36, true>);
-        return occ == 5 ? fn_ptr(whitted_tree_kernel<false, false, 5, false, 36, true>) : occ == 6 ? fn_ptr(whitted_tree_kernel<false, false, 6, false, 36, true>)
-                                                                                                 : fn_ptr(whitted_tree_kernel<false, false, 1, false, 36, true>);
+// The tree kernel: GRID = grid walk, SHARED = shared walk (the packet walk is the lane walk here), PRIV from the depth
+// (tree_private_dwords); the schedule never runs features with random draws.
+constexpr int canonical_priv(const KernelVariant& v, int priv) {
+    return (v.lds || v.walk == WALK_GRID || (priv != 36 && priv != 84)) ? 0 : priv;      // LDS scenes and the grid walk: frames in LDS
+}
+constexpr KernelVariant canonical_tree(KernelVariant v, int priv) {
+    v.stoch = false;
+    if (v.walk == WALK_PACKET || (v.walk == WALK_SHARED && v.lds)) v.walk = WALK_LANE;
+    if ((v.occ != 5 && v.occ != 6) || v.walk == WALK_GRID || v.count || v.schlick || v.batch || (v.walk == WALK_SHARED && priv == 0)) v.occ = 1;
+    return v;
+}
+constexpr bool built_tree(const KernelVariant& v, int priv) {
+    if (v.stoch || v.walk == WALK_PACKET || (v.walk == WALK_SHARED && v.lds)) return false;
+    if (priv != 0 && (v.lds || v.walk == WALK_GRID)) return false;
+    if (v.occ == 1) return true;
+    return v.walk != WALK_GRID && !v.count && !v.schlick && !v.batch && !(v.walk == WALK_SHARED && priv == 0);
+}
+
+// Every request reaches a build, and nothing is built that no request reaches.
+constexpr bool variants_are_consistent() {
+    constexpr int raw_occs[] = {0, 1, 5, 6, 8}, raw_privs[] = {0, 36, 84, 12};
+    for (int i = 0; i < kLevelVariants; i++) {
+        for (int occ : raw_occs) {
+            KernelVariant v = variant_at(i);
+            v.occ = occ;
+            if (!built_level(canonical_level(v, true), true) || !built_level(canonical_level(v, false), false)) return false;
+            for (int priv : raw_privs)
+                if (!built_tree(canonical_tree(v, canonical_priv(v, priv)), canonical_priv(v, priv))) return false;
+        }
+        const KernelVariant v = variant_at(i);
+        if (built_level(v, true) && !(canonical_level(v, true) == v)) return false;
+        if (built_level(v, false) && !(canonical_level(v, false) == v)) return false;
+        for (int priv : kPrivs)
+            if (built_tree(v, priv) && !(canonical_priv(v, priv) == priv && canonical_tree(v, priv) == v)) return false;
     }
-    if (shared && !lds && !grid && priv == 84) {
-        if (count) return fn_ptr(whitted_tree_kernel<true, false, 1, false, 84, true>);
-        return occ == 5 ? fn_ptr(whitted_tree_kernel<false, false, 5, false, 84, true>) : occ == 6 ? fn_ptr(whitted_tree_kernel<false, false, 6, false, 84, true>)
-                                                                                                 : fn_ptr(whitted_tree_kernel<false, false, 1, false, 84, true>);
+    return true;
+}
+static_assert(variants_are_consistent(), "a kernel request maps to a variant that is not built, or a built variant is unreachable");
+
+enum class Level { Primary, Secondary, Tile };
+template <Level KERNEL> struct LevelKernels {
+    static constexpr int n = kLevelVariants;
+    static constexpr bool has_batch = KERNEL != Level::Secondary;
+    static constexpr bool built(int i) { return built_level(variant_at(i), has_batch); }
+    template <int I> static constexpr KernelFn fn() {
+        constexpr KernelVariant v = variant_at(I);
+        if constexpr (KERNEL == Level::Primary) return wf_primary_kernel<v.count, v.lds, v.walk, v.occ, v.stoch, v.schlick, v.batch>;
+        else if constexpr (KERNEL == Level::Secondary) return wf_secondary_kernel<v.count, v.lds, v.walk, v.occ, v.stoch, v.schlick>;
+        else return wf_tile_kernel<v.count, v.lds, v.walk, v.occ, v.stoch, v.schlick, v.batch>;
     }
-    if (shared && !lds && !grid && priv == 0) {
-        if (count) return fn_ptr(whitted_tree_kernel<true, false, 1, false, 0, true>);
-        return fn_ptr(whitted_tree_kernel<false, false, 1, false, 0, true>);
+};
+struct TreeKernels {                                // position: variant_index * 3 + position of PRIV in kPrivs
+    static constexpr int n = kTreeVariants;
+    static constexpr bool built(int i) { return built_tree(variant_at(i / 3), kPrivs[i % 3]); }
+    template <int I> static constexpr KernelFn fn() {
+        constexpr KernelVariant v = variant_at(I / 3);
+        return whitted_tree_kernel<v.count, v.lds, v.occ, v.walk == WALK_GRID, kPrivs[I % 3], v.walk == WALK_SHARED, v.schlick, v.batch>;
     }
-    if (grid) return count ? (lds ? fn_ptr(whitted_tree_kernel<true, true, 1, true>) : fn_ptr(whitted_tree_kernel<true, false, 1, true>))
-                           : (lds ? fn_ptr(whitted_tree_kernel<false, true, 1, true>) : fn_ptr(whitted_tree_kernel<false, false, 1, true>));
-    if (!lds && priv == 36) {
-        if (count) return fn_ptr(whitted_tree_kernel<true, false, 1, false, 36>);
-        return occ == 5 ? fn_ptr(whitted_tree_kernel<false, false, 5, false, 36>) : occ == 6 ? fn_ptr(whitted_tree_kernel<false, false, 6, false, 36>)
-                                                                                           : fn_ptr(whitted_tree_kernel<false, false, 1, false, 36>);
-    }
-    if (!lds && priv == 84) {
-        if (count) return fn_ptr(whitted_tree_kernel<true, false, 1, false, 84>);
-        return occ == 5 ? fn_ptr(whitted_tree_kernel<false, false, 5, false, 84>) : occ == 6 ? fn_ptr(whitted_tree_kernel<false, false, 6, false, 84>)
-                                                                                           : fn_ptr(whitted_tree_kernel<false, false, 1, false, 84>);
-    }
-    if (count) return lds ? fn_ptr(whitted_tree_kernel<true, true, 1>) : fn_ptr(whitted_tree_kernel<true, false, 1>);
-    if (occ == 5) return lds ? fn_ptr(whitted_tree_kernel<false, true, 5>) : fn_ptr(whitted_tree_kernel<false, false, 5>);
-    if (occ == 6) return lds ? fn_ptr(whitted_tree_kernel<false, true, 6>) : fn_ptr(whitted_tree_kernel<false, false, 6>);
-    return lds ? fn_ptr(whitted_tree_kernel<false, true, 1>) : fn_ptr(whitted_tree_kernel<false, false, 1>);
+};
+// the walk over a family's positions: a kernel is instantiated only where built() says so
+template <class K, int I> constexpr KernelFn variant_fn() {
+    if constexpr (K::built(I)) return K::template fn<I>();
+    else return nullptr;
+}
+template <class K, int... I> static const void* kernel_lookup(int i, std::integer_sequence<int, I...>) {
+    static constexpr KernelFn table[] = {variant_fn<K, I>()...};
+    return i >= 0 && i < K::n ? reinterpret_cast<const void*>(table[i]) : nullptr;
+}
+template <class K> static const void* kernel_at(int i) { return kernel_lookup<K>(i, std::make_integer_sequence<int, K::n>{}); }
+
+KernelVariant level_variant(KernelVariant v, bool has_batch) { return canonical_level(v, has_batch); }
+template <class K> static const void* level_kernel(const KernelVariant& v) { return kernel_at<K>(variant_index(canonical_level(v, K::has_batch))); }
+static const void* tree_kernel(const LaunchParams& P, const KernelVariant& v) {
+    const int priv = canonical_priv(v, tree_private_dwords(P, v.lds));
+    const int i = variant_index(canonical_tree(v, priv));
+    return i < 0 ? nullptr : kernel_at<TreeKernels>(i * 3 + (priv == 36 ? 1 : priv == 84 ? 2 : 0));
 }
 static hipError_t launch_by_pointer(const void* fn, const LaunchParams& P, dim3 grid, dim3 block, size_t shmem, hipStream_t stream) {
+    if (!fn) return hipErrorInvalidDeviceFunction;
     LaunchParams Pc = P;
     void* args[] = {&Pc};
     return hipLaunchKernel(fn, grid, block, args, shmem, stream);
 }
-
-hipError_t launch_tree(const LaunchParams& P, bool count, bool lds, int occ, bool shared, hipStream_t stream) {
-    return launch_by_pointer(tree_fn(count, lds, occ, P.accel == 1, tree_private_dwords(P, lds), shared, feat_schlick(P.features), P.n_frames > 1), P, dim3((unsigned)P.grid_blocks),
-                             dim3(64 * P.wg_waves), tree_kernel_lds_bytes(P, lds), stream);
-}
-hipError_t launch_wf_primary(const LaunchParams& P, bool count, bool lds, int walk, int occ, hipStream_t stream) {
-    // identity tile map and no learned order: a 2-D grid, blockIdx = (tile column, tile row) -- see tile_pixel()
-    // (LDS scenes only: the kernels of scenes read from HBM number their tiles through the learned order)
-    const bool grid2d = lds && P.xcd_chunk == 1 && P.wf_tile_rows > 1 && P.tiles_x * P.wf_tile_rows == P.n_tiles;
-    const dim3 grid = grid2d ? dim3((unsigned)P.tiles_x, (unsigned)P.wf_tile_rows) : dim3((unsigned)P.grid_blocks);
-    return launch_by_pointer(wf_primary_pick(P, count, lds, walk, occ), P, grid,
-                             dim3(64 * P.wg_waves), wavefront_lds_bytes(P, lds), stream);
-}
-hipError_t launch_wf_secondary(const LaunchParams& P, bool count, bool lds, int walk, int occ, unsigned waves,
-                               hipStream_t stream) {
-    return launch_by_pointer(wf_secondary_fn(count, lds, walk, occ, feat_stochastic(P.features), feat_schlick(P.features)), P, dim3((waves + P.wg_waves - 1) / P.wg_waves),
-                             dim3(64 * P.wg_waves), wavefront_lds_bytes(P, lds), stream);
-}
-// waves of the deeper-level kernel that can be resident on the device at once (LDS-scene variants: 256-thread workgroups)
-hipError_t wf_resident_waves(const LaunchParams& P, bool primary, bool count, bool lds, int walk, int occ, unsigned* waves) {
-    const void* fn = primary ? wf_primary_pick(P, count, lds, walk, occ) : wf_secondary_fn(count, lds, walk, occ, feat_stochastic(P.features), feat_schlick(P.features));
+// workgroups of `fn` that can be resident on the whole device
+static hipError_t resident_blocks(const void* fn, int block, size_t shmem, int* blocks) {
+    if (!fn) return hipErrorInvalidDeviceFunction;
     int per_cu = 0, dev = 0, cus = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * P.wg_waves, wavefront_lds_bytes(P, lds));
-    if (e != hipSuccess) return e;
-    if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
-    if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
-    *waves = (unsigned)((per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1) * P.wg_waves);
-    return hipSuccess;
-}
-// tile schedule: 256-thread workgroups
-size_t tile_kernel_lds_bytes(const LaunchParams& P, bool lds) {
-    return scene_lds_bytes(P, lds) + (size_t)P.trav_stack_dwords * 4 * 4 + (sizeof(TileLds) + 15) / 16 * 16 + (lds ? (size_t)kTileLdsRayDwords * 4 : 0);
-}
-// workgroups of this variant that can be resident on the whole device (persistent grid size)
-hipError_t tile_kernel_resident_blocks(const LaunchParams& P, bool count, bool lds, int walk, int occ, int* blocks) {
-    const void* fn = wf_tile_pick(P, count, lds, walk, occ);
-    const size_t shmem = tile_kernel_lds_bytes(P, lds);
-    if (shmem > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        if (e != hipSuccess) return e;
-    }
-    int per_cu = 0, dev = 0, cus = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 256, shmem);
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, block, shmem);
     if (e != hipSuccess) return e;
     if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
     if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
     *blocks = (per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
     return hipSuccess;
 }
-hipError_t launch_wf_tile(const LaunchParams& P, bool count, bool lds, int walk, int occ, unsigned blocks, hipStream_t stream) {
-    return launch_by_pointer(wf_tile_pick(P, count, lds, walk, occ), P, dim3(blocks), dim3(256),
-                             tile_kernel_lds_bytes(P, lds), stream);
+
+hipError_t launch_tree(const LaunchParams& P, const KernelVariant& v, hipStream_t stream) {
+    return launch_by_pointer(tree_kernel(P, v), P, dim3((unsigned)P.grid_blocks), dim3(64 * P.wg_waves), tree_kernel_lds_bytes(P, v.lds), stream);
+}
+hipError_t launch_wf_primary(const LaunchParams& P, const KernelVariant& v, hipStream_t stream) {
+    // identity tile map and no learned order: a 2-D grid, blockIdx = (tile column, tile row) -- see tile_pixel()
+    // (LDS scenes only: the kernels of scenes read from HBM number their tiles through the learned order)
+    const bool grid2d = v.lds && P.xcd_chunk == 1 && P.wf_tile_rows > 1 && P.tiles_x * P.wf_tile_rows == P.n_tiles;
+    const dim3 grid = grid2d ? dim3((unsigned)P.tiles_x, (unsigned)P.wf_tile_rows) : dim3((unsigned)P.grid_blocks);
+    return launch_by_pointer(level_kernel<LevelKernels<Level::Primary>>(v), P, grid, dim3(64 * P.wg_waves), wavefront_lds_bytes(P, v.lds), stream);
+}
+hipError_t launch_wf_secondary(const LaunchParams& P, const KernelVariant& v, unsigned waves, hipStream_t stream) {
+    return launch_by_pointer(level_kernel<LevelKernels<Level::Secondary>>(v), P, dim3((waves + P.wg_waves - 1) / P.wg_waves),
+                             dim3(64 * P.wg_waves), wavefront_lds_bytes(P, v.lds), stream);
+}
+// waves of the deeper-level kernel that can be resident on the device at once (LDS-scene variants: 256-thread workgroups)
+hipError_t wf_resident_waves(const LaunchParams& P, const KernelVariant& v, unsigned* waves) {
+    int blocks = 0;
+    hipError_t e = resident_blocks(level_kernel<LevelKernels<Level::Secondary>>(v), 64 * P.wg_waves, wavefront_lds_bytes(P, v.lds), &blocks);
+    if (e == hipSuccess) *waves = (unsigned)(blocks * P.wg_waves);
+    return e;
+}
+// tile schedule: 256-thread workgroups
+size_t tile_kernel_lds_bytes(const LaunchParams& P, bool lds) {
+    return scene_lds_bytes(P, lds) + (size_t)P.trav_stack_dwords * 4 * 4 + (sizeof(TileLds) + 15) / 16 * 16 + (lds ? (size_t)kTileLdsRayDwords * 4 : 0);
+}
+// workgroups of this variant that can be resident on the whole device (persistent grid size)
+hipError_t tile_kernel_resident_blocks(const LaunchParams& P, const KernelVariant& v, int* blocks) {
+    const void* fn = level_kernel<LevelKernels<Level::Tile>>(v);
+    const size_t shmem = tile_kernel_lds_bytes(P, v.lds);
+    if (fn && shmem > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+        if (e != hipSuccess) return e;
+    }
+    return resident_blocks(fn, 256, shmem, blocks);
+}
+hipError_t launch_wf_tile(const LaunchParams& P, const KernelVariant& v, unsigned blocks, hipStream_t stream) {
+    return launch_by_pointer(level_kernel<LevelKernels<Level::Tile>>(v), P, dim3(blocks), dim3(256), tile_kernel_lds_bytes(P, v.lds), stream);
 }
 
 
@@ -1332,21 +1321,11 @@ hipError_t launch_sum_samples(const LaunchParams& P, size_t first_px, size_t n_p
 }
 
 hipError_t prepare_kernels(size_t max_lds) {
-    // only the tree kernel without an LDS scene copy can need more than the 64 KiB default
-    const void* fns[] = {tree_fn(true, false, 1, false), tree_fn(false, false, 1, false), tree_fn(false, false, 5, false),
-                         tree_fn(false, false, 6, false), tree_fn(true, false, 1, true), tree_fn(false, false, 1, true),
-                         tree_fn(true, false, 1, false, 0, true), tree_fn(false, false, 1, false, 0, true),
-                         tree_fn(true, false, 1, false, 0, false, true), tree_fn(false, false, 1, false, 0, false, true),
-                         tree_fn(true, false, 1, true, 0, false, true), tree_fn(false, false, 1, true, 0, false, true),
-                         tree_fn(true, false, 1, false, 0, true, true), tree_fn(false, false, 1, false, 0, true, true)};
-    for (const void* f : fns) {
-        hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds);
-        if (e != hipSuccess) return e;
-    }
-    for (int k = 0; k < 16; k++) {           // ... and their batch builds (count x grid x shared x schlick)
-        if ((k & 2) && (k & 4)) continue;    // (GRID mode has no shared walk)
-        hipError_t e = hipFuncSetAttribute(tree_fn(k & 1, false, 1, (k & 2) != 0, 0, (k & 4) != 0, (k & 8) != 0, true),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds);
+    // only the tree kernel without an LDS scene copy and with its frames in LDS can need more than the 64 KiB default
+    for (int i = 0; i < kTreeVariants; i += 3) {          // (PRIV == 0: every third position)
+        const void* fn = kernel_at<TreeKernels>(i);
+        if (!fn || variant_at(i / 3).lds) continue;
+        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;

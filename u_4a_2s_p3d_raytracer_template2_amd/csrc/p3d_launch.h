@@ -1,0 +1,71 @@
+// p3d_launch.h -- what p3d_kernels.hip and bvh_device.hip export to the host side (p3d_capi.cpp).
+#ifndef P3D_LAUNCH_H
+#define P3D_LAUNCH_H
+
+#include <hip/hip_runtime_api.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include <vector>
+
+#include "bvh_builder.h"
+#include "p3d_device_types.h"
+
+namespace p3d {
+
+// One build of a ray kernel, as the host asks for it.  Not every combination is built: the dispatchers of
+// p3d_kernels.hip map a request to the build that serves it (level_variant() below tells which one that is).
+struct KernelVariant {
+    bool count = false;     // P3D_FLAG_COUNTERS
+    bool lds = false;       // scene read from an LDS copy
+    int walk = 0;           // WALK_LANE / _PACKET / _GRID / _SHARED (p3d_shade.h)
+    int occ = 1;            // register budget in waves per SIMD: 5 or 6; anything else is the compiler's default
+    bool stoch = false;     // features with random draws
+    bool schlick = false;   // P3D_FEATURE_SCHLICK
+    bool batch = false;     // frame batch (p3d_render_frames)
+    constexpr bool operator==(const KernelVariant& o) const {
+        return count == o.count && lds == o.lds && walk == o.walk && occ == o.occ && stoch == o.stoch && schlick == o.schlick &&
+               batch == o.batch;
+    }
+};
+
+// ---- p3d_kernels.hip
+// the build of a level kernel that serves v (has_batch: wf_primary_kernel and wf_tile_kernel; the deeper levels are shared)
+KernelVariant level_variant(KernelVariant v, bool has_batch);
+size_t tree_kernel_lds_bytes(const LaunchParams& P, bool lds);
+size_t wavefront_lds_bytes(const LaunchParams& P, bool lds);
+size_t tile_kernel_lds_bytes(const LaunchParams& P, bool lds);
+hipError_t launch_tree(const LaunchParams& P, const KernelVariant& v, hipStream_t stream);
+hipError_t launch_wf_primary(const LaunchParams& P, const KernelVariant& v, hipStream_t stream);
+hipError_t launch_wf_secondary(const LaunchParams& P, const KernelVariant& v, unsigned waves, hipStream_t stream);
+hipError_t launch_wf_tile(const LaunchParams& P, const KernelVariant& v, unsigned blocks, hipStream_t stream);
+hipError_t wf_resident_waves(const LaunchParams& P, const KernelVariant& v, unsigned* waves);
+hipError_t tile_kernel_resident_blocks(const LaunchParams& P, const KernelVariant& v, int* blocks);
+hipError_t prepare_kernels(size_t max_lds);
+hipError_t launch_wf_resolve(const LaunchParams& P, unsigned blocks, hipStream_t stream);
+hipError_t launch_wf_resolve_fused(const LaunchParams& P, const ResolveLevels& R, unsigned shards, hipStream_t stream);
+hipError_t launch_clear_words(uint32_t* p, uint32_t n, hipStream_t stream);
+hipError_t launch_frame_cams(FrameCam* dst, const FrameCam* cams, int n, hipStream_t stream);
+hipError_t launch_raygen_table(float* fx, float* fy, int res_x, int res_y, hipStream_t stream);
+hipError_t launch_sum_samples(const LaunchParams& P, size_t first_px, size_t n_px, hipStream_t stream);
+hipError_t launch_deinterleave(const void* gathered, void* frames, int res_x, int res_y, int row_block,
+                               int world, size_t rank_stride, int bpp, int n_frames, size_t in_stride,
+                               size_t out_stride, hipStream_t stream);
+bool kernels_have_stamps();
+hipError_t launch_debug_check_rcp(uint32_t first, uint64_t count, unsigned long long* n_bad, uint32_t* first_bad, hipStream_t stream);
+hipError_t launch_debug_check_rcp_len(uint32_t first, uint64_t count, unsigned long long* n_bad, uint32_t* first_bad, hipStream_t stream);
+hipError_t launch_debug_powf(uint32_t n, const float* x, const float* y, float* out, hipStream_t stream);
+hipError_t launch_debug_pow(uint32_t n, const double* x, const double* y, double* out, hipStream_t stream);
+hipError_t launch_debug_schlick_kr(uint32_t n, const float* ior_1, const float* new_ior, const float* cos_theta_i, float* out,
+                                   hipStream_t stream);
+hipError_t launch_debug_intersect(uint32_t n, const uint32_t* type, const float* prim12, const float* origin,
+                                  const float* dir, int32_t* hit, float* t, float* normal, hipStream_t stream);
+
+// ---- bvh_device.hip
+hipError_t build_lbvh_device(const std::vector<BuildPrim>& prims, const BvhOptions& opt, NodePair* d_nodes,
+                             uint32_t* d_refs, BvhStats& stats, hipStream_t stream);
+hipError_t sort_tiles_by_cost(const uint32_t* cost, uint32_t* cost_sorted, uint32_t* iota, uint32_t* order, uint32_t n,
+                              void* temp, size_t& temp_bytes, hipStream_t stream);
+
+}  // namespace p3d
+#endif
