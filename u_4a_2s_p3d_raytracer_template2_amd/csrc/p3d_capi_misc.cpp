@@ -1,0 +1,258 @@
+// p3d_capi_misc.cpp -- the small entries of include/p3d_hip.h: errors, device queries, synchronisation, counters,
+// profile and timers, de-interleaving, device memory for callers, and the debug entries that run one device function.
+#include <cstring>
+
+#include "p3d_scene_state.h"
+
+using namespace p3d;
+
+namespace {
+thread_local std::string g_err;
+}
+
+extern "C" int p3d_internal_set_error(int code, const char* msg) { g_err = msg ? msg : ""; return code; }
+// device and stream a scene is bound to (for p3d_comm.cpp)
+extern "C" int p3d_internal_scene_binding(p3d_scene* s, int* device, void** stream) {
+    if (!s) return fail(P3D_ERR_ARG, "scene is NULL");
+    *device = s->device; *stream = (void*)s->stream;
+    return P3D_OK;
+}
+
+extern "C" {
+
+int p3d_abi_version(void) { return P3D_ABI_VERSION; }
+const char* p3d_last_error(void) { return g_err.c_str(); }
+
+int p3d_device_count(int* count) {
+    if (!count) return fail(P3D_ERR_ARG, "count is NULL");
+    int n = 0;
+    hipError_t e = hipGetDeviceCount(&n);
+    if (e != hipSuccess) { *count = 0; return fail(P3D_ERR_NO_DEVICE, hipGetErrorString(e)); }
+    *count = n;
+    return P3D_OK;
+}
+
+int p3d_local_rows(int32_t res_y, int32_t row_block, int32_t world) {
+    if (row_block <= 0) row_block = 16;
+    if (world <= 0) world = 1;
+    int nblocks = (res_y + row_block - 1) / row_block;
+    return ((nblocks + world - 1) / world) * row_block;
+}
+
+int p3d_sync(p3d_scene* s) {
+    if (!s) return fail(P3D_ERR_ARG, "scene is NULL");
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return P3D_OK;
+}
+
+int p3d_get_counters(p3d_scene* s, p3d_counters* out) {
+    if (!s || !out) return fail(P3D_ERR_ARG, "scene/out is NULL");
+    if (!s->counters_valid) return fail(P3D_ERR_STATE, "no render with P3D_FLAG_COUNTERS yet");
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    DeviceCounters c;
+    HIP_TRY(hipMemcpy(&c, s->d_counters.p, sizeof c, hipMemcpyDeviceToHost));
+    out->closest_queries = c.closest_queries; out->shadow_queries = c.shadow_queries;
+    out->box_tests = c.box_tests; out->sphere_tests = c.sphere_tests; out->tri_tests = c.tri_tests;
+    out->aabox_tests = c.aabox_tests; out->plane_tests = c.plane_tests; out->pixels = c.pixels;
+    return P3D_OK;
+}
+
+int p3d_debug_set_stamps(p3d_scene* s, void* device_buffer) {
+    if (!s) return fail(P3D_ERR_ARG, "scene is NULL");
+    if (device_buffer && !kernels_have_stamps())
+        return fail(P3D_ERR_STATE, "this build has no stamp hooks: use the diagnostic build (make -C csrc stamps, libp3d_hip_stamps.so)");
+    s->dbg_stamps = (unsigned long long*)device_buffer;
+    return P3D_OK;
+}
+
+int p3d_debug_set_stamp_level(p3d_scene* s, int32_t level) {
+    if (!s) return fail(P3D_ERR_ARG, "scene is NULL");
+    if (level < 1 || level > kMaxDepth) return fail(P3D_ERR_ARG, "level must be in 1..16");
+    s->dbg_stamp_level = level;
+    return P3D_OK;
+}
+
+int p3d_get_profile(p3d_scene* s, float* frame_ms, float* kernel_ms) {
+    if (!s || !frame_ms || !kernel_ms) return fail(P3D_ERR_ARG, "NULL argument");
+    if (!s->profile_valid) return fail(P3D_ERR_STATE, "no render with P3D_FLAG_PROFILE yet");
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipEventSynchronize(s->ev_prof[1]));
+    HIP_TRY(hipEventElapsedTime(frame_ms, s->ev_prof[0], s->ev_prof[1]));
+    HIP_TRY(hipEventElapsedTime(kernel_ms, s->ev_prof[2], s->ev_prof[3]));
+    return P3D_OK;
+}
+
+int p3d_last_schedule(p3d_scene* s, int32_t* schedule) {
+    if (!s || !schedule) return fail(P3D_ERR_ARG, "NULL argument");
+    if (s->last_schedule < 0) return fail(P3D_ERR_STATE, "no render yet");
+    *schedule = s->last_schedule;
+    return P3D_OK;
+}
+
+int p3d_timer_begin(p3d_scene* s) {
+    if (!s) return fail(P3D_ERR_ARG, "scene is NULL");
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipEventRecord(s->ev0, s->stream));
+    s->timer_open = true;
+    return P3D_OK;
+}
+
+int p3d_timer_end(p3d_scene* s, float* ms) {
+    if (!s || !ms) return fail(P3D_ERR_ARG, "scene/ms is NULL");
+    if (!s->timer_open) return fail(P3D_ERR_STATE, "p3d_timer_begin was not called");
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipEventRecord(s->ev1, s->stream));
+    HIP_TRY(hipEventSynchronize(s->ev1));
+    HIP_TRY(hipEventElapsedTime(ms, s->ev0, s->ev1));
+    s->timer_open = false;
+    return P3D_OK;
+}
+
+int p3d_deinterleave_frames(p3d_scene* s, const void* gathered, void* frames, int32_t res_x, int32_t res_y,
+                            int32_t row_block, int32_t world, int32_t bpp, uint64_t rank_stride_bytes,
+                            int32_t n_frames, uint64_t tile_stride_bytes, uint64_t frame_stride_bytes) {
+    if (!s || !gathered || !frames) return fail(P3D_ERR_ARG, "NULL argument");
+    if (res_x <= 0 || res_y <= 0 || world <= 0 || n_frames <= 0) return fail(P3D_ERR_ARG, "bad sizes");
+    if (row_block <= 0) row_block = 16;
+    if (bpp != 3 && bpp != 4 && bpp != 12) return fail(P3D_ERR_ARG, "bytes_per_pixel must be 3, 4 or 12");
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t tile = (size_t)p3d_local_rows(res_y, row_block, world) * res_x * bpp;
+    const size_t in_stride = tile_stride_bytes ? (size_t)tile_stride_bytes : tile;
+    const size_t stride = rank_stride_bytes ? (size_t)rank_stride_bytes : in_stride * n_frames;
+    const size_t out_stride = frame_stride_bytes ? (size_t)frame_stride_bytes : (size_t)res_y * res_x * bpp;
+    HIP_TRY(launch_deinterleave(gathered, frames, res_x, res_y, row_block, world, stride, bpp, n_frames, in_stride,
+                                out_stride, s->stream));
+    return P3D_OK;
+}
+
+int p3d_deinterleave(p3d_scene* s, const void* gathered, void* frame, int32_t res_x, int32_t res_y,
+                     int32_t row_block, int32_t world, int32_t bpp, uint64_t rank_stride_bytes) {
+    return p3d_deinterleave_frames(s, gathered, frame, res_x, res_y, row_block, world, bpp, rank_stride_bytes, 1, 0, 0);
+}
+
+int p3d_device_alloc(p3d_scene* s, uint64_t bytes, void** out) {
+    if (!s || !out) return fail(P3D_ERR_ARG, "scene/out is NULL");
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipMalloc(out, bytes ? (size_t)bytes : 1));
+    return P3D_OK;
+}
+int p3d_device_free(p3d_scene* s, void* ptr) {
+    if (!s) return fail(P3D_ERR_ARG, "scene is NULL");
+    HIP_TRY(hipSetDevice(s->device));
+    if (ptr) HIP_TRY(hipFree(ptr));
+    return P3D_OK;
+}
+int p3d_upload(p3d_scene* s, void* device_dst, const void* host_src, uint64_t bytes) {
+    if (!s || !device_dst || !host_src) return fail(P3D_ERR_ARG, "NULL argument");
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipMemcpyAsync(device_dst, host_src, (size_t)bytes, hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return P3D_OK;
+}
+int p3d_download(p3d_scene* s, void* host_dst, const void* device_src, uint64_t bytes) {
+    if (!s || !host_dst || !device_src) return fail(P3D_ERR_ARG, "NULL argument");
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipMemcpyAsync(host_dst, device_src, (size_t)bytes, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return P3D_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// One argument of a debug entry on the device: `bytes` of scratch, filled from `in` before the launch (if any) and copied
+// to `out` after it (if any).
+struct DebugArg {
+    const void* in; void* out; size_t bytes;
+    void* d = nullptr;
+    template <typename T> T* as() const { return (T*)d; }
+};
+
+// Runs one debug launch on `device`: scratch for the arguments, inputs up, launch, wait, outputs back.  The scratch is freed on
+// every path; a HIP error is reported as "<entry>: <error>".
+template <size_t N, typename Launch>
+int debug_run(const char* entry, int device, DebugArg (&args)[N], Launch launch) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(P3D_ERR_NO_DEVICE, "no HIP device visible");
+    hipError_t e = hipSetDevice(device);
+    for (DebugArg& a : args) if (e == hipSuccess) e = hipMalloc(&a.d, a.bytes);
+    for (DebugArg& a : args) if (e == hipSuccess && a.in) e = hipMemcpy(a.d, a.in, a.bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = launch();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    for (DebugArg& a : args) if (e == hipSuccess && a.out) e = hipMemcpy(a.out, a.d, a.bytes, hipMemcpyDeviceToHost);
+    for (DebugArg& a : args) (void)hipFree(a.d);
+    if (e != hipSuccess) return fail(P3D_ERR_HIP, std::string(entry) + ": " + hipGetErrorString(e));
+    return P3D_OK;
+}
+
+typedef hipError_t (*RcpCheckLaunch)(uint32_t, uint64_t, unsigned long long*, uint32_t*, hipStream_t);
+int debug_check_reciprocal(const char* entry, RcpCheckLaunch launch, int device, uint32_t first_bits, uint64_t count,
+                           uint64_t* n_bad, uint32_t* first_bad) {
+    if (!n_bad || !first_bad) return fail(P3D_ERR_ARG, "NULL argument");
+    *n_bad = 0; *first_bad = 0xFFFFFFFFu;
+    if (count == 0) return P3D_OK;
+    if (count > (1ull << 32)) return fail(P3D_ERR_ARG, "count exceeds the 2^32 bit patterns");
+    unsigned long long r[2] = {0ull, 0xFFFFFFFFull};      // [0] mismatches, [1] (low word) first mismatching pattern
+    DebugArg a[1] = {{r, r, sizeof r}};
+    int rc = debug_run(entry, device, a, [&] {
+        return launch(first_bits, count, a[0].as<unsigned long long>(), (uint32_t*)(a[0].as<unsigned long long>() + 1), nullptr);
+    });
+    if (rc) return rc;
+    *n_bad = r[0]; *first_bad = (uint32_t)r[1];
+    return P3D_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int p3d_debug_intersect(int device, uint32_t n, const uint32_t* type, const float* prim12, const float* origin,
+                        const float* dir, int32_t* hit, float* t, float* normal) {
+    if (!type || !prim12 || !origin || !dir || !hit || !t || !normal) return fail(P3D_ERR_ARG, "NULL argument");
+    if (n == 0) return P3D_OK;
+    const size_t N = n;
+    DebugArg a[7] = {{type, nullptr, N * 4}, {prim12, nullptr, N * 48}, {origin, nullptr, N * 12}, {dir, nullptr, N * 12},
+                     {nullptr, hit, N * 4}, {nullptr, t, N * 4}, {nullptr, normal, N * 12}};
+    return debug_run("p3d_debug_intersect", device, a, [&] {
+        return launch_debug_intersect(n, a[0].as<uint32_t>(), a[1].as<float>(), a[2].as<float>(), a[3].as<float>(), a[4].as<int32_t>(),
+                                      a[5].as<float>(), a[6].as<float>(), nullptr);
+    });
+}
+
+int p3d_debug_check_rcp(int device, uint32_t first_bits, uint64_t count, uint64_t* n_bad, uint32_t* first_bad) {
+    return debug_check_reciprocal("p3d_debug_check_rcp", launch_debug_check_rcp, device, first_bits, count, n_bad, first_bad);
+}
+int p3d_debug_check_rcp_len(int device, uint32_t first_bits, uint64_t count, uint64_t* n_bad, uint32_t* first_bad) {
+    return debug_check_reciprocal("p3d_debug_check_rcp_len", launch_debug_check_rcp_len, device, first_bits, count, n_bad, first_bad);
+}
+
+int p3d_debug_powf(int device, uint32_t n, const float* x, const float* y, float* out) {
+    if (!x || !y || !out) return fail(P3D_ERR_ARG, "NULL argument");
+    if (n == 0) return P3D_OK;
+    const size_t N = n;
+    DebugArg a[3] = {{x, nullptr, N * 4}, {y, nullptr, N * 4}, {nullptr, out, N * 4}};
+    return debug_run("p3d_debug_powf", device, a, [&] { return launch_debug_powf(n, a[0].as<float>(), a[1].as<float>(), a[2].as<float>(), nullptr); });
+}
+
+int p3d_debug_pow(int device, uint32_t n, const double* x, const double* y, double* out) {
+    if (!x || !y || !out) return fail(P3D_ERR_ARG, "NULL argument");
+    if (n == 0) return P3D_OK;
+    const size_t N = n;
+    DebugArg a[3] = {{x, nullptr, N * 8}, {y, nullptr, N * 8}, {nullptr, out, N * 8}};
+    return debug_run("p3d_debug_pow", device, a, [&] { return launch_debug_pow(n, a[0].as<double>(), a[1].as<double>(), a[2].as<double>(), nullptr); });
+}
+
+int p3d_debug_schlick_kr(int device, uint32_t n, const float* ior_1, const float* new_ior, const float* cos_theta_i, float* out) {
+    if (!ior_1 || !new_ior || !cos_theta_i || !out) return fail(P3D_ERR_ARG, "NULL argument");
+    if (n == 0) return P3D_OK;
+    const size_t N = n;
+    DebugArg a[4] = {{ior_1, nullptr, N * 4}, {new_ior, nullptr, N * 4}, {cos_theta_i, nullptr, N * 4}, {nullptr, out, N * 4}};
+    return debug_run("p3d_debug_schlick_kr", device, a, [&] {
+        return launch_debug_schlick_kr(n, a[0].as<float>(), a[1].as<float>(), a[2].as<float>(), a[3].as<float>(), nullptr);
+    });
+}
+
+}  // extern "C"
