@@ -35,6 +35,13 @@ namespace p3d {
 __device__ __forceinline__ uint32_t lane_rank(uint64_t mask) {          // # set bits below this lane
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
+// the scene id a frame's hit_id plane records for a primary hit (-1: the ray left the scene)
+__device__ __forceinline__ int32_t hit_id_of(const Hit& h) { return (h.ref == 0xFFFFFFFFu) ? -1 : (int32_t)h.sid; }
+// "color / (4 * 4)" of the anti-aliased path (RT/main.cpp:800)
+__device__ __forceinline__ V3 div16(V3 c) { return mk(fdiv(c.x, 16.0f), fdiv(c.y, 16.0f), fdiv(c.z, 16.0f)); }
+__device__ __forceinline__ SceneOffsets scene_offsets(const LaunchParams& P) {
+    return SceneOffsets{P.off_nodes, P.off_leaves, P.off_spheres, P.off_sphere_meta, P.off_tris, P.off_tri_normals, P.off_boxes, P.off_mats, P.tri_quads};
+}
 
 template <bool COUNT>
 __device__ __forceinline__ void flush_counters(const LaunchParams& P, const Ctr& ctr, uint32_t pixels) {
@@ -94,7 +101,7 @@ __global__ __launch_bounds__(256) void sum_samples_kernel(const LaunchParams P, 
             const float* a = P.wf_planes + (size_t)smp * P.wf_plane_stride + 3 * p;
             acc = add(acc, mk(a[0], a[1], a[2]));
         }
-        write_pixel(P, p, mk(fdiv(acc.x, 16.0f), fdiv(acc.y, 16.0f), fdiv(acc.z, 16.0f)));
+        write_pixel(P, p, div16(acc));
     }
 }
 
@@ -165,6 +172,53 @@ __device__ __forceinline__ Ray camera_ray(const LaunchParams& P, int x, int y, i
     return primary_ray_lens(P, P, sm.z, sm.w, sm.x, sm.y);
 }
 
+// ------------------------------------------------------------------ workspace records
+// RayRec and NodeRec (p3d_device_types.h) move as 16-byte quads: {o | ior} {d | link} and {color | KR} {refl_ret | mat}
+// {refr_ret | link}.  The five statements below are the only code that knows which quad and lane holds what; every
+// schedule parks, queues, returns and resolves through them.
+static_assert(offsetof(RayRec, ior) == 12 && offsetof(RayRec, link) == 28 && offsetof(NodeRec, KR) == 12 && offsetof(NodeRec, mat) == 28 &&
+              offsetof(NodeRec, link) == 44, "the quad view below follows the records' layout");
+
+// Write a child ray.  present = false (pair mode only) leaves the marker of a sibling pair's unused half instead.
+__device__ __forceinline__ void store_ray(RayRec* r, bool present, const Ray& ray, float ior, uint32_t link) {
+    float4* rq = reinterpret_cast<float4*>(r);
+    const float4 z = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(kPairEmpty));
+    rq[0] = present ? make_float4(ray.o.x, ray.o.y, ray.o.z, ior) : z;
+    rq[1] = present ? make_float4(ray.d.x, ray.d.y, ray.d.z, __uint_as_float(link)) : z;
+}
+// Read a queued ray.
+__device__ __forceinline__ void load_ray(const RayRec* r, Ray& ray, float& ior_1, uint32_t& link) {
+    const float4* rq = reinterpret_cast<const float4*>(r);
+    const float4 a = rq[0], b = rq[1];
+    ray.o = mk(a.x, a.y, a.z); ray.d = mk(b.x, b.y, b.z);
+    ior_1 = a.w; link = __float_as_uint(b.w);
+}
+// Write a parked node: both return slots start as zero, which is what the reference adds for a child it never traced.
+__device__ __forceinline__ void park_node(NodeRec* n, const NodeOut& o, uint32_t link) {
+    float4* nd = reinterpret_cast<float4*>(n);
+    nd[0] = make_float4(o.color.x, o.color.y, o.color.z, o.KR);
+    nd[1] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(o.mat));
+    nd[2] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(link));
+}
+// Store a child's return value into the slot of its parent (nodes = the parent's level) that the child's link names.
+__device__ __forceinline__ void store_return(NodeRec* nodes, uint32_t link, V3 ret) {
+    NodeRec* parent = nodes + (link & ~kLinkRefr);
+    float* dst = (link & kLinkRefr) ? parent->refr_ret : parent->refl_ret;
+    dst[0] = ret.x; dst[1] = ret.y; dst[2] = ret.z;
+}
+// Read a parked node and resolve it: color + (refl_ret*KR*spec + refr_ret*(1-KR)), RT/main.cpp:719; link = whom the
+// result goes to.  STORED: the children's returns are the record's own slots; else (pair mode, where they never went
+// through memory) the caller's.
+template <bool STORED = true, class SV>
+__device__ __forceinline__ V3 resolve_node(const SV& sv, const NodeRec* n, uint32_t& link, V3 refl_ret = V3(), V3 refr_ret = V3()) {
+    const float4* nd = reinterpret_cast<const float4*>(n);
+    const float4 a = nd[0], b = nd[1], c = nd[2];
+    if (STORED) { refl_ret = mk(b.x, b.y, b.z); refr_ret = mk(c.x, c.y, c.z); }
+    const Mtl M = load_material(sv, __float_as_uint(b.w));
+    link = __float_as_uint(c.w);
+    return combine_node(mk(a.x, a.y, a.z), a.w, M.spec, refl_ret, refr_ret);
+}
+
 // ------------------------------------------------------------------ WAVEFRONT schedule
 // One shard's slice of the level queues (see LaunchParams::wf_shards).
 struct Shard {
@@ -200,11 +254,10 @@ __device__ __forceinline__ Shard shard_of(const LaunchParams& P, uint32_t s, uin
 }
 
 // Hand a finished node's return value to whoever waits for it.
-__device__ __forceinline__ void deliver(const LaunchParams& P, const Shard& sh, int level, uint32_t link, V3 ret) {
+// (parents = this shard's nodes of level - 1; level 1 returns to the pixel)
+__device__ __forceinline__ void deliver(const LaunchParams& P, NodeRec* parents, int level, uint32_t link, V3 ret) {
     if (level == 1) { sink_sample(P, (size_t)link, ret); return; }
-    NodeRec* parent = sh.nodes_parent + (link & ~kLinkRefr);
-    float* dst = (link & kLinkRefr) ? parent->refr_ret : parent->refl_ret;
-    dst[0] = ret.x; dst[1] = ret.y; dst[2] = ret.z;
+    store_return(parents, link, ret);
 }
 
 // Park a node with children and queue its child rays.  Must be reached by ALL lanes of the
@@ -213,7 +266,7 @@ __device__ __forceinline__ void deliver(const LaunchParams& P, const Shard& sh, 
 __device__ __forceinline__ void emit(const LaunchParams& P, const Shard& sh, int level, bool valid, uint32_t link,
                                      float ior_1, const NodeOut& o) {
     const int lane = threadIdx.x & 63;
-    if (valid && o.terminal) deliver(P, sh, level, link, o.ret);
+    if (valid && o.terminal) deliver(P, sh.nodes_parent, level, link, o.ret);
     const bool parks = valid && !o.terminal;
     const uint64_t m_node = __ballot(parks);
     if (m_node == 0) return;                                   // wave-uniform
@@ -230,33 +283,22 @@ __device__ __forceinline__ void emit(const LaunchParams& P, const Shard& sh, int
     ray_base = __shfl(ray_base, (int)__builtin_ctzll(m_node));
     if (!parks) return;
     const uint32_t my_node = node_base + lane_rank(m_node);
-    float4* nd = reinterpret_cast<float4*>(sh.nodes_self + my_node);
-    nd[0] = make_float4(o.color.x, o.color.y, o.color.z, o.KR);
-    nd[1] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(o.mat));
-    nd[2] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(link));
+    park_node(sh.nodes_self + my_node, o, link);
     if (pairs) {
         const uint32_t slot = ray_base + 2u * lane_rank(m_node);
-        float4* rq = reinterpret_cast<float4*>(sh.rays_out + slot);
-        const float4 z = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(kPairEmpty));
-        rq[0] = o.has_refl ? make_float4(o.refl.o.x, o.refl.o.y, o.refl.o.z, ior_1) : z;
-        rq[1] = o.has_refl ? make_float4(o.refl.d.x, o.refl.d.y, o.refl.d.z, __uint_as_float(my_node)) : z;
-        rq[2] = o.has_refr ? make_float4(o.refr.o.x, o.refr.o.y, o.refr.o.z, o.newIor) : z;
-        rq[3] = o.has_refr ? make_float4(o.refr.d.x, o.refr.d.y, o.refr.d.z, __uint_as_float(my_node | kLinkRefr)) : z;
+        store_ray(sh.rays_out + slot, o.has_refl, o.refl, ior_1, my_node);
+        store_ray(sh.rays_out + slot + 1, o.has_refr, o.refr, o.newIor, my_node | kLinkRefr);
         if (sh.rng_out) { sh.rng_out[slot] = o.rng_refl; sh.rng_out[slot + 1] = o.rng_refr; }
         return;
     }
     if (o.has_refl) {                                           // reflection child keeps ior_1
         const uint32_t slot = ray_base + lane_rank(m_refl);
-        float4* rq = reinterpret_cast<float4*>(sh.rays_out + slot);
-        rq[0] = make_float4(o.refl.o.x, o.refl.o.y, o.refl.o.z, ior_1);
-        rq[1] = make_float4(o.refl.d.x, o.refl.d.y, o.refl.d.z, __uint_as_float(my_node));
+        store_ray(sh.rays_out + slot, true, o.refl, ior_1, my_node);
         if (sh.rng_out) sh.rng_out[slot] = o.rng_refl;
     }
     if (o.has_refr) {
         const uint32_t slot = ray_base + n_refl + lane_rank(m_refr);
-        float4* rq = reinterpret_cast<float4*>(sh.rays_out + slot);
-        rq[0] = make_float4(o.refr.o.x, o.refr.o.y, o.refr.o.z, o.newIor);
-        rq[1] = make_float4(o.refr.d.x, o.refr.d.y, o.refr.d.z, __uint_as_float(my_node | kLinkRefr));
+        store_ray(sh.rays_out + slot, true, o.refr, o.newIor, my_node | kLinkRefr);
         if (sh.rng_out) sh.rng_out[slot] = o.rng_refr;
     }
 }
@@ -268,7 +310,7 @@ template <> struct View<false> {
     typedef GlobalScene type;
     static __device__ __forceinline__ GlobalScene make(const LaunchParams& P) {
         GlobalScene g; g.q = reinterpret_cast<const float4*>(P.blob);
-        g.o = SceneOffsets{P.off_nodes, P.off_leaves, P.off_spheres, P.off_sphere_meta, P.off_tris, P.off_tri_normals, P.off_boxes, P.off_mats, P.tri_quads};
+        g.o = scene_offsets(P);
         g.qn = reinterpret_cast<const uint4*>(P.qnodes);
         for (int a = 0; a < 3; a++) { g.qs[a] = P.q_scale[a]; g.qb[a] = P.q_base[a]; }
         return g;
@@ -284,7 +326,7 @@ template <> struct View<true> {
         for (uint32_t i = threadIdx.x; i < P.blob_quads; i += blockDim.x) dst[i] = src[i];
         __syncthreads();
         LdsScene l;
-        l.o = SceneOffsets{P.off_nodes, P.off_leaves, P.off_spheres, P.off_sphere_meta, P.off_tris, P.off_tri_normals, P.off_boxes, P.off_mats, P.tri_quads};
+        l.o = scene_offsets(P);
         return l;
     }
     static __device__ __forceinline__ LdsScene make_shading(const LaunchParams& P) { return make(P); }
@@ -304,15 +346,10 @@ __device__ __forceinline__ void combine_pair(const LaunchParams& P, const Shard&
     if ((lane & 1) != 0 || !(valid || other_valid)) return;
     const uint32_t parent = (valid ? link : other_link) & ~kLinkRefr;
     const GlobalScene gv = View<false>::make(P);
-    const float4* nd = reinterpret_cast<const float4*>(sh.nodes_parent + parent);
-    const float4 a = nd[0], b = nd[1], c = nd[2];
-    const Mtl M = load_material(gv, __float_as_uint(b.w));
-    const V3 ret = combine_node(mk(a.x, a.y, a.z), a.w, M.spec, mine, other);
-    const uint32_t up = __float_as_uint(c.w);
+    uint32_t up;
+    const V3 ret = resolve_node<false>(gv, sh.nodes_parent + parent, up, mine, other);
     if (P.wf_level == 2) { sink_sample(P, (size_t)up, ret); return; }
-    NodeRec* g = sh.nodes_grand + (up & ~kLinkRefr);
-    float* dst = (up & kLinkRefr) ? g->refr_ret : g->refl_ret;
-    dst[0] = ret.x; dst[1] = ret.y; dst[2] = ret.z;
+    store_return(sh.nodes_grand, up, ret);
 }
 
 // this wave's traversal stack: after the (optional) scene copy, one region per wave
@@ -403,7 +440,7 @@ __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void wf_primary_kernel
     stamp(P, tile, 1);
     const Hit h = find_closest<COUNT, WALK>(P, sv, ray, valid, tc, ctr);
     stamp(P, tile, 2);
-    if (valid && P.hit_id && P.wf_sample == 0) P.hit_id[p] = (h.ref == 0xFFFFFFFFu) ? -1 : (int32_t)h.sid;
+    if (valid && P.hit_id && P.wf_sample == 0) P.hit_id[p] = hit_id_of(h);
     // the random stream of a pixel sample is keyed by the pixel's place in the FULL frame, so a frame
     // sharded over several GPUs draws the same numbers as on one (frame f of a batch: seed + f)
     const uint32_t rng = STOCH ? rng_mix(rng_mix(BATCH ? P.seed + (uint32_t)f : P.seed, (uint32_t)(y * P.res_x + x)), (uint32_t)P.wf_sample) : 0u;
@@ -428,6 +465,29 @@ __device__ __forceinline__ uint32_t wave_width(uint32_t count, uint32_t waves_pe
     uint32_t width = 64;
     while (width > min_width && resident * (width >> 1) >= count) width >>= 1;
     return width;
+}
+
+// One step of a deeper level for one batch of the wave: lane's ray = entry i of the shard's queue (valid: there is one).
+// Must be reached by all lanes of the wave together.  st1 = this is the wave's first batch: the one its stamps describe.
+template <bool COUNT, bool LDS, int WALK, bool STOCH, bool SCHLICK>
+__device__ __forceinline__ void queued_ray_step(const LaunchParams& P, const typename View<LDS>::type& sv, const Shard& sh, const TravCtx& tc,
+                                                Ctr& ctr, uint32_t i, bool valid, uint32_t wave_id, bool st1) {
+    uint32_t link = 0, rng = 0; float ior_1 = 1.0f;
+    Ray ray; ray.o = mk(0.0f, 0.0f, 0.0f); ray.d = mk(1.0f, 0.0f, 0.0f);
+    if (valid) {
+        load_ray(sh.rays_in + i, ray, ior_1, link);
+        if (STOCH) rng = sh.rng_in[i];
+    }
+    const bool live = valid && link != kPairEmpty;           // (the unused half of a sibling pair)
+    // (stamp 1, the queue read, is taken for LDS scenes only)
+    if (LDS && stamps_on(P) && st1) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stamp_wave(P, wave_id, 1); }
+    const Hit h = find_closest<COUNT, WALK>(P, sv, ray, live, tc, ctr);
+    stamp_wave(P, wave_id, 2, st1);
+    const NodeOut o = shade_hit<COUNT, WALK, typename View<LDS>::type, STOCH, SCHLICK>(P, sv, ray, h, live, P.wf_level, ior_1, tc, ctr, rng);
+    stamp_wave(P, wave_id, 3, st1);
+    if (P.wf_pair_in) combine_pair(P, sh, live, link, o);
+    else emit(P, sh, P.wf_level, live, link, ior_1, o);
+    stamp_wave(P, wave_id, 4, st1);
 }
 
 // level >= 2: one queued ray per lane, persistent waves striding over the queue
@@ -463,26 +523,7 @@ __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void wf_secondary_kern
             const uint32_t first = __shfl(incl - nb, s);             // batches in the shards before it
             const Shard sh = shard_of(P, (uint32_t)s, par);
             const uint32_t i = (b - first) * 64u + lane;
-            const bool valid = i < sh.count_in;
-            uint32_t link = 0, rng = 0; float ior_1 = 1.0f;
-            Ray ray; ray.o = mk(0.0f, 0.0f, 0.0f); ray.d = mk(1.0f, 0.0f, 0.0f);
-            if (valid) {
-                const float4* rq = reinterpret_cast<const float4*>(sh.rays_in + i);
-                float4 a = rq[0], bq = rq[1];
-                ray.o = mk(a.x, a.y, a.z); ray.d = mk(bq.x, bq.y, bq.z);
-                ior_1 = a.w; link = __float_as_uint(bq.w);
-                if (STOCH) rng = sh.rng_in[i];
-            }
-            const bool live = valid && link != kPairEmpty;           // (the unused half of a sibling pair)
-            if (stamps_on(P) && st1) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); stamp_wave(P, wave_id, 1); }
-            const Hit h = find_closest<COUNT, WALK>(P, sv, ray, live, tc, ctr);
-            stamp_wave(P, wave_id, 2, st1);
-            const NodeOut o = shade_hit<COUNT, WALK, typename View<LDS>::type, STOCH, SCHLICK>(P, sv, ray, h, live, P.wf_level, ior_1, tc,
-                                                                                    ctr, rng);
-            stamp_wave(P, wave_id, 3, st1);
-            if (P.wf_pair_in) combine_pair(P, sh, live, link, o);
-            else emit(P, sh, P.wf_level, live, link, ior_1, o);
-            stamp_wave(P, wave_id, 4, st1);
+            queued_ray_step<COUNT, LDS, WALK, STOCH, SCHLICK>(P, sv, sh, tc, ctr, i, i < sh.count_in, wave_id, st1);
         }
         if (stamps_on(P) && n_batches) { stamp_wave(P, wave_id, 5); P.dbg_stamps[(size_t)wave_id * 8 + 6] = n_batches; }
         flush_counters<COUNT>(P, ctr, 0u);
@@ -511,25 +552,7 @@ __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void wf_secondary_kern
         const bool st1 = n_batches == 0;
         stamp_wave(P, wave_id, 0, st1);
         const uint32_t i = base + lane;
-        const bool valid = (uint32_t)lane < width && i < sh.count_in;
-        uint32_t link = 0, rng = 0; float ior_1 = 1.0f;
-        Ray ray; ray.o = mk(0.0f, 0.0f, 0.0f); ray.d = mk(1.0f, 0.0f, 0.0f);
-        if (valid) {
-            const float4* rq = reinterpret_cast<const float4*>(sh.rays_in + i);
-            float4 a = rq[0], b = rq[1];
-            ray.o = mk(a.x, a.y, a.z); ray.d = mk(b.x, b.y, b.z);
-            ior_1 = a.w; link = __float_as_uint(b.w);
-            if (STOCH) rng = sh.rng_in[i];
-        }
-        const bool live = valid && link != kPairEmpty;
-        const Hit h = find_closest<COUNT, WALK>(P, sv, ray, live, tc, ctr);
-        stamp_wave(P, wave_id, 2, st1);
-        const NodeOut o = shade_hit<COUNT, WALK, typename View<LDS>::type, STOCH, SCHLICK>(P, sv, ray, h, live, P.wf_level, ior_1, tc,
-                                                                                ctr, rng);
-        stamp_wave(P, wave_id, 3, st1);
-        if (P.wf_pair_in) combine_pair(P, sh, live, link, o);
-        else emit(P, sh, P.wf_level, live, link, ior_1, o);
-        stamp_wave(P, wave_id, 4, st1);
+        queued_ray_step<COUNT, LDS, WALK, STOCH, SCHLICK>(P, sv, sh, tc, ctr, i, (uint32_t)lane < width && i < sh.count_in, wave_id, st1);
     }
     if (stamps_on(P) && n_batches) { stamp_wave(P, wave_id, 5); P.dbg_stamps[(size_t)wave_id * 8 + 6] = n_batches; }
     flush_counters<COUNT>(P, ctr, 0u);
@@ -543,11 +566,9 @@ __global__ __launch_bounds__(256) void wf_resolve_kernel(const LaunchParams P) {
     const uint32_t per_shard = gridDim.x / S;
     const GlobalScene gv = View<false>::make(P);
     for (uint32_t i = (blockIdx.x / S) * blockDim.x + threadIdx.x; i < count; i += per_shard * blockDim.x) {
-        const float4* nd = reinterpret_cast<const float4*>(sh.nodes_self + i);
-        float4 a = nd[0], b = nd[1], c = nd[2];
-        Mtl M = load_material(gv, __float_as_uint(b.w));
-        V3 ret = combine_node(mk(a.x, a.y, a.z), a.w, M.spec, mk(b.x, b.y, b.z), mk(c.x, c.y, c.z));
-        deliver(P, sh, P.wf_level, __float_as_uint(c.w), ret);
+        uint32_t link;
+        const V3 ret = resolve_node(gv, sh.nodes_self + i, link);
+        deliver(P, sh.nodes_parent, P.wf_level, link, ret);
     }
 }
 
@@ -559,18 +580,13 @@ __global__ __launch_bounds__(1024) void wf_resolve_fused_kernel(const LaunchPara
     const uint32_t s = blockIdx.x, par = P.wf_ctrl[32] & 1u;
     const GlobalScene gv = View<false>::make(P);
     for (int l = R.top; l >= 1; l--) {
-        Shard sh;
-        sh.rays_in = nullptr; sh.count_in = 0; sh.rays_out = nullptr; sh.count_out = nullptr; sh.rng_in = nullptr; sh.rng_out = nullptr;
-        sh.nodes_self = R.nodes[l] + (size_t)s * R.cap[l];
-        sh.nodes_parent = l > 1 ? R.nodes[l - 1] + (size_t)s * R.cap[l - 1] : nullptr;
-        sh.ncount_self = nullptr;
+        const NodeRec* nodes = R.nodes[l] + (size_t)s * R.cap[l];
+        NodeRec* parents = l > 1 ? R.nodes[l - 1] + (size_t)s * R.cap[l - 1] : nullptr;
         const uint32_t count = l == 1 ? (P.wf_alt + (size_t)(par * 2u + 1u) * kWfShards)[s] : R.ncount[l][s];
         for (uint32_t i = threadIdx.x; i < count; i += blockDim.x) {
-            const float4* nd = reinterpret_cast<const float4*>(sh.nodes_self + i);
-            float4 a = nd[0], b = nd[1], c = nd[2];
-            Mtl M = load_material(gv, __float_as_uint(b.w));
-            V3 ret = combine_node(mk(a.x, a.y, a.z), a.w, M.spec, mk(b.x, b.y, b.z), mk(c.x, c.y, c.z));
-            deliver(P, sh, l, __float_as_uint(c.w), ret);
+            uint32_t link;
+            const V3 ret = resolve_node(gv, nodes + i, link);
+            deliver(P, parents, l, link, ret);
         }
         __syncthreads();             // the workgroup's own stores are visible to it after the barrier
     }
@@ -609,10 +625,10 @@ struct TileCtx {
     uint32_t lds_off;                     // dword offset of the TileLds inside p3d_lds
     uint32_t lq_off;                      // dword offset of the LDS ray buffers (0 = none: scenes read from HBM)
     // ray slot `i` of level `l`: in LDS below kTileLdsRays (when the kernel has the buffers), else in the HBM slot
-    __device__ __forceinline__ float4* ray_slot(int l, uint32_t i) const {
+    __device__ __forceinline__ RayRec* ray_slot(int l, uint32_t i) const {
         if (lq_off != 0u && i < kTileLdsRays)
-            return reinterpret_cast<float4*>(p3d_lds + lq_off) + ((uint32_t)(l & 1) * kTileLdsRays + i) * 2u;
-        return reinterpret_cast<float4*>(rays + tile_ray_offset(l) + i);
+            return reinterpret_cast<RayRec*>(reinterpret_cast<float4*>(p3d_lds + lq_off) + ((uint32_t)(l & 1) * kTileLdsRays + i) * 2u);   // (two quads per ray)
+        return rays + tile_ray_offset(l) + i;
     }
     RayRec* rays; NodeRec* nodes; uint32_t* keys;     // this workgroup's slot
     int tx, ty;                           // tile coordinates
@@ -637,9 +653,7 @@ __device__ __forceinline__ void tile_deliver(const LaunchParams& P, const TileCt
         a[0] = a[0] + c.x; a[1] = a[1] + c.y; a[2] = a[2] + c.z;
         return;
     }
-    NodeRec* parent = X.nodes + tile_node_offset(level - 1) + (link & ~kLinkRefr);
-    float* dst = (link & kLinkRefr) ? parent->refr_ret : parent->refl_ret;
-    dst[0] = ret.x; dst[1] = ret.y; dst[2] = ret.z;
+    store_return(X.nodes + tile_node_offset(level - 1), link, ret);
 }
 
 // like emit(): must be reached by all lanes of the wave together
@@ -665,22 +679,15 @@ __device__ __forceinline__ void tile_emit(const LaunchParams& P, const TileCtx& 
     ray_base = __shfl(ray_base, first);
     if (!parks) return;
     const uint32_t my_node = node_base + lane_rank(m_node);
-    float4* nd = reinterpret_cast<float4*>(X.nodes + tile_node_offset(level) + my_node);
-    nd[0] = make_float4(o.color.x, o.color.y, o.color.z, o.KR);
-    nd[1] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(o.mat));
-    nd[2] = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(link));
+    park_node(X.nodes + tile_node_offset(level) + my_node, o, link);
     if (o.has_refl) {                                           // reflection child keeps ior_1
         const uint32_t slot = ray_base + lane_rank(m_refl);
-        float4* rq = X.ray_slot(level + 1, slot);
-        rq[0] = make_float4(o.refl.o.x, o.refl.o.y, o.refl.o.z, ior_1);
-        rq[1] = make_float4(o.refl.d.x, o.refl.d.y, o.refl.d.z, __uint_as_float(my_node));
+        store_ray(X.ray_slot(level + 1, slot), true, o.refl, ior_1, my_node);
         if (X.keys) X.keys[tile_ray_offset(level + 1) + slot] = o.rng_refl;
     }
     if (o.has_refr) {
         const uint32_t slot = ray_base + n_refl + lane_rank(m_refr);
-        float4* rq = X.ray_slot(level + 1, slot);
-        rq[0] = make_float4(o.refr.o.x, o.refr.o.y, o.refr.o.z, o.newIor);
-        rq[1] = make_float4(o.refr.d.x, o.refr.d.y, o.refr.d.z, __uint_as_float(my_node | kLinkRefr));
+        store_ray(X.ray_slot(level + 1, slot), true, o.refr, o.newIor, my_node | kLinkRefr);
         if (X.keys) X.keys[tile_ray_offset(level + 1) + slot] = o.rng_refr;
     }
 }
@@ -758,15 +765,12 @@ __global__ __launch_bounds__(256) P3D_OCC(OCC) void wf_tile_kernel(const LaunchP
                     } else {
                         valid = in_batch && i < n;
                         if (valid) {
-                            const float4* rq = X.ray_slot(l, i);
-                            const float4 a = rq[0], b = rq[1];
-                            ray.o = mk(a.x, a.y, a.z); ray.d = mk(b.x, b.y, b.z);
-                            ior_1 = a.w; link = __float_as_uint(b.w);
+                            load_ray(X.ray_slot(l, i), ray, ior_1, link);
                             if (STOCH) rng = X.keys[tile_ray_offset(l) + i];
                         }
                     }
                     const Hit h = find_closest<COUNT, WALK>(P, sv, ray, valid, tc, ctr);
-                    if (l == 1 && smp == 0 && inside && P.hit_id) P.hit_id[p] = (h.ref == 0xFFFFFFFFu) ? -1 : (int32_t)h.sid;
+                    if (l == 1 && smp == 0 && inside && P.hit_id) P.hit_id[p] = hit_id_of(h);
                     const NodeOut o = shade_hit<COUNT, WALK, typename View<LDS>::type, STOCH, SCHLICK>(P, sv, ray, h, valid, l, ior_1, tc,
                                                                                               ctr, rng, smp);
                     tile_emit<BATCH>(P, X, l, valid, link, ior_1, o);
@@ -776,18 +780,16 @@ __global__ __launch_bounds__(256) P3D_OCC(OCC) void wf_tile_kernel(const LaunchP
             for (int l = D - 1; l >= 1; l--) {                   // ---- resolve: RT/main.cpp:719, deepest level first
                 const uint32_t n = T->n_nodes[l];
                 for (uint32_t i = (uint32_t)tid; i < n; i += 256u) {
-                    const float4* nd = reinterpret_cast<const float4*>(X.nodes + tile_node_offset(l) + i);
-                    const float4 a = nd[0], b = nd[1], c = nd[2];
-                    const Mtl M = load_material(sv, __float_as_uint(b.w));
-                    const V3 ret = combine_node(mk(a.x, a.y, a.z), a.w, M.spec, mk(b.x, b.y, b.z), mk(c.x, c.y, c.z));
-                    tile_deliver<BATCH>(P, X, l, __float_as_uint(c.w), ret);
+                    uint32_t link;
+                    const V3 ret = resolve_node(sv, X.nodes + tile_node_offset(l) + i, link);
+                    tile_deliver<BATCH>(P, X, l, link, ret);
                 }
                 __syncthreads();
             }
         }
         if (P.spp > 0 && inside) {                               // "color / (4 * 4)", RT/main.cpp:800
             const float* a = T->acc + 3 * tid;
-            write_pixel(P, p, mk(fdiv(a[0], 16.0f), fdiv(a[1], 16.0f), fdiv(a[2], 16.0f)));
+            write_pixel(P, p, div16(mk(a[0], a[1], a[2])));
         }
         my_pixels += inside ? 1u : 0u;
     }
@@ -826,6 +828,60 @@ enum { FR_C = 0, FR_KR = 3, FR_META = 4, FR_A = 5, FR_RD = 8, FR_IOR = 11 };
 #define FR_HAS_REFR 0x40000000u
 #define FR_WAIT_REFR 0x80000000u
 
+// A node with children: push its frame and go on with its first child (the reflection ray, if it has one).
+// (fr by value and, below, a flag with break: as references / an early return the tree kernels spill more registers)
+template <class SV, class FR>
+__device__ __forceinline__ void push_frame(const SV& sv, FR fr, int& fsp, const NodeOut& o, Ray& ray, float& ior_1) {
+    const V3 zero = mk(0.0f, 0.0f, 0.0f);
+    fr.put3(fsp, FR_C, o.color);
+    fr.f(fsp, FR_KR) = __float_as_uint(o.KR);
+    if (o.has_refl) {
+        fr.f(fsp, FR_META) = o.mat | (o.has_refr ? FR_HAS_REFR : 0u);
+        fr.put3(fsp, FR_A, o.refr.o);
+        fr.put3(fsp, FR_RD, o.refr.d);
+        fr.f(fsp, FR_IOR) = __float_as_uint(o.newIor);
+        ray = o.refl;                                    // ior_1 unchanged
+    } else {
+        Mtl M = load_material(sv, o.mat);
+        fr.f(fsp, FR_META) = o.mat | FR_WAIT_REFR;
+        fr.put3(fsp, FR_A, cmul(mul(zero, o.KR), M.spec));
+        ray = o.refr; ior_1 = o.newIor;
+    }
+    fsp++;
+}
+// Return path of a finished node: combine ret into its parents (RT/main.cpp:719) until one of them still has its
+// refraction child to trace -- then ray / ior_1 are that child's and the result is true -- or the stack is empty.
+template <class SV, class FR>
+__device__ __forceinline__ bool pop_frames(const SV& sv, FR fr, int& fsp, V3& ret, Ray& ray, float& ior_1) {
+    const V3 zero = mk(0.0f, 0.0f, 0.0f);
+    bool resumed = false;
+    while (fsp > 0) {
+        const int k = fsp - 1;
+        const uint32_t meta = fr.f(k, FR_META);
+        const V3 C = fr.get3(k, FR_C);
+        const float KR = __uint_as_float(fr.f(k, FR_KR));
+        if (!(meta & FR_WAIT_REFR)) {
+            Mtl M = load_material(sv, meta & 0x3FFFFFFFu);
+            const V3 A = cmul(mul(ret, KR), M.spec);
+            if (meta & FR_HAS_REFR) {
+                ray.o = fr.get3(k, FR_A);
+                ray.d = fr.get3(k, FR_RD);
+                ior_1 = __uint_as_float(fr.f(k, FR_IOR));
+                fr.put3(k, FR_A, A);
+                fr.f(k, FR_META) = meta | FR_WAIT_REFR;
+                resumed = true;
+                break;
+            }
+            ret = add(C, add(A, mul(zero, 1.0f - KR)));
+        } else {
+            const V3 A = fr.get3(k, FR_A);
+            ret = add(C, add(A, mul(ret, 1.0f - KR)));
+        }
+        fsp--;
+    }
+    return resumed;
+}
+
 // One primary ray's whole tree: rayTracing(ray, 1, 1.0) of RT/main.cpp:530-721, iterative.
 template <bool COUNT, bool GRID, class SV, class FR, bool SCHLICK = false>
 __device__ __forceinline__ V3 trace_tree(const LaunchParams& P, const SV& sv, Ray ray, const TravCtx& tc, FR fr,
@@ -834,57 +890,16 @@ __device__ __forceinline__ V3 trace_tree(const LaunchParams& P, const SV& sv, Ra
     float ior_1 = 1.0f;
     bool first = true;
     V3 ret = mk(0.0f, 0.0f, 0.0f);
-    const V3 zero = mk(0.0f, 0.0f, 0.0f);
     for (;;) {
         Hit h = find_closest<COUNT, GRID ? WALK_GRID : WALK_LANE>(P, sv, ray, true, tc, ctr);
-        if (first) { primary_hit = (h.ref == 0xFFFFFFFFu) ? -1 : (int32_t)h.sid; first = false; }
+        if (first) { primary_hit = hit_id_of(h); first = false; }
         NodeOut o = shade_hit<COUNT, GRID ? WALK_GRID : WALK_LANE, SV, false, SCHLICK>(P, sv, ray, h, true, fsp + 1, ior_1, tc, ctr);
         if (!o.terminal) {
-            fr.put3(fsp, FR_C, o.color);
-            fr.f(fsp, FR_KR) = __float_as_uint(o.KR);
-            if (o.has_refl) {
-                fr.f(fsp, FR_META) = o.mat | (o.has_refr ? FR_HAS_REFR : 0u);
-                fr.put3(fsp, FR_A, o.refr.o);
-                fr.put3(fsp, FR_RD, o.refr.d);
-                fr.f(fsp, FR_IOR) = __float_as_uint(o.newIor);
-                ray = o.refl;                                    // ior_1 unchanged
-            } else {
-                Mtl M = load_material(sv, o.mat);
-                fr.f(fsp, FR_META) = o.mat | FR_WAIT_REFR;
-                fr.put3(fsp, FR_A, cmul(mul(zero, o.KR), M.spec));
-                ray = o.refr; ior_1 = o.newIor;
-            }
-            fsp++;
+            push_frame(sv, fr, fsp, o, ray, ior_1);
             continue;
         }
         ret = o.ret;
-        // ---- return path: combine into parents (RT/main.cpp:719)
-        bool resumed = false;
-        while (fsp > 0) {
-            int k = fsp - 1;
-            uint32_t meta = fr.f(k, FR_META);
-            V3 C = fr.get3(k, FR_C);
-            float KR = __uint_as_float(fr.f(k, FR_KR));
-            if (!(meta & FR_WAIT_REFR)) {
-                Mtl M = load_material(sv, meta & 0x3FFFFFFFu);
-                V3 A = cmul(mul(ret, KR), M.spec);
-                if (meta & FR_HAS_REFR) {
-                    ray.o = fr.get3(k, FR_A);
-                    ray.d = fr.get3(k, FR_RD);
-                    ior_1 = __uint_as_float(fr.f(k, FR_IOR));
-                    fr.put3(k, FR_A, A);
-                    fr.f(k, FR_META) = meta | FR_WAIT_REFR;
-                    resumed = true;
-                    break;
-                }
-                ret = add(C, add(A, mul(zero, 1.0f - KR)));
-            } else {
-                V3 A = fr.get3(k, FR_A);
-                ret = add(C, add(A, mul(ret, 1.0f - KR)));
-            }
-            fsp--;
-        }
-        if (!resumed) return ret;
+        if (!pop_frames(sv, fr, fsp, ret, ray, ior_1)) return ret;
     }
 }
 
@@ -904,60 +919,21 @@ __device__ __forceinline__ void trace_trees_shared(const LaunchParams& P, const 
     if (alive) ray = camera_ray<BATCH>(P, x, y, 0, f);
     while (__ballot(alive) != 0) {
         const Hit h = find_closest<COUNT, WALK_SHARED>(P, sv, ray, alive, tc, ctr);
-        if (alive && first) { if (smp == 0) hid = (h.ref == 0xFFFFFFFFu) ? -1 : (int32_t)h.sid; first = false; }
+        if (alive && first) { if (smp == 0) hid = hit_id_of(h); first = false; }
         const NodeOut o = shade_hit<COUNT, WALK_SHARED, SV, false, SCHLICK>(P, sv, ray, h, alive, fsp + 1, ior_1, tc, ctr);
         if (!alive) continue;
         if (!o.terminal) {
-            fr.put3(fsp, FR_C, o.color);
-            fr.f(fsp, FR_KR) = __float_as_uint(o.KR);
-            if (o.has_refl) {
-                fr.f(fsp, FR_META) = o.mat | (o.has_refr ? FR_HAS_REFR : 0u);
-                fr.put3(fsp, FR_A, o.refr.o);
-                fr.put3(fsp, FR_RD, o.refr.d);
-                fr.f(fsp, FR_IOR) = __float_as_uint(o.newIor);
-                ray = o.refl;                                    // ior_1 unchanged
-            } else {
-                Mtl M = load_material(sv, o.mat);
-                fr.f(fsp, FR_META) = o.mat | FR_WAIT_REFR;
-                fr.put3(fsp, FR_A, cmul(mul(zero, o.KR), M.spec));
-                ray = o.refr; ior_1 = o.newIor;
-            }
-            fsp++;
+            push_frame(sv, fr, fsp, o, ray, ior_1);
             continue;
         }
         V3 ret = o.ret;
-        bool resumed = false;                                    // ---- return path: combine into parents (RT/main.cpp:719)
-        while (fsp > 0) {
-            const int k = fsp - 1;
-            const uint32_t meta = fr.f(k, FR_META);
-            const V3 C = fr.get3(k, FR_C);
-            const float KR = __uint_as_float(fr.f(k, FR_KR));
-            if (!(meta & FR_WAIT_REFR)) {
-                Mtl M = load_material(sv, meta & 0x3FFFFFFFu);
-                const V3 A = cmul(mul(ret, KR), M.spec);
-                if (meta & FR_HAS_REFR) {
-                    ray.o = fr.get3(k, FR_A);
-                    ray.d = fr.get3(k, FR_RD);
-                    ior_1 = __uint_as_float(fr.f(k, FR_IOR));
-                    fr.put3(k, FR_A, A);
-                    fr.f(k, FR_META) = meta | FR_WAIT_REFR;
-                    resumed = true;
-                    break;
-                }
-                ret = add(C, add(A, mul(zero, 1.0f - KR)));
-            } else {
-                const V3 A = fr.get3(k, FR_A);
-                ret = add(C, add(A, mul(ret, 1.0f - KR)));
-            }
-            fsp--;
-        }
-        if (resumed) continue;
+        if (pop_frames(sv, fr, fsp, ret, ray, ior_1)) continue;
         const V3 c = clampc(ret);                                // "rayTracing(...).clamp()" of this sample
         if (P.spp == 0) { color = c; alive = false; continue; }
         acc = add(acc, c);                                       // RT/main.cpp:797, in sample order
         smp++;
         if (smp < ns) { ray = camera_ray<BATCH>(P, x, y, smp, f); fsp = 0; ior_1 = 1.0f; }
-        else { color = mk(fdiv(acc.x, 16.0f), fdiv(acc.y, 16.0f), fdiv(acc.z, 16.0f)); alive = false; }
+        else { color = div16(acc); alive = false; }
     }
 }
 
@@ -983,17 +959,7 @@ __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void whitted_tree_kern
     int32_t hid = -1;
     if constexpr (SHARED) {
         trace_trees_shared<COUNT, typename View<LDS>::type, decltype(fr), SCHLICK, BATCH>(P, sv, x, y, f, in_image, st, fr, color, hid, ctr);
-        if (in_image) {
-            const size_t p = (size_t)out_row<BATCH>(P, f, row) * P.res_x + x;
-            write_pixel(P, p, color);
-            if (P.hit_id) P.hit_id[p] = hid;
-            flush_counters<COUNT>(P, ctr, 1u);
-        }
-        stamp(P, tile, 4);
-        if (!LDS && P.tile_cost && threadIdx.x == 0) P.tile_cost[tile] = (uint32_t)(__builtin_amdgcn_s_memrealtime() - t_tile);
-        return;
-    }
-    if (P.spp == 0) {                                    // RT/main.cpp:756-775
+    } else if (P.spp == 0) {                                    // RT/main.cpp:756-775
         color = clampc(trace_tree<COUNT, GRID, typename View<LDS>::type, decltype(fr), SCHLICK>(P, sv, camera_ray<BATCH>(P, x, y, 0, f), st, fr, hid, ctr));
     } else {                                             // RT/main.cpp:776-801
         const int ns = P.spp * P.spp;
@@ -1003,12 +969,14 @@ __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void whitted_tree_kern
             color = add(color, c);
             if (s == 0) hid = h2;
         }
-        color = mk(fdiv(color.x, 16.0f), fdiv(color.y, 16.0f), fdiv(color.z, 16.0f));
+        color = div16(color);
     }
-    const size_t p = (size_t)out_row<BATCH>(P, f, row) * P.res_x + x;
-    write_pixel(P, p, color);
-    if (P.hit_id) P.hit_id[p] = hid;
-    flush_counters<COUNT>(P, ctr, 1u);
+    if (!SHARED || in_image) {      // (shared walk: lanes outside the image came along as helpers)
+        const size_t p = (size_t)out_row<BATCH>(P, f, row) * P.res_x + x;
+        write_pixel(P, p, color);
+        if (P.hit_id) P.hit_id[p] = hid;
+        flush_counters<COUNT>(P, ctr, 1u);
+    }
     stamp(P, tile, 4);              // (diagnostic; the wave has reconverged here: its slowest lane is done)
     if (!LDS && P.tile_cost && threadIdx.x == 0) P.tile_cost[tile] = (uint32_t)(__builtin_amdgcn_s_memrealtime() - t_tile);
 }
@@ -1040,51 +1008,6 @@ __global__ void deinterleave_kernel(const uint8_t* __restrict__ gathered, uint8_
         *reinterpret_cast<T*>(dst + y * row_bytes + off) =
             *reinterpret_cast<const T*>(src + (size_t)rank * rank_stride + lrow * row_bytes + off);
     }
-}
-
-// ------------------------------------------------------------------ unit probe
-__global__ void debug_intersect_kernel(uint32_t n, const uint32_t* type, const float* prim12,
-                                       const float* origin, const float* dir, int32_t* hit, float* t,
-                                       float* normal) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float* d = prim12 + 12 * (size_t)i;
-    Ray r; r.o = mk(origin[3 * i], origin[3 * i + 1], origin[3 * i + 2]);
-    r.d = mk(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2]);
-    float tt = 0.0f; bool h = false; V3 nn = mk(0.0f, 0.0f, 0.0f);
-    switch (type[i]) {
-    case 0: {
-        V3 c = mk(d[0], d[1], d[2]);
-        h = hit_sphere(r, c, d[3], tt);
-        if (h) { V3 hp = add(r.o, mul(r.d, tt)); nn = normalized(normalized(sub(hp, c))); }
-        break;
-    }
-    case 1: {
-        V3 p0 = mk(d[0], d[1], d[2]), p1 = mk(d[3], d[4], d[5]), p2 = mk(d[6], d[7], d[8]);
-        V3 e1 = sub(p1, p0), e2 = sub(p2, p0);
-        h = hit_triangle(r, p0, e1, e2, tt);
-        if (h) {     // the host-side statement of this lives in scene_flatten.cpp; the probe keeps the device arithmetic
-            V3 m = mk((e1.y * e2.z) - (e1.z * e2.y), (e1.z * e2.x) - (e1.x * e2.z), (e1.x * e2.y) - (e1.y * e2.x));
-            nn = normalized(normalized(m));
-        }
-        break;
-    }
-    case 2: {
-        V3 f;
-        h = hit_aabox(r, mk(d[0], d[1], d[2]), mk(d[3], d[4], d[5]), tt, f);
-        if (h) nn = normalized(f);
-        break;
-    }
-    default: {
-        V3 pn = mk(d[0], d[1], d[2]);
-        h = hit_plane(r, pn, d[3], tt);
-        if (h) nn = normalized(pn);
-        break;
-    }
-    }
-    hit[i] = h ? 1 : 0;
-    t[i] = tt;
-    normal[3 * i] = nn.x; normal[3 * i + 1] = nn.y; normal[3 * i + 2] = nn.z;
 }
 
 // ------------------------------------------------------------------ launchers (host)
@@ -1353,69 +1276,5 @@ hipError_t launch_deinterleave(const void* gathered, void* frames, int res_x, in
     return hipGetLastError();
 }
 
-// every bit pattern in [first, first + count): frcp(x) against the division it replaces (NaNs compare equal to NaNs)
-__global__ void debug_check_rcp_kernel(uint32_t first, uint64_t count, unsigned long long* n_bad, uint32_t* first_bad) {
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t bits = first + (uint32_t)i;
-        const float x = __uint_as_float(bits);
-        const float a = frcp(x), b = 1.0f / x;
-        const bool same = __float_as_uint(a) == __float_as_uint(b) || (a != a && b != b);
-        if (!same) { atomicAdd(n_bad, 1ull); atomicMin(first_bad, bits); }
-    }
-}
-// the same for rcp_len(x), the reciprocal of a square root's output
-__global__ void debug_check_rcp_len_kernel(uint32_t first, uint64_t count, unsigned long long* n_bad, uint32_t* first_bad) {
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t bits = first + (uint32_t)i;
-        const float x = __uint_as_float(bits);
-        const float a = rcp_len(x), b = 1.0f / x;
-        const bool same = __float_as_uint(a) == __float_as_uint(b) || (a != a && b != b);
-        if (!same) { atomicAdd(n_bad, 1ull); atomicMin(first_bad, bits); }
-    }
-}
 bool kernels_have_stamps() { return kStamps; }
-hipError_t launch_debug_check_rcp(uint32_t first, uint64_t count, unsigned long long* n_bad, uint32_t* first_bad, hipStream_t stream) {
-    hipLaunchKernelGGL(debug_check_rcp_kernel, dim3(256 * 16), dim3(256), 0, stream, first, count, n_bad, first_bad);
-    return hipGetLastError();
-}
-hipError_t launch_debug_check_rcp_len(uint32_t first, uint64_t count, unsigned long long* n_bad, uint32_t* first_bad, hipStream_t stream) {
-    hipLaunchKernelGGL(debug_check_rcp_len_kernel, dim3(256 * 16), dim3(256), 0, stream, first, count, n_bad, first_bad);
-    return hipGetLastError();
-}
-
-__global__ void debug_powf_kernel(uint32_t n, const float* x, const float* y, float* out) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = p3d_powf(x[i], y[i]);
-}
-hipError_t launch_debug_powf(uint32_t n, const float* x, const float* y, float* out, hipStream_t stream) {
-    hipLaunchKernelGGL(debug_powf_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, x, y, out);
-    return hipGetLastError();
-}
-
-__global__ void debug_pow_kernel(uint32_t n, const double* x, const double* y, double* out) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = p3d_pow(x[i], y[i]);
-}
-hipError_t launch_debug_pow(uint32_t n, const double* x, const double* y, double* out, hipStream_t stream) {
-    hipLaunchKernelGGL(debug_pow_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, x, y, out);
-    return hipGetLastError();
-}
-// the KR expression of shade_hit<..., SCHLICK = true> on (ior_1, newIor, cos_theta_i) triples
-__global__ void debug_schlick_kr_kernel(uint32_t n, const float* ior_1, const float* new_ior, const float* cos_theta_i, float* out) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = p3d_schlick_kr(ior_1[i], new_ior[i], cos_theta_i[i], PowTab());
-}
-hipError_t launch_debug_schlick_kr(uint32_t n, const float* ior_1, const float* new_ior, const float* cos_theta_i, float* out,
-                                   hipStream_t stream) {
-    hipLaunchKernelGGL(debug_schlick_kr_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, ior_1, new_ior, cos_theta_i, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_debug_intersect(uint32_t n, const uint32_t* type, const float* prim12, const float* origin,
-                                  const float* dir, int32_t* hit, float* t, float* normal, hipStream_t stream) {
-    hipLaunchKernelGGL(debug_intersect_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, type, prim12,
-                       origin, dir, hit, t, normal);
-    return hipGetLastError();
-}
-
 }  // namespace p3d

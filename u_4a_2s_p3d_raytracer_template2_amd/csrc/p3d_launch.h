@@ -1,4 +1,4 @@
-// p3d_launch.h -- what p3d_kernels.hip and bvh_device.hip export to the host side (p3d_capi.cpp).
+// p3d_launch.h -- what p3d_kernels.hip, p3d_debug_kernels.hip and bvh_device.hip export to the host side (p3d_capi.cpp).
 #ifndef P3D_LAUNCH_H
 #define P3D_LAUNCH_H
 
@@ -52,6 +52,8 @@ hipError_t launch_deinterleave(const void* gathered, void* frames, int res_x, in
                                int world, size_t rank_stride, int bpp, int n_frames, size_t in_stride,
                                size_t out_stride, hipStream_t stream);
 bool kernels_have_stamps();
+
+// ---- p3d_debug_kernels.hip: unit probes of the device arithmetic (p3d_debug_* of include/p3d_hip.h)
 hipError_t launch_debug_check_rcp(uint32_t first, uint64_t count, unsigned long long* n_bad, uint32_t* first_bad, hipStream_t stream);
 hipError_t launch_debug_check_rcp_len(uint32_t first, uint64_t count, unsigned long long* n_bad, uint32_t* first_bad, hipStream_t stream);
 hipError_t launch_debug_powf(uint32_t n, const float* x, const float* y, float* out, hipStream_t stream);
