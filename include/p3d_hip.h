@@ -273,6 +273,16 @@ int p3d_get_counters(p3d_scene* scene, p3d_counters* out);
  * 0 compiler default, 5 / 6 trade spilled registers for latency hiding, -1 keeps. */
 int p3d_set_tuning(p3d_scene* scene, int32_t xcd_chunk, int32_t workspace_mib, int32_t waves_per_simd);
 
+/* More launch tuning that never changes results: tiles = 16x16-pixel tiles a workgroup of the wavefront schedule's level-1
+ * launch runs one after the other: 1, 2 or 3; 0 restores the default. Only scenes served from LDS, on the per-lane walk,
+ * without counters, features or frame batches, and with xcd_chunk == 1 have such kernels; every other frame runs with 1
+ * whatever is set here (p3d_last_primary_tiles() tells). P3D_PRIMARY_TILES=1..3 in the environment sets the same for every
+ * scene created afterwards (measurement scripts: profiles/r06_primary_tiles.txt). */
+int p3d_set_primary_tiles(p3d_scene* scene, int32_t tiles);
+/* Tiles per workgroup the level-1 launch of the most recent p3d_render() / p3d_render_frames() of this scene ran with
+ * (1 on the tile and tree schedules). P3D_ERR_STATE before the first render. */
+int p3d_last_primary_tiles(p3d_scene* scene, int32_t* tiles);
+
 /* Elapsed device time of the most recent render made with P3D_FLAG_PROFILE (waits for it):
  * the whole frame (all launches of the call, samples and bands included) and its dominant
  * kernel alone -- wf_primary_kernel, or whitted_tree_kernel with P3D_FLAG_TREE_KERNEL -- for

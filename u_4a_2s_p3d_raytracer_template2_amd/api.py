@@ -82,7 +82,7 @@ class SceneStats(C.Structure):
 # every symbol include/p3d_hip.h declares (tests check that the library exports them all)
 C_ABI_SYMBOLS = ["p3d_abi_version", "p3d_last_error", "p3d_device_count", "p3d_scene_create",
                  "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_sync",
-                 "p3d_get_counters", "p3d_get_profile", "p3d_last_schedule", "p3d_set_tuning", "p3d_set_stream", "p3d_timer_begin", "p3d_timer_end", "p3d_deinterleave_frames",
+                 "p3d_get_counters", "p3d_get_profile", "p3d_last_schedule", "p3d_set_tuning", "p3d_set_primary_tiles", "p3d_last_primary_tiles", "p3d_set_stream", "p3d_timer_begin", "p3d_timer_end", "p3d_deinterleave_frames",
                  "p3d_deinterleave", "p3d_debug_intersect", "p3d_debug_powf", "p3d_debug_pow", "p3d_debug_schlick_kr", "p3d_debug_check_rcp", "p3d_debug_check_rcp_len", "p3d_tune_schedule", "p3d_debug_set_stamps", "p3d_debug_set_stamp_level",
                  "p3d_comm_unique_id", "p3d_comm_create", "p3d_comm_create_all", "p3d_comm_destroy", "p3d_comm_info",
                  "p3d_gather", "p3d_gather_all", "p3d_device_alloc", "p3d_device_free", "p3d_upload", "p3d_download"]
@@ -132,6 +132,8 @@ def lib():
     L.p3d_get_profile.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.p3d_last_schedule.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     L.p3d_set_tuning.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+    L.p3d_set_primary_tiles.argtypes = [C.c_void_p, C.c_int32]
+    L.p3d_last_primary_tiles.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     L.p3d_timer_begin.argtypes = [C.c_void_p]
     L.p3d_timer_end.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.p3d_deinterleave.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
@@ -369,6 +371,16 @@ class DeviceScene:
     def set_tuning(self, xcd_chunk=0, workspace_mib=0, waves_per_simd=-1):
         _check(lib().p3d_set_tuning(self.h, int(xcd_chunk), int(workspace_mib), int(waves_per_simd)),
                "p3d_set_tuning")
+
+    def set_primary_tiles(self, tiles):
+        """16x16 tiles per workgroup of the wavefront schedule's level-1 launch: 1, 2 or 3 (0: the default)."""
+        _check(lib().p3d_set_primary_tiles(self.h, int(tiles)), "p3d_set_primary_tiles")
+
+    def last_primary_tiles(self):
+        """Tiles per workgroup the most recent render's level-1 launch ran with (1 where no such kernel is built)."""
+        v = C.c_int32()
+        _check(lib().p3d_last_primary_tiles(self.h, C.byref(v)), "p3d_last_primary_tiles")
+        return v.value
 
     def sync(self):
         _check(lib().p3d_sync(self.h), "p3d_sync")

@@ -91,6 +91,13 @@ int p3d_last_schedule(p3d_scene* s, int32_t* schedule) {
     return P3D_OK;
 }
 
+int p3d_last_primary_tiles(p3d_scene* s, int32_t* tiles) {
+    if (!s || !tiles) return fail(P3D_ERR_ARG, "NULL argument");
+    if (s->last_schedule < 0) return fail(P3D_ERR_STATE, "no render yet");
+    *tiles = s->last_primary_tiles;
+    return P3D_OK;
+}
+
 int p3d_timer_begin(p3d_scene* s) {
     if (!s) return fail(P3D_ERR_ARG, "scene is NULL");
     HIP_TRY(hipSetDevice(s->device));

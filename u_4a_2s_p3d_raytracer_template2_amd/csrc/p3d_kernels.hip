@@ -23,6 +23,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
 #include <utility>
 
 #include "p3d_device_types.h"
@@ -154,6 +155,14 @@ __device__ __forceinline__ bool tile_pixel(const LaunchParams& P, int& x, int& y
     row = row0 + (lane >> 4) + wave * 4;                          // row in the compact local buffer
     f = batch_frame<BATCH>(P, row0);
     y = image_row(P, BATCH ? row - f * P.frame_rows : row);
+    return x < P.res_x && y < P.res_y;
+}
+// The 2-D launch's branch of tile_pixel() for a tile the caller names: column tx, row ty of the band (one frame, LDS scenes).
+__device__ __forceinline__ bool tile_pixel_at(const LaunchParams& P, int tx, int ty, int& x, int& y, int& row) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    x = tx * 16 + (lane & 15);
+    row = (ty + P.wf_tile_row0) * (P.wg_waves * 4) + (lane >> 4) + wave * 4;
+    y = image_row(P, row);
     return x < P.res_x && y < P.res_y;
 }
 
@@ -413,9 +422,9 @@ __device__ __forceinline__ void stamp_wave(const LaunchParams& P, uint32_t wave_
 // grid, scene copied once per workgroup, every wave drawing 16x4 tiles from device counters with the next number
 // prefetched -- was measured and dropped: 520 us with one counter (a word saturates at ~88 returning atomics per
 // microsecond), 110 us with 64 counters on separate lines, against 50 us for this plain grid.)
-// (Measured and dropped in round 3, profiles/r03_exp03_sharing_wg_levers.txt / r03_exp04_tiles_lpt_bound.txt: 8- and 16-wave
-//  workgroups -- level 1 of config 2 46 -> 51 -> 54 us -- and 2-4 tiles per workgroup one after the other: the waves of
-//  this launch start at ~830 per microsecond whatever the workgroup shape, and the loop's registers cost occupancy.)
+// (Measured and dropped in round 3, profiles/r03_exp03_sharing_wg_levers.txt: 8- and 16-wave workgroups -- level 1 of
+//  config 2 46 -> 51 -> 54 us: the waves of this launch start at ~830 per microsecond whatever the workgroup shape.)
+//
 template <bool COUNT, bool LDS, int WALK, int OCC, bool STOCH = false, bool SCHLICK = false, bool BATCH = false>
 __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void wf_primary_kernel(const LaunchParams P) {
     const uint32_t par = P.wf_ctrl[0] & 1u;                     // this pass's counter set (LaunchParams::wf_alt)
@@ -450,6 +459,73 @@ __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void wf_primary_kernel
     stamp(P, tile, 4);
     if (!LDS && P.tile_cost && threadIdx.x == 0) P.tile_cost[tile] = (uint32_t)(__builtin_amdgcn_s_memrealtime() - t_tile);
     if (valid) flush_counters<COUNT>(P, ctr, P.wf_sample == 0 ? 1u : 0u);
+}
+
+// wf_primary_kernel with TILES (2 or 3) tiles per workgroup, for scenes served from LDS on the 2-D launch, built where
+// has_primary_tiles() says so: per-lane walk, no counters, no features, one frame, so the steps below are those of
+// wf_primary_kernel<false, true, WALK, OCC> and nothing else.  (wf_primary_kernel keeps its own statements: routed through
+// primary_tile_lds() its ~120 builds came out of the compiler with other scalar-register spills, 18 more in the counting
+// grid-walk builds, and the registered profiles and the register account, tools/kdiff.py, are those builds'.  For the same
+// reason this is a kernel of its own name and not a template parameter of wf_primary_kernel, which would rename them all.)
+//
+// One tile: the camera rays of the tile's pixels, traced, shaded, and their children queued in the tile's shard
+// (tile % kWfShards, whichever workgroup runs the tile: the queues' contents do not depend on the launch's shape).
+// Must be reached by all lanes of the wave together (emit).
+template <int WALK>
+__device__ __forceinline__ void primary_tile_lds(const LaunchParams& P, const LdsScene& sv, const TravCtx& tc, uint32_t par, int tile, bool valid,
+                                                 int x, int y, int row) {
+    const Shard sh = shard_of(P, (uint32_t)tile % kWfShards, par);
+    Ctr ctr = {0, 0, 0, 0, 0, 0, 0};
+    const size_t p = (size_t)row * P.res_x + x;
+    stamp(P, tile, 0);
+    Ray ray; ray.o = mk(0.0f, 0.0f, 0.0f); ray.d = mk(1.0f, 0.0f, 0.0f);
+    if (valid) ray = camera_ray<false>(P, x, y, P.wf_sample, 0);
+    stamp(P, tile, 1);
+    const Hit h = find_closest<false, WALK>(P, sv, ray, valid, tc, ctr);
+    stamp(P, tile, 2);
+    if (valid && P.hit_id && P.wf_sample == 0) P.hit_id[p] = hit_id_of(h);
+    const NodeOut o = shade_hit<false, WALK, LdsScene, false, false>(P, sv, ray, h, valid, 1, 1.0f, tc, ctr, 0u);
+    stamp(P, tile, 3);
+    emit(P, sh, 1, valid, (uint32_t)p, 1.0f, o);
+    stamp(P, tile, 4);
+}
+
+// Workgroup (bx, by) runs the tiles of column bx in tile rows by, by + gridDim.y, by + 2 gridDim.y one after the other.
+// Once per workgroup: the parity read, the first-block clearing, the scene copy and its barrier, the wave's stack.
+// Per tile: tile -> pixel, shard_of(), the camera ray, find_closest(), shade_hit(), emit() -- and the launch parameters
+// those read, see below.  The loop carries nothing but its wave-uniform counter from one tile to the next.
+template <int WALK, int OCC, int TILES>
+__global__ __launch_bounds__(256) P3D_OCC(OCC) void wf_primary_kernel_tiles(const LaunchParams P) {
+    static_assert(TILES >= 2 && TILES <= kMaxPrimaryTiles, "one tile per workgroup is wf_primary_kernel");
+    const uint32_t par = P.wf_ctrl[0] & 1u;                     // this pass's counter set (LaunchParams::wf_alt)
+    if (blockIdx.x == 0 && blockIdx.y == 0) {
+        if (threadIdx.x == 0) P.wf_ctrl[32] = par;
+        for (uint32_t i = threadIdx.x; i < P.wf_clear_words; i += blockDim.x) P.wf_clear[i] = 0u;
+        uint32_t* other = P.wf_alt + (size_t)((1u - par) * 2u) * kWfShards;
+        for (uint32_t i = threadIdx.x; i < 2u * kWfShards; i += blockDim.x) other[i] = 0u;
+    }
+    const LdsScene sv = View<true>::make_shading(P);
+    const TravCtx tc = wave_stack<true>(P, 0);
+    const int tx = blockIdx.x;
+#pragma nounroll
+    for (int k = 0; k < TILES; k++) {
+        const int ty = (int)(blockIdx.y + (uint32_t)k * gridDim.y);          // wave-uniform: the loop's state stays in scalar registers
+        if (ty >= P.wf_tile_rows) break;                                      // past the band's last tile row (after the barrier)
+        // The tile reads its launch parameters through a pointer the compiler cannot see through.  Read from P they are all
+        // loop-invariant: the compiler hoists ~100 of them, they stay live across the whole loop, and the kernel spilled 101
+        // scalar registers into lanes of 86 vector registers (scratch under the budget of 6 waves per SIMD): what cost round 3's
+        // run-time loop its occupancy.  Read here they are scalar loads where they are used, as in wf_primary_kernel: 30 more
+        // s_load per tile, 1 spilled scalar register, no scratch.  The kernel's one argument IS the kernarg segment:
+        static_assert(std::is_same_v<decltype(&wf_primary_kernel_tiles<WALK, OCC, TILES>), void (*)(const LaunchParams)>,
+                      "Q below reads the kernarg segment as the kernel's only argument, a LaunchParams at offset 0");
+        auto args = __builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(args));
+        const LaunchParams& Q = *(const LaunchParams*)args;
+        int x, y, row;
+        const bool valid = tile_pixel_at(Q, tx, ty, x, y, row);
+        if (__ballot(valid) == 0) continue;
+        primary_tile_lds<WALK>(Q, sv, tc, par, ty * Q.tiles_x + tx, valid, x, y, row);
+    }
 }
 
 // Lanes a wave of a deeper level uses: a short queue is spread over ALL the shard's waves with
@@ -1048,20 +1124,7 @@ constexpr KernelVariant variant_at(int i) {
     return v;
 }
 
-// The level kernels (wf_primary_kernel, wf_tile_kernel; wf_secondary_kernel has no BATCH: the deeper levels are shared).
-constexpr KernelVariant canonical_level(KernelVariant v, bool has_batch) {
-    if (!has_batch) v.batch = false;
-    if (v.walk == WALK_SHARED && v.lds) v.walk = WALK_LANE;        // LDS scenes have no shared walk
-    // a register budget only for the timed builds of the BVH walks: grid, counting, stochastic, Schlick and batch builds use the default
-    if ((v.occ != 5 && v.occ != 6) || v.walk == WALK_GRID || v.count || v.stoch || v.schlick || v.batch) v.occ = 1;
-    return v;
-}
-constexpr bool built_level(const KernelVariant& v, bool has_batch) {
-    if (v.batch && !has_batch) return false;
-    if (v.walk == WALK_SHARED && v.lds) return false;
-    if (v.occ == 1) return true;
-    return v.walk != WALK_GRID && !v.count && !v.stoch && !v.schlick && !v.batch;
-}
+// The level kernels: canonical_level() and built_level() of p3d_kernel_variant.h.
 // The tree kernel: GRID = grid walk, SHARED = shared walk (the packet walk is the lane walk here), PRIV from the depth
 // (tree_private_dwords); the schedule never runs features with random draws.
 constexpr int canonical_priv(const KernelVariant& v, int priv) {
@@ -1087,13 +1150,21 @@ constexpr bool variants_are_consistent() {
         for (int occ : raw_occs) {
             KernelVariant v = variant_at(i);
             v.occ = occ;
-            if (!built_level(canonical_level(v, true), true) || !built_level(canonical_level(v, false), false)) return false;
+            v.tiles = kMaxPrimaryTiles;                 // (only the level-1 kernel has the variant)
+            if (!built_level(canonical_level(v, Level::Tile), Level::Tile) || !built_level(canonical_level(v, Level::Secondary), Level::Secondary)) return false;
+            for (int tiles = 0; tiles <= kMaxPrimaryTiles + 1; tiles++) {
+                v.tiles = tiles;
+                if (!built_level(canonical_level(v, Level::Primary), Level::Primary)) return false;
+            }
+            v.tiles = 1;
             for (int priv : raw_privs)
                 if (!built_tree(canonical_tree(v, canonical_priv(v, priv)), canonical_priv(v, priv))) return false;
         }
-        const KernelVariant v = variant_at(i);
-        if (built_level(v, true) && !(canonical_level(v, true) == v)) return false;
-        if (built_level(v, false) && !(canonical_level(v, false) == v)) return false;
+        KernelVariant v = variant_at(i);
+        for (v.tiles = kMaxPrimaryTiles; v.tiles >= 1; v.tiles--)
+            for (Level k : {Level::Primary, Level::Secondary, Level::Tile})
+                if (built_level(v, k) && !(canonical_level(v, k) == v)) return false;
+        v.tiles = 1;
         for (int priv : kPrivs)
             if (built_tree(v, priv) && !(canonical_priv(v, priv) == priv && canonical_tree(v, priv) == v)) return false;
     }
@@ -1101,14 +1172,16 @@ constexpr bool variants_are_consistent() {
 }
 static_assert(variants_are_consistent(), "a kernel request maps to a variant that is not built, or a built variant is unreachable");
 
-enum class Level { Primary, Secondary, Tile };
-template <Level KERNEL> struct LevelKernels {
-    static constexpr int n = kLevelVariants;
-    static constexpr bool has_batch = KERNEL != Level::Secondary;
-    static constexpr bool built(int i) { return built_level(variant_at(i), has_batch); }
+template <Level KERNEL> struct LevelKernels {       // position: variant_index * per_variant + (TILES - 1)
+    static constexpr Level level = KERNEL;
+    static constexpr int per_variant = KERNEL == Level::Primary ? kMaxPrimaryTiles : 1;
+    static constexpr int n = kLevelVariants * per_variant;
+    static constexpr KernelVariant at(int i) { KernelVariant v = variant_at(i / per_variant); v.tiles = 1 + i % per_variant; return v; }
+    static constexpr bool built(int i) { return built_level(at(i), KERNEL); }
     template <int I> static constexpr KernelFn fn() {
-        constexpr KernelVariant v = variant_at(I);
-        if constexpr (KERNEL == Level::Primary) return wf_primary_kernel<v.count, v.lds, v.walk, v.occ, v.stoch, v.schlick, v.batch>;
+        constexpr KernelVariant v = at(I);
+        if constexpr (KERNEL == Level::Primary && v.tiles > 1) return wf_primary_kernel_tiles<v.walk, v.occ, v.tiles>;
+        else if constexpr (KERNEL == Level::Primary) return wf_primary_kernel<v.count, v.lds, v.walk, v.occ, v.stoch, v.schlick, v.batch>;
         else if constexpr (KERNEL == Level::Secondary) return wf_secondary_kernel<v.count, v.lds, v.walk, v.occ, v.stoch, v.schlick>;
         else return wf_tile_kernel<v.count, v.lds, v.walk, v.occ, v.stoch, v.schlick, v.batch>;
     }
@@ -1132,8 +1205,12 @@ template <class K, int... I> static const void* kernel_lookup(int i, std::intege
 }
 template <class K> static const void* kernel_at(int i) { return kernel_lookup<K>(i, std::make_integer_sequence<int, K::n>{}); }
 
-KernelVariant level_variant(KernelVariant v, bool has_batch) { return canonical_level(v, has_batch); }
-template <class K> static const void* level_kernel(const KernelVariant& v) { return kernel_at<K>(variant_index(canonical_level(v, K::has_batch))); }
+KernelVariant level_variant(KernelVariant v, Level k) { return canonical_level(v, k); }
+template <class K> static const void* level_kernel(const KernelVariant& v) {
+    const KernelVariant served = canonical_level(v, K::level);
+    const int i = variant_index(served);
+    return i < 0 ? nullptr : kernel_at<K>(i * K::per_variant + served.tiles - 1);
+}
 static const void* tree_kernel(const LaunchParams& P, const KernelVariant& v) {
     const int priv = canonical_priv(v, tree_private_dwords(P, v.lds));
     const int i = variant_index(canonical_tree(v, priv));
@@ -1161,11 +1238,11 @@ hipError_t launch_tree(const LaunchParams& P, const KernelVariant& v, hipStream_
     return launch_by_pointer(tree_kernel(P, v), P, dim3((unsigned)P.grid_blocks), dim3(64 * P.wg_waves), tree_kernel_lds_bytes(P, v.lds), stream);
 }
 hipError_t launch_wf_primary(const LaunchParams& P, const KernelVariant& v, hipStream_t stream) {
-    // identity tile map and no learned order: a 2-D grid, blockIdx = (tile column, tile row) -- see tile_pixel()
-    // (LDS scenes only: the kernels of scenes read from HBM number their tiles through the learned order)
-    const bool grid2d = v.lds && P.xcd_chunk == 1 && P.wf_tile_rows > 1 && P.tiles_x * P.wf_tile_rows == P.n_tiles;
-    const dim3 grid = grid2d ? dim3((unsigned)P.tiles_x, (unsigned)P.wf_tile_rows) : dim3((unsigned)P.grid_blocks);
-    return launch_by_pointer(level_kernel<LevelKernels<Level::Primary>>(v), P, grid, dim3(64 * P.wg_waves), wavefront_lds_bytes(P, v.lds), stream);
+    // identity tile map and no learned order: a 2-D grid, blockIdx = (tile column, tile row) -- see tile_pixel() and
+    // primary_grid() (LDS scenes only: the kernels of scenes read from HBM number their tiles through the learned order)
+    const KernelVariant served = served_primary(v, P.tiles_x, P.wf_tile_rows, P.n_tiles, P.xcd_chunk);
+    const PrimaryGrid g = primary_grid(served, P.tiles_x, P.wf_tile_rows, P.n_tiles, P.xcd_chunk, P.grid_blocks);
+    return launch_by_pointer(level_kernel<LevelKernels<Level::Primary>>(served), P, dim3(g.x, g.y), dim3(64 * P.wg_waves), wavefront_lds_bytes(P, v.lds), stream);
 }
 hipError_t launch_wf_secondary(const LaunchParams& P, const KernelVariant& v, unsigned waves, hipStream_t stream) {
     return launch_by_pointer(level_kernel<LevelKernels<Level::Secondary>>(v), P, dim3((waves + P.wg_waves - 1) / P.wg_waves),

@@ -10,28 +10,13 @@
 
 #include "bvh_builder.h"
 #include "p3d_device_types.h"
+#include "p3d_kernel_variant.h"
 
 namespace p3d {
 
-// One build of a ray kernel, as the host asks for it.  Not every combination is built: the dispatchers of
-// p3d_kernels.hip map a request to the build that serves it (level_variant() below tells which one that is).
-struct KernelVariant {
-    bool count = false;     // P3D_FLAG_COUNTERS
-    bool lds = false;       // scene read from an LDS copy
-    int walk = 0;           // WALK_LANE / _PACKET / _GRID / _SHARED (p3d_shade.h)
-    int occ = 1;            // register budget in waves per SIMD: 5 or 6; anything else is the compiler's default
-    bool stoch = false;     // features with random draws
-    bool schlick = false;   // P3D_FEATURE_SCHLICK
-    bool batch = false;     // frame batch (p3d_render_frames)
-    constexpr bool operator==(const KernelVariant& o) const {
-        return count == o.count && lds == o.lds && walk == o.walk && occ == o.occ && stoch == o.stoch && schlick == o.schlick &&
-               batch == o.batch;
-    }
-};
-
 // ---- p3d_kernels.hip
-// the build of a level kernel that serves v (has_batch: wf_primary_kernel and wf_tile_kernel; the deeper levels are shared)
-KernelVariant level_variant(KernelVariant v, bool has_batch);
+// the build of level kernel k that serves v (p3d_kernel_variant.h: canonical_level)
+KernelVariant level_variant(KernelVariant v, Level k);
 size_t tree_kernel_lds_bytes(const LaunchParams& P, bool lds);
 size_t wavefront_lds_bytes(const LaunchParams& P, bool lds);
 size_t tile_kernel_lds_bytes(const LaunchParams& P, bool lds);

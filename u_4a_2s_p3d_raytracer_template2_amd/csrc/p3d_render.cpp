@@ -159,7 +159,7 @@ int FramePlan::query_tile() {
     tile_blocks = 0;
     tile_ok = tile_kernel_lds_bytes(PT, lds_scene) <= kMaxLdsBytes && D <= 16;
     if (!tile_ok) return P3D_OK;
-    const KernelVariant served = level_variant(with_budget(kv, tile_occ), true);
+    const KernelVariant served = level_variant(with_budget(kv, tile_occ), Level::Tile);
     const size_t olds = tile_kernel_lds_bytes(PT, lds_scene);
     auto* slot = &s->tile_occ[shared_walk ? 1 : 0];
     if (!(slot->v == served) || slot->lds != olds) {
@@ -505,6 +505,16 @@ int run_wavefront_pass(p3d_scene* s, p3d_scene::Workspace& ws, hipStream_t strea
     // (5 waves per SIMD), 78 under that budget without a spill -- config 2 0.0720 -> 0.0692 ms/frame, config 4 on this
     // schedule 5.30 -> 5.05 ms (profiles/r03_exp10_register_budgets.txt)
     v = with_budget(v, s->occupancy ? s->occupancy : 6);
+    // tiles per workgroup of the level-1 launch (p3d_set_primary_tiles; p3d_kernel_variant.h says which builds have the variant)
+    v.tiles = s->primary_tiles;
+    {
+        const KernelVariant served = served_primary(v, P.tiles_x, P.wf_tile_rows, P.n_tiles, P.xcd_chunk);
+        s->last_primary_tiles = served.tiles;
+        if (s->verbose) {
+            const PrimaryGrid g = primary_grid(served, P.tiles_x, P.wf_tile_rows, P.n_tiles, P.xcd_chunk, P.grid_blocks);
+            fprintf(stderr, "p3d: level 1: %d tile(s) per workgroup, grid %u x %u\n", served.tiles, g.x, g.y);
+        }
+    }
     const size_t n_counts = kCountWords;
     uint32_t* counts = (uint32_t*)ws.counts.p;                              // [level][shard] ray counts, then node counts
     // No clearing launch and nothing about a frame in host state (a captured frame can be replayed any number of
@@ -526,7 +536,7 @@ int run_wavefront_pass(p3d_scene* s, p3d_scene::Workspace& ws, hipStream_t strea
     P.wf_nodes_parent = nullptr; P.wf_ncap_parent = 0;
     P.wf_nodes_self = nodes(1); P.wf_ncount_self = ncount(1); P.wf_ncap_self = cap(1);
     {   // persistent grids: as many waves as can be resident (cached occupancy queries)
-        const KernelVariant deeper = level_variant(v, false);
+        const KernelVariant deeper = level_variant(v, Level::Secondary);
         if (!(s->wf_occ.v == deeper) || s->wf_occ.stack != P.trav_stack_dwords) {
             HIP_TRY(wf_resident_waves(P, deeper, &s->wf_occ.waves));
             s->wf_occ.v = deeper; s->wf_occ.stack = P.trav_stack_dwords;
@@ -702,6 +712,7 @@ int render_batch(p3d_scene* s, const p3d_camera* cams, int32_t n_frames, const p
     if (sched == SCHED_WAVEFRONT && !plan.wavefront_ok) sched = SCHED_TREE;
     if (sched == SCHED_TREE && plan.stochastic) return fail(P3D_ERR_LIMIT, "workspace budget too small for the schedules the features need");
     s->last_schedule = sched;
+    s->last_primary_tiles = 1;          // (the wavefront schedule says what its level-1 launch ran with)
     LaunchParams& P = plan.P;
     const size_t lds = sched == SCHED_TREE   ? tree_kernel_lds_bytes(P, plan.lds_scene)
                        : sched == SCHED_TILE ? tile_kernel_lds_bytes(plan.PT, plan.lds_scene)

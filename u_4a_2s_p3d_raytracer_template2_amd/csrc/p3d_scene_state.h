@@ -218,6 +218,8 @@ struct p3d_scene {
     uint32_t dbg_skip = 0;               // diagnostic builds only (LaunchParams::dbg_skip)
     unsigned long long* dbg_stamps = nullptr; int dbg_stamp_level = 1;   // the caller's buffer (p3d_debug_set_stamps)
     int occupancy = 0;     // 0 = compiler default register budget, else 5 / 6 / 8 waves per SIMD
+    int primary_tiles = p3d::kDefaultPrimaryTiles;   // 16x16 tiles a workgroup of the level-1 launch runs (p3d_set_primary_tiles)
+    int last_primary_tiles = 1;                      // ... and what the most recent render's level-1 launch ran with
     uint32_t tri_quads = 3;    // 16-byte quads per triangle test record (3; 4 = round 2's 64-byte stride, P3D_TRI_STRIDE=64)
     bool verbose = false;      // P3D_VERBOSE=1: launch geometry on stderr (diagnostic)
     int share_min_idle = 16;   // work-sharing walk of scenes read from HBM: idle lanes before a steal round (0 or > 64: private walks)

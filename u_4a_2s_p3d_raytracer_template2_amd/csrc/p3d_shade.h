@@ -6,6 +6,7 @@
 #ifndef P3D_SHADE_H
 #define P3D_SHADE_H
 
+#include "p3d_kernel_variant.h"
 #include "p3d_traverse.h"
 #include "p3d_powf.h"
 #include "p3d_pow.h"
@@ -52,7 +53,7 @@ __device__ __forceinline__ Mtl load_material(const SV& sv, uint32_t m) {
 struct TravCtx { TravStack lane; WaveStack wave; uint32_t* share; };
 // WALK_SHARED (scenes read from HBM only): the per-lane walk with the lanes of a wave sharing their pending subtrees
 // (p3d_traverse.h: closest_hit_shared).  Like the packet walk it must be reached by all lanes of the wave together.
-enum { WALK_LANE = 0, WALK_PACKET = 1, WALK_GRID = 2, WALK_SHARED = 3 };
+// (the WALK_* constants: p3d_kernel_variant.h)
 
 template <bool COUNT> __device__ __forceinline__ Hit closest_shared(const LaunchParams& P, const GlobalScene& sv, const Ray& ray, bool active,
                                                                     const TravCtx& tc, Ctr& ctr) {
