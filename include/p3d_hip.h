@@ -261,6 +261,48 @@ int p3d_render(p3d_scene* scene, const p3d_camera* cam, const p3d_render_params*
  *    stream itself, so a replay renders the cameras it was captured with. */
 int p3d_render_frames(p3d_scene* scene, const p3d_camera* cams, int32_t n, const p3d_render_params* params,
                       const p3d_outputs* out);
+/* A stream of rays the caller supplies, and what comes back for each.  Ray i is (origin[i], dir[i]); its results sit at
+ * index i of every plane -- no image conventions: no clamp, no quantisation, no bottom-up rows, no "/ 16". */
+typedef struct p3d_rays {
+    uint32_t     n;         /* number of rays; 0 is allowed and does nothing             */
+    const float* origin;    /* [n][3]                                                    */
+    const float* dir;       /* [n][3], used as given: NOT normalised (as rayTracing())   */
+    int32_t      memory;    /* 0 host, 1 device pointers on the scene's device           */
+} p3d_rays;
+
+typedef struct p3d_ray_outputs {  /* every plane may be NULL */
+    float*   rgb32f;   /* [n][3] what rayTracing(ray, 1, 1.0) returns: UNCLAMPED            */
+    int32_t* hit_id;   /* [n] scene index of the closest hit, -1 on a miss                  */
+    float*   t;        /* [n] the intersector's t of that hit (units of |dir|); +inf on a miss */
+    float*   normal;   /* [n][3] getNormal(hit point).normalize() of that hit; 0,0,0 on a miss */
+    int32_t  memory;   /* as p3d_outputs::memory: 0 = copy back and return when done, 1 = enqueue only */
+} p3d_ray_outputs;
+
+/* Replaces a caller's own loop around rayTracing(ray, 1, 1.0) (RT/main.cpp:530-721, with processLight() and every
+ * intercepts() beneath it): ray i is traced as rayTracing(Ray(origin[i], dir[i]), 1, 1.0) -- depth 1, outside ior 1.0 --
+ * for cameras the reference does not have, picking, probes and visibility queries.
+ *  - params: max_depth, accel, flags and features are read.  accel selects the shadow-ray semantics exactly as
+ *    for frames; closest hits are "nearest, lowest scene index on ties" (SURVEY Q1), as for frames.
+ *  - asynchronous on the scene's stream like p3d_render; with p3d_ray_outputs::memory == 0 it copies and waits (and with
+ *    p3d_rays::memory == 0 it uploads the rays first).  Under a stream capture it behaves like p3d_render: the lazy grid
+ *    build of the first GRID-mode call is refused while capturing.
+ *  - flags: P3D_FLAG_NO_LDS_SCENE and P3D_FLAG_PRIVATE_WALK are honoured; P3D_FLAG_WAVEFRONT is accepted and does nothing
+ *    (ray streams run the wavefront schedule only).  Every other flag -- tile and tree forcing, counters, profile, packet
+ *    walk, device samples -- is refused with P3D_ERR_ARG.
+ *  - features: 0 and P3D_FEATURE_SOFT_SHADOW.  A stream has no sample index, so soft shadows are always the deterministic
+ *    4x4 sub-light grid of RT/main.cpp:601-618.  Schlick, fuzzy reflection and the skybox are refused with P3D_ERR_ARG.
+ *  - P3D_ERR_ARG also for: spp != 0, samples != NULL, world > 1 or rank != 0, a NULL origin or dir with n > 0, max_depth
+ *    outside 1..16.
+ *  - a scene created with cull_never_hit is refused with P3D_ERR_STATE: that shortcut rests on |dir| <= sqrt(2), which a
+ *    caller's ray does not promise.
+ *  - results for non-finite origins or directions are unspecified (the call still returns).
+ *  - the workspace obeys the p3d_set_tuning() budget: streams that need more run in bands of rays, the way frames run in
+ *    bands of rows.  A stream of 2^31 rays or more is refused with P3D_ERR_LIMIT before anything is allocated.
+ *  - the handle's frame state is not touched: the measured schedule choice, the learned tile orders, p3d_last_schedule()
+ *    and p3d_last_primary_tiles() are what they were, and a frame rendered after a stream is, in bits and in schedule,
+ *    the frame it would have been without it. */
+int p3d_trace_rays(p3d_scene* scene, const p3d_rays* rays, const p3d_render_params* params,
+                   const p3d_ray_outputs* out);
 int p3d_sync(p3d_scene* scene);
 /* counters of the most recent render made with P3D_FLAG_COUNTERS (waits for it) */
 int p3d_get_counters(p3d_scene* scene, p3d_counters* out);

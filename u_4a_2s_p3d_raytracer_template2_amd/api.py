@@ -69,6 +69,17 @@ class Outputs(C.Structure):
     _fields_ = [("rgb8", C.c_void_p), ("rgb32f", C.c_void_p), ("hit_id", C.c_void_p), ("memory", C.c_int32)]
 
 
+class Rays(C.Structure):
+    """p3d_rays: n rays, origin / dir [n][3] floats on the host (memory 0) or the scene's device (memory 1)."""
+    _fields_ = [("n", C.c_uint32), ("origin", C.c_void_p), ("dir", C.c_void_p), ("memory", C.c_int32)]
+
+
+class RayOutputs(C.Structure):
+    """p3d_ray_outputs: every plane may be NULL."""
+    _fields_ = [("rgb32f", C.c_void_p), ("hit_id", C.c_void_p), ("t", C.c_void_p), ("normal", C.c_void_p),
+                ("memory", C.c_int32)]
+
+
 class SceneStats(C.Structure):
     _fields_ = [("n_nodes", C.c_uint32), ("n_leaves", C.c_uint32), ("max_depth", C.c_uint32),
                 ("n_leaf_refs", C.c_uint32), ("n_spheres", C.c_uint32), ("n_triangles", C.c_uint32),
@@ -81,7 +92,7 @@ class SceneStats(C.Structure):
 
 # every symbol include/p3d_hip.h declares (tests check that the library exports them all)
 C_ABI_SYMBOLS = ["p3d_abi_version", "p3d_last_error", "p3d_device_count", "p3d_scene_create",
-                 "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_sync",
+                 "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_trace_rays", "p3d_sync",
                  "p3d_get_counters", "p3d_get_profile", "p3d_last_schedule", "p3d_set_tuning", "p3d_set_primary_tiles", "p3d_last_primary_tiles", "p3d_set_stream", "p3d_timer_begin", "p3d_timer_end", "p3d_deinterleave_frames",
                  "p3d_deinterleave", "p3d_debug_intersect", "p3d_debug_powf", "p3d_debug_pow", "p3d_debug_schlick_kr", "p3d_debug_check_rcp", "p3d_debug_check_rcp_len", "p3d_tune_schedule", "p3d_debug_set_stamps", "p3d_debug_set_stamp_level",
                  "p3d_comm_unique_id", "p3d_comm_create", "p3d_comm_create_all", "p3d_comm_destroy", "p3d_comm_info",
@@ -126,6 +137,7 @@ def lib():
     L.p3d_local_rows.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     L.p3d_render.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(Outputs)]
     L.p3d_render_frames.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.POINTER(RenderParams), C.POINTER(Outputs)]
+    L.p3d_trace_rays.argtypes = [C.c_void_p, C.POINTER(Rays), C.POINTER(RenderParams), C.POINTER(RayOutputs)]
     L.p3d_sync.argtypes = [C.c_void_p]
     L.p3d_get_counters.argtypes = [C.c_void_p, C.POINTER(Counters)]
     L.p3d_set_stream.argtypes = [C.c_void_p, C.c_void_p]
@@ -172,6 +184,8 @@ def lib():
     L.p3dh_scene_desc.argtypes = [C.c_void_p, C.POINTER(SceneDesc)]
     L.p3dh_scene_camera.argtypes = [C.c_void_p, C.POINTER(Camera)]
     L.p3dh_primary_ray.argtypes = [C.c_void_p, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.p3dh_trace_rays.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.p3dh_generate_samples.argtypes = [C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p]
     L.p3dh_bvh_build.restype = C.c_void_p
     L.p3dh_bvh_build.argtypes = [C.POINTER(SceneDesc), C.c_uint32]
@@ -277,6 +291,14 @@ class HostScene:
         lib().p3dh_primary_ray(self.h, px, py, o, d)
         return np.array(o, np.float32), np.array(d, np.float32)
 
+    def trace_rays(self, origins, dirs, max_depth=4, accel=ACCEL_BVH, soft_shadow=False, device=0):
+        """traceRays() of the C++ host layer: rayTracing(ray, 1, 1.0) per ray on one GPU -> rgb32f, hit_id, t, normal."""
+        o, d, n = _ray_arrays(origins, dirs)
+        out = _ray_planes(n, RAY_PLANES)
+        _check(lib().p3dh_trace_rays(self.h, n, o.ctypes.data, d.ctypes.data, int(max_depth), int(accel), 1 if soft_shadow else 0,
+                                     int(device), *[out[k].ctypes.data for k in RAY_PLANES]), "traceRays")
+        return out
+
     def arrays(self):
         """numpy views of the flattened scene (type, data12, material, materials12, lights6, bg)."""
         d = self.desc()
@@ -302,6 +324,25 @@ def orbit_eyes(eye, n, step_deg, d_beta_deg=0.0):
     lib().p3dh_orbit_eyes(float(eye[0]), float(eye[1]), float(eye[2]), int(n), float(step_deg), float(d_beta_deg),
                           out.ctypes.data_as(C.c_void_p))
     return out
+
+
+RAY_PLANES = ("rgb32f", "hit_id", "t", "normal")       # the planes of p3d_ray_outputs, in its order
+
+
+def _ray_arrays(origins, dirs):
+    o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+    if len(o) != len(d):
+        raise ValueError("origins and dirs differ in length")
+    return o, d, len(o)
+
+
+def _ray_planes(n, want):
+    shape = {"rgb32f": ((n, 3), np.float32), "hit_id": ((n,), np.int32), "t": ((n,), np.float32), "normal": ((n, 3), np.float32)}
+    for k in want:
+        if k not in shape:
+            raise ValueError("unknown ray output plane %r" % (k,))
+    return {k: np.zeros(shape[k][0], shape[k][1]) for k in want}
 
 
 def make_desc(ptype, data12, material, materials12, lights6, bg):
@@ -487,6 +528,30 @@ class DeviceScene:
         p = self._params(max_depth, accel, spp, samples, rank, world, row_block, counters, tree, no_lds, profile, wavefront, soft_shadow, fuzzy_reflection, seed, tile, samples_ptr, packet, private_walk, skybox, schlick)
         o = Outputs(rgb8_ptr or None, rgb32f_ptr or None, hit_ptr or None, 1)
         _check(lib().p3d_render_frames(self.h, arr, n, C.byref(p), C.byref(o)), "p3d_render_frames")
+
+    def _ray_params(self, max_depth, accel, no_lds, private_walk, soft_shadow):
+        return self._params(max_depth, accel, 0, None, 0, 1, 0, False, no_lds=no_lds, private_walk=private_walk, soft_shadow=soft_shadow)
+
+    def trace_rays(self, origins, dirs, max_depth=4, accel=ACCEL_BVH, want=RAY_PLANES, no_lds=False, private_walk=False,
+                   soft_shadow=False):
+        """p3d_trace_rays on host arrays: ray i = rayTracing(Ray(origins[i], dirs[i]), 1, 1.0), directions used as given.
+        Returns the planes named in `want`: rgb32f (n, 3) UNCLAMPED, hit_id (n,), t (n,), normal (n, 3)."""
+        o, d, n = _ray_arrays(origins, dirs)
+        out = _ray_planes(n, want)
+        r = Rays(n, o.ctypes.data if n else None, d.ctypes.data if n else None, 0)
+        ro = RayOutputs(*[out[k].ctypes.data if k in out and n else None for k in RAY_PLANES], 0)
+        p = self._ray_params(max_depth, accel, no_lds, private_walk, soft_shadow)
+        _check(lib().p3d_trace_rays(self.h, C.byref(r), C.byref(p), C.byref(ro)), "p3d_trace_rays")
+        return out
+
+    def trace_rays_device(self, n, origin_ptr, dir_ptr, rgb32f_ptr=0, hit_ptr=0, t_ptr=0, normal_ptr=0, max_depth=4, accel=ACCEL_BVH,
+                          no_lds=False, private_walk=False, soft_shadow=False):
+        """Enqueue a ray stream whose rays and output planes are caller-owned DEVICE buffers (raw pointers; 0 = no such
+        plane); asynchronous on the scene's stream."""
+        r = Rays(int(n), origin_ptr or None, dir_ptr or None, 1)
+        ro = RayOutputs(rgb32f_ptr or None, hit_ptr or None, t_ptr or None, normal_ptr or None, 1)
+        p = self._ray_params(max_depth, accel, no_lds, private_walk, soft_shadow)
+        _check(lib().p3d_trace_rays(self.h, C.byref(r), C.byref(p), C.byref(ro)), "p3d_trace_rays")
 
     def deinterleave_frames(self, gathered_ptr, frames_ptr, res_x, res_y, row_block, world, bpp, n_frames,
                             rank_stride_bytes=0, tile_stride_bytes=0, frame_stride_bytes=0):

@@ -62,6 +62,26 @@ void p3dh_generate_samples(uint32_t seed, int32_t res_x, int32_t res_y, int32_t 
     generate_samples(seed, res_x, res_y, spp, aperture, out);
 }
 
+// traceRays() of the host layer on n rays (origin3 / dir3: n x 3 floats); every output plane may be NULL.  Returns its status.
+int p3dh_trace_rays(const p3dh_scene* h, uint32_t n, const float* origin3, const float* dir3, int32_t max_depth, int32_t accel,
+                    int32_t soft_shadow, int32_t device, float* colors3, int32_t* hit_id, float* t, float* normal3) {
+    std::vector<Ray> rays(n);
+    for (uint32_t i = 0; i < n; i++) {
+        rays[i].origin = Vector(origin3[3 * i], origin3[3 * i + 1], origin3[3 * i + 2]);
+        rays[i].direction = Vector(dir3[3 * i], dir3[3 * i + 1], dir3[3 * i + 2]);
+    }
+    RenderOptions opt;
+    opt.max_depth = max_depth; opt.accel = accel; opt.SOFT_SHADOW = soft_shadow != 0; opt.device = device;
+    TraceResult res;
+    const int rc = traceRays(h->scene, opt, rays, res, nullptr);
+    if (rc) return rc;
+    if (colors3) memcpy(colors3, res.colors.data(), (size_t)n * 12);
+    if (hit_id) memcpy(hit_id, res.hit_id.data(), (size_t)n * 4);
+    if (t) memcpy(t, res.t.data(), (size_t)n * 4);
+    if (normal3) memcpy(normal3, res.normal.data(), (size_t)n * 12);
+    return rc;
+}
+
 // ---- host-only BVH build, for tests that run without a GPU
 struct p3dh_bvh {
     std::vector<p3d::NodePair> nodes;

@@ -578,4 +578,37 @@ int renderFrames(const Scene& scene, const RenderOptions& opt, const std::vector
     return P3D_OK;
 }
 
+int traceRays(const Scene& scene, const RenderOptions& opt, const std::vector<Ray>& rays, TraceResult& out, std::string* err) {
+    auto bad = [&](int rc) { if (err) *err = p3d_last_error(); return rc; };
+    const size_t n = rays.size();
+    if (n > 0xFFFFFFFFull) { if (err) *err = "too many rays"; return P3D_ERR_LIMIT; }
+    Scene::Flat flat;
+    scene.flatten(flat);
+    p3d_render_params prm;
+    memset(&prm, 0, sizeof prm);
+    prm.max_depth = opt.max_depth;
+    prm.accel = opt.accel < 0 ? (int)scene.GetAccelStruct() : opt.accel;
+    prm.world = 1;
+    prm.flags = opt.counters ? P3D_FLAG_COUNTERS : 0;           // (refused by the library, like the switches below)
+    prm.features = (opt.SOFT_SHADOW ? P3D_FEATURE_SOFT_SHADOW : 0u) | (opt.FUZZY_REFLECTION ? P3D_FEATURE_FUZZY_REFLECTION : 0u) |
+                   (opt.SCHLICK_APPROX ? P3D_FEATURE_SCHLICK : 0u) | (opt.SKYBOX ? P3D_FEATURE_SKYBOX : 0u);
+    std::vector<float> origin(3 * n), dir(3 * n);
+    for (size_t i = 0; i < n; i++) {
+        origin[3 * i] = rays[i].origin.x; origin[3 * i + 1] = rays[i].origin.y; origin[3 * i + 2] = rays[i].origin.z;
+        dir[3 * i] = rays[i].direction.x; dir[3 * i + 1] = rays[i].direction.y; dir[3 * i + 2] = rays[i].direction.z;
+    }
+    out.colors.assign(3 * n, 0.0f); out.hit_id.assign(n, -1); out.t.assign(n, 0.0f); out.normal.assign(3 * n, 0.0f);
+    p3d_scene* dev = nullptr;
+    int rc = p3d_scene_create(&flat.desc, nullptr, opt.device, &dev);
+    if (rc) return bad(rc);
+    p3d_rays r;
+    r.n = (uint32_t)n; r.origin = origin.data(); r.dir = dir.data(); r.memory = 0;
+    p3d_ray_outputs o;
+    o.rgb32f = out.colors.data(); o.hit_id = out.hit_id.data(); o.t = out.t.data(); o.normal = out.normal.data(); o.memory = 0;
+    rc = p3d_trace_rays(dev, &r, &prm, &o);
+    if (rc) bad(rc);
+    p3d_scene_destroy(dev);
+    return rc;
+}
+
 }  // namespace p3d_host

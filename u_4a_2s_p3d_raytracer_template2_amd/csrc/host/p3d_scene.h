@@ -256,5 +256,18 @@ std::vector<Vector> orbit_eyes(Vector eye, int n, float step_deg, float d_beta_d
 int renderFrames(const Scene& scene, const RenderOptions& opt, const std::vector<Vector>& eyes, bool want_colors, bool want_hit,
                  RenderResult& out, std::string* err);
 
+
+// A caller's own loop around rayTracing(ray, 1, 1.0) (RT/main.cpp:530-721) as one call: ray i of `rays` is traced at depth 1
+// with outside ior 1.0, its direction used as given (not normalised), through p3d_trace_rays on one device.  From opt:
+// max_depth, accel, SOFT_SHADOW (always the deterministic 4x4 sub-light grid: a ray has no sample index) and device; the
+// other switches are refused as p3d_trace_rays refuses them.  Every plane of `out` holds rays.size() entries.
+struct TraceResult {
+    std::vector<float> colors;       // [n][3] rayTracing()'s return value, UNCLAMPED
+    std::vector<int32_t> hit_id;     // [n] scene index of the closest hit, -1 on a miss
+    std::vector<float> t;            // [n] the intersector's t of that hit, +inf on a miss
+    std::vector<float> normal;       // [n][3] getNormal(hit point).normalize(), 0 on a miss
+};
+int traceRays(const Scene& scene, const RenderOptions& opt, const std::vector<Ray>& rays, TraceResult& out, std::string* err = nullptr);
+
 }  // namespace p3d_host
 #endif

@@ -193,6 +193,17 @@ struct LaunchParams {
     const FrameCam* frame_cams;
 };
 
+// A ray stream (p3d_trace_rays): what its level-1 launch, wf_rays_kernel, takes NEXT TO the launch parameters -- which stay
+// what frames pass, to the byte, so that no frame kernel changes with this entry.  Ray i is origin / dir record i (12 bytes
+// each, used as given).  In the launch parameters of a stream a "tile" is one workgroup's 64 * wg_waves consecutive rays,
+// tiles_x == 1 and a band of tile rows is a band of rays; level-1 links are ray indices; LaunchParams::rgb32f[3 i] gets
+// ray i's UNCLAMPED return value and LaunchParams::hit_id[i], t[i], normal[3 i] its closest hit.  Every output may be nullptr.
+struct RayStreamIO {
+    const float* origin; const float* dir;
+    float* t; float* normal;
+    uint32_t count;
+};
+
 // Every level of a pass for the fused resolve launch (small frames / shards, wf_resolve_fused_kernel): level l's
 // parked nodes (shard s at nodes[l] + s * cap[l]) and their per-shard counts; levels top .. 1 are combined.
 struct ResolveLevels { NodeRec* nodes[18]; const uint32_t* ncount[18]; uint32_t cap[18]; int32_t top; };

@@ -59,6 +59,12 @@ struct BudgetKey {
 };
 inline BudgetKey budget_key(const FrameConfig& c) { return {c.res_x, c.res_y, c.max_depth, c.spp}; }
 
+// a ray stream's reading of the workspace budget (p3d_trace_rays): streams keep their own, so that they never touch a frame's key
+struct RayStreamKey {
+    uint64_t budget; int32_t max_depth; uint32_t n;
+    bool operator==(const RayStreamKey& o) const { return budget == o.budget && max_depth == o.max_depth && n == o.n; }
+};
+
 // a tile order: what decides the tiles' number (res, rank / world / row_block, n) and their relative cost, the schedule whose
 // tiles they are, and for batches the tile count itself
 struct TileOrderKey {

@@ -26,8 +26,9 @@ struct KernelVariant {
     }
 };
 
-// The level kernels: wf_primary_kernel, wf_secondary_kernel (no BATCH: the deeper levels are shared) and wf_tile_kernel.
-enum class Level { Primary, Secondary, Tile };
+// The level kernels: wf_primary_kernel, wf_secondary_kernel (no BATCH: the deeper levels are shared), wf_tile_kernel, and
+// wf_rays_kernel: level 1 of a ray stream (p3d_trace_rays).
+enum class Level { Primary, Secondary, Tile, Rays };
 constexpr int kMaxPrimaryTiles = 3;
 // what a handle asks for until p3d_set_primary_tiles() says otherwise: 2 measured 2.4 % faster than 1 on the 1080p frame of
 // mount_low with four frames in flight, 3 measured 1.6 % (profiles/r06_primary_tiles.txt)
@@ -39,9 +40,17 @@ constexpr int kDefaultPrimaryTiles = 2;
 constexpr bool has_primary_tiles(const KernelVariant& v, Level k) {
     return k == Level::Primary && v.lds && v.walk == WALK_LANE && !v.count && !v.stoch && !v.schlick && !v.batch;
 }
+// The ray-stream level-1 kernel is built per scene placement and walk and nothing else: the per-lane, grid and shared walks
+// (a packet request gets the per-lane walk), at the register budget frames run their level kernels at by default.
+constexpr int kRaysOcc = 6;
 // the build of level kernel k that serves request v
 constexpr KernelVariant canonical_level(KernelVariant v, Level k) {
     if (k == Level::Secondary) v.batch = false;
+    if (k == Level::Rays) {
+        v.count = v.stoch = v.schlick = v.batch = false;
+        v.occ = kRaysOcc;
+        if (v.walk == WALK_PACKET) v.walk = WALK_LANE;
+    }
     if (v.walk == WALK_SHARED && v.lds) v.walk = WALK_LANE;        // LDS scenes have no shared walk
     // a register budget only for the timed builds of the BVH walks: grid, counting, stochastic, Schlick and batch builds use the default
     if ((v.occ != 5 && v.occ != 6) || v.walk == WALK_GRID || v.count || v.stoch || v.schlick || v.batch) v.occ = 1;
@@ -51,6 +60,8 @@ constexpr KernelVariant canonical_level(KernelVariant v, Level k) {
 // ... and whether v itself is one of the builds of k: the one statement of which builds exist
 constexpr bool built_level(const KernelVariant& v, Level k) {
     if (v.batch && k == Level::Secondary) return false;
+    if (k == Level::Rays && (v.count || v.stoch || v.schlick || v.batch || v.walk == WALK_PACKET || v.occ != (v.walk == WALK_GRID ? 1 : kRaysOcc)))
+        return false;
     if (v.walk == WALK_SHARED && v.lds) return false;
     if (v.tiles != 1 && (v.tiles < 2 || v.tiles > kMaxPrimaryTiles || !has_primary_tiles(v, k))) return false;
     if (v.occ == 1) return true;

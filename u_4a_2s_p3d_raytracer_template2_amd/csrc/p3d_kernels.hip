@@ -80,6 +80,11 @@ __device__ __forceinline__ void sink_sample(const LaunchParams& P, size_t p, V3 
     a[0] = c.x; a[1] = c.y; a[2] = c.z;
 }
 
+// One finished ray of a ray stream (p3d_trace_rays): what rayTracing(ray, 1, 1.0) returns, as it is -- no clamp, no image.
+__device__ __forceinline__ void sink_ray(const LaunchParams& P, size_t i, V3 ret) {
+    if (P.rgb32f) { P.rgb32f[3 * i] = ret.x; P.rgb32f[3 * i + 1] = ret.y; P.rgb32f[3 * i + 2] = ret.z; }
+}
+
 // row of the compact local buffer -> image row (this rank's row blocks are every world-th one)
 __device__ __forceinline__ int image_row(const LaunchParams& P, int row) {
     const int blk = P.row_block_shift >= 0 ? (row >> P.row_block_shift) : row / P.row_block;
@@ -263,19 +268,26 @@ __device__ __forceinline__ Shard shard_of(const LaunchParams& P, uint32_t s, uin
 }
 
 // Hand a finished node's return value to whoever waits for it.
-// (parents = this shard's nodes of level - 1; level 1 returns to the pixel)
+// (parents = this shard's nodes of level - 1; level 1 returns to the pixel, or -- STREAM: the launches of a ray stream
+//  that can hold a level-1 node, wf_rays_kernel and the resolve launches -- to the ray's entry of the caller's planes)
+template <bool STREAM = false>
 __device__ __forceinline__ void deliver(const LaunchParams& P, NodeRec* parents, int level, uint32_t link, V3 ret) {
-    if (level == 1) { sink_sample(P, (size_t)link, ret); return; }
+    if (level == 1) {
+        if (STREAM) sink_ray(P, (size_t)link, ret);
+        else sink_sample(P, (size_t)link, ret);
+        return;
+    }
     store_return(parents, link, ret);
 }
 
 // Park a node with children and queue its child rays.  Must be reached by ALL lanes of the
 // wave together (converged): slots are handed out with ballot + mbcnt prefix sums and one
 // atomic per counter per wave.
+template <bool STREAM = false>
 __device__ __forceinline__ void emit(const LaunchParams& P, const Shard& sh, int level, bool valid, uint32_t link,
                                      float ior_1, const NodeOut& o) {
     const int lane = threadIdx.x & 63;
-    if (valid && o.terminal) deliver(P, sh.nodes_parent, level, link, o.ret);
+    if (valid && o.terminal) deliver<STREAM>(P, sh.nodes_parent, level, link, o.ret);
     const bool parks = valid && !o.terminal;
     const uint64_t m_node = __ballot(parks);
     if (m_node == 0) return;                                   // wave-uniform
@@ -528,6 +540,50 @@ __global__ __launch_bounds__(256) P3D_OCC(OCC) void wf_primary_kernel_tiles(cons
     }
 }
 
+// Level 1 of a ray stream (p3d_trace_rays): wf_primary_kernel's steps for rays the caller supplies.  Workgroup b of the band
+// is the band's "tile" b -- the 64 * wg_waves consecutive rays from (wf_tile_row0 + b) * blockDim on, shard b % kWfShards --
+// and a lane's link is its ray's index in the stream, so the deeper levels and the resolve launches run unchanged.  No
+// camera, no tile map, no counters, no features with random draws: one build per scene placement and walk
+// (p3d_kernel_variant.h: Level::Rays).  Consecutive lanes read consecutive 12-byte records: one 768-byte run per array per wave.
+// hit_id / t / normal are written here, under wave-uniform tests of their pointers: a caller that asks for colours only
+// pays three scalar compares.  Lanes past the stream's last ray neither read nor write; they stay for the wave-wide steps.
+template <bool LDS, int WALK, int OCC>
+__global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void wf_rays_kernel(const LaunchParams P, const RayStreamIO R) {
+    const uint32_t par = P.wf_ctrl[0] & 1u;                     // this pass's counter set (LaunchParams::wf_alt)
+    if (blockIdx.x == 0) {
+        if (threadIdx.x == 0) P.wf_ctrl[32] = par;
+        for (uint32_t i = threadIdx.x; i < P.wf_clear_words; i += blockDim.x) P.wf_clear[i] = 0u;
+        uint32_t* other = P.wf_alt + (size_t)((1u - par) * 2u) * kWfShards;
+        for (uint32_t i = threadIdx.x; i < 2u * kWfShards; i += blockDim.x) other[i] = 0u;
+    }
+    const typename View<LDS>::type sv = View<LDS>::make_shading(P);
+    const uint32_t i = ((uint32_t)P.wf_tile_row0 + blockIdx.x) * blockDim.x + threadIdx.x;     // (the host keeps streams below 2^31 rays)
+    const bool valid = i < R.count;
+    if (__ballot(valid) == 0) return;
+    const Shard sh = shard_of(P, blockIdx.x % kWfShards, par);
+    const TravCtx tc = wave_stack<LDS>(P, 0);
+    Ctr ctr = {0, 0, 0, 0, 0, 0, 0};
+    Ray ray; ray.o = mk(0.0f, 0.0f, 0.0f); ray.d = mk(1.0f, 0.0f, 0.0f);
+    if (valid) {                                                 // Ray(origin[i], dir[i]): the direction is NOT normalised
+        const float* po = R.origin + 3 * (size_t)i;
+        const float* pd = R.dir + 3 * (size_t)i;
+        ray.o = mk(po[0], po[1], po[2]); ray.d = mk(pd[0], pd[1], pd[2]);
+    }
+    const Hit h = find_closest<false, WALK>(P, sv, ray, valid, tc, ctr);
+    if (P.hit_id || R.t || R.normal) {                           // wave-uniform
+        const bool hit = valid && h.ref != 0xFFFFFFFFu;
+        if (valid && P.hit_id) P.hit_id[i] = hit_id_of(h);
+        if (valid && R.t) R.t[i] = hit ? h.t : __builtin_inff();
+        if (R.normal) {                                      // getNormal(hit point).normalize(), RT/main.cpp:587-589
+            V3 n = mk(0.0f, 0.0f, 0.0f);
+            if (hit) n = prim_normal(P, sv, h.ref, ray, add(ray.o, mul(ray.d, h.t)));
+            if (valid) { float* pn = R.normal + 3 * (size_t)i; pn[0] = n.x; pn[1] = n.y; pn[2] = n.z; }
+        }
+    }
+    const NodeOut o = shade_hit<false, WALK, typename View<LDS>::type, false, false>(P, sv, ray, h, valid, 1, 1.0f, tc, ctr, 0u);
+    emit<true>(P, sh, 1, valid, i, 1.0f, o);
+}
+
 // Lanes a wave of a deeper level uses: a short queue is spread over ALL the shard's waves with
 // fewer rays each instead of filling 64-wide waves.  Deeper levels hold few, incoherent rays and
 // are bound by the latency of one wave's ray step, not by issue slots: narrow waves diverge less
@@ -635,6 +691,8 @@ __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void wf_secondary_kern
 }
 
 // walk one level back up: node = color + (refl_ret*KR*spec + refr_ret*(1-KR)), RT/main.cpp:719
+// (STREAM: the builds a ray stream's passes launch, whose level-1 nodes return to sink_ray(); see deliver())
+template <bool STREAM>
 __global__ __launch_bounds__(256) void wf_resolve_kernel(const LaunchParams P) {
     constexpr uint32_t S = kWfShards;
     const Shard sh = shard_of(P, blockIdx.x % S, P.wf_ctrl[32] & 1u);
@@ -644,7 +702,7 @@ __global__ __launch_bounds__(256) void wf_resolve_kernel(const LaunchParams P) {
     for (uint32_t i = (blockIdx.x / S) * blockDim.x + threadIdx.x; i < count; i += per_shard * blockDim.x) {
         uint32_t link;
         const V3 ret = resolve_node(gv, sh.nodes_self + i, link);
-        deliver(P, sh.nodes_parent, P.wf_level, link, ret);
+        deliver<STREAM>(P, sh.nodes_parent, P.wf_level, link, ret);
     }
 }
 
@@ -652,6 +710,7 @@ __global__ __launch_bounds__(256) void wf_resolve_kernel(const LaunchParams P) {
 // shard's levels only depend on each other and a __syncthreads() between levels replaces the launch boundary.  For
 // small frames -- a rank's share of a frame tiled over several GPUs -- where a level holds a few nodes per thread and a
 // frame is bound by the number of launches (tools/shard_probe.py); large frames keep one wide launch per level.
+template <bool STREAM>
 __global__ __launch_bounds__(1024) void wf_resolve_fused_kernel(const LaunchParams P, const ResolveLevels R) {
     const uint32_t s = blockIdx.x, par = P.wf_ctrl[32] & 1u;
     const GlobalScene gv = View<false>::make(P);
@@ -662,7 +721,7 @@ __global__ __launch_bounds__(1024) void wf_resolve_fused_kernel(const LaunchPara
         for (uint32_t i = threadIdx.x; i < count; i += blockDim.x) {
             uint32_t link;
             const V3 ret = resolve_node(gv, nodes + i, link);
-            deliver(P, parents, l, link, ret);
+            deliver<STREAM>(P, parents, l, link, ret);
         }
         __syncthreads();             // the workgroup's own stores are visible to it after the barrier
     }
@@ -1152,6 +1211,7 @@ constexpr bool variants_are_consistent() {
             v.occ = occ;
             v.tiles = kMaxPrimaryTiles;                 // (only the level-1 kernel has the variant)
             if (!built_level(canonical_level(v, Level::Tile), Level::Tile) || !built_level(canonical_level(v, Level::Secondary), Level::Secondary)) return false;
+            if (!built_level(canonical_level(v, Level::Rays), Level::Rays)) return false;
             for (int tiles = 0; tiles <= kMaxPrimaryTiles + 1; tiles++) {
                 v.tiles = tiles;
                 if (!built_level(canonical_level(v, Level::Primary), Level::Primary)) return false;
@@ -1162,7 +1222,7 @@ constexpr bool variants_are_consistent() {
         }
         KernelVariant v = variant_at(i);
         for (v.tiles = kMaxPrimaryTiles; v.tiles >= 1; v.tiles--)
-            for (Level k : {Level::Primary, Level::Secondary, Level::Tile})
+            for (Level k : {Level::Primary, Level::Secondary, Level::Tile, Level::Rays})
                 if (built_level(v, k) && !(canonical_level(v, k) == v)) return false;
         v.tiles = 1;
         for (int priv : kPrivs)
@@ -1172,21 +1232,25 @@ constexpr bool variants_are_consistent() {
 }
 static_assert(variants_are_consistent(), "a kernel request maps to a variant that is not built, or a built variant is unreachable");
 
+using RaysKernelFn = void (*)(const LaunchParams, const RayStreamIO);
 template <Level KERNEL> struct LevelKernels {       // position: variant_index * per_variant + (TILES - 1)
+    using Fn = std::conditional_t<KERNEL == Level::Rays, RaysKernelFn, KernelFn>;
     static constexpr Level level = KERNEL;
     static constexpr int per_variant = KERNEL == Level::Primary ? kMaxPrimaryTiles : 1;
     static constexpr int n = kLevelVariants * per_variant;
     static constexpr KernelVariant at(int i) { KernelVariant v = variant_at(i / per_variant); v.tiles = 1 + i % per_variant; return v; }
     static constexpr bool built(int i) { return built_level(at(i), KERNEL); }
-    template <int I> static constexpr KernelFn fn() {
+    template <int I> static constexpr Fn fn() {
         constexpr KernelVariant v = at(I);
         if constexpr (KERNEL == Level::Primary && v.tiles > 1) return wf_primary_kernel_tiles<v.walk, v.occ, v.tiles>;
         else if constexpr (KERNEL == Level::Primary) return wf_primary_kernel<v.count, v.lds, v.walk, v.occ, v.stoch, v.schlick, v.batch>;
         else if constexpr (KERNEL == Level::Secondary) return wf_secondary_kernel<v.count, v.lds, v.walk, v.occ, v.stoch, v.schlick>;
+        else if constexpr (KERNEL == Level::Rays) return wf_rays_kernel<v.lds, v.walk, v.occ>;
         else return wf_tile_kernel<v.count, v.lds, v.walk, v.occ, v.stoch, v.schlick, v.batch>;
     }
 };
 struct TreeKernels {                                // position: variant_index * 3 + position of PRIV in kPrivs
+    using Fn = KernelFn;
     static constexpr int n = kTreeVariants;
     static constexpr bool built(int i) { return built_tree(variant_at(i / 3), kPrivs[i % 3]); }
     template <int I> static constexpr KernelFn fn() {
@@ -1195,12 +1259,12 @@ struct TreeKernels {                                // position: variant_index *
     }
 };
 // the walk over a family's positions: a kernel is instantiated only where built() says so
-template <class K, int I> constexpr KernelFn variant_fn() {
+template <class K, int I> constexpr typename K::Fn variant_fn() {
     if constexpr (K::built(I)) return K::template fn<I>();
     else return nullptr;
 }
 template <class K, int... I> static const void* kernel_lookup(int i, std::integer_sequence<int, I...>) {
-    static constexpr KernelFn table[] = {variant_fn<K, I>()...};
+    static constexpr typename K::Fn table[] = {variant_fn<K, I>()...};
     return i >= 0 && i < K::n ? reinterpret_cast<const void*>(table[i]) : nullptr;
 }
 template <class K> static const void* kernel_at(int i) { return kernel_lookup<K>(i, std::make_integer_sequence<int, K::n>{}); }
@@ -1244,6 +1308,15 @@ hipError_t launch_wf_primary(const LaunchParams& P, const KernelVariant& v, hipS
     const PrimaryGrid g = primary_grid(served, P.tiles_x, P.wf_tile_rows, P.n_tiles, P.xcd_chunk, P.grid_blocks);
     return launch_by_pointer(level_kernel<LevelKernels<Level::Primary>>(served), P, dim3(g.x, g.y), dim3(64 * P.wg_waves), wavefront_lds_bytes(P, v.lds), stream);
 }
+// level 1 of a ray stream: one workgroup per 64 * wg_waves rays of the band (wf_tile_rows workgroups)
+hipError_t launch_wf_rays(const LaunchParams& P, const RayStreamIO& R, const KernelVariant& v, hipStream_t stream) {
+    const void* fn = level_kernel<LevelKernels<Level::Rays>>(v);
+    if (!fn) return hipErrorInvalidDeviceFunction;
+    LaunchParams Pc = P;
+    RayStreamIO Rc = R;
+    void* args[] = {&Pc, &Rc};
+    return hipLaunchKernel(fn, dim3((unsigned)P.wf_tile_rows), dim3(64 * P.wg_waves), args, wavefront_lds_bytes(P, v.lds), stream);
+}
 hipError_t launch_wf_secondary(const LaunchParams& P, const KernelVariant& v, unsigned waves, hipStream_t stream) {
     return launch_by_pointer(level_kernel<LevelKernels<Level::Secondary>>(v), P, dim3((waves + P.wg_waves - 1) / P.wg_waves),
                              dim3(64 * P.wg_waves), wavefront_lds_bytes(P, v.lds), stream);
@@ -1274,12 +1347,14 @@ hipError_t launch_wf_tile(const LaunchParams& P, const KernelVariant& v, unsigne
 }
 
 
-hipError_t launch_wf_resolve_fused(const LaunchParams& P, const ResolveLevels& R, unsigned shards, hipStream_t stream) {
-    hipLaunchKernelGGL(wf_resolve_fused_kernel, dim3(shards), dim3(1024), 0, stream, P, R);
+hipError_t launch_wf_resolve_fused(const LaunchParams& P, const ResolveLevels& R, unsigned shards, bool ray_stream, hipStream_t stream) {
+    if (ray_stream) hipLaunchKernelGGL(wf_resolve_fused_kernel<true>, dim3(shards), dim3(1024), 0, stream, P, R);
+    else hipLaunchKernelGGL(wf_resolve_fused_kernel<false>, dim3(shards), dim3(1024), 0, stream, P, R);
     return hipGetLastError();
 }
-hipError_t launch_wf_resolve(const LaunchParams& P, unsigned blocks, hipStream_t stream) {
-    hipLaunchKernelGGL(wf_resolve_kernel, dim3(blocks), dim3(256), 0, stream, P);
+hipError_t launch_wf_resolve(const LaunchParams& P, unsigned blocks, bool ray_stream, hipStream_t stream) {
+    if (ray_stream) hipLaunchKernelGGL(wf_resolve_kernel<true>, dim3(blocks), dim3(256), 0, stream, P);
+    else hipLaunchKernelGGL(wf_resolve_kernel<false>, dim3(blocks), dim3(256), 0, stream, P);
     return hipGetLastError();
 }
 

@@ -22,13 +22,15 @@ size_t wavefront_lds_bytes(const LaunchParams& P, bool lds);
 size_t tile_kernel_lds_bytes(const LaunchParams& P, bool lds);
 hipError_t launch_tree(const LaunchParams& P, const KernelVariant& v, hipStream_t stream);
 hipError_t launch_wf_primary(const LaunchParams& P, const KernelVariant& v, hipStream_t stream);
+hipError_t launch_wf_rays(const LaunchParams& P, const RayStreamIO& R, const KernelVariant& v, hipStream_t stream);
 hipError_t launch_wf_secondary(const LaunchParams& P, const KernelVariant& v, unsigned waves, hipStream_t stream);
 hipError_t launch_wf_tile(const LaunchParams& P, const KernelVariant& v, unsigned blocks, hipStream_t stream);
 hipError_t wf_resident_waves(const LaunchParams& P, const KernelVariant& v, unsigned* waves);
 hipError_t tile_kernel_resident_blocks(const LaunchParams& P, const KernelVariant& v, int* blocks);
 hipError_t prepare_kernels(size_t max_lds);
-hipError_t launch_wf_resolve(const LaunchParams& P, unsigned blocks, hipStream_t stream);
-hipError_t launch_wf_resolve_fused(const LaunchParams& P, const ResolveLevels& R, unsigned shards, hipStream_t stream);
+// (ray_stream: the builds whose level-1 nodes return to a ray stream's planes instead of a frame's pixels)
+hipError_t launch_wf_resolve(const LaunchParams& P, unsigned blocks, bool ray_stream, hipStream_t stream);
+hipError_t launch_wf_resolve_fused(const LaunchParams& P, const ResolveLevels& R, unsigned shards, bool ray_stream, hipStream_t stream);
 hipError_t launch_clear_words(uint32_t* p, uint32_t n, hipStream_t stream);
 hipError_t launch_frame_cams(FrameCam* dst, const FrameCam* cams, int n, hipStream_t stream);
 hipError_t launch_raygen_table(float* fx, float* fy, int res_x, int res_y, hipStream_t stream);

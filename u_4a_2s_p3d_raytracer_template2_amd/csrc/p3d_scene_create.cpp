@@ -184,6 +184,7 @@ int p3d_scene_create(const p3d_scene_desc* d, const p3d_build_opts* opts, int de
     s->stats.n_boxes = (uint32_t)boxes.size(); s->stats.n_planes = (uint32_t)planes.size();
     s->stats.n_culled = n_culled;
     s->unit_rays_only = n_culled > 0;
+    s->cull_never_hit = opts && opts->cull_never_hit;
     s->stats.device_bytes = s->blob.bytes() + s->qnodes.bytes() + s->planes.bytes() + s->plane_meta.bytes() + s->lights.bytes();
     *out = s.release();
     return P3D_OK;

@@ -148,6 +148,7 @@ struct p3d_scene {
     bool lds_capable = false;            // ... and then carry the f32 nodes the LDS walk reads
     int last_schedule = -1;
     bool unit_rays_only = false;         // built with cull_never_hit: cannot serve un-normalised (NONE-mode) shadow rays
+    bool cull_never_hit = false;         // ... the option itself, whether or not it found a triangle to leave out: ray streams are refused
     uint32_t packet_node_limit = 64;     // trees up to this many node pairs use the wave-wide walk
     float bg[3] = {0, 0, 0};
     uint32_t n_lights = 0, n_materials = 0;
@@ -195,6 +196,13 @@ struct p3d_scene {
     // configuration changes, so that several scene handles, or a framework holding most of the HBM, shrink the
     // bands / fall back to another schedule instead of failing in hipMalloc
     size_t budget_avail = 0; p3d::Keyed<p3d::BudgetKey> budget_key;
+    // Ray streams (p3d_trace_rays) keep their state apart from the frames': staging for host rays and host outputs, and their
+    // own reading of the budget.  Nothing above is keyed on, or changed by, a stream (the workspaces ws[0] are scratch that
+    // only grows; the occupancy cache wf_occ is keyed by the build it describes).
+    struct RayStream {
+        p3d::RawBuf origin, dir, rgb32f, hit_id, t, normal;
+        size_t budget_avail = 0; p3d::Keyed<p3d::RayStreamKey> key;
+    } rays;
     p3d::RawBuf d_counters;              // one DeviceCounters
     bool counters_valid = false;
     p3d::TimingEvent ev0, ev1;
