@@ -232,6 +232,46 @@ int p3d_scene_set_skybox(p3d_scene* scene, const uint8_t* const faces[6], const 
                          const uint32_t bytes_per_pixel[6]);
 int p3d_scene_get_stats(const p3d_scene* scene, p3d_scene_stats* out);
 
+/* Primitives to move, and optionally the lights, of an existing scene handle. */
+typedef struct p3d_prim_update {
+    uint32_t        n;          /* primitives to replace; 0 is allowed                                   */
+    const uint32_t* index;      /* [n] scene indices (p3d_scene_desc order); NULL = primitives 0..n-1    */
+    const float*    prim_data;  /* [n][12], the form p3d_scene_desc::prim_data has for that primitive's kind */
+    int32_t         memory;     /* 0 host, 1 device pointers on the scene's device (index and prim_data)  */
+    const float*    lights;     /* NULL, or [n_lights][6] position + colour of ALL lights: HOST memory always */
+} p3d_prim_update;
+/* What a render loop with moving spheres, triangles, boxes, planes or lights calls instead of destroying the handle and
+ * creating a new one per frame (the reference has no such loop: its scene is loaded once, RT/main.cpp:912-936).  The new
+ * records are written on the device and the BVH is REFITTED there: same topology, new boxes.
+ *  - equality of frames: after the call every entry -- p3d_render, p3d_render_frames, p3d_trace_rays; every accel mode,
+ *    schedule, flag and feature; LDS and HBM placement, sharding, samples -- produces what a handle created from the
+ *    updated description produces, in every bit (a closest hit is "nearest, lowest scene index on ties" whatever the
+ *    tree).
+ *  - what may change: geometry, and the lights' positions and colours.  Kind, material, primitive count, material table,
+ *    number of lights and background stay what they were at creation.
+ *  - tree quality: the tree keeps the topology it was built with, so its quality degrades as primitives move away from
+ *    where they were; frames stay equal and get slower.  Creating a new handle is the remedy.  The statistics keep
+ *    creation's sah_cost; device_bytes grows by what the first update allocates (f32 nodes of scenes read from HBM, one
+ *    parent and one counter word per node pair, staging for host-memory updates).
+ *  - ordering: runs after everything already enqueued on the scene's stream, and returns when scene and tree are
+ *    consistent; it waits on the device (the root's boxes come back to set the quantisation grid).
+ *  - stream capture: refused with P3D_ERR_STATE while the stream is being captured.  A graph captured BEFORE an update
+ *    must be captured again: the quantisation grid of scenes read from HBM travels in the launch parameters by value.
+ *  - P3D_ERR_ARG: NULL scene or update; n > 0 with a NULL prim_data; memory outside 0 and 1; for host memory an index
+ *    >= the primitive count (with a NULL index: n above it), checked before anything is changed.  For device memory such
+ *    entries are skipped on the device: the call leaves a consistent tree and THEN returns P3D_ERR_ARG.  With duplicate
+ *    indices, which of their values holds is unspecified; results for non-finite data are unspecified.
+ *  - a handle created with cull_never_hit is refused with P3D_ERR_STATE: a moved triangle may no longer be one the
+ *    reference can never hit.
+ *  - GRID mode: the uniform grid's shape is observable (RT/grid.cpp:265-309), so the update drops the built grid and the
+ *    next GRID frame builds it again from the new points, under the rule of the first GRID frame (p3d_scene_create).
+ *    The host needs the points for that: after an update from DEVICE memory, GRID-mode frames and ray streams are refused
+ *    with P3D_ERR_STATE until updates from host memory have covered those primitives.  BVH and NONE mode have no such limit.
+ *  - lights: all of them are replaced; the 4x4 sub-lights of P3D_FEATURE_SOFT_SHADOW follow on next use.
+ *  - the handle's other state stays: the measured schedule choice, the learned tile orders (predictions, never results),
+ *    p3d_last_schedule() and the ray-stream state.  A frame after an update measures nothing again. */
+int p3d_scene_update(p3d_scene* scene, const p3d_prim_update* update);
+
 /* Rows of the compact per-rank tile buffer: ceil(n_row_blocks / world) * row_block, the
  * same on every rank so that the gather moves equal-sized buffers (rows past the image are
  * never written). */

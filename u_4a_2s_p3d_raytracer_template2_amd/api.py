@@ -80,6 +80,12 @@ class RayOutputs(C.Structure):
                 ("memory", C.c_int32)]
 
 
+class PrimUpdate(C.Structure):
+    """p3d_prim_update: n primitives to replace ([n][12] floats, optionally [n] scene indices) on the host (memory 0) or the
+    scene's device (memory 1); lights: NULL or [n_lights][6] on the host."""
+    _fields_ = [("n", C.c_uint32), ("index", C.c_void_p), ("prim_data", C.c_void_p), ("memory", C.c_int32), ("lights", C.c_void_p)]
+
+
 class SceneStats(C.Structure):
     _fields_ = [("n_nodes", C.c_uint32), ("n_leaves", C.c_uint32), ("max_depth", C.c_uint32),
                 ("n_leaf_refs", C.c_uint32), ("n_spheres", C.c_uint32), ("n_triangles", C.c_uint32),
@@ -92,7 +98,7 @@ class SceneStats(C.Structure):
 
 # every symbol include/p3d_hip.h declares (tests check that the library exports them all)
 C_ABI_SYMBOLS = ["p3d_abi_version", "p3d_last_error", "p3d_device_count", "p3d_scene_create",
-                 "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_trace_rays", "p3d_sync",
+                 "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_scene_update", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_trace_rays", "p3d_sync",
                  "p3d_get_counters", "p3d_get_profile", "p3d_last_schedule", "p3d_set_tuning", "p3d_set_primary_tiles", "p3d_last_primary_tiles", "p3d_set_stream", "p3d_timer_begin", "p3d_timer_end", "p3d_deinterleave_frames",
                  "p3d_deinterleave", "p3d_debug_intersect", "p3d_debug_powf", "p3d_debug_pow", "p3d_debug_schlick_kr", "p3d_debug_check_rcp", "p3d_debug_check_rcp_len", "p3d_tune_schedule", "p3d_debug_set_stamps", "p3d_debug_set_stamp_level",
                  "p3d_comm_unique_id", "p3d_comm_create", "p3d_comm_create_all", "p3d_comm_destroy", "p3d_comm_info",
@@ -134,6 +140,7 @@ def lib():
     L.p3d_scene_destroy.argtypes = [C.c_void_p]
     L.p3d_scene_set_skybox.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.p3d_scene_get_stats.argtypes = [C.c_void_p, C.POINTER(SceneStats)]
+    L.p3d_scene_update.argtypes = [C.c_void_p, C.POINTER(PrimUpdate)]
     L.p3d_local_rows.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     L.p3d_render.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(Outputs)]
     L.p3d_render_frames.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.POINTER(RenderParams), C.POINTER(Outputs)]
@@ -396,6 +403,28 @@ class DeviceScene:
         s = SceneStats()
         _check(lib().p3d_scene_get_stats(self.h, C.byref(s)), "p3d_scene_get_stats")
         return s.as_dict()
+
+    def update(self, prim12, indices=None, lights6=None):
+        """p3d_scene_update from host arrays: primitives `indices` (None: 0 .. n-1) get the geometry prim12 [n, 12], in the
+        form p3d_scene_desc::prim_data has for their kind; lights6 (None: unchanged) replaces all lights [n_lights, 6].
+        The BVH is refitted on the device; every later frame equals that of a handle created from the moved scene."""
+        data = np.ascontiguousarray(prim12 if prim12 is not None else np.zeros((0, 12)), np.float32).reshape(-1, 12)
+        n = len(data)
+        idx = None
+        if indices is not None:
+            idx = np.ascontiguousarray(indices, np.uint32).ravel()
+            if len(idx) != n:
+                raise ValueError("indices and prim12 differ in length")
+        li = np.ascontiguousarray(lights6, np.float32).reshape(-1, 6) if lights6 is not None else None
+        u = PrimUpdate(n, idx.ctypes.data if idx is not None and n else None, data.ctypes.data if n else None, 0,
+                       li.ctypes.data if li is not None and len(li) else None)
+        _check(lib().p3d_scene_update(self.h, C.byref(u)), "p3d_scene_update")
+
+    def update_device(self, n, prim_ptr, index_ptr=0):
+        """p3d_scene_update from caller-owned DEVICE buffers (raw pointers): prim_ptr [n][12] floats, index_ptr [n] uint32
+        scene indices or 0 for primitives 0 .. n-1."""
+        u = PrimUpdate(int(n), index_ptr or None, prim_ptr or None, 1, None)
+        _check(lib().p3d_scene_update(self.h, C.byref(u)), "p3d_scene_update")
 
     def set_skybox(self, faces):
         """Six uint8 arrays [H, W, 3 or 4]: right, left, top, bottom, front, back; row 0 = bottom row (Scene::LoadSkybox)."""

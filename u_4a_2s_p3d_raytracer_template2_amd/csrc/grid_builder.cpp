@@ -10,35 +10,36 @@ namespace p3d {
 
 static const float kEps = 0.001f;                                        // RT/macros.h:1
 
+void grid_prim_bounds(uint32_t type, const float* v, GridPrim& g) {
+    switch (type) {
+    case P3D_SPHERE:                                                 // RT/scene.cpp:180-186
+        for (int a = 0; a < 3; a++) { g.lo[a] = v[a] - v[3]; g.hi[a] = v[a] + v[3]; }
+        break;
+    case P3D_TRIANGLE:                                               // RT/scene.cpp:26-39: min/max, then -= / += EPSILON
+        for (int a = 0; a < 3; a++) {
+            float lo = std::min(std::min(v[a], v[3 + a]), v[6 + a]);
+            float hi = std::max(std::max(v[a], v[3 + a]), v[6 + a]);
+            g.lo[a] = lo - kEps; g.hi[a] = hi + kEps;
+        }
+        break;
+    case P3D_BOX:                                                    // RT/scene.cpp:194-196
+        for (int a = 0; a < 3; a++) { g.lo[a] = v[a]; g.hi[a] = v[3 + a]; }
+        break;
+    default:                                                         // Plane: Object::GetBoundingBox(), RT/scene.h:75
+        for (int a = 0; a < 3; a++) { g.lo[a] = -1.0f; g.hi[a] = 1.0f; }
+        break;
+    }
+}
+
 void grid_prims_from_desc(const p3d_scene_desc& d, std::vector<GridPrim>& out) {
     out.clear();
     out.reserve(d.n_prims);
-    uint32_t n_sph = 0, n_tri = 0, n_box = 0, n_pln = 0;
+    uint32_t n_kind[4] = {0, 0, 0, 0};
     for (uint32_t i = 0; i < d.n_prims; i++) {
-        const float* v = d.prim_data + 12 * (size_t)i;
+        const uint32_t kind = d.prim_type[i] <= P3D_BOX ? d.prim_type[i] : (uint32_t)P3D_PLANE;
         GridPrim g;
-        switch (d.prim_type[i]) {
-        case P3D_SPHERE:                                                 // RT/scene.cpp:180-186
-            for (int a = 0; a < 3; a++) { g.lo[a] = v[a] - v[3]; g.hi[a] = v[a] + v[3]; }
-            g.ref = (0u << kRefKindShift) | n_sph++;
-            break;
-        case P3D_TRIANGLE:                                               // RT/scene.cpp:26-39: min/max, then -= / += EPSILON
-            for (int a = 0; a < 3; a++) {
-                float lo = std::min(std::min(v[a], v[3 + a]), v[6 + a]);
-                float hi = std::max(std::max(v[a], v[3 + a]), v[6 + a]);
-                g.lo[a] = lo - kEps; g.hi[a] = hi + kEps;
-            }
-            g.ref = (1u << kRefKindShift) | n_tri++;
-            break;
-        case P3D_BOX:                                                    // RT/scene.cpp:194-196
-            for (int a = 0; a < 3; a++) { g.lo[a] = v[a]; g.hi[a] = v[3 + a]; }
-            g.ref = (2u << kRefKindShift) | n_box++;
-            break;
-        default:                                                         // Plane: Object::GetBoundingBox(), RT/scene.h:75
-            for (int a = 0; a < 3; a++) { g.lo[a] = -1.0f; g.hi[a] = 1.0f; }
-            g.ref = (3u << kRefKindShift) | n_pln++;
-            break;
-        }
+        grid_prim_bounds(kind, d.prim_data + 12 * (size_t)i, g);
+        g.ref = (kind << kRefKindShift) | n_kind[kind]++;
         out.push_back(g);
     }
 }

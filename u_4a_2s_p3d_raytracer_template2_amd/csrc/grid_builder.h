@@ -24,6 +24,9 @@ struct GridHost {
 // primitive's device reference
 struct GridPrim { float lo[3], hi[3]; uint32_t ref; };
 
+// lo / hi of one primitive of kind `type` (P3D_*; anything else: a plane) from its 12 floats, with the reference's float
+// arithmetic; g.ref is left alone
+void grid_prim_bounds(uint32_t type, const float* prim12, GridPrim& g);
 // bounding boxes of a scene description in scene order, with the reference's float arithmetic
 void grid_prims_from_desc(const p3d_scene_desc& d, std::vector<GridPrim>& out);
 // false: the reference's cell-count formula asks for more than 2^31 cells (nothing is built)

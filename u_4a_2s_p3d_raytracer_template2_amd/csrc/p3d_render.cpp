@@ -118,8 +118,9 @@ int ensure_grid(p3d_scene* s) {
     // stream capture can hold.  Render one GRID frame before capturing.
     if (capturing(s->stream))
         return fail(P3D_ERR_STATE, "the first GRID-mode frame of a scene builds and uploads the grid: render one before capturing the stream");
+    if (s->grid_stale_count)
+        return fail(P3D_ERR_STATE, "primitives were updated from device memory: GRID mode needs their points on the host, update them from host memory");
     if (!build_grid(s->grid_src, s->grid_info)) return fail(P3D_ERR_LIMIT, "the reference's grid formula asks for more than 2^31 cells");
-    std::vector<GridPrim>().swap(s->grid_src);          // (28 B per primitive: only the build needed it)
     HIP_TRY(s->grid_cells.upload(s->grid_info.cell_start));
     HIP_TRY(s->grid_items.upload(s->grid_info.items));
     s->stats.device_bytes += s->grid_cells.bytes() + s->grid_items.bytes();

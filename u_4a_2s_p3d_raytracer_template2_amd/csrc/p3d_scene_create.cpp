@@ -174,6 +174,11 @@ int p3d_scene_create(const p3d_scene_desc* d, const p3d_build_opts* opts, int de
         else if (kind == 1u) g.ref = (1u << kRefKindShift) | TL.map_tri[idx];
         else if (kind == 2u) g.ref = (2u << kRefKindShift) | TL.map_box[idx];
     }
+    {   // the same references, by scene index, are where p3d_scene_update finds a primitive's record
+        std::vector<uint32_t> map(s->grid_src.size());
+        for (size_t i = 0; i < map.size(); i++) map[i] = s->grid_src[i].ref;
+        if ((e = s->prim_map.upload(map)) != hipSuccess) return hip_fail(e, "upload primitive map");
+    }
     if ((e = s->d_counters.ensure(sizeof(DeviceCounters))) != hipSuccess) return hip_fail(e, "alloc counters");
     if ((e = hipMemset(s->d_counters.p, 0, sizeof(DeviceCounters))) != hipSuccess) return hip_fail(e, "clear counters");
     memcpy(s->bg, d->background, sizeof s->bg);
@@ -185,7 +190,7 @@ int p3d_scene_create(const p3d_scene_desc* d, const p3d_build_opts* opts, int de
     s->stats.n_culled = n_culled;
     s->unit_rays_only = n_culled > 0;
     s->cull_never_hit = opts && opts->cull_never_hit;
-    s->stats.device_bytes = s->blob.bytes() + s->qnodes.bytes() + s->planes.bytes() + s->plane_meta.bytes() + s->lights.bytes();
+    s->stats.device_bytes = s->blob.bytes() + s->qnodes.bytes() + s->planes.bytes() + s->plane_meta.bytes() + s->lights.bytes() + s->prim_map.bytes();
     *out = s.release();
     return P3D_OK;
 }

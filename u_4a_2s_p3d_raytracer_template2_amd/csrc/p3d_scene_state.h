@@ -1,5 +1,5 @@
 // p3d_scene_state.h -- the scene handle behind the C-ABI of include/p3d_hip.h, shared by the files that implement it
-// (p3d_scene_create.cpp, p3d_render.cpp, p3d_capi_misc.cpp).  Internal: not installed with include/.
+// (p3d_scene_create.cpp, p3d_scene_update.cpp, p3d_render.cpp, p3d_capi_misc.cpp).  Internal: not installed with include/.
 // Every device resource in it is owned by a member that frees it: deleting a p3d_scene releases all of them.
 #ifndef P3D_SCENE_STATE_H
 #define P3D_SCENE_STATE_H
@@ -136,10 +136,22 @@ struct p3d_scene {
     p3d::DevBuf<p3d::PlaneRec> planes;
     p3d::DevBuf<p3d::PrimMeta> plane_meta;
     p3d::DevBuf<p3d::LightRec> lights;
-    // GRID mode (accel 1): the reference's uniform grid, built from grid_src on the first GRID frame
+    // GRID mode (accel 1): the reference's uniform grid, built from grid_src on the first GRID frame (and on the first
+    // one after a p3d_scene_update, which refreshes grid_src: one entry per primitive, in scene order, kept)
     std::vector<p3d::GridPrim> grid_src;
     p3d::DevBuf<uint32_t> grid_cells, grid_items;
     p3d::GridHost grid_info; bool grid_ready = false;
+    // p3d_scene_update: where each primitive's record sits (scene index -> kind << 30 | index in the kind's leaf-ordered
+    // array; planes index their own), and what the refit needs next to the scene, allocated by the first update
+    p3d::DevBuf<uint32_t> prim_map;
+    struct Refit {
+        p3d::RawBuf nodes;                   // f32 node pairs of a scene that carries quantised ones only (else: the blob's)
+        p3d::RawBuf parent, arrived, status; // per node pair: parent, arrival counter; root boxes + bad-index count
+        p3d::RawBuf stage_prims, stage_index;   // host-memory updates pass through these
+        bool ready = false;
+    } refit;
+    // primitives whose grid_src entry predates an update from device memory: GRID mode is refused while there are any
+    std::vector<uint8_t> grid_stale; size_t grid_stale_count = 0;
     p3d::DevBuf<p3d::LightRec> soft_lights;     // 16 sub-lights per light, built on first use (SOFT_SHADOW, spp == 0)
     p3d::DevBuf<uint8_t> sky;                   // cube map of P3D_FEATURE_SKYBOX: the six faces back to back
     uint32_t sky_off[6] = {0, 0, 0, 0, 0, 0}, sky_w[6] = {0, 0, 0, 0, 0, 0}, sky_h[6] = {0, 0, 0, 0, 0, 0}, sky_bpp[6] = {0, 0, 0, 0, 0, 0};

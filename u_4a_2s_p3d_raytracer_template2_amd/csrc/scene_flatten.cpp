@@ -137,6 +137,18 @@ void type_leaves(std::vector<NodePair>& nodes, const std::vector<uint32_t>& refs
     F.spheres.swap(sph); F.sphere_meta.swap(sph_meta); F.tris.swap(tri); F.boxes.swap(box);
 }
 
+void quantisation_grid(const double mn_in[3], const double mx_in[3], float scale[3], float base[3]) {
+    for (int a = 0; a < 3; a++) {
+        double mn = mn_in[a], mx = mx_in[a];
+        if (mn > mx) { mn = 0.0; mx = 1.0; }                       // no box at all
+        // all boxes land in codes [2, 65533]: room for the one-code margin without clamping
+        const double ext = std::max(mx - mn, 1e-6 * std::max({std::fabs(mn), std::fabs(mx), 1.0}));
+        scale[a] = (float)(ext / 65530.0);
+        if (!(scale[a] > 0.0f)) scale[a] = 1e-30f;
+        base[a] = (float)(mn - 2.5 * (double)scale[a]);
+    }
+}
+
 void quantise_nodes(const std::vector<NodePair>& nodes, QuantisedNodes& Q) {
     auto child_box = [](const NodePair& n, int c, float lo[3], float hi[3]) {
         if (c == 0) { lo[0] = n.lo0[0]; lo[1] = n.lo0[1]; lo[2] = n.lo0[2]; hi[0] = n.hi0x; hi[1] = n.hi0yz[0]; hi[2] = n.hi0yz[1]; }
@@ -150,14 +162,7 @@ void quantise_nodes(const std::vector<NodePair>& nodes, QuantisedNodes& Q) {
             if (!(lo[0] <= hi[0])) continue;                       // absent child (NaN bounds)
             for (int a = 0; a < 3; a++) { mn[a] = std::min<double>(mn[a], lo[a]); mx[a] = std::max<double>(mx[a], hi[a]); }
         }
-    for (int a = 0; a < 3; a++) {
-        if (mn[a] > mx[a]) { mn[a] = 0.0; mx[a] = 1.0; }           // no box at all
-        // all boxes land in codes [2, 65533]: room for the one-code margin without clamping
-        const double ext = std::max(mx[a] - mn[a], 1e-6 * std::max({std::fabs(mn[a]), std::fabs(mx[a]), 1.0}));
-        Q.scale[a] = (float)(ext / 65530.0);
-        if (!(Q.scale[a] > 0.0f)) Q.scale[a] = 1e-30f;
-        Q.base[a] = (float)(mn[a] - 2.5 * (double)Q.scale[a]);
-    }
+    quantisation_grid(mn, mx, Q.scale, Q.base);
     Q.nodes.resize(nodes.size());
     for (size_t i = 0; i < nodes.size(); i++) {
         const NodePair& n = nodes[i];

@@ -46,6 +46,9 @@ void type_leaves(std::vector<NodePair>& nodes, const std::vector<uint32_t>& refs
 // code 0, outside every real box; its reference is the empty leaf.
 struct QuantisedNodes { std::vector<QNode> nodes; float scale[3], base[3]; };
 void quantise_nodes(const std::vector<NodePair>& nodes, QuantisedNodes& out);
+// ... and the grid itself from the bounds of all boxes (mn > mx on an axis: there is no box): shared with the refit of
+// p3d_scene_update, which codes the nodes again on the device under the same formula
+void quantisation_grid(const double mn[3], const double mx[3], float scale[3], float base[3]);
 
 }  // namespace p3d
 #endif
