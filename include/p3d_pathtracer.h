@@ -63,6 +63,22 @@ struct p3d_comm;
 int p3d_pt_reduce_sum(struct p3d_comm* comm, p3d_pt* pt, float* linear, uint64_t count);
 /* integer hash of PT/common.glsl:31-36 evaluated on the device (known-answer probe) */
 int p3d_pt_debug_hash(int device, uint32_t n, const uint32_t* a, const uint32_t* b, uint32_t* out);
+/* Device probes of the frame kernel's own hit_world(), scatter() and directlighting() (PT/P3D_RT.glsl:12-232,
+ * PT/common.glsl:217-324) on `n` cases the caller supplies: host arrays, the call returns when done.  Case i runs in lane
+ * i % 64 of workgroup i / 64 of a launch shaped like the frame kernel's, so the caller decides which rays share a wave.
+ * mat[n][11] = albedo[3], specColor[3], roughness, refIdx, refractColor[3].
+ * hit_world: a case with active == 0 skips the call (its lane is masked off, as in rayColor) and its outputs stay as the
+ * caller filled them.  On a miss t == tmax and seed_out is reported; pos, normal, mat_type and mat are unspecified. */
+int p3d_pt_debug_hit_world(int device, uint32_t n, const float* origin, const float* dir, const float* time, const float* tmin,
+                           const float* tmax, const float* seed, const int32_t* active, int32_t* hit, float* t, float* pos,
+                           float* normal, int32_t* mat_type, float* mat, float* seed_out);
+int p3d_pt_debug_scatter(int device, uint32_t n, const float* in_origin, const float* in_dir, const float* in_time,
+                         const float* rec_pos, const float* rec_normal, const float* rec_t, const int32_t* mat_type,
+                         const float* mat, const float* seed, float* atten, float* out_origin, float* out_dir, float* out_time,
+                         float* seed_out);
+int p3d_pt_debug_direct_lighting(int device, uint32_t n, const float* light_pos, const float* ray_origin, const float* ray_dir,
+                                 const float* ray_time, const float* rec_pos, const float* rec_normal, const float* rec_t,
+                                 const int32_t* mat_type, const float* mat, const float* seed, float* rgb, float* seed_out);
 
 #ifdef __cplusplus
 }

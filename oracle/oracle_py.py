@@ -93,6 +93,11 @@ def lib():
         L.pto_hash_stream.argtypes = [C.c_float, C.c_int, fp, fp]
         L.pto_sample.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, fp]
         L.pto_render.argtypes = [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, fp, fp]
+        dp = C.POINTER(C.c_double)
+        L.pto_hit_world.argtypes = [C.c_int] + [fp] * 6 + [ip, fp, fp, fp, ip, fp, fp, ip]
+        L.pto_scatter.argtypes = [C.c_int] + [fp] * 6 + [ip, fp, fp] + [fp] * 5 + [dp, dp, ip, dp]
+        L.pto_direct_lighting.argtypes = [C.c_int] + [fp] * 7 + [ip, fp, fp] + [fp, fp, dp, ip, dp]
+        L.pto_small_spheres.argtypes = [fp, ip, fp]
         _lib = L
     return _lib
 
@@ -325,3 +330,73 @@ def pt_render(res_x, res_y, n_frames, time0=0.0, dt=1.0 / 60.0, threads=1, want_
                      float(mouse[0]), float(mouse[1]), int(threads),
                      _f(rgba), _f(lin) if want_sum else None)
     return rgba, lin
+
+
+def _d(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _c32(a, shape):
+    a = np.ascontiguousarray(a, np.float32)
+    assert a.shape == shape, (a.shape, shape)
+    return a
+
+
+def pt_hit_world(origin, direction, time, tmin, tmax, seed):
+    """hit_world() of the restatement, one case at a time: {hit, t, pos, normal, mat_type, mat[11], seed_out, prim}
+    (prim: -1 miss, 0/1 floor triangles, 2..5 big spheres in source order, 6 + cell for a small sphere)."""
+    n = len(seed)
+    o, d = _c32(origin, (n, 3)), _c32(direction, (n, 3))
+    tm, t0, t1, sd = (_c32(x, (n,)) for x in (time, tmin, tmax, seed))
+    out = {"hit": np.zeros(n, np.int32), "t": np.zeros(n, np.float32), "pos": np.zeros((n, 3), np.float32),
+           "normal": np.zeros((n, 3), np.float32), "mat_type": np.zeros(n, np.int32), "mat": np.zeros((n, 11), np.float32),
+           "seed_out": np.zeros(n, np.float32), "prim": np.zeros(n, np.int32)}
+    lib().pto_hit_world(n, _f(o), _f(d), _f(tm), _f(t0), _f(t1), _f(sd), _i(out["hit"]), _f(out["t"]), _f(out["pos"]),
+                        _f(out["normal"]), _i(out["mat_type"]), _f(out["mat"]), _f(out["seed_out"]), _i(out["prim"]))
+    return out
+
+
+def _pt_rec(rec, n):
+    return (_c32(rec["pos"], (n, 3)), _c32(rec["normal"], (n, 3)), _c32(rec["t"], (n,)),
+            np.ascontiguousarray(rec["mat_type"], np.int32), _c32(rec["mat"], (n, 11)))
+
+
+def pt_scatter(ray, rec, seed):
+    """scatter() in float ({atten, o, d, t, seed_out}) and its high-precision variant ({hp_atten, hp_o, hp_d} float64),
+    with the branch taken (0 diffuse, 1 metal, 2 reflect, 3 refract, 4 total internal reflection) and `margin`, the
+    distance of the nearest branch decision of either variant from flipping."""
+    n = len(seed)
+    o, d, t = _c32(ray["o"], (n, 3)), _c32(ray["d"], (n, 3)), _c32(ray["t"], (n,))
+    pos, nrm, rt, mt, mat = _pt_rec(rec, n)
+    sd = _c32(seed, (n,))
+    out = {"atten": np.zeros((n, 3), np.float32), "o": np.zeros((n, 3), np.float32), "d": np.zeros((n, 3), np.float32),
+           "t": np.zeros(n, np.float32), "seed_out": np.zeros(n, np.float32), "hp_atten": np.zeros((n, 3)),
+           "branch": np.zeros(n, np.int32), "margin": np.zeros(n)}
+    hp_out = np.zeros((n, 7))
+    lib().pto_scatter(n, _f(o), _f(d), _f(t), _f(pos), _f(nrm), _f(rt), _i(mt), _f(mat), _f(sd), _f(out["atten"]), _f(out["o"]),
+                      _f(out["d"]), _f(out["t"]), _f(out["seed_out"]), _d(out["hp_atten"]), _d(hp_out), _i(out["branch"]),
+                      _d(out["margin"]))
+    out["hp_o"], out["hp_d"] = hp_out[:, 0:3].copy(), hp_out[:, 3:6].copy()
+    return out
+
+
+def pt_direct_lighting(light_pos, ray, rec, seed):
+    """directlighting() in float ({rgb, seed_out}) and in high precision ({hp_rgb}), `lit` (0 facing away, 1 shadowed,
+    2 lit) and `margin` as in pt_scatter."""
+    n = len(seed)
+    lp = _c32(light_pos, (n, 3))
+    o, d, t = _c32(ray["o"], (n, 3)), _c32(ray["d"], (n, 3)), _c32(ray["t"], (n,))
+    pos, nrm, rt, mt, mat = _pt_rec(rec, n)
+    sd = _c32(seed, (n,))
+    out = {"rgb": np.zeros((n, 3), np.float32), "seed_out": np.zeros(n, np.float32), "hp_rgb": np.zeros((n, 3)),
+           "lit": np.zeros(n, np.int32), "margin": np.zeros(n)}
+    lib().pto_direct_lighting(n, _f(lp), _f(o), _f(d), _f(t), _f(pos), _f(nrm), _f(rt), _i(mt), _f(mat), _f(sd), _f(out["rgb"]),
+                              _f(out["seed_out"]), _d(out["hp_rgb"]), _i(out["lit"]), _d(out["margin"]))
+    return out
+
+
+def pt_small_spheres():
+    """The 10x10 procedural field: (centre[100,3], class[100], roughness[100]); cell 10 * (x + 5) + (z + 5)."""
+    c, cls, rough = np.zeros((100, 3), np.float32), np.zeros(100, np.int32), np.zeros(100, np.float32)
+    lib().pto_small_spheres(_f(c), _i(cls), _f(rough))
+    return c, cls, rough

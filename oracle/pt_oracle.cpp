@@ -172,15 +172,18 @@ bool hit_movingSphere(v3 c0, v3 c1, float radius, float t0, float t1, const Ray&
     return false;
 }
 
-bool hit_world(Frame& F, const Ray& r, float tmin, float tmax, HitRecord& rec) {            // PT/P3D_RT.glsl:12-180
+// which (optional): the primitive of the closest hit -- 0, 1 the floor triangles, 2..5 the big spheres in source order, 6 + cell
+// index (10 * (x + 5) + y + 5) for a small sphere -- for the probe-input tests; the shader has no such output
+bool hit_world(Frame& F, const Ray& r, float tmin, float tmax, HitRecord& rec, int* which = nullptr) {            // PT/P3D_RT.glsl:12-180
     bool hit = false;
+    int prim = -1;
     rec.t = tmax;
-    if (hit_triangle(V(-10.0f, -0.01f, 10.0f), V(10.0f, -0.01f, 10.0f), V(-10.0f, -0.01f, -10.0f), r, tmin, rec.t, rec)) { hit = true; rec.material = diffuseM(V(0.2f, 0.2f, 0.2f)); }
-    if (hit_triangle(V(-10.0f, -0.01f, -10.0f), V(10.0f, -0.01f, 10.0f), V(10.0f, -0.01f, -10.0f), r, tmin, rec.t, rec)) { hit = true; rec.material = diffuseM(V(0.2f, 0.2f, 0.2f)); }
-    if (hit_sphere(V(-4.0f, 1.0f, 0.0f), 1.0f, r, tmin, rec.t, rec)) { hit = true; rec.material = diffuseM(V(0.4f, 0.2f, 0.1f)); }
-    if (hit_sphere(V(4.0f, 1.0f, 0.0f), 1.0f, r, tmin, rec.t, rec)) { hit = true; rec.material = metalM(V(0.7f, 0.6f, 0.5f), 0.0f); }
-    if (hit_sphere(V(0.0f, 1.0f, 0.0f), 1.0f, r, tmin, rec.t, rec)) { hit = true; rec.material = dialectricM(V(0, 0, 0), 1.333f, 0.0f); }
-    if (hit_sphere(V(0.0f, 1.0f, 0.0f), -0.5f, r, tmin, rec.t, rec)) { hit = true; rec.material = dialectricM(V(0, 0, 0), 1.333f, 0.0f); }
+    if (hit_triangle(V(-10.0f, -0.01f, 10.0f), V(10.0f, -0.01f, 10.0f), V(-10.0f, -0.01f, -10.0f), r, tmin, rec.t, rec)) { hit = true; prim = 0; rec.material = diffuseM(V(0.2f, 0.2f, 0.2f)); }
+    if (hit_triangle(V(-10.0f, -0.01f, -10.0f), V(10.0f, -0.01f, 10.0f), V(10.0f, -0.01f, -10.0f), r, tmin, rec.t, rec)) { hit = true; prim = 1; rec.material = diffuseM(V(0.2f, 0.2f, 0.2f)); }
+    if (hit_sphere(V(-4.0f, 1.0f, 0.0f), 1.0f, r, tmin, rec.t, rec)) { hit = true; prim = 2; rec.material = diffuseM(V(0.4f, 0.2f, 0.1f)); }
+    if (hit_sphere(V(4.0f, 1.0f, 0.0f), 1.0f, r, tmin, rec.t, rec)) { hit = true; prim = 3; rec.material = metalM(V(0.7f, 0.6f, 0.5f), 0.0f); }
+    if (hit_sphere(V(0.0f, 1.0f, 0.0f), 1.0f, r, tmin, rec.t, rec)) { hit = true; prim = 4; rec.material = dialectricM(V(0, 0, 0), 1.333f, 0.0f); }
+    if (hit_sphere(V(0.0f, 1.0f, 0.0f), -0.5f, r, tmin, rec.t, rec)) { hit = true; prim = 5; rec.material = dialectricM(V(0, 0, 0), 1.333f, 0.0f); }
     const int numxy = 5;
     for (int x = -numxy; x < numxy; ++x)
         for (int y = -numxy; y < numxy; ++y) {
@@ -192,18 +195,19 @@ bool hit_world(Frame& F, const Ray& r, float tmin, float tmax, HitRecord& rec) {
             if (length(center - V(4.0f, 0.2f, 0.0f)) > 0.9f) {
                 if (choose < 0.3f) {
                     v3 center1 = center + V(0.0f, hash1(F.gSeed) * 0.5f, 0.0f);      // consumes the pixel's RNG on every call
-                    if (hit_movingSphere(center, center1, 0.2f, 0.0f, 1.0f, r, tmin, rec.t, rec)) { hit = true; v3 a = hash3(seed); v3 b = hash3(seed); rec.material = diffuseM(a * b); }
+                    if (hit_movingSphere(center, center1, 0.2f, 0.0f, 1.0f, r, tmin, rec.t, rec)) { hit = true; prim = 6 + 10 * (x + numxy) + (y + numxy); v3 a = hash3(seed); v3 b = hash3(seed); rec.material = diffuseM(a * b); }
                 } else if (choose < 0.5f) {
-                    if (hit_sphere(center, 0.2f, r, tmin, rec.t, rec)) { hit = true; v3 a = hash3(seed); v3 b = hash3(seed); rec.material = diffuseM(a * b); }
+                    if (hit_sphere(center, 0.2f, r, tmin, rec.t, rec)) { hit = true; prim = 6 + 10 * (x + numxy) + (y + numxy); v3 a = hash3(seed); v3 b = hash3(seed); rec.material = diffuseM(a * b); }
                 } else if (choose < 0.7f) {
-                    if (hit_sphere(center, 0.2f, r, tmin, rec.t, rec)) { hit = true; rec.material = metalM((hash3(seed) + V(1.0f, 1.0f, 1.0f)) * 0.5f, 0.0f); }
+                    if (hit_sphere(center, 0.2f, r, tmin, rec.t, rec)) { hit = true; prim = 6 + 10 * (x + numxy) + (y + numxy); rec.material = metalM((hash3(seed) + V(1.0f, 1.0f, 1.0f)) * 0.5f, 0.0f); }
                 } else if (choose < 0.9f) {
-                    if (hit_sphere(center, 0.2f, r, tmin, rec.t, rec)) { hit = true; v3 a = (hash3(seed) + V(1.0f, 1.0f, 1.0f)) * 0.5f; float rg = hash1(seed); rec.material = metalM(a, rg); }
+                    if (hit_sphere(center, 0.2f, r, tmin, rec.t, rec)) { hit = true; prim = 6 + 10 * (x + numxy) + (y + numxy); v3 a = (hash3(seed) + V(1.0f, 1.0f, 1.0f)) * 0.5f; float rg = hash1(seed); rec.material = metalM(a, rg); }
                 } else {
-                    if (hit_sphere(center, 0.2f, r, tmin, rec.t, rec)) { hit = true; rec.material = dialectricM(hash3(seed), 1.2f, 0.0f); }
+                    if (hit_sphere(center, 0.2f, r, tmin, rec.t, rec)) { hit = true; prim = 6 + 10 * (x + numxy) + (y + numxy); rec.material = dialectricM(hash3(seed), 1.2f, 0.0f); }
                 }
             }
         }
+    if (which) *which = prim;
     return hit;
 }
 
@@ -314,6 +318,142 @@ v3 sample_color(float res_x, float res_y, int x, int y, float iTime, float mouse
     return rayColor(F, getRay(F, cam, ps));
 }
 
+// ---- high-precision variants of scatter() and directlighting() for the device probes' tolerance: the same RNG draws (the
+// integer hash and the float divisions of the draws are exact on every implementation and stay in float), every sin, cos, pow,
+// exp and all arithmetic downstream of the draws in double.  Branch decisions are taken from the float evaluation so both
+// variants follow one path; `margin` reports how close either evaluation came to flipping one.
+struct d3 { double x, y, z; };
+inline d3 D(double a, double b, double c) { d3 r = {a, b, c}; return r; }
+inline d3 D(v3 a) { return D(a.x, a.y, a.z); }
+inline d3 operator+(d3 a, d3 b) { return D(a.x + b.x, a.y + b.y, a.z + b.z); }
+inline d3 operator-(d3 a, d3 b) { return D(a.x - b.x, a.y - b.y, a.z - b.z); }
+inline d3 operator-(d3 a) { return D(-a.x, -a.y, -a.z); }
+inline d3 operator*(d3 a, double f) { return D(a.x * f, a.y * f, a.z * f); }
+inline d3 operator*(double f, d3 a) { return D(f * a.x, f * a.y, f * a.z); }
+inline d3 operator*(d3 a, d3 b) { return D(a.x * b.x, a.y * b.y, a.z * b.z); }
+inline d3 operator/(d3 a, double f) { return D(a.x / f, a.y / f, a.z / f); }
+inline double dot(d3 a, d3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+inline double length(d3 a) { return sqrt(dot(a, a)); }
+inline d3 normalize(d3 a) { return a / length(a); }
+inline d3 mix(d3 a, d3 b, double t) { return a * (1.0 - t) + b * t; }
+const double pi_d = (double)pi, eps_d = (double)epsilon;
+
+d3 randomInUnitSphere_hp(float& seed) {
+    v3 u = hash3(seed);
+    d3 h = D((double)u.x * 2.0 - 1.0, (double)u.y * (double)6.28318530718f, (double)u.z);
+    double r = pow(h.z, (double)(1.0f / 3.0f));
+    double s = sqrt(1.0 - h.x * h.x);
+    return D(r * (s * sin(h.y)), r * (s * cos(h.y)), r * h.x);
+}
+double schlick_hp(double cosine, double r0) { r0 = r0 * r0; return r0 + (1.0 - r0) * pow(1.0 - cosine, 5.0); }
+inline double dmin(double a, double b) { return a < b ? a : b; }
+
+enum { BR_DIFFUSE = 0, BR_METAL = 1, BR_REFLECT = 2, BR_REFRACT = 3, BR_TIR = 4 };
+
+// returns the branch taken; out7 = o, d, t
+int scatter_hp(float& gSeed, const Ray& rIn, const HitRecord& rec, double* atten, double* out7, double* margin) {
+    const Material& m = rec.material;
+    d3 pos = D(rec.pos), n = D(rec.normal), ind = D(rIn.d);
+    d3 o, d, at;
+    int branch;
+    *margin = 1e30;
+    if (m.type == MT_DIFFUSE) {
+        d3 S = pos + n + normalize(randomInUnitSphere_hp(gSeed));
+        d = normalize(normalize(S - pos));
+        o = pos + n * eps_d;
+        at = D(m.albedo) * fmax(dot(d, n), 0.0) / pi_d;
+        branch = BR_DIFFUSE;
+    } else if (m.type == MT_METAL) {
+        d = normalize(ind - 2.0 * dot(ind, n) * n);
+        d = d + (double)m.roughness * randomInUnitSphere_hp(gSeed);
+        o = pos + n * eps_d;
+        at = D(m.specColor);
+        branch = BR_METAL;
+    } else {
+        at = D(m.albedo);
+        const float fdot = dot(rIn.d, rec.normal);
+        const double ddot = dot(ind, n);
+        *margin = dmin(fabs((double)fdot), fabs(ddot));
+        d3 outward; double niOverNt, cosine, etaI, etaT; float f_ni, f_cos, f_etaI, f_etaT;
+        if (fdot > 0.0f) {
+            outward = -n; niOverNt = (double)m.refIdx; cosine = ddot; etaI = (double)m.refIdx; etaT = 1.0;
+            f_ni = m.refIdx; f_cos = fdot; f_etaI = m.refIdx; f_etaT = 1.0f;
+        } else {
+            outward = n; niOverNt = 1.0 / (double)m.refIdx; cosine = -ddot; etaI = 1.0; etaT = (double)m.refIdx;
+            f_ni = 1.0f / m.refIdx; f_cos = -fdot; f_etaI = 1.0f; f_etaT = m.refIdx;
+        }
+        const float f_r0 = (f_etaI - f_etaT) / (f_etaI + f_etaT);
+        const float f_k = 1.0f - f_ni * f_ni * (1.0f - f_cos * f_cos);
+        const float f_prob = (f_k < 0.0f) ? 1.0f : schlick(f_cos, f_r0);
+        const double r0 = (etaI - etaT) / (etaI + etaT);
+        const double k = 1.0 - niOverNt * niOverNt * (1.0 - cosine * cosine);
+        const double prob = (f_k < 0.0f) ? 1.0 : schlick_hp(cosine, r0);
+        *margin = dmin(*margin, dmin(fabs((double)f_k), fabs(k)));
+        const float h = hash1(gSeed);
+        *margin = dmin(*margin, dmin(fabs((double)h - (double)f_prob), fabs((double)h - prob)));
+        if (h < f_prob) {
+            d = ind - 2.0 * dot(n, ind) * n;
+            d = d + (double)m.roughness * randomInUnitSphere_hp(gSeed);
+            o = pos + outward * eps_d;
+            branch = (f_k < 0.0f) ? BR_TIR : BR_REFLECT;
+        } else {
+            d3 refr = normalize(niOverNt * ind + (niOverNt * cosine - sqrt(k > 0.0 ? k : 0.0)) * outward);
+            refr = mix(refr, normalize(outward + randomInUnitSphere_hp(gSeed)), (double)m.roughness * (double)m.roughness);
+            const double mt = -(double)rec.t;
+            at = at * D(exp((double)m.refractColor.x * mt), exp((double)m.refractColor.y * mt), exp((double)m.refractColor.z * mt));
+            o = pos - outward * eps_d;
+            d = refr;
+            branch = BR_REFRACT;
+        }
+    }
+    atten[0] = at.x; atten[1] = at.y; atten[2] = at.z;
+    out7[0] = o.x; out7[1] = o.y; out7[2] = o.z; out7[3] = d.x; out7[4] = d.y; out7[5] = d.z; out7[6] = (double)rIn.t;
+    return branch;
+}
+
+// lit: 0 the surface faces away, 1 shadowed, 2 lit
+void directlighting_hp(Frame& F, v3 lpos, const Ray& r, const HitRecord& rec, double* rgb, double* margin, int* lit) {
+    rgb[0] = rgb[1] = rgb[2] = 0.0;
+    const v3 f_lightDir = normalize(lpos - rec.pos);
+    const float f_dot = dot(rec.normal, f_lightDir);
+    d3 n = D(rec.normal);
+    d3 lightDir = normalize(D(lpos) - D(rec.pos));
+    const double d_dot = dot(n, lightDir);
+    *margin = dmin(fabs((double)f_dot), fabs(d_dot));
+    *lit = 0;
+    if (!(fmaxf(f_dot, 0.0f) > 0.0f)) return;
+    Ray feeler; feeler.o = rec.pos + epsilon * rec.normal; feeler.d = f_lightDir; feeler.t = 0.0f;
+    const float size = length(f_lightDir);
+    {   // how close the shadow test came to its limits: the same feeler over a slightly longer segment, on a copy of the RNG
+        Frame G = F; HitRecord far_rec;
+        if (hit_world(G, feeler, 0.0f, size + 2e-5f, far_rec)) *margin = dmin(*margin, dmin(fabs((double)far_rec.t - (double)size), fabs((double)far_rec.t)));
+    }
+    HitRecord dummy;
+    *lit = 1;
+    if (hit_world(F, feeler, 0.0f, size, dummy)) return;
+    *lit = 2;
+    d3 specCol, diffCol; double shininess, diffuse, specular;
+    const Material& m = rec.material;
+    if (m.type == MT_DIFFUSE) { specCol = D(0.1f, 0.1f, 0.1f); diffCol = D(m.albedo); shininess = 10.0; diffuse = 1.0; specular = 0.0; }
+    else if (m.type == MT_METAL) { specCol = D(m.albedo); diffCol = D(0, 0, 0); shininess = 100.0; diffuse = 0.0; specular = 1.0; }
+    else { specCol = D(0.004f, 0.004f, 0.004f); diffCol = D(0, 0, 0); shininess = 100.0; diffuse = 0.0; specular = 1.0; }
+    lightDir = normalize(lightDir);
+    d3 H = normalize(lightDir - D(r.d));
+    diffCol = diffCol * fmax(0.0, dot(n, lightDir));
+    specCol = specCol * pow(fmax(0.0, dot(n, H)), shininess);
+    d3 c = diffCol * diffuse + specCol * specular;
+    rgb[0] = c.x; rgb[1] = c.y; rgb[2] = c.z;
+}
+
+inline v3 V3p(const float* p) { return V(p[0], p[1], p[2]); }
+HitRecord load_rec(const float* pos, const float* normal, float t, int type, const float* mat) {
+    HitRecord rec; memset(&rec, 0, sizeof rec);
+    rec.pos = V3p(pos); rec.normal = V3p(normal); rec.t = t;
+    rec.material.type = type; rec.material.albedo = V3p(mat); rec.material.specColor = V3p(mat + 3);
+    rec.material.roughness = mat[6]; rec.material.refIdx = mat[7]; rec.material.refractColor = V3p(mat + 8);
+    return rec;
+}
+
 }  // namespace
 
 extern "C" {
@@ -356,6 +496,84 @@ void pto_render(int res_x, int res_y, int n_frames, float time0, float dt, float
     std::vector<std::thread> pool;
     for (int t = 0; t < threads; t++) pool.emplace_back([&, t]() { for (int y = t; y < res_y; y += threads) rows(y, y + 1); });
     for (auto& th : pool) th.join();
+}
+
+// ---- entries for the device probes (tests/test_gpu_pathtracer_probes.py): one case at a time, no wave concept.
+// mat[11] = albedo, specColor, roughness, refIdx, refractColor.
+void pto_hit_world(int n, const float* origin, const float* dir, const float* time, const float* tmin, const float* tmax,
+                   const float* seed, int32_t* hit, float* t, float* pos, float* normal, int32_t* mat_type, float* mat,
+                   float* seed_out, int32_t* prim) {
+    for (int i = 0; i < n; i++) {
+        Frame F; memset(&F, 0, sizeof F); F.gSeed = seed[i];
+        Ray r; r.o = V3p(origin + 3 * i); r.d = V3p(dir + 3 * i); r.t = time[i];
+        HitRecord rec; memset(&rec, 0, sizeof rec);
+        int which = -1;
+        bool h = hit_world(F, r, tmin[i], tmax[i], rec, &which);
+        hit[i] = h ? 1 : 0; t[i] = rec.t; seed_out[i] = F.gSeed; prim[i] = which;
+        const Material& m = rec.material;
+        const float row[11] = {m.albedo.x, m.albedo.y, m.albedo.z, m.specColor.x, m.specColor.y, m.specColor.z, m.roughness, m.refIdx,
+                               m.refractColor.x, m.refractColor.y, m.refractColor.z};
+        memcpy(pos + 3 * i, &rec.pos, 12); memcpy(normal + 3 * i, &rec.normal, 12); mat_type[i] = m.type; memcpy(mat + 11 * i, row, 44);
+    }
+}
+// float scatter(): atten[3], out ray (o[3], d[3], t), seed_out.  With hp_atten non-NULL also the high-precision variant
+// (hp_atten[3], hp_out[7] as doubles), the branch taken (0 diffuse, 1 metal, 2 reflect, 3 refract, 4 total internal
+// reflection) and the distance of the nearest branch decision from flipping (1e30: no decision on this path).
+void pto_scatter(int n, const float* in_o, const float* in_d, const float* in_t, const float* rec_pos, const float* rec_normal,
+                 const float* rec_t, const int32_t* mat_type, const float* mat, const float* seed, float* atten, float* out_o,
+                 float* out_d, float* out_t, float* seed_out, double* hp_atten, double* hp_out, int32_t* branch, double* margin) {
+    for (int i = 0; i < n; i++) {
+        Ray r; r.o = V3p(in_o + 3 * i); r.d = V3p(in_d + 3 * i); r.t = in_t[i];
+        HitRecord rec = load_rec(rec_pos + 3 * i, rec_normal + 3 * i, rec_t[i], mat_type[i], mat + 11 * i);
+        Frame F; memset(&F, 0, sizeof F); F.gSeed = seed[i];
+        v3 a = V(0, 0, 0); Ray s; memset(&s, 0, sizeof s);
+        scatter(F, r, rec, a, s);
+        memcpy(atten + 3 * i, &a, 12); memcpy(out_o + 3 * i, &s.o, 12); memcpy(out_d + 3 * i, &s.d, 12); out_t[i] = s.t;
+        seed_out[i] = F.gSeed;
+        if (hp_atten) {
+            float sd = seed[i];
+            branch[i] = scatter_hp(sd, r, rec, hp_atten + 3 * i, hp_out + 7 * i, margin + i);
+            if (sd != F.gSeed) branch[i] = -1;          // the two variants drew differently: cannot happen on one path
+        }
+    }
+}
+// float directlighting() (light colour (1,1,1)): rgb[3], seed_out; hp_rgb / margin as for pto_scatter,
+// lit: 0 the surface faces away, 1 shadowed, 2 lit.
+void pto_direct_lighting(int n, const float* lpos, const float* ray_o, const float* ray_d, const float* ray_t, const float* rec_pos,
+                         const float* rec_normal, const float* rec_t, const int32_t* mat_type, const float* mat, const float* seed,
+                         float* rgb, float* seed_out, double* hp_rgb, int32_t* lit, double* margin) {
+    for (int i = 0; i < n; i++) {
+        Ray r; r.o = V3p(ray_o + 3 * i); r.d = V3p(ray_d + 3 * i); r.t = ray_t[i];
+        HitRecord rec = load_rec(rec_pos + 3 * i, rec_normal + 3 * i, rec_t[i], mat_type[i], mat + 11 * i);
+        Frame F; memset(&F, 0, sizeof F); F.gSeed = seed[i];
+        v3 c = directlighting(F, V3p(lpos + 3 * i), V(1, 1, 1), r, rec);
+        memcpy(rgb + 3 * i, &c, 12); seed_out[i] = F.gSeed;
+        if (hp_rgb) {
+            Frame G; memset(&G, 0, sizeof G); G.gSeed = seed[i];
+            directlighting_hp(G, V3p(lpos + 3 * i), r, rec, hp_rgb + 3 * i, margin + i, lit + i);
+            if (G.gSeed != F.gSeed) lit[i] = -1;
+        }
+    }
+}
+// the 10x10 procedural field: centre[100][3], class (-1 absent, 0 moving, 1 diffuse, 2 metal, 3 fuzzy metal, 4 glass) and
+// roughness (of class 3; 0 otherwise), cell index 10 * (x + 5) + (y + 5)
+void pto_small_spheres(float* centre, int32_t* cls, float* rough) {
+    for (int x = -5; x < 5; ++x)
+        for (int y = -5; y < 5; ++y) {
+            const int i = 10 * (x + 5) + (y + 5);
+            float fx = (float)x, fy = (float)y;
+            float seed = fx + fy / 1000.0f;
+            v3 rand1 = hash3(seed);
+            v3 center = V(fx + 0.9f * rand1.x, 0.2f, fy + 0.9f * rand1.y);
+            memcpy(centre + 3 * i, &center, 12);
+            rough[i] = 0.0f;
+            if (!(length(center - V(4.0f, 0.2f, 0.0f)) > 0.9f)) cls[i] = -1;
+            else if (rand1.z < 0.3f) cls[i] = 0;
+            else if (rand1.z < 0.5f) cls[i] = 1;
+            else if (rand1.z < 0.7f) cls[i] = 2;
+            else if (rand1.z < 0.9f) { cls[i] = 3; hash3(seed); rough[i] = hash1(seed); }
+            else cls[i] = 4;
+        }
 }
 
 }  // extern "C"

@@ -208,6 +208,9 @@ def lib():
     L.p3d_pt_timer_begin.argtypes = [C.c_void_p]
     L.p3d_pt_timer_end.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.p3d_pt_debug_hash.argtypes = [C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.p3d_pt_debug_hit_world.argtypes = [C.c_int, C.c_uint32] + [C.c_void_p] * 14
+    L.p3d_pt_debug_scatter.argtypes = [C.c_int, C.c_uint32] + [C.c_void_p] * 14
+    L.p3d_pt_debug_direct_lighting.argtypes = [C.c_int, C.c_uint32] + [C.c_void_p] * 12
     _lib = L
     return L
 
@@ -224,7 +227,8 @@ class PtOutputs(C.Structure):
 
 # include/p3d_pathtracer.h
 PT_C_ABI_SYMBOLS = ["p3d_pt_create", "p3d_pt_destroy", "p3d_pt_set_stream", "p3d_pt_render", "p3d_pt_sync",
-                    "p3d_pt_timer_begin", "p3d_pt_timer_end", "p3d_pt_debug_hash", "p3d_pt_reduce_sum"]
+                    "p3d_pt_timer_begin", "p3d_pt_timer_end", "p3d_pt_debug_hash", "p3d_pt_reduce_sum",
+                    "p3d_pt_debug_hit_world", "p3d_pt_debug_scatter", "p3d_pt_debug_direct_lighting"]
 
 
 def _check(rc, what):
@@ -829,12 +833,14 @@ class PathTracer:
         return PtParams(int(res_x), int(res_y), int(n_frames), int(first_frame), int(frame_stride), float(time0),
                         float(dt), float(mouse[0]), float(mouse[1]))
 
-    def render(self, res_x, res_y, n_frames, first_frame=0, frame_stride=1, time0=0.0, dt=1.0 / 60.0, mouse=(0.0, 0.0)):
-        """Host arrays: rgba [H,W,4] (gamma-encoded running mean + frame count), linear [H,W,3] (sum)."""
-        rgba = np.zeros((res_y, res_x, 4), np.float32)
+    def render(self, res_x, res_y, n_frames, first_frame=0, frame_stride=1, time0=0.0, dt=1.0 / 60.0, mouse=(0.0, 0.0),
+               want_rgba=True):
+        """Host arrays: rgba [H,W,4] (gamma-encoded running mean + frame count), linear [H,W,3] (sum).
+        want_rgba=False passes rgba = NULL (the linear-only form, whose frames may be cut into runs) and returns None for it."""
+        rgba = np.zeros((res_y, res_x, 4), np.float32) if want_rgba else None
         lin = np.zeros((res_y, res_x, 3), np.float32)
         p = self._params(res_x, res_y, n_frames, first_frame, frame_stride, time0, dt, mouse)
-        o = PtOutputs(rgba.ctypes.data, lin.ctypes.data, 0)
+        o = PtOutputs(rgba.ctypes.data if want_rgba else None, lin.ctypes.data, 0)
         _check(lib().p3d_pt_render(self.h, C.byref(p), C.byref(o)), "p3d_pt_render")
         return rgba, lin
 
@@ -850,4 +856,62 @@ def pt_debug_hash(a, b, device=0):
     b = np.ascontiguousarray(b, np.uint32)
     out = np.zeros(len(a), np.uint32)
     _check(lib().p3d_pt_debug_hash(int(device), len(a), a.ctypes.data, b.ctypes.data, out.ctypes.data), "p3d_pt_debug_hash")
+    return out
+
+
+def _f32(a, shape):
+    a = np.ascontiguousarray(a, np.float32)
+    assert a.shape == shape, (a.shape, shape)
+    return a
+
+
+def _rec_arrays(rec, n):
+    return (_f32(rec["pos"], (n, 3)), _f32(rec["normal"], (n, 3)), _f32(rec["t"], (n,)),
+            np.ascontiguousarray(rec["mat_type"], np.int32), _f32(rec["mat"], (n, 11)))
+
+
+def pt_debug_hit_world(origin, direction, time, tmin, tmax, seed, active=None, fill=None, device=0):
+    """The frame kernel's hit_world() on caller-supplied rays (p3d_pt_debug_hit_world).  Case i is lane i % 64 of
+    workgroup i / 64.  `fill` (a dict like the result) presets the outputs: cases with active == 0 keep them."""
+    n = len(seed)
+    o, d = _f32(origin, (n, 3)), _f32(direction, (n, 3))
+    tm, t0, t1, sd = (_f32(x, (n,)) for x in (time, tmin, tmax, seed))
+    act = np.ones(n, np.int32) if active is None else np.ascontiguousarray(active, np.int32)
+    shapes = {"hit": ((n,), np.int32), "t": ((n,), np.float32), "pos": ((n, 3), np.float32), "normal": ((n, 3), np.float32),
+              "mat_type": ((n,), np.int32), "mat": ((n, 11), np.float32), "seed_out": ((n,), np.float32)}
+    out = {k: (np.zeros(sh, dt) if fill is None else np.ascontiguousarray(fill[k], dt).reshape(sh).copy()) for k, (sh, dt) in shapes.items()}
+    _check(lib().p3d_pt_debug_hit_world(int(device), n, o.ctypes.data, d.ctypes.data, tm.ctypes.data, t0.ctypes.data, t1.ctypes.data,
+                                        sd.ctypes.data, act.ctypes.data, out["hit"].ctypes.data, out["t"].ctypes.data,
+                                        out["pos"].ctypes.data, out["normal"].ctypes.data, out["mat_type"].ctypes.data,
+                                        out["mat"].ctypes.data, out["seed_out"].ctypes.data), "p3d_pt_debug_hit_world")
+    return out
+
+
+def pt_debug_scatter(ray, rec, seed, device=0):
+    """The frame kernel's scatter() (p3d_pt_debug_scatter).  ray = {o, d, t}; rec = {pos, normal, t, mat_type, mat}."""
+    n = len(seed)
+    o, d, t = _f32(ray["o"], (n, 3)), _f32(ray["d"], (n, 3)), _f32(ray["t"], (n,))
+    pos, nrm, rt, mt, mat = _rec_arrays(rec, n)
+    sd = _f32(seed, (n,))
+    out = {"atten": np.zeros((n, 3), np.float32), "o": np.zeros((n, 3), np.float32), "d": np.zeros((n, 3), np.float32),
+           "t": np.zeros(n, np.float32), "seed_out": np.zeros(n, np.float32)}
+    _check(lib().p3d_pt_debug_scatter(int(device), n, o.ctypes.data, d.ctypes.data, t.ctypes.data, pos.ctypes.data, nrm.ctypes.data,
+                                      rt.ctypes.data, mt.ctypes.data, mat.ctypes.data, sd.ctypes.data, out["atten"].ctypes.data,
+                                      out["o"].ctypes.data, out["d"].ctypes.data, out["t"].ctypes.data, out["seed_out"].ctypes.data),
+           "p3d_pt_debug_scatter")
+    return out
+
+
+def pt_debug_direct_lighting(light_pos, ray, rec, seed, device=0):
+    """The frame kernel's direct_lighting() (p3d_pt_debug_direct_lighting): {rgb, seed_out}."""
+    n = len(seed)
+    lp = _f32(light_pos, (n, 3))
+    o, d, t = _f32(ray["o"], (n, 3)), _f32(ray["d"], (n, 3)), _f32(ray["t"], (n,))
+    pos, nrm, rt, mt, mat = _rec_arrays(rec, n)
+    sd = _f32(seed, (n,))
+    out = {"rgb": np.zeros((n, 3), np.float32), "seed_out": np.zeros(n, np.float32)}
+    _check(lib().p3d_pt_debug_direct_lighting(int(device), n, lp.ctypes.data, o.ctypes.data, d.ctypes.data, t.ctypes.data,
+                                              pos.ctypes.data, nrm.ctypes.data, rt.ctypes.data, mt.ctypes.data, mat.ctypes.data,
+                                              sd.ctypes.data, out["rgb"].ctypes.data, out["seed_out"].ctypes.data),
+           "p3d_pt_debug_direct_lighting")
     return out

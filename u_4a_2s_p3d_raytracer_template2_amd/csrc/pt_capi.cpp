@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <vector>
 
 namespace p3dpt {
 struct f3 { float x, y, z; };
@@ -22,6 +23,9 @@ struct PtLaunch {
 };
 hipError_t launch_pt_frames(const PtLaunch& P, hipStream_t stream);
 hipError_t launch_pt_hash(uint32_t n, const uint32_t* a, const uint32_t* b, uint32_t* out, hipStream_t stream);
+// probe kernels (pt_kernels.hip): which = 0 hit_world, 1 scatter, 2 direct_lighting; packed rows of the widths below
+hipError_t launch_pt_probe(int which, uint32_t n, const float* in, float* out, hipStream_t stream);
+enum { PT_HW_IN = 12, PT_HW_OUT = 22, PT_SC_IN = 28, PT_SC_OUT = 12, PT_DL_IN = 32, PT_DL_OUT = 4 };
 }  // namespace p3dpt
 
 using namespace p3dpt;
@@ -186,6 +190,108 @@ int p3d_pt_debug_hash(int device, uint32_t n, const uint32_t* a, const uint32_t*
     if (e == hipSuccess) e = hipMemcpy(out, dout, n * 4, hipMemcpyDeviceToHost);
     (void)hipFree(da); (void)hipFree(db); (void)hipFree(dout);
     if (e != hipSuccess) return fail(P3D_ERR_HIP, hipGetErrorString(e));
+    return P3D_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// one synchronous probe launch: rows in, rows out (the out rows go up first: a lane that skips its case leaves its row alone)
+int run_probe(int device, int which, uint32_t n, const std::vector<float>& in, std::vector<float>& out) {
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) return fail(P3D_ERR_NO_DEVICE, "no HIP device visible");
+    if (device < 0 || device >= nd) return fail(P3D_ERR_ARG, "device index out of range");
+    PT_TRY(hipSetDevice(device));
+    float *din = nullptr, *dout = nullptr;
+    hipError_t e = hipMalloc((void**)&din, in.size() * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&dout, out.size() * 4);
+    if (e == hipSuccess) e = hipMemcpy(din, in.data(), in.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(dout, out.data(), out.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = launch_pt_probe(which, n, din, dout, nullptr);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out.data(), dout, out.size() * 4, hipMemcpyDeviceToHost);
+    (void)hipFree(din); (void)hipFree(dout);
+    if (e != hipSuccess) return fail(P3D_ERR_HIP, hipGetErrorString(e));
+    return P3D_OK;
+}
+inline float ibits(int32_t v) { float f; memcpy(&f, &v, 4); return f; }
+inline int32_t fbits(float f) { int32_t v; memcpy(&v, &f, 4); return v; }
+void pack_ray(float* q, const float* o, const float* d, float t) { memcpy(q, o, 12); memcpy(q + 3, d, 12); q[6] = t; }
+void pack_rec(float* q, const float* pos, const float* normal, float t, int32_t type, const float* mat) {
+    memcpy(q, pos, 12); memcpy(q + 3, normal, 12); q[6] = t; q[7] = ibits(type); memcpy(q + 8, mat, 44);
+}
+}  // namespace
+
+extern "C" {
+
+int p3d_pt_debug_hit_world(int device, uint32_t n, const float* origin, const float* dir, const float* time, const float* tmin,
+                           const float* tmax, const float* seed, const int32_t* active, int32_t* hit, float* t, float* pos,
+                           float* normal, int32_t* mat_type, float* mat, float* seed_out) {
+    if (!origin || !dir || !time || !tmin || !tmax || !seed || !active || !hit || !t || !pos || !normal || !mat_type || !mat || !seed_out)
+        return fail(P3D_ERR_ARG, "NULL argument");
+    if (n == 0) return P3D_OK;
+    std::vector<float> in((size_t)n * PT_HW_IN, 0.0f), out((size_t)n * PT_HW_OUT, 0.0f);
+    for (size_t i = 0; i < n; i++) {
+        float* q = &in[i * PT_HW_IN];
+        pack_ray(q, origin + 3 * i, dir + 3 * i, time[i]);
+        q[7] = tmin[i]; q[8] = tmax[i]; q[9] = seed[i]; q[10] = ibits(active[i] != 0);
+        float* r = &out[i * PT_HW_OUT];
+        r[0] = ibits(hit[i]); r[1] = seed_out[i];
+        pack_rec(r + 2, pos + 3 * i, normal + 3 * i, t[i], mat_type[i], mat + 11 * i);
+    }
+    const int rc = run_probe(device, 0, n, in, out);
+    if (rc != P3D_OK) return rc;
+    for (size_t i = 0; i < n; i++) {
+        const float* r = &out[i * PT_HW_OUT];
+        hit[i] = fbits(r[0]); seed_out[i] = r[1];
+        memcpy(pos + 3 * i, r + 2, 12); memcpy(normal + 3 * i, r + 5, 12); t[i] = r[8]; mat_type[i] = fbits(r[9]);
+        memcpy(mat + 11 * i, r + 10, 44);
+    }
+    return P3D_OK;
+}
+
+int p3d_pt_debug_scatter(int device, uint32_t n, const float* in_origin, const float* in_dir, const float* in_time,
+                         const float* rec_pos, const float* rec_normal, const float* rec_t, const int32_t* mat_type,
+                         const float* mat, const float* seed, float* atten, float* out_origin, float* out_dir, float* out_time,
+                         float* seed_out) {
+    if (!in_origin || !in_dir || !in_time || !rec_pos || !rec_normal || !rec_t || !mat_type || !mat || !seed || !atten || !out_origin ||
+        !out_dir || !out_time || !seed_out)
+        return fail(P3D_ERR_ARG, "NULL argument");
+    if (n == 0) return P3D_OK;
+    std::vector<float> in((size_t)n * PT_SC_IN, 0.0f), out((size_t)n * PT_SC_OUT, 0.0f);
+    for (size_t i = 0; i < n; i++) {
+        float* q = &in[i * PT_SC_IN];
+        pack_ray(q, in_origin + 3 * i, in_dir + 3 * i, in_time[i]);
+        pack_rec(q + 7, rec_pos + 3 * i, rec_normal + 3 * i, rec_t[i], mat_type[i], mat + 11 * i);
+        q[26] = seed[i];
+    }
+    const int rc = run_probe(device, 1, n, in, out);
+    if (rc != P3D_OK) return rc;
+    for (size_t i = 0; i < n; i++) {
+        const float* r = &out[i * PT_SC_OUT];
+        memcpy(atten + 3 * i, r, 12); memcpy(out_origin + 3 * i, r + 3, 12); memcpy(out_dir + 3 * i, r + 6, 12);
+        out_time[i] = r[9]; seed_out[i] = r[10];
+    }
+    return P3D_OK;
+}
+
+int p3d_pt_debug_direct_lighting(int device, uint32_t n, const float* light_pos, const float* ray_origin, const float* ray_dir,
+                                 const float* ray_time, const float* rec_pos, const float* rec_normal, const float* rec_t,
+                                 const int32_t* mat_type, const float* mat, const float* seed, float* rgb, float* seed_out) {
+    if (!light_pos || !ray_origin || !ray_dir || !ray_time || !rec_pos || !rec_normal || !rec_t || !mat_type || !mat || !seed || !rgb || !seed_out)
+        return fail(P3D_ERR_ARG, "NULL argument");
+    if (n == 0) return P3D_OK;
+    std::vector<float> in((size_t)n * PT_DL_IN, 0.0f), out((size_t)n * PT_DL_OUT, 0.0f);
+    for (size_t i = 0; i < n; i++) {
+        float* q = &in[i * PT_DL_IN];
+        memcpy(q, light_pos + 3 * i, 12);
+        pack_ray(q + 3, ray_origin + 3 * i, ray_dir + 3 * i, ray_time[i]);
+        pack_rec(q + 10, rec_pos + 3 * i, rec_normal + 3 * i, rec_t[i], mat_type[i], mat + 11 * i);
+        q[29] = seed[i];
+    }
+    const int rc = run_probe(device, 2, n, in, out);
+    if (rc != P3D_OK) return rc;
+    for (size_t i = 0; i < n; i++) { memcpy(rgb + 3 * i, &out[i * PT_DL_OUT], 12); seed_out[i] = out[i * PT_DL_OUT + 3]; }
     return P3D_OK;
 }
 

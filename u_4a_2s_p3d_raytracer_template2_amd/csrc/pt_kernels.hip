@@ -177,12 +177,18 @@ __device__ __forceinline__ bool hit_world(const SmallSphere* tab, const SphereSe
     // the 64 ranges (butterfly min/max) and tests only those cells -- a scalar branch per candidate,
     // no divergence.  Rays whose direction is not unit length (fuzzy metals add an offset without
     // re-normalising, and the shader's sphere test assumes |d| = 1) are not geometric: they keep the
-    // whole field.  The pixel RNG is advanced for EVERY moving-sphere candidate, in index order, as
-    // the shader does.
+    // whole field.  What "unit length" has to mean: with d.d = 1 + e the shader's discriminant is
+    // r^2 - p^2 + e q^2 (p, q: the centre's distance from and along the ray), i.e. it sees a sphere of
+    // radius sqrt(r^2 + e q^2) at range q, and the geometric bounds hold only while that stays inside
+    // the smallest margin, the slab's 0.05: e q^2 <= 0.25^2 - 0.2^2.  The bound was 1e-3, which the
+    // scene's fuzzy metals (roughness down to 0.024) do reach without being unit length, and fails from
+    // q = 4.7; 4e-6 holds out to q = 75, past anything a ray from within 40 units of the scene can
+    // span, and is still 15x the |e| <= 2.4e-7 that normalize() or reflect() of a unit vector leave.
+    // The pixel RNG is advanced for EVERY moving-sphere candidate, in index order, as the shader does.
     int ix0 = 100, ix1 = -100, iz0 = 100, iz1 = -100;             // empty range
     {
         const float dd = dot3(r.d, r.d);
-        if (!(fabsf(dd - 1.0f) < 1e-3f)) { ix0 = -5; ix1 = 4; iz0 = -5; iz1 = 4; }
+        if (!(fabsf(dd - 1.0f) < 4e-6f)) { ix0 = -5; ix1 = 4; iz0 = -5; iz1 = 4; }
         else {
             float ta = tmin, tb = rec.t;
             const float ylo = -0.05f, yhi = 0.95f;
@@ -452,6 +458,89 @@ __global__ void pt_hash_kernel(uint32_t n, const uint32_t* a, const uint32_t* b,
     if (i < n) out[i] = base_hash(a[i], b[i]);
 }
 
+// ---- device probes (p3d_pt_debug_hit_world / _scatter / _direct_lighting): the frame kernel's own hit_world(), scatter()
+// and direct_lighting() on cases the caller supplies, in the frame kernel's launch shape -- 64-thread workgroups, the
+// sphere table in LDS, the ballot sets, the union scratch.  Case i is lane i % 64 of workgroup i / 64.  Packed rows:
+//   ray     o[3] d[3] t                                   (7)
+//   rec     pos[3] normal[3] t type albedo[3] spec[3] rough refIdx refract[3]      (19, type as int bits)
+__device__ __forceinline__ Ray load_ray(const float* p) { Ray r; r.o = F3(p[0], p[1], p[2]); r.d = F3(p[3], p[4], p[5]); r.t = p[6]; return r; }
+__device__ __forceinline__ Rec load_rec(const float* p) {
+    Rec c; c.pos = F3(p[0], p[1], p[2]); c.normal = F3(p[3], p[4], p[5]); c.t = p[6];
+    c.m.type = (int)__float_as_uint(p[7]); c.m.albedo = F3(p[8], p[9], p[10]); c.m.spec = F3(p[11], p[12], p[13]);
+    c.m.rough = p[14]; c.m.refIdx = p[15]; c.m.refract = F3(p[16], p[17], p[18]);
+    return c;
+}
+__device__ __forceinline__ void store_rec(float* p, const Rec& c) {
+    p[0] = c.pos.x; p[1] = c.pos.y; p[2] = c.pos.z; p[3] = c.normal.x; p[4] = c.normal.y; p[5] = c.normal.z; p[6] = c.t;
+    p[7] = __uint_as_float((uint32_t)c.m.type); p[8] = c.m.albedo.x; p[9] = c.m.albedo.y; p[10] = c.m.albedo.z;
+    p[11] = c.m.spec.x; p[12] = c.m.spec.y; p[13] = c.m.spec.z; p[14] = c.m.rough; p[15] = c.m.refIdx;
+    p[16] = c.m.refract.x; p[17] = c.m.refract.y; p[18] = c.m.refract.z;
+}
+__device__ __forceinline__ SphereSets build_sphere_sets(const SmallSphere* tab) {       // as pt_frames_kernel forms them
+    SphereSets sets;
+    const int lane = (int)threadIdx.x;
+    const int c0 = tab[lane].cls, c1 = lane < 36 ? tab[64 + lane].cls : -1;
+    sets.present_lo = __ballot(c0 >= 0); sets.present_hi = __ballot(c1 >= 0);
+    sets.moving_lo = __ballot(c0 == 0); sets.moving_hi = __ballot(c1 == 0);
+    return sets;
+}
+enum { PT_HW_IN = 12, PT_HW_OUT = 22, PT_SC_IN = 28, PT_SC_OUT = 12, PT_DL_IN = 32, PT_DL_OUT = 4 };
+
+// in: ray(7) tmin tmax seed active(int bits) pad; out: hit(int bits) seed_out rec(19) pad.  A lane with active == 0 (or past n)
+// skips the call inside the `if`: the exec mask is partial, as in ray_color, and its output row is not written.
+__global__ __launch_bounds__(64) void pt_probe_hit_world_kernel(uint32_t n, const float* in, float* out) {
+    __shared__ SmallSphere tab[100];
+    __shared__ int wave_union[4];
+    build_small_spheres(tab);
+    __syncthreads();
+    const SphereSets sets = build_sphere_sets(tab);
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    const bool inside = i < n;
+    const float* p = in + (size_t)(inside ? i : 0) * PT_HW_IN;
+    if (inside && __float_as_uint(p[10]) != 0u) {
+        const Ray r = load_ray(p);
+        float gSeed = p[9];
+        Rec rec;
+        rec.pos = F3(0, 0, 0); rec.normal = F3(0, 0, 0); rec.t = 0.0f; rec.m = diffuse_mat(F3(0, 0, 0));
+        const bool hit = hit_world(tab, sets, wave_union, gSeed, r, p[7], p[8], rec);
+        float* q = out + (size_t)i * PT_HW_OUT;
+        q[0] = __uint_as_float(hit ? 1u : 0u); q[1] = gSeed;
+        store_rec(q + 2, rec);
+    }
+}
+// in: ray(7) rec(19) seed pad; out: atten[3] ray(7) seed_out pad
+__global__ __launch_bounds__(64) void pt_probe_scatter_kernel(uint32_t n, const float* in, float* out) {
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    const float* p = in + (size_t)i * PT_SC_IN;
+    const Ray r = load_ray(p);
+    const Rec rec = load_rec(p + 7);
+    float gSeed = p[26];
+    f3 atten = F3(0, 0, 0); Ray o; o.o = F3(0, 0, 0); o.d = F3(0, 0, 0); o.t = 0.0f;
+    scatter(gSeed, r, rec, atten, o);
+    float* q = out + (size_t)i * PT_SC_OUT;
+    q[0] = atten.x; q[1] = atten.y; q[2] = atten.z; q[3] = o.o.x; q[4] = o.o.y; q[5] = o.o.z; q[6] = o.d.x; q[7] = o.d.y; q[8] = o.d.z;
+    q[9] = o.t; q[10] = gSeed;
+}
+// in: lpos[3] ray(7) rec(19) seed pad; out: rgb[3] seed_out
+__global__ __launch_bounds__(64) void pt_probe_direct_lighting_kernel(uint32_t n, const float* in, float* out) {
+    __shared__ SmallSphere tab[100];
+    __shared__ int wave_union[4];
+    build_small_spheres(tab);
+    __syncthreads();
+    const SphereSets sets = build_sphere_sets(tab);
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    if (i < n) {
+        const float* p = in + (size_t)i * PT_DL_IN;
+        const Ray r = load_ray(p + 3);
+        const Rec rec = load_rec(p + 10);
+        float gSeed = p[29];
+        const f3 c = direct_lighting(tab, sets, wave_union, gSeed, F3(p[0], p[1], p[2]), r, rec);
+        float* q = out + (size_t)i * PT_DL_OUT;
+        q[0] = c.x; q[1] = c.y; q[2] = c.z; q[3] = gSeed;
+    }
+}
+
 hipError_t launch_pt_frames(const PtLaunch& P, hipStream_t stream) {
     const int tiles = ((P.ires_x + 15) / 16) * ((P.ires_y + 3) / 4);
     const int chunks = P.n_chunks > 1 ? P.n_chunks : 1;
@@ -464,6 +553,13 @@ hipError_t launch_pt_frames(const PtLaunch& P, hipStream_t stream) {
 }
 hipError_t launch_pt_hash(uint32_t n, const uint32_t* a, const uint32_t* b, uint32_t* out, hipStream_t stream) {
     hipLaunchKernelGGL(pt_hash_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, a, b, out);
+    return hipGetLastError();
+}
+hipError_t launch_pt_probe(int which, uint32_t n, const float* in, float* out, hipStream_t stream) {
+    const dim3 grid((n + 63u) / 64u), block(64);
+    if (which == 0) hipLaunchKernelGGL(pt_probe_hit_world_kernel, grid, block, 0, stream, n, in, out);
+    else if (which == 1) hipLaunchKernelGGL(pt_probe_scatter_kernel, grid, block, 0, stream, n, in, out);
+    else hipLaunchKernelGGL(pt_probe_direct_lighting_kernel, grid, block, 0, stream, n, in, out);
     return hipGetLastError();
 }
 
