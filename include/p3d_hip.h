@@ -301,6 +301,43 @@ int p3d_render(p3d_scene* scene, const p3d_camera* cam, const p3d_render_params*
  *    stream itself, so a replay renders the cameras it was captured with. */
 int p3d_render_frames(p3d_scene* scene, const p3d_camera* cams, int32_t n, const p3d_render_params* params,
                       const p3d_outputs* out);
+
+/* What a frame knows about its primary hits besides their colour: the planes a denoiser, a depth compositor, an edge-aware
+ * upsampler, picking with a hit point or reprojection between cameras read. */
+typedef struct p3d_aov_outputs {   /* every plane may be NULL; memory as p3d_outputs::memory of the same call */
+    float* depth;    /* [rows][res_x]    the intersector's t of the primary hit; +inf on a miss           */
+    float* normal;   /* [rows][res_x][3] getNormal(hit point).normalize() of that hit; 0,0,0 on a miss    */
+    float* albedo;   /* [rows][res_x][3] diffuse rgb of the hit primitive's material; 0,0,0 on a miss     */
+} p3d_aov_outputs;
+/* p3d_render_frames(scene, cams, n, params, out) in every bit of rgb8, rgb32f and hit_id, with the AOV planes written by
+ * the same launches, where the closest hit of the primary ray is still in registers (the reference has no such output: its
+ * rayTracing() keeps t, the normal and the material to itself, RT/main.cpp:575-589).  n == 1 is one frame, as p3d_render.
+ * With aov == NULL, or all three planes NULL, the call is p3d_render_frames exactly.
+ *  - which hit: the one hit_id describes -- the primary ray's closest hit, of sample 0 when spp > 0.  depth and normal are
+ *    the bits p3d_trace_rays returns as t and normal for that same primary ray.
+ *  - depth: no image convention -- no clamp, no quantisation; in units of the primary ray's direction as PrimaryRay builds
+ *    it (RT/camera.h:91-127), so the hit point is origin + depth * direction.
+ *  - albedo: floats 0..2 of the hit's material record as p3d_scene_desc::materials gave them, not multiplied by Kd.
+ *  - layout: that of rgb32f and hit_id -- bottom row first, rows = res_y, or p3d_local_rows() when world > 1; frame f of a
+ *    batch starts f * rows * res_x pixels in; rows past the image (the padding of a shard's last row block) are not
+ *    written into device-memory planes, and hold unspecified values in host-memory planes, which are copied back whole from
+ *    the handle's staging buffers -- as for rgb8, rgb32f and hit_id.  Sharded planes stitch with
+ *    p3d_deinterleave[_frames]: bytes_per_pixel 4 for depth, 12 for normal and albedo.
+ *  - every schedule, accel mode, feature, flag, sample count, sharding and workspace budget (banded frames) that
+ *    p3d_render_frames accepts is accepted, with the same refusals; a NULL out is P3D_ERR_ARG as there (the planes are in
+ *    the memory out->memory names).  A frame with planes runs builds of the level-1, tile and tree kernels that hold the
+ *    writes; a frame without runs the kernels it ran before this entry existed.  The multi-tile level-1 kernels
+ *    (p3d_set_primary_tiles) have no such build: a frame with planes runs one tile per workgroup, and
+ *    p3d_last_primary_tiles() says so.
+ *  - host memory (out->memory == 0): the planes are staged in device buffers the handle owns and copied back before the
+ *    call returns.
+ *  - handle state: the planes are part of no cache key.  A call with them shares the measured schedule choice, the learned
+ *    tile orders and the workspaces of the same configuration without them; alternating the two re-measures nothing.
+ *    The choice is measured by the frames WITHOUT planes only: a call with planes uses the choice already made (the tile
+ *    schedule while there is none), times no candidate and leaves the measurement where it was.
+ *  - after p3d_scene_update the planes follow the moved geometry like everything else. */
+int p3d_render_aov(p3d_scene* scene, const p3d_camera* cams, int32_t n, const p3d_render_params* params,
+                   const p3d_outputs* out, const p3d_aov_outputs* aov);
 /* A stream of rays the caller supplies, and what comes back for each.  Ray i is (origin[i], dir[i]); its results sit at
  * index i of every plane -- no image conventions: no clamp, no quantisation, no bottom-up rows, no "/ 16". */
 typedef struct p3d_rays {
@@ -357,7 +394,7 @@ int p3d_set_tuning(p3d_scene* scene, int32_t xcd_chunk, int32_t workspace_mib, i
 
 /* More launch tuning that never changes results: tiles = 16x16-pixel tiles a workgroup of the wavefront schedule's level-1
  * launch runs one after the other: 1, 2 or 3; 0 restores the default. Only scenes served from LDS, on the per-lane walk,
- * without counters, features or frame batches, and with xcd_chunk == 1 have such kernels; every other frame runs with 1
+ * without counters, features, frame batches or AOV planes, and with xcd_chunk == 1 have such kernels; every other frame runs with 1
  * whatever is set here (p3d_last_primary_tiles() tells). P3D_PRIMARY_TILES=1..3 in the environment sets the same for every
  * scene created afterwards (measurement scripts: profiles/r06_primary_tiles.txt). */
 int p3d_set_primary_tiles(p3d_scene* scene, int32_t tiles);

@@ -69,6 +69,12 @@ class Outputs(C.Structure):
     _fields_ = [("rgb8", C.c_void_p), ("rgb32f", C.c_void_p), ("hit_id", C.c_void_p), ("memory", C.c_int32)]
 
 
+class AovOutputs(C.Structure):
+    """p3d_aov_outputs: depth [rows][W], normal and albedo [rows][W][3] floats; every plane may be NULL; host or device
+    memory as the p3d_outputs of the same call says."""
+    _fields_ = [("depth", C.c_void_p), ("normal", C.c_void_p), ("albedo", C.c_void_p)]
+
+
 class Rays(C.Structure):
     """p3d_rays: n rays, origin / dir [n][3] floats on the host (memory 0) or the scene's device (memory 1)."""
     _fields_ = [("n", C.c_uint32), ("origin", C.c_void_p), ("dir", C.c_void_p), ("memory", C.c_int32)]
@@ -98,7 +104,7 @@ class SceneStats(C.Structure):
 
 # every symbol include/p3d_hip.h declares (tests check that the library exports them all)
 C_ABI_SYMBOLS = ["p3d_abi_version", "p3d_last_error", "p3d_device_count", "p3d_scene_create",
-                 "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_scene_update", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_trace_rays", "p3d_sync",
+                 "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_scene_update", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_render_aov", "p3d_trace_rays", "p3d_sync",
                  "p3d_get_counters", "p3d_get_profile", "p3d_last_schedule", "p3d_set_tuning", "p3d_set_primary_tiles", "p3d_last_primary_tiles", "p3d_set_stream", "p3d_timer_begin", "p3d_timer_end", "p3d_deinterleave_frames",
                  "p3d_deinterleave", "p3d_debug_intersect", "p3d_debug_powf", "p3d_debug_pow", "p3d_debug_schlick_kr", "p3d_debug_check_rcp", "p3d_debug_check_rcp_len", "p3d_tune_schedule", "p3d_debug_set_stamps", "p3d_debug_set_stamp_level",
                  "p3d_comm_unique_id", "p3d_comm_create", "p3d_comm_create_all", "p3d_comm_destroy", "p3d_comm_info",
@@ -144,6 +150,8 @@ def lib():
     L.p3d_local_rows.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     L.p3d_render.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(Outputs)]
     L.p3d_render_frames.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.POINTER(RenderParams), C.POINTER(Outputs)]
+    L.p3d_render_aov.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.POINTER(RenderParams), C.POINTER(Outputs),
+                                 C.POINTER(AovOutputs)]
     L.p3d_trace_rays.argtypes = [C.c_void_p, C.POINTER(Rays), C.POINTER(RenderParams), C.POINTER(RayOutputs)]
     L.p3d_sync.argtypes = [C.c_void_p]
     L.p3d_get_counters.argtypes = [C.c_void_p, C.POINTER(Counters)]
@@ -338,6 +346,7 @@ def orbit_eyes(eye, n, step_deg, d_beta_deg=0.0):
 
 
 RAY_PLANES = ("rgb32f", "hit_id", "t", "normal")       # the planes of p3d_ray_outputs, in its order
+AOV_PLANES = ("depth", "normal", "albedo")             # the planes of p3d_aov_outputs, in its order
 
 
 def _ray_arrays(origins, dirs):
@@ -561,6 +570,45 @@ class DeviceScene:
         p = self._params(max_depth, accel, spp, samples, rank, world, row_block, counters, tree, no_lds, profile, wavefront, soft_shadow, fuzzy_reflection, seed, tile, samples_ptr, packet, private_walk, skybox, schlick)
         o = Outputs(rgb8_ptr or None, rgb32f_ptr or None, hit_ptr or None, 1)
         _check(lib().p3d_render_frames(self.h, arr, n, C.byref(p), C.byref(o)), "p3d_render_frames")
+
+    def render_aov(self, cam_or_cams, max_depth=4, accel=ACCEL_BVH, spp=0, samples=None, rank=0, world=1, row_block=16,
+                   want=AOV_PLANES, **switches):
+        """p3d_render_aov into host numpy arrays: the frames of render_frames (one Camera, or a sequence of n) and, written by
+        the same launches, the planes named in `want` for the primary hit hit_id describes -- depth (n, rows, W): the
+        intersector's t, +inf on a miss; normal (n, rows, W, 3); albedo (n, rows, W, 3): the material's diffuse rgb; zeros
+        on a miss.  rows = res_y for world == 1, local_rows otherwise.  switches: the keyword switches of render_frames
+        (wavefront, tile, tree, no_lds, private_walk, soft_shadow, ...).  Returns the dict of render_frames plus the planes."""
+        for k in want:
+            if k not in AOV_PLANES:
+                raise ValueError("unknown AOV plane %r" % (k,))
+        arr, n = _camera_array([cam_or_cams] if isinstance(cam_or_cams, Camera) else cam_or_cams)
+        c0 = arr[0]
+        rows = c0.res_y if world == 1 else local_rows(c0.res_y, row_block, world)
+        out = {"rgb8": np.zeros((n, rows, c0.res_x, 3), np.uint8), "rgb32f": np.zeros((n, rows, c0.res_x, 3), np.float32),
+               "hit_id": np.full((n, rows, c0.res_x), -2, np.int32)}
+        for k in want:
+            out[k] = np.zeros((n, rows, c0.res_x) if k == "depth" else (n, rows, c0.res_x, 3), np.float32)
+        if samples is not None:
+            samples = np.ascontiguousarray(samples, np.float32)
+        counters = bool(switches.pop("counters", False))
+        p = self._params(max_depth, accel, spp, samples, rank, world, row_block, counters, **switches)
+        ptr = lambda k: out[k].ctypes.data if k in out and out[k].size else None
+        o = Outputs(ptr("rgb8"), ptr("rgb32f"), ptr("hit_id"), 0)
+        a = AovOutputs(*[ptr(k) for k in AOV_PLANES])
+        _check(lib().p3d_render_aov(self.h, arr, n, C.byref(p), C.byref(o), C.byref(a)), "p3d_render_aov")
+        if counters:
+            out["counters"] = self.counters()
+        return out
+
+    def render_aov_device(self, cam_or_cams, rgb8_ptr=0, rgb32f_ptr=0, hit_ptr=0, depth_ptr=0, normal_ptr=0, albedo_ptr=0,
+                          max_depth=4, accel=ACCEL_BVH, spp=0, samples=None, rank=0, world=1, row_block=16, **switches):
+        """Enqueue p3d_render_aov into caller-owned DEVICE buffers (raw pointers; 0 = no such plane); asynchronous."""
+        arr, n = _camera_array([cam_or_cams] if isinstance(cam_or_cams, Camera) else cam_or_cams)
+        counters = bool(switches.pop("counters", False))
+        p = self._params(max_depth, accel, spp, samples, rank, world, row_block, counters, **switches)
+        o = Outputs(rgb8_ptr or None, rgb32f_ptr or None, hit_ptr or None, 1)
+        a = AovOutputs(depth_ptr or None, normal_ptr or None, albedo_ptr or None)
+        _check(lib().p3d_render_aov(self.h, arr, n, C.byref(p), C.byref(o), C.byref(a)), "p3d_render_aov")
 
     def _ray_params(self, max_depth, accel, no_lds, private_walk, soft_shadow):
         return self._params(max_depth, accel, 0, None, 0, 1, 0, False, no_lds=no_lds, private_walk=private_walk, soft_shadow=soft_shadow)

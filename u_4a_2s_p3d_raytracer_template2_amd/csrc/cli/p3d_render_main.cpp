@@ -2,9 +2,12 @@
 // (RT/main.cpp:949-976: init_scene -> renderScene -> save image) on an MI355X.
 //   p3d_render <scene.p3f> [--res W H] [--accel 0|1|2] [--depth D] [--spp N] [--seed S]
 //              [--device K | --gpus N] [--out image.png|image.ppm] [--counters] [--soft-shadow] [--fuzzy-reflection]
+//              [--aov PREFIX]
 // --gpus N: devices 0..N-1 each render every N-th block of 16 rows, one RCCL gather to device 0.
 // --orbit N STEP_DEG: N frames of the reference's mouse orbit (alpha advancing by STEP_DEG per frame, RT/main.cpp:339-341,
 // 419-421) in ONE p3d_render_frames call; --out then takes a %d pattern (e.g. frame_%03d.png) for the frame number.
+// --aov PREFIX: also writes the primary hits' depth, normal and albedo planes (p3d_render_aov) as float32 NumPy files
+// PREFIX_depth.npy (H, W), PREFIX_normal.npy and PREFIX_albedo.npy (H, W, 3), bottom row first like img_Data.
 // Defaults are the reference's: resolution / accel / spp from the file, MAX_DEPTH 4.
 #include <chrono>
 #include <cstdio>
@@ -26,16 +29,33 @@ static int save_ppm(const char* path, const std::vector<uint8_t>& img, int w, in
     return 0;
 }
 
+// NumPy .npy, format 1.0: magic, version, a little-endian header length, a Python dict padded with spaces to a multiple of
+// 64 bytes and ended by a newline, then the float32 data in C order.
+static int save_npy(const std::string& path, const std::vector<float>& v, int h, int w, int c) {
+    FILE* f = fopen(path.c_str(), "wb");
+    if (!f) return -1;
+    char shape[64];
+    if (c > 1) snprintf(shape, sizeof shape, "(%d, %d, %d)", h, w, c); else snprintf(shape, sizeof shape, "(%d, %d)", h, w);
+    std::string hdr = std::string("{'descr': '<f4', 'fortran_order': False, 'shape': ") + shape + ", }";
+    while ((10 + hdr.size() + 1) % 64) hdr += ' ';
+    hdr += '\n';
+    const unsigned char pre[10] = {0x93, 'N', 'U', 'M', 'P', 'Y', 1, 0, (unsigned char)(hdr.size() & 255), (unsigned char)(hdr.size() >> 8)};
+    bool ok = fwrite(pre, 1, 10, f) == 10 && fwrite(hdr.data(), 1, hdr.size(), f) == hdr.size() &&
+              fwrite(v.data(), sizeof(float), v.size(), f) == v.size();
+    return (fclose(f) == 0 && ok) ? 0 : -1;
+}
+
 int main(int argc, char** argv) {
     if (argc < 2) {
         fprintf(stderr, "usage: %s scene.p3f [--res W H] [--accel A] [--depth D] [--spp N] [--seed S] "
-                        "[--device K | --gpus N] [--out file.ppm] [--orbit N STEP_DEG] [--counters] [--soft-shadow] [--fuzzy-reflection] [--schlick]\n", argv[0]);
+                        "[--device K | --gpus N] [--out file.ppm] [--orbit N STEP_DEG] [--counters] [--soft-shadow] [--fuzzy-reflection] [--schlick] [--aov PREFIX]\n", argv[0]);
         return 2;
     }
     RenderOptions opt;
     int rw = 0, rh = 0, orbit_n = 0;
     float orbit_step = 0.0f;
     std::string out = "RT_Output.png";                       // the reference's file name, RT/main.cpp:968
+    std::string aov;                                         // --aov PREFIX
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i];
         auto need = [&](int n) { if (i + n >= argc) { fprintf(stderr, "%s needs %d value(s)\n", a.c_str(), n); exit(2); } };
@@ -52,6 +72,7 @@ int main(int argc, char** argv) {
         else if (a == "--soft-shadow") opt.SOFT_SHADOW = true;
         else if (a == "--fuzzy-reflection") opt.FUZZY_REFLECTION = true;
         else if (a == "--schlick") opt.SCHLICK_APPROX = true;
+        else if (a == "--aov") { need(1); aov = argv[++i]; opt.want_aov = true; }
         else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     Scene scene;
@@ -65,6 +86,7 @@ int main(int argc, char** argv) {
         if (ppm) { std::vector<uint8_t> v(img, img + (size_t)W * H * 3); return save_ppm(path.c_str(), v, W, H); }
         return save_png(path.c_str(), img, W, H);
     };
+    if (orbit_n > 0 && opt.want_aov) { fprintf(stderr, "--aov writes the planes of one frame: not with --orbit\n"); return 2; }
     if (orbit_n > 0) {
         {   // exactly one conversion, %d or %0Nd: the pattern is handed to snprintf
             const size_t pc = out.find('%');
@@ -108,5 +130,13 @@ int main(int argc, char** argv) {
         return 1;
     }
     printf("Image file created: %s\n", out.c_str());
+    if (opt.want_aov) {
+        if (save_npy(aov + "_depth.npy", res.depth, H, W, 1) || save_npy(aov + "_normal.npy", res.normal, H, W, 3) ||
+            save_npy(aov + "_albedo.npy", res.albedo, H, W, 3)) {
+            fprintf(stderr, "Error saving the AOV files\n");
+            return 1;
+        }
+        printf("AOV files created: %s_depth.npy %s_normal.npy %s_albedo.npy\n", aov.c_str(), aov.c_str(), aov.c_str());
+    }
     return 0;
 }

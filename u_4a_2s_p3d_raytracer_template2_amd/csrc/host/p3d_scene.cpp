@@ -371,7 +371,8 @@ int render_multi_gpu(const Scene::Flat& flat, const p3d_camera& cam, p3d_render_
     const int n = opt.gpus, row_block = 16;
     std::vector<p3d_scene*> dev(n, nullptr);
     std::vector<p3d_comm*> comm(n, nullptr);
-    struct Plane { int bpp; void* host; std::vector<void*> tile; void* gathered = nullptr; void* frame = nullptr; };
+    enum What { RGB8, RGB32F, HIT_ID, DEPTH, NORMAL, ALBEDO };
+    struct Plane { What what; int bpp; void* host; std::vector<void*> tile; void* gathered = nullptr; void* frame = nullptr; };
     std::vector<Plane> planes;
     int rc = P3D_OK;
     auto cleanup = [&]() {
@@ -388,9 +389,14 @@ int render_multi_gpu(const Scene::Flat& flat, const p3d_camera& cam, p3d_render_
     const size_t npx = (size_t)cam.res_x * cam.res_y;
     const size_t tile_px = (size_t)p3d_local_rows(cam.res_y, row_block, n) * cam.res_x;
     out.img_Data.assign(npx * 3, 0);
-    planes.push_back(Plane{3, out.img_Data.data(), {}});
-    if (want_colors) { out.colors.assign(npx * 3, 0.0f); planes.push_back(Plane{12, out.colors.data(), {}}); }
-    if (want_hit) { out.hit_id.assign(npx, -1); planes.push_back(Plane{4, out.hit_id.data(), {}}); }
+    planes.push_back(Plane{RGB8, 3, out.img_Data.data(), {}});
+    if (want_colors) { out.colors.assign(npx * 3, 0.0f); planes.push_back(Plane{RGB32F, 12, out.colors.data(), {}}); }
+    if (want_hit) { out.hit_id.assign(npx, -1); planes.push_back(Plane{HIT_ID, 4, out.hit_id.data(), {}}); }
+    if (opt.want_aov) {          // the AOV planes travel like hit_id: one more entry each in the list the gather walks
+        out.depth.assign(npx, 0.0f); planes.push_back(Plane{DEPTH, 4, out.depth.data(), {}});
+        out.normal.assign(npx * 3, 0.0f); planes.push_back(Plane{NORMAL, 12, out.normal.data(), {}});
+        out.albedo.assign(npx * 3, 0.0f); planes.push_back(Plane{ALBEDO, 12, out.albedo.data(), {}});
+    }
     for (auto& pl : planes) {
         pl.tile.assign(n, nullptr);
         if (!rc) rc = p3d_device_alloc(dev[0], (uint64_t)tile_px * pl.bpp * n, &pl.gathered);
@@ -403,11 +409,15 @@ int render_multi_gpu(const Scene::Flat& flat, const p3d_camera& cam, p3d_render_
         prm.rank = r; prm.world = n; prm.row_block = row_block;
         p3d_outputs o;
         o.memory = 1; o.rgb8 = (uint8_t*)planes[0].tile[r]; o.rgb32f = nullptr; o.hit_id = nullptr;
+        p3d_aov_outputs a = {nullptr, nullptr, nullptr};
         for (auto& pl : planes) {
-            if (pl.bpp == 12) o.rgb32f = (float*)pl.tile[r];
-            if (pl.bpp == 4) o.hit_id = (int32_t*)pl.tile[r];
+            if (pl.what == RGB32F) o.rgb32f = (float*)pl.tile[r];
+            if (pl.what == HIT_ID) o.hit_id = (int32_t*)pl.tile[r];
+            if (pl.what == DEPTH) a.depth = (float*)pl.tile[r];
+            if (pl.what == NORMAL) a.normal = (float*)pl.tile[r];
+            if (pl.what == ALBEDO) a.albedo = (float*)pl.tile[r];
         }
-        rc = p3d_render(dev[r], &cam, &prm, &o);
+        rc = opt.want_aov ? p3d_render_aov(dev[r], &cam, 1, &prm, &o, &a) : p3d_render(dev[r], &cam, &prm, &o);
     }
     for (auto& pl : planes) {
         std::vector<const void*> tiles(pl.tile.begin(), pl.tile.end());
@@ -499,8 +509,13 @@ int renderScene(const Scene& scene, const RenderOptions& opt, bool want_colors, 
     p3d_outputs o;
     o.rgb8 = out.img_Data.data(); o.rgb32f = want_colors ? out.colors.data() : nullptr;
     o.hit_id = want_hit ? out.hit_id.data() : nullptr; o.memory = 0;
+    p3d_aov_outputs a = {nullptr, nullptr, nullptr};
+    if (opt.want_aov) {
+        out.depth.assign(npx, 0.0f); out.normal.assign(npx * 3, 0.0f); out.albedo.assign(npx * 3, 0.0f);
+        a.depth = out.depth.data(); a.normal = out.normal.data(); a.albedo = out.albedo.data();
+    }
     rc = p3d_timer_begin(dev);
-    if (!rc) rc = p3d_render(dev, &cam, &prm, &o);
+    if (!rc) rc = opt.want_aov ? p3d_render_aov(dev, &cam, 1, &prm, &o, &a) : p3d_render(dev, &cam, &prm, &o);
     if (!rc) rc = p3d_timer_end(dev, &out.kernel_ms);
     if (!rc && opt.counters) rc = p3d_get_counters(dev, &out.counters);
     if (rc) { bad(rc); p3d_scene_destroy(dev); return rc; }

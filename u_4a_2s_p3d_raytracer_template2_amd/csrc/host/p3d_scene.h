@@ -230,11 +230,17 @@ struct RenderOptions {
     // misses return Scene::GetSkyboxColor(ray) (RT/scene.cpp:383-461; never called by the reference) when the
     // scene carries a cube map (Scene::SetSkybox): off by default, like in the reference's rayTracing()
     bool SKYBOX = false;
+    // renderScene() also fills RenderResult::depth / normal / albedo (p3d_render_aov: the primary hit's t, normal and
+    // diffuse colour, written by the frame's own launches); with gpus > 1 they are gathered like hit_id
+    bool want_aov = false;
 };
 struct RenderResult {
     std::vector<uint8_t> img_Data;   // RGB8, bottom row first (RT/main.cpp:76)
     std::vector<float> colors;       // optional float RGB
     std::vector<int32_t> hit_id;     // optional
+    // RenderOptions::want_aov (renderScene only), bottom row first like the others: the primary hit's t (+inf on a miss),
+    // getNormal(hit point).normalize() and its material's diffuse rgb (zeros on a miss)
+    std::vector<float> depth, normal, albedo;      // [res_y][res_x], [res_y][res_x][3], [res_y][res_x][3]
     p3d_counters counters{};
     float kernel_ms = 0;
 };

@@ -191,6 +191,11 @@ struct LaunchParams {
     // n_frames <= 1: one frame, whose camera is the fields above (frame_cams unused).
     int32_t n_frames, frame_rows, out_rows;
     const FrameCam* frame_cams;
+    // ---- AOV planes of a frame (p3d_render_aov), indexed like hit_id and written where hit_id is: the primary hit's t
+    // (+inf on a miss), getNormal(hit point).normalize() and the diffuse rgb of its material (zeros on a miss).  Each may be
+    // nullptr.  Only the AOV builds of the kernels read them (KernelVariant::aov): a frame without planes runs the builds
+    // without.  They sit behind every field frames had before them, so no older field moved in the kernarg segment.
+    float* aov_depth; float* aov_normal; float* aov_albedo;
 };
 
 // A ray stream (p3d_trace_rays): what its level-1 launch, wf_rays_kernel, takes NEXT TO the launch parameters -- which stay

@@ -20,9 +20,10 @@ struct KernelVariant {
     bool schlick = false;   // P3D_FEATURE_SCHLICK
     bool batch = false;     // frame batch (p3d_render_frames)
     int tiles = 1;          // level-1 kernel: 16x16 tiles a workgroup runs one after the other (1, 2 or 3)
+    bool aov = false;       // the frame writes AOV planes (p3d_render_aov): the kernels that see primary hits are built twice
     constexpr bool operator==(const KernelVariant& o) const {
         return count == o.count && lds == o.lds && walk == o.walk && occ == o.occ && stoch == o.stoch && schlick == o.schlick &&
-               batch == o.batch && tiles == o.tiles;
+               batch == o.batch && tiles == o.tiles && aov == o.aov;
     }
 };
 
@@ -38,34 +39,41 @@ constexpr int kDefaultPrimaryTiles = 2;
 // for the timed builds without features: the variant exists to spread a workgroup's fixed cost (scene copy, launch
 // parameters, shard set-up) over more pixels, and the other builds are not bound by it.
 constexpr bool has_primary_tiles(const KernelVariant& v, Level k) {
-    return k == Level::Primary && v.lds && v.walk == WALK_LANE && !v.count && !v.stoch && !v.schlick && !v.batch;
+    return k == Level::Primary && v.lds && v.walk == WALK_LANE && !v.count && !v.stoch && !v.schlick && !v.batch && !v.aov;
 }
+// AOV planes are written where a primary hit is in registers: the level-1 kernel, the tile kernel and the tree kernel have a
+// build with the writes (AOV = true) next to the build without, which is the code it was before the planes existed, to the
+// instruction -- a run-time test of the plane pointers in ONE build moved the register allocation of the tile and tree
+// kernels ("AOV planes").  The deeper levels and a ray stream's level 1 never see a frame's primary hit.
+constexpr bool has_aov(Level k) { return k == Level::Primary || k == Level::Tile; }
 // The ray-stream level-1 kernel is built per scene placement and walk and nothing else: the per-lane, grid and shared walks
 // (a packet request gets the per-lane walk), at the register budget frames run their level kernels at by default.
 constexpr int kRaysOcc = 6;
 // the build of level kernel k that serves request v
 constexpr KernelVariant canonical_level(KernelVariant v, Level k) {
     if (k == Level::Secondary) v.batch = false;
+    if (!has_aov(k)) v.aov = false;
     if (k == Level::Rays) {
         v.count = v.stoch = v.schlick = v.batch = false;
         v.occ = kRaysOcc;
         if (v.walk == WALK_PACKET) v.walk = WALK_LANE;
     }
     if (v.walk == WALK_SHARED && v.lds) v.walk = WALK_LANE;        // LDS scenes have no shared walk
-    // a register budget only for the timed builds of the BVH walks: grid, counting, stochastic, Schlick and batch builds use the default
-    if ((v.occ != 5 && v.occ != 6) || v.walk == WALK_GRID || v.count || v.stoch || v.schlick || v.batch) v.occ = 1;
+    // a register budget only for the timed builds of the BVH walks: grid, counting, stochastic, Schlick, batch and AOV builds use the default
+    if ((v.occ != 5 && v.occ != 6) || v.walk == WALK_GRID || v.count || v.stoch || v.schlick || v.batch || v.aov) v.occ = 1;
     if (v.tiles < 2 || v.tiles > kMaxPrimaryTiles || !has_primary_tiles(v, k)) v.tiles = 1;
     return v;
 }
 // ... and whether v itself is one of the builds of k: the one statement of which builds exist
 constexpr bool built_level(const KernelVariant& v, Level k) {
     if (v.batch && k == Level::Secondary) return false;
+    if (v.aov && !has_aov(k)) return false;
     if (k == Level::Rays && (v.count || v.stoch || v.schlick || v.batch || v.walk == WALK_PACKET || v.occ != (v.walk == WALK_GRID ? 1 : kRaysOcc)))
         return false;
     if (v.walk == WALK_SHARED && v.lds) return false;
     if (v.tiles != 1 && (v.tiles < 2 || v.tiles > kMaxPrimaryTiles || !has_primary_tiles(v, k))) return false;
     if (v.occ == 1) return true;
-    return v.walk != WALK_GRID && !v.count && !v.stoch && !v.schlick && !v.batch;
+    return v.walk != WALK_GRID && !v.count && !v.stoch && !v.schlick && !v.batch && !v.aov;
 }
 
 // Grid of the level-1 launch over a band of tile_rows rows of tiles_x tiles.  LDS scenes on the identity tile map launch

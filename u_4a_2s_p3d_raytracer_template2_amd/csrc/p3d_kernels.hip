@@ -44,6 +44,28 @@ __device__ __forceinline__ SceneOffsets scene_offsets(const LaunchParams& P) {
     return SceneOffsets{P.off_nodes, P.off_leaves, P.off_spheres, P.off_sphere_meta, P.off_tris, P.off_tri_normals, P.off_boxes, P.off_mats, P.tri_quads};
 }
 
+// The AOV planes of compact pixel p (p3d_render_aov: LaunchParams::aov_*), written where hit_id is, from the primary ray and
+// its closest hit.  Only the AOV = true builds of the kernels call it (p3d_kernel_variant.h: has_aov): a frame without planes
+// runs the builds without, which hold none of this.  Each plane is one wave-uniform test of its pointer.  The normal is
+// computed for lanes with a hit only, by the helper a ray stream's level 1 uses (wf_rays_kernel), so the two entries agree in
+// every bit; the albedo is the diffuse rgb of the hit's material record as the scene description gave it.  Per lane one
+// 4-byte and two 12-byte stores: the 16 lanes of a tile row write 64 / 192 consecutive bytes per plane.  No atomics, no LDS.
+template <class SV>
+__device__ __forceinline__ void write_aov(const LaunchParams& P, const SV& sv, size_t p, bool valid, const Ray& ray, const Hit& h) {
+    const bool hit = valid && h.ref != 0xFFFFFFFFu;
+    if (valid && P.aov_depth) P.aov_depth[p] = hit ? h.t : __builtin_inff();
+    if (P.aov_normal) {                                      // getNormal(hit point).normalize(), RT/main.cpp:587-589
+        V3 n = mk(0.0f, 0.0f, 0.0f);
+        if (hit) n = prim_normal(P, sv, h.ref, ray, add(ray.o, mul(ray.d, h.t)));
+        if (valid) { float* pn = P.aov_normal + 3 * p; pn[0] = n.x; pn[1] = n.y; pn[2] = n.z; }
+    }
+    if (P.aov_albedo) {                                      // Material::GetDiffColor(), RT/scene.h:23-55: not multiplied by Kd
+        V3 a = mk(0.0f, 0.0f, 0.0f);
+        if (hit) a = load_material(sv, h.mat).diff;
+        if (valid) { float* pa = P.aov_albedo + 3 * p; pa[0] = a.x; pa[1] = a.y; pa[2] = a.z; }
+    }
+}
+
 template <bool COUNT>
 __device__ __forceinline__ void flush_counters(const LaunchParams& P, const Ctr& ctr, uint32_t pixels) {
     if (COUNT) {
@@ -437,7 +459,7 @@ __device__ __forceinline__ void stamp_wave(const LaunchParams& P, uint32_t wave_
 // (Measured and dropped in round 3, profiles/r03_exp03_sharing_wg_levers.txt: 8- and 16-wave workgroups -- level 1 of
 //  config 2 46 -> 51 -> 54 us: the waves of this launch start at ~830 per microsecond whatever the workgroup shape.)
 //
-template <bool COUNT, bool LDS, int WALK, int OCC, bool STOCH = false, bool SCHLICK = false, bool BATCH = false>
+template <bool COUNT, bool LDS, int WALK, int OCC, bool STOCH = false, bool SCHLICK = false, bool BATCH = false, bool AOV = false>
 __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void wf_primary_kernel(const LaunchParams P) {
     const uint32_t par = P.wf_ctrl[0] & 1u;                     // this pass's counter set (LaunchParams::wf_alt)
     if (blockIdx.x == 0 && blockIdx.y == 0) {
@@ -462,6 +484,7 @@ __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void wf_primary_kernel
     const Hit h = find_closest<COUNT, WALK>(P, sv, ray, valid, tc, ctr);
     stamp(P, tile, 2);
     if (valid && P.hit_id && P.wf_sample == 0) P.hit_id[p] = hit_id_of(h);
+    if (AOV && P.wf_sample == 0) write_aov(P, sv, p, valid, ray, h);             // wave-uniform
     // the random stream of a pixel sample is keyed by the pixel's place in the FULL frame, so a frame
     // sharded over several GPUs draws the same numbers as on one (frame f of a batch: seed + f)
     const uint32_t rng = STOCH ? rng_mix(rng_mix(BATCH ? P.seed + (uint32_t)f : P.seed, (uint32_t)(y * P.res_x + x)), (uint32_t)P.wf_sample) : 0u;
@@ -474,7 +497,7 @@ __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void wf_primary_kernel
 }
 
 // wf_primary_kernel with TILES (2 or 3) tiles per workgroup, for scenes served from LDS on the 2-D launch, built where
-// has_primary_tiles() says so: per-lane walk, no counters, no features, one frame, so the steps below are those of
+// has_primary_tiles() says so: per-lane walk, no counters, no features, one frame, no AOV planes, so the steps below are those of
 // wf_primary_kernel<false, true, WALK, OCC> and nothing else.  (wf_primary_kernel keeps its own statements: routed through
 // primary_tile_lds() its ~120 builds came out of the compiler with other scalar-register spills, 18 more in the counting
 // grid-walk builds, and the registered profiles and the register account, tools/kdiff.py, are those builds'.  For the same
@@ -827,7 +850,7 @@ __device__ __forceinline__ void tile_emit(const LaunchParams& P, const TileCtx& 
     }
 }
 
-template <bool COUNT, bool LDS, int WALK, int OCC, bool STOCH = false, bool SCHLICK = false, bool BATCH = false>
+template <bool COUNT, bool LDS, int WALK, int OCC, bool STOCH = false, bool SCHLICK = false, bool BATCH = false, bool AOV = false>
 __global__ __launch_bounds__(256) P3D_OCC(OCC) void wf_tile_kernel(const LaunchParams P) {
     const typename View<LDS>::type sv = View<LDS>::make_shading(P);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -906,6 +929,7 @@ __global__ __launch_bounds__(256) P3D_OCC(OCC) void wf_tile_kernel(const LaunchP
                     }
                     const Hit h = find_closest<COUNT, WALK>(P, sv, ray, valid, tc, ctr);
                     if (l == 1 && smp == 0 && inside && P.hit_id) P.hit_id[p] = hit_id_of(h);
+                    if (AOV && l == 1 && smp == 0) write_aov(P, sv, p, inside, ray, h);        // wave-uniform
                     const NodeOut o = shade_hit<COUNT, WALK, typename View<LDS>::type, STOCH, SCHLICK>(P, sv, ray, h, valid, l, ior_1, tc,
                                                                                               ctr, rng, smp);
                     tile_emit<BATCH>(P, X, l, valid, link, ior_1, o);
@@ -1018,16 +1042,21 @@ __device__ __forceinline__ bool pop_frames(const SV& sv, FR fr, int& fsp, V3& re
 }
 
 // One primary ray's whole tree: rayTracing(ray, 1, 1.0) of RT/main.cpp:530-721, iterative.
-template <bool COUNT, bool GRID, class SV, class FR, bool SCHLICK = false>
+// AOV builds: aov_p() is the pixel's place in the AOV planes, written from the primary hit of the tree that is asked to
+// (aov: sample 0's)
+template <bool COUNT, bool GRID, class SV, class FR, bool SCHLICK = false, bool AOV = false, class PX>
 __device__ __forceinline__ V3 trace_tree(const LaunchParams& P, const SV& sv, Ray ray, const TravCtx& tc, FR fr,
-                                         int32_t& primary_hit, Ctr& ctr) {
+                                         int32_t& primary_hit, Ctr& ctr, bool aov, PX aov_p) {
     int fsp = 0;              // frames on the stack == depth - 1
     float ior_1 = 1.0f;
     bool first = true;
     V3 ret = mk(0.0f, 0.0f, 0.0f);
     for (;;) {
         Hit h = find_closest<COUNT, GRID ? WALK_GRID : WALK_LANE>(P, sv, ray, true, tc, ctr);
-        if (first) { primary_hit = hit_id_of(h); first = false; }
+        if (first) {
+            primary_hit = hit_id_of(h); first = false;
+            if (AOV && aov) write_aov(P, sv, aov_p(), true, ray, h);
+        }
         NodeOut o = shade_hit<COUNT, GRID ? WALK_GRID : WALK_LANE, SV, false, SCHLICK>(P, sv, ray, h, true, fsp + 1, ior_1, tc, ctr);
         if (!o.terminal) {
             push_frame(sv, fr, fsp, o, ray, ior_1);
@@ -1041,9 +1070,9 @@ __device__ __forceinline__ V3 trace_tree(const LaunchParams& P, const SV& sv, Ra
 // The same trees with the wave's lanes in ONE loop (work-sharing walk, WALK_SHARED): every iteration all 64 lanes reach
 // find_closest() / shade_hit() together -- a lane whose pixel is finished (or outside the image) comes along as a helper
 // of the others' walks -- and a lane that finishes a sample's tree starts its next sample at once.
-template <bool COUNT, class SV, class FR, bool SCHLICK = false, bool BATCH = false>
+template <bool COUNT, class SV, class FR, bool SCHLICK = false, bool BATCH = false, bool AOV = false, class PX>
 __device__ __forceinline__ void trace_trees_shared(const LaunchParams& P, const SV& sv, int x, int y, int f, bool valid, const TravCtx& tc, FR fr,
-                                                   V3& color, int32_t& hid, Ctr& ctr) {
+                                                   V3& color, int32_t& hid, Ctr& ctr, PX aov_p) {
     const int ns = P.spp > 0 ? P.spp * P.spp : 1;
     const V3 zero = mk(0.0f, 0.0f, 0.0f);
     int smp = 0, fsp = 0;
@@ -1054,6 +1083,7 @@ __device__ __forceinline__ void trace_trees_shared(const LaunchParams& P, const 
     if (alive) ray = camera_ray<BATCH>(P, x, y, 0, f);
     while (__ballot(alive) != 0) {
         const Hit h = find_closest<COUNT, WALK_SHARED>(P, sv, ray, alive, tc, ctr);
+        if (AOV && __ballot(alive && first && smp == 0) != 0) write_aov(P, sv, aov_p(), alive && first && smp == 0, ray, h);   // wave-uniform
         if (alive && first) { if (smp == 0) hid = hit_id_of(h); first = false; }
         const NodeOut o = shade_hit<COUNT, WALK_SHARED, SV, false, SCHLICK>(P, sv, ray, h, alive, fsp + 1, ior_1, tc, ctr);
         if (!alive) continue;
@@ -1073,7 +1103,7 @@ __device__ __forceinline__ void trace_trees_shared(const LaunchParams& P, const 
 }
 
 // PRIV = dwords of private memory for the frames (12 per level below the first), 0 = frames in LDS
-template <bool COUNT, bool LDS, int OCC, bool GRID = false, int PRIV = 0, bool SHARED = false, bool SCHLICK = false, bool BATCH = false>
+template <bool COUNT, bool LDS, int OCC, bool GRID = false, int PRIV = 0, bool SHARED = false, bool SCHLICK = false, bool BATCH = false, bool AOV = false>
 __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void whitted_tree_kernel(const LaunchParams P) {
     const typename View<LDS>::type sv = View<LDS>::make_shading(P);
     const int lane = threadIdx.x & 63;
@@ -1092,15 +1122,17 @@ __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void whitted_tree_kern
     Ctr ctr = {0, 0, 0, 0, 0, 0, 0};
     V3 color = mk(0.0f, 0.0f, 0.0f);
     int32_t hid = -1;
+    // the pixel's place in the AOV planes (the final write's p), formed only where an AOV build writes them
+    const auto aov_p = [&]() { return (size_t)out_row<BATCH>(P, f, row) * P.res_x + x; };
     if constexpr (SHARED) {
-        trace_trees_shared<COUNT, typename View<LDS>::type, decltype(fr), SCHLICK, BATCH>(P, sv, x, y, f, in_image, st, fr, color, hid, ctr);
+        trace_trees_shared<COUNT, typename View<LDS>::type, decltype(fr), SCHLICK, BATCH, AOV>(P, sv, x, y, f, in_image, st, fr, color, hid, ctr, aov_p);
     } else if (P.spp == 0) {                                    // RT/main.cpp:756-775
-        color = clampc(trace_tree<COUNT, GRID, typename View<LDS>::type, decltype(fr), SCHLICK>(P, sv, camera_ray<BATCH>(P, x, y, 0, f), st, fr, hid, ctr));
+        color = clampc(trace_tree<COUNT, GRID, typename View<LDS>::type, decltype(fr), SCHLICK, AOV>(P, sv, camera_ray<BATCH>(P, x, y, 0, f), st, fr, hid, ctr, true, aov_p));
     } else {                                             // RT/main.cpp:776-801
         const int ns = P.spp * P.spp;
         for (int s = 0; s < ns; s++) {
             int32_t h2 = -1;
-            V3 c = clampc(trace_tree<COUNT, GRID, typename View<LDS>::type, decltype(fr), SCHLICK>(P, sv, camera_ray<BATCH>(P, x, y, s, f), st, fr, h2, ctr));
+            V3 c = clampc(trace_tree<COUNT, GRID, typename View<LDS>::type, decltype(fr), SCHLICK, AOV>(P, sv, camera_ray<BATCH>(P, x, y, s, f), st, fr, h2, ctr, s == 0, aov_p));
             color = add(color, c);
             if (s == 0) hid = h2;
         }
@@ -1168,17 +1200,17 @@ size_t wavefront_lds_bytes(const LaunchParams& P, bool lds) {
 using KernelFn = void (*)(const LaunchParams);
 constexpr int kOccs[3] = {1, 5, 6};               // register budgets: the compiler's default, 5 and 6 waves per SIMD
 constexpr int kPrivs[3] = {0, 36, 84};            // tree kernel: dwords of private frames (0: frames in LDS)
-constexpr int kLevelVariants = 2 * 2 * 4 * 3 * 2 * 2 * 2, kTreeVariants = kLevelVariants * 3;
+constexpr int kLevelVariants = 2 * 2 * 4 * 3 * 2 * 2 * 2 * 2, kTreeVariants = kLevelVariants * 3;
 
 // position of a canonical variant (occ is 1, 5 or 6) in a family's table, and the variant at a position.  A walk that is
 // none of the four has no position, so the launch fails with hipErrorInvalidDeviceFunction; no caller passes one.
 constexpr int variant_index(const KernelVariant& v) {
     if (v.walk < WALK_LANE || v.walk > WALK_SHARED) return -1;
-    return (((((v.count * 2 + v.lds) * 4 + v.walk) * 3 + (v.occ == 5 ? 1 : v.occ == 6 ? 2 : 0)) * 2 + v.stoch) * 2 + v.schlick) * 2 + v.batch;
+    return ((((((v.count * 2 + v.lds) * 4 + v.walk) * 3 + (v.occ == 5 ? 1 : v.occ == 6 ? 2 : 0)) * 2 + v.stoch) * 2 + v.schlick) * 2 + v.batch) * 2 + v.aov;
 }
 constexpr KernelVariant variant_at(int i) {
     KernelVariant v;
-    v.batch = i % 2; i /= 2; v.schlick = i % 2; i /= 2; v.stoch = i % 2; i /= 2;
+    v.aov = i % 2; i /= 2; v.batch = i % 2; i /= 2; v.schlick = i % 2; i /= 2; v.stoch = i % 2; i /= 2;
     v.occ = kOccs[i % 3]; i /= 3; v.walk = i % 4; i /= 4; v.lds = i % 2; v.count = i / 2;
     return v;
 }
@@ -1192,20 +1224,21 @@ constexpr int canonical_priv(const KernelVariant& v, int priv) {
 constexpr KernelVariant canonical_tree(KernelVariant v, int priv) {
     v.stoch = false;
     if (v.walk == WALK_PACKET || (v.walk == WALK_SHARED && v.lds)) v.walk = WALK_LANE;
-    if ((v.occ != 5 && v.occ != 6) || v.walk == WALK_GRID || v.count || v.schlick || v.batch || (v.walk == WALK_SHARED && priv == 0)) v.occ = 1;
+    if ((v.occ != 5 && v.occ != 6) || v.walk == WALK_GRID || v.count || v.schlick || v.batch || v.aov || (v.walk == WALK_SHARED && priv == 0)) v.occ = 1;
     return v;
 }
 constexpr bool built_tree(const KernelVariant& v, int priv) {
     if (v.stoch || v.walk == WALK_PACKET || (v.walk == WALK_SHARED && v.lds)) return false;
     if (priv != 0 && (v.lds || v.walk == WALK_GRID)) return false;
     if (v.occ == 1) return true;
-    return v.walk != WALK_GRID && !v.count && !v.schlick && !v.batch && !(v.walk == WALK_SHARED && priv == 0);
+    return v.walk != WALK_GRID && !v.count && !v.schlick && !v.batch && !v.aov && !(v.walk == WALK_SHARED && priv == 0);
 }
 
-// Every request reaches a build, and nothing is built that no request reaches.
-constexpr bool variants_are_consistent() {
+// Every request reaches a build, and nothing is built that no request reaches: checked for the variants at positions
+// [first, last) (in four parts below: one constant evaluation over all of them passes the compiler's step limit).
+constexpr bool variants_are_consistent(int first, int last) {
     constexpr int raw_occs[] = {0, 1, 5, 6, 8}, raw_privs[] = {0, 36, 84, 12};
-    for (int i = 0; i < kLevelVariants; i++) {
+    for (int i = first; i < last; i++) {
         for (int occ : raw_occs) {
             KernelVariant v = variant_at(i);
             v.occ = occ;
@@ -1230,7 +1263,11 @@ constexpr bool variants_are_consistent() {
     }
     return true;
 }
-static_assert(variants_are_consistent(), "a kernel request maps to a variant that is not built, or a built variant is unreachable");
+#define P3D_VARIANTS_CONSISTENT(q)                                                                      \
+    static_assert(variants_are_consistent((q) * kLevelVariants / 4, ((q) + 1) * kLevelVariants / 4), \
+                  "a kernel request maps to a variant that is not built, or a built variant is unreachable")
+P3D_VARIANTS_CONSISTENT(0); P3D_VARIANTS_CONSISTENT(1); P3D_VARIANTS_CONSISTENT(2); P3D_VARIANTS_CONSISTENT(3);
+#undef P3D_VARIANTS_CONSISTENT
 
 using RaysKernelFn = void (*)(const LaunchParams, const RayStreamIO);
 template <Level KERNEL> struct LevelKernels {       // position: variant_index * per_variant + (TILES - 1)
@@ -1243,10 +1280,10 @@ template <Level KERNEL> struct LevelKernels {       // position: variant_index *
     template <int I> static constexpr Fn fn() {
         constexpr KernelVariant v = at(I);
         if constexpr (KERNEL == Level::Primary && v.tiles > 1) return wf_primary_kernel_tiles<v.walk, v.occ, v.tiles>;
-        else if constexpr (KERNEL == Level::Primary) return wf_primary_kernel<v.count, v.lds, v.walk, v.occ, v.stoch, v.schlick, v.batch>;
+        else if constexpr (KERNEL == Level::Primary) return wf_primary_kernel<v.count, v.lds, v.walk, v.occ, v.stoch, v.schlick, v.batch, v.aov>;
         else if constexpr (KERNEL == Level::Secondary) return wf_secondary_kernel<v.count, v.lds, v.walk, v.occ, v.stoch, v.schlick>;
         else if constexpr (KERNEL == Level::Rays) return wf_rays_kernel<v.lds, v.walk, v.occ>;
-        else return wf_tile_kernel<v.count, v.lds, v.walk, v.occ, v.stoch, v.schlick, v.batch>;
+        else return wf_tile_kernel<v.count, v.lds, v.walk, v.occ, v.stoch, v.schlick, v.batch, v.aov>;
     }
 };
 struct TreeKernels {                                // position: variant_index * 3 + position of PRIV in kPrivs
@@ -1255,7 +1292,7 @@ struct TreeKernels {                                // position: variant_index *
     static constexpr bool built(int i) { return built_tree(variant_at(i / 3), kPrivs[i % 3]); }
     template <int I> static constexpr KernelFn fn() {
         constexpr KernelVariant v = variant_at(I / 3);
-        return whitted_tree_kernel<v.count, v.lds, v.occ, v.walk == WALK_GRID, kPrivs[I % 3], v.walk == WALK_SHARED, v.schlick, v.batch>;
+        return whitted_tree_kernel<v.count, v.lds, v.occ, v.walk == WALK_GRID, kPrivs[I % 3], v.walk == WALK_SHARED, v.schlick, v.batch, v.aov>;
     }
 };
 // the walk over a family's positions: a kernel is instantiated only where built() says so

@@ -1,4 +1,4 @@
-// p3d_render.cpp -- p3d_render, p3d_render_frames, p3d_trace_rays and p3d_tune_schedule of include/p3d_hip.h: a frame (or a
+// p3d_render.cpp -- p3d_render, p3d_render_frames, p3d_render_aov, p3d_trace_rays and p3d_tune_schedule of include/p3d_hip.h: a frame (or a
 // batch of frames, or a stream of the caller's rays) as a sequence of steps -- validate the request, fill the launch
 // parameters, size the workspaces, choose the schedule, enqueue it.  The kernels are those of p3d_kernels.hip (p3d_launch.h).
 #include <chrono>
@@ -188,7 +188,7 @@ int FramePlan::query_tile() {
     if (!tile_ok) return P3D_OK;
     const KernelVariant served = level_variant(with_budget(kv, tile_occ), Level::Tile);
     const size_t olds = tile_kernel_lds_bytes(PT, lds_scene);
-    auto* slot = &s->tile_occ[shared_walk ? 1 : 0];
+    auto* slot = &s->tile_occ[kv.aov ? 1 : 0][shared_walk ? 1 : 0];
     if (!(slot->v == served) || slot->lds != olds) {
         HIP_TRY(tile_kernel_resident_blocks(PT, served, &slot->blocks));
         slot->v = served; slot->lds = olds;
@@ -424,8 +424,11 @@ int choose_schedule(p3d_scene* s, const FrameConfig& cfg, const p3d_render_param
         }
         if (s->tune_force >= 0) {
             if (s->tune_force < NC) cand = s->tune_force;
-        } else if (cap) {
-            // events cannot be read while the stream is being captured: use what is known, measure nothing
+        } else if (cap || plan.kv.aov) {
+            // events cannot be read while the stream is being captured: use what is known, measure nothing.
+            // A frame with AOV planes (p3d_render_aov) does the same: it runs the AOV builds of the kernels, at the default
+            // register budget, and its time would count for a candidate the frames without planes run other builds of -- so
+            // it neither times a candidate nor advances or re-keys the measurement; the frames without planes do.
             if (pk.measured(key, NC)) cand = pk.best;
         } else {
             pk.begin(key);
@@ -511,6 +514,7 @@ int run_tile(p3d_scene* s, const FrameConfig& cfg, FramePlan& plan, bool profile
         HIP_TRY(launch_clear_words((uint32_t*)s->tile_ctrl.p, 64, s->stream));
     }
     PT.samples = P.samples; PT.rgb8 = P.rgb8; PT.rgb32f = P.rgb32f; PT.hit_id = P.hit_id; PT.frame_cams = P.frame_cams;
+    PT.aov_depth = P.aov_depth; PT.aov_normal = P.aov_normal; PT.aov_albedo = P.aov_albedo;
     PT.wf_nsamples = P.wf_nsamples;
     PT.tw_base = (uint8_t*)s->tile_ws.p; PT.tw_slot_bytes = plan.slot_bytes; PT.tw_ctrl = (uint32_t*)s->tile_ctrl.p;
     PT.tw_rays_off = 0; PT.tw_nodes_off = (uint32_t)plan.slot_rays; PT.tw_rng_off = (uint32_t)(plan.slot_rays + plan.slot_nodes);
@@ -526,7 +530,7 @@ int run_tile(p3d_scene* s, const FrameConfig& cfg, FramePlan& plan, bool profile
     }
     if (s->verbose)
         fprintf(stderr, "p3d: tile schedule: %d workgroups (occupancy query: %d on the device), %zu B LDS each, %zu B workspace slot, %d tiles\n",
-                plan.tile_blocks, s->tile_occ[plan.shared_walk ? 1 : 0].blocks, tile_kernel_lds_bytes(PT, plan.lds_scene), plan.slot_bytes, PT.n_tiles);
+                plan.tile_blocks, s->tile_occ[plan.kv.aov ? 1 : 0][plan.shared_walk ? 1 : 0].blocks, tile_kernel_lds_bytes(PT, plan.lds_scene), plan.slot_bytes, PT.n_tiles);
     HIP_TRY(launch_wf_tile(PT, with_budget(plan.kv, plan.tile_occ), (unsigned)plan.tile_blocks, s->stream));
     if (profile) HIP_TRY(hipEventRecord(s->ev_prof[3], s->stream));
     return tile_order_end(s, lpt);
@@ -722,8 +726,10 @@ int write_frame_cams(p3d_scene* s, const p3d_camera* cams, int n_frames, LaunchP
 }
 
 // the sample array and the output planes (the caller's, or the handle's for host outputs); the counters start at zero
-int bind_samples_and_outputs(p3d_scene* s, const FrameConfig& cfg, const p3d_render_params* prm, const p3d_outputs* out, size_t npx,
-                             LaunchParams& P) {
+// (aov: the planes of p3d_render_aov, in the memory `out` names, or nullptr.  Whether a frame has them is in no FrameConfig:
+//  no cache key, schedule choice or tile order knows; it selects the kernels' AOV builds, KernelVariant::aov, and nothing else)
+int bind_samples_and_outputs(p3d_scene* s, const FrameConfig& cfg, const p3d_render_params* prm, const p3d_outputs* out,
+                             const p3d_aov_outputs* aov, size_t npx, LaunchParams& P) {
     if (cfg.spp > 0) {
         size_t bytes = (size_t)cfg.n_frames * cfg.res_y * cfg.res_x * cfg.spp * cfg.spp * 4 * sizeof(float);
         if (prm->flags & P3D_FLAG_DEVICE_SAMPLES) {
@@ -741,6 +747,13 @@ int bind_samples_and_outputs(p3d_scene* s, const FrameConfig& cfg, const p3d_ren
         if (out->rgb32f) { HIP_TRY(s->fb_rgb32f.ensure(npx * 12)); P.rgb32f = (float*)s->fb_rgb32f.p; }
         if (out->hit_id) { HIP_TRY(s->fb_hit.ensure(npx * 4)); P.hit_id = (int32_t*)s->fb_hit.p; }
     }
+    if (aov && out->memory == 1) {
+        P.aov_depth = aov->depth; P.aov_normal = aov->normal; P.aov_albedo = aov->albedo;
+    } else if (aov) {
+        if (aov->depth) { HIP_TRY(s->fb_depth.ensure(npx * 4)); P.aov_depth = (float*)s->fb_depth.p; }
+        if (aov->normal) { HIP_TRY(s->fb_normal.ensure(npx * 12)); P.aov_normal = (float*)s->fb_normal.p; }
+        if (aov->albedo) { HIP_TRY(s->fb_albedo.ensure(npx * 12)); P.aov_albedo = (float*)s->fb_albedo.p; }
+    }
     if (cfg.flags & P3D_FLAG_COUNTERS) {
         HIP_TRY(launch_clear_words((uint32_t*)s->d_counters.p, (uint32_t)(sizeof(DeviceCounters) / 4), s->stream));
         s->counters_valid = true;
@@ -752,7 +765,9 @@ int bind_samples_and_outputs(p3d_scene* s, const FrameConfig& cfg, const p3d_ren
 // n frames of one configuration in the same launches (n == 1: p3d_render).  The batch is ONE tall image: frame f's
 // local_rows compact rows follow frame f - 1's, so tiles, shards, bands, the tile counter and the tile order cover it
 // unchanged; the kernels map a stacked row to (frame, row in frame) -- see LaunchParams::n_frames.
-int render_batch(p3d_scene* s, const p3d_camera* cams, int32_t n_frames, const p3d_render_params* prm, const p3d_outputs* out) {
+// aov: the depth / normal / albedo planes of p3d_render_aov, written by the same launches (nullptr: none).
+int render_batch(p3d_scene* s, const p3d_camera* cams, int32_t n_frames, const p3d_render_params* prm, const p3d_outputs* out,
+                 const p3d_aov_outputs* aov = nullptr) {
     FrameConfig cfg;
     int rc = validate_request(s, cams, n_frames, prm, out, cfg);
     if (rc) return rc;
@@ -761,6 +776,7 @@ int render_batch(p3d_scene* s, const p3d_camera* cams, int32_t n_frames, const p
     FramePlan plan;
     plan.s = s;
     if ((rc = fill_scene_params(s, cfg, prm, plan)) != P3D_OK) return rc;
+    plan.kv.aov = aov && (aov->depth || aov->normal || aov->albedo);       // the builds that write the planes
     if ((rc = fill_frame_geometry(s, cfg, cams[0], plan.P)) != P3D_OK) return rc;
     if ((rc = plan_workspaces(s, cfg, plan)) != P3D_OK) return rc;
     ScheduleChoice ch;
@@ -784,7 +800,7 @@ int render_batch(p3d_scene* s, const p3d_camera* cams, int32_t n_frames, const p
 
     if (cfg.batch() && (rc = write_frame_cams(s, cams, n_frames, P)) != P3D_OK) return rc;
     const size_t npx = (size_t)P.local_rows * cfg.res_x;
-    if ((rc = bind_samples_and_outputs(s, cfg, prm, out, npx, P)) != P3D_OK) return rc;
+    if ((rc = bind_samples_and_outputs(s, cfg, prm, out, aov, npx, P)) != P3D_OK) return rc;
 
     const bool profile = (prm->flags & P3D_FLAG_PROFILE) != 0;
     const TimingEvent* ev_pick = cfg.batch() ? s->ev_pick_batch : s->ev_pick;
@@ -806,6 +822,9 @@ int render_batch(p3d_scene* s, const p3d_camera* cams, int32_t n_frames, const p
         if (out->rgb8) HIP_TRY(hipMemcpyAsync(out->rgb8, P.rgb8, cpx * 3, hipMemcpyDeviceToHost, s->stream));
         if (out->rgb32f) HIP_TRY(hipMemcpyAsync(out->rgb32f, P.rgb32f, cpx * 12, hipMemcpyDeviceToHost, s->stream));
         if (out->hit_id) HIP_TRY(hipMemcpyAsync(out->hit_id, P.hit_id, cpx * 4, hipMemcpyDeviceToHost, s->stream));
+        if (P.aov_depth) HIP_TRY(hipMemcpyAsync(aov->depth, P.aov_depth, cpx * 4, hipMemcpyDeviceToHost, s->stream));
+        if (P.aov_normal) HIP_TRY(hipMemcpyAsync(aov->normal, P.aov_normal, cpx * 12, hipMemcpyDeviceToHost, s->stream));
+        if (P.aov_albedo) HIP_TRY(hipMemcpyAsync(aov->albedo, P.aov_albedo, cpx * 12, hipMemcpyDeviceToHost, s->stream));
         HIP_TRY(hipStreamSynchronize(s->stream));
     }
     return P3D_OK;
@@ -879,6 +898,12 @@ int p3d_render(p3d_scene* s, const p3d_camera* cam, const p3d_render_params* prm
 
 int p3d_render_frames(p3d_scene* s, const p3d_camera* cams, int32_t n, const p3d_render_params* prm, const p3d_outputs* out) {
     return render_batch(s, cams, n, prm, out);
+}
+
+int p3d_render_aov(p3d_scene* s, const p3d_camera* cams, int32_t n, const p3d_render_params* prm, const p3d_outputs* out,
+                   const p3d_aov_outputs* aov) {
+    // the rules of p3d_render_frames: a NULL out is refused there too -- the planes are in the memory it names
+    return render_batch(s, cams, n, prm, out, aov);
 }
 
 int p3d_tune_schedule(p3d_scene** scenes, int32_t n, const p3d_camera* cam, const p3d_render_params* prm, const p3d_outputs* outs,

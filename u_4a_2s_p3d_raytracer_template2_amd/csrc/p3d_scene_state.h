@@ -166,6 +166,7 @@ struct p3d_scene {
     uint32_t n_lights = 0, n_materials = 0;
     p3d_scene_stats stats{};
     p3d::RawBuf fb_rgb8, fb_rgb32f, fb_hit, samples;
+    p3d::RawBuf fb_depth, fb_normal, fb_albedo;   // host-memory AOV planes of p3d_render_aov are staged here, like hit_id in fb_hit
     p3d::RawBuf ray_tab; int tab_res_x = 0, tab_res_y = 0;   // cached per-column / per-row ray factors
     // Wavefront workspaces: ray queues (levels 2..D), parked nodes (levels 1..D-1), counters.
     // A frame of several sample passes (spp > 0) runs up to kLanes passes at a
@@ -197,8 +198,9 @@ struct p3d_scene {
     } tile_lpt, wave_lpt;            // 16x16 tiles of the tile schedule / 16x4 wave tiles of the tree and wavefront level-1 launches
     TileOrder tile_lpt_batch, wave_lpt_batch;   // ... of frame batches (p3d_render_frames), keyed on n and the tile count too
     bool tile_lpt_enabled = true;
-    // cached occupancy queries (private / shared walk), keyed by the build they were made for (walk -1: none yet)
-    struct { p3d::KernelVariant v = {false, false, -1}; size_t lds = 0; int blocks = 0; } tile_occ[2];
+    // cached occupancy queries ([without / with AOV planes][private / shared walk]), keyed by the build they were made for
+    // (walk -1: none yet): alternating p3d_render and p3d_render_aov asks for neither again
+    struct { p3d::KernelVariant v = {false, false, -1}; size_t lds = 0; int blocks = 0; } tile_occ[2][2];
     struct { p3d::KernelVariant v = {false, false, -1}; uint32_t stack = 0; unsigned waves = 0; } wf_occ;   // ... of the deeper-level kernel
     // upper limit of the workspace one frame may allocate (wavefront schedule: worst-case level queues of a band
     // of tile rows; tile schedule: one slot per resident workgroup).  64 GiB holds BASELINE config 4's wavefront
