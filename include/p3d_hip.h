@@ -526,6 +526,17 @@ int p3d_debug_check_rcp(int device, uint32_t first_bits, uint64_t count, uint64_
  * square root's output. */
 int p3d_debug_check_rcp_len(int device, uint32_t first_bits, uint64_t count, uint64_t* n_bad, uint32_t* first_bad);
 
+/* The tree of the device builder (p3d_build_opts::builder == 1; csrc/bvh_device.hip), built by the function p3d_scene_create
+ * calls, over n >= 4 build primitives given as host arrays: padded bounds lo3[n*3], hi3[n*3] and the reference ref[n] each
+ * carries into the leaf list. Returns, with L = (n + 1) / 2 leaves of two primitives (the last of an odd n holds one):
+ * nodes16[(L-1)*16] = the L - 1 node pairs as the kernels read them (12 floats: child 0's lo xyz, hi xyz, child 1's lo xyz,
+ * hi xyz; child0, child1 -- an inner node's index, or ~(first << 3 | count - 1) for the leaf that starts at leaf_refs[first];
+ * two zero dwords), leaf_refs[n], stats4 = {n_nodes, n_leaves, n_leaf_refs, max_depth}, and sah_cost. max_depth counts the
+ * leaf level: the walks' stacks are sized from it. n < 4 or a NULL pointer: P3D_ERR_ARG (scenes of fewer than 64
+ * primitives are built on the host by p3d_scene_create; that threshold is not this entry's). */
+int p3d_debug_lbvh_build(int device, uint32_t n, const float* lo3, const float* hi3, const uint32_t* ref, uint32_t* nodes16,
+                         uint32_t* leaf_refs, uint32_t* stats4, float* sah_cost);
+
 #ifdef __cplusplus
 }
 #endif

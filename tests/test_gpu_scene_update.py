@@ -430,3 +430,35 @@ def test_refusals(tmp_path):
     ds.update(data, lights6=m.lights["B"])
     assert_same(ds.render(m.cam), m.oracle("B"), "the handle still updates")
     ds.close(); culled.close()
+
+
+# ---- a device-built tree, and a deep one
+
+def test_refit_of_a_device_built_chain(tmp_path):
+    """The geometric-series scene (tests/lbvh_scenes.py): built on the device (builder=1) its tree is a chain some 38 levels
+    deep.  Every second sphere moves out of its own box; the refitted handle renders what a handle freshly built on the
+    device from the moved scene renders (a different tree), and what the oracle renders.  Both trees are first checked
+    against the reference of test_gpu_lbvh.py, max_depth exactly: the launches below size their stacks from it."""
+    import lbvh_scenes as LS
+    import test_gpu_lbvh as LB
+    assert LB._PROBE["failed"] == 0, "a probe test of this run failed: nothing is rendered through such a tree"
+    a, b = LS.write_lbvh_scene(str(tmp_path / "chain_a.p3f"), "geometric"), str(tmp_path / "chain_b.p3f")
+    M.rewrite_p3f(a, b, lambda kind, k, v: M.shift_out_of_own_box(kind, v) if kind == "s" and k % 2 == 1 else None)
+    m = Moving(a, b)
+    assert len(m.moved) == LS.N_SPHERES // 2
+    m.preconditions(m.oracle("A", depth=3), m.oracle("B", depth=3))
+    depth = {k: LB.check_case(*api.host_build_prims(m.host[k].desc())) for k in "AB"}
+    assert depth["A"] >= 30
+    ds, fresh = m.fresh("A", builder=1), m.fresh("B", builder=1)
+    for h, k in ((ds, "A"), (fresh, "B")):                           # the device builder's trees
+        assert h.stats()["max_depth"] == depth[k] and h.stats()["n_nodes"] == LS.N_SPHERES // 2 - 1
+    assert_same(ds.render(m.cam, max_depth=3, accel=2, counters=True), m.oracle("A", depth=3), "before the update", rays=True)
+    ds.update(m.data["B"])
+    ref = m.oracle("B", depth=3)
+    for sched in SCHEDULES:
+        for no_lds in (False, True):
+            what = "%s no_lds %d" % (list(sched)[0], no_lds)
+            got = ds.render(m.cam, max_depth=3, accel=2, counters=True, no_lds=no_lds, **sched)
+            assert_same(got, fresh.render(m.cam, max_depth=3, accel=2, counters=True, no_lds=no_lds, **sched), what + " vs fresh", rays=True)
+            assert_same(got, ref, what + " vs oracle", rays=True)
+    ds.close(); fresh.close()

@@ -266,6 +266,50 @@ def test_bvh_builder_invariants(name, leaf_max):
     assert max_depth <= b["max_depth"] + 1 <= 64
 
 
+@pytest.mark.parametrize("name", ["mount_low", "balls_box", "mount_high"])
+def test_build_prims_dump_is_the_padded_scene(name):
+    """api.host_build_prims: what both BVH builders are given -- one entry per bounded primitive in scene order, its
+    reference kind << 30 | index within the kind, and its bounds padded by max(1e-3, 1e-5 * largest |coordinate|) in f32
+    (csrc/scene_flatten.cpp), restated here operation by operation, so equal bit for bit."""
+    hs = P.HostScene(scene_path(name))
+    t, d, *_ = hs.arrays()
+    lo, hi, ref = api.host_build_prims(hs.desc())
+    keep = np.flatnonzero(t != 3)
+    assert len(ref) == len(keep) and lo.shape == hi.shape == (len(keep), 3) and lo.dtype == np.float32
+    f32 = np.float32
+    count = {0: 0, 1: 0, 2: 0}
+    for k, si in enumerate(keep):
+        kind, v = int(t[si]), d[si].astype(f32)
+        assert int(ref[k]) == (kind << 30) | count[kind]
+        count[kind] += 1
+        if kind == 0:
+            r = np.abs(v[3])
+            blo, bhi = v[:3] - r, v[:3] + r
+        elif kind == 1:
+            p = v[:9].reshape(3, 3)
+            blo, bhi = p.min(0), p.max(0)
+        else:
+            blo, bhi = np.minimum(v[:3], v[3:6]), np.maximum(v[:3], v[3:6])
+        pad = max(f32(1e-3), f32(1e-5) * max(np.abs(blo).max(), np.abs(bhi).max()))
+        assert np.array_equal((blo - pad).view(np.uint32), lo[k].view(np.uint32)), (k, si)
+        assert np.array_equal((bhi + pad).view(np.uint32), hi[k].view(np.uint32)), (k, si)
+
+
+def test_device_bvh_probe_rejects_bad_arguments():
+    """p3d_debug_lbvh_build answers P3D_ERR_ARG to fewer than 4 primitives and to NULL pointers before it touches a device."""
+    L = P.lib()
+    lo, hi = np.zeros((4, 3), np.float32), np.ones((4, 3), np.float32)
+    ref, nodes, refs, st, sah = np.arange(4, dtype=np.uint32), np.zeros((1, 16), np.uint32), np.zeros(4, np.uint32), np.zeros(4, np.uint32), C.c_float()
+    ptrs = [lo.ctypes.data, hi.ctypes.data, ref.ctypes.data, nodes.ctypes.data, refs.ctypes.data, st.ctypes.data, C.addressof(sah)]
+    for n in (0, 1, 3):
+        assert L.p3d_debug_lbvh_build(0, n, *ptrs) == -1 and b"4 primitives" in L.p3d_last_error()
+    for k in range(len(ptrs)):
+        assert L.p3d_debug_lbvh_build(0, 4, *[None if j == k else p for j, p in enumerate(ptrs)]) == -1
+        assert b"NULL" in L.p3d_last_error()
+    with pytest.raises(P.P3DError):
+        api.device_bvh(lo[:3], hi[:3], ref[:3])
+
+
 @pytest.mark.parametrize("name", ["mount_low", "balls_box", "mount_high", "dragon"])
 def test_quantised_nodes_contain_the_f32_boxes(name):
     """Scenes read from HBM walk 32-byte node pairs of 16-bit plane codes (plane = base + code * scale).  Every coded

@@ -106,7 +106,7 @@ class SceneStats(C.Structure):
 C_ABI_SYMBOLS = ["p3d_abi_version", "p3d_last_error", "p3d_device_count", "p3d_scene_create",
                  "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_scene_update", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_render_aov", "p3d_trace_rays", "p3d_sync",
                  "p3d_get_counters", "p3d_get_profile", "p3d_last_schedule", "p3d_set_tuning", "p3d_set_primary_tiles", "p3d_last_primary_tiles", "p3d_set_stream", "p3d_timer_begin", "p3d_timer_end", "p3d_deinterleave_frames",
-                 "p3d_deinterleave", "p3d_debug_intersect", "p3d_debug_powf", "p3d_debug_pow", "p3d_debug_schlick_kr", "p3d_debug_check_rcp", "p3d_debug_check_rcp_len", "p3d_tune_schedule", "p3d_debug_set_stamps", "p3d_debug_set_stamp_level",
+                 "p3d_deinterleave", "p3d_debug_intersect", "p3d_debug_powf", "p3d_debug_pow", "p3d_debug_schlick_kr", "p3d_debug_check_rcp", "p3d_debug_check_rcp_len", "p3d_debug_lbvh_build", "p3d_tune_schedule", "p3d_debug_set_stamps", "p3d_debug_set_stamp_level",
                  "p3d_comm_unique_id", "p3d_comm_create", "p3d_comm_create_all", "p3d_comm_destroy", "p3d_comm_info",
                  "p3d_gather", "p3d_gather_all", "p3d_device_alloc", "p3d_device_free", "p3d_upload", "p3d_download"]
 
@@ -186,6 +186,7 @@ def lib():
     L.p3d_debug_schlick_kr.argtypes = [C.c_int, C.c_uint32] + [C.c_void_p] * 4
     L.p3d_debug_check_rcp.argtypes = [C.c_int, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
     L.p3d_debug_check_rcp_len.argtypes = [C.c_int, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
+    L.p3d_debug_lbvh_build.argtypes = [C.c_int, C.c_uint32] + [C.c_void_p] * 7
     L.p3d_tune_schedule.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     # host shim
     L.p3dh_scene_load.restype = C.c_void_p
@@ -208,6 +209,8 @@ def lib():
     L.p3dh_bvh_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     L.p3dh_bvh_dump.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.p3dh_bvh_quantise.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.p3dh_build_prims.restype = C.c_int64
+    L.p3dh_build_prims.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
     L.p3d_pt_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
     L.p3d_pt_destroy.argtypes = [C.c_void_p]
     L.p3d_pt_set_stream.argtypes = [C.c_void_p, C.c_void_p]
@@ -830,6 +833,35 @@ def host_bvh(desc, leaf_max=0):
     lib().p3dh_bvh_free(h)
     return {"nodes": nodes, "refs": refs, "n_leaves": int(info[2]), "max_depth": int(info[3]),
             "n_prims": int(info[4]), "qnodes": qnodes, "qscale": qscale, "qbase": qbase}
+
+
+def host_build_prims(desc):
+    """What either BVH builder is given for a scene (no GPU): (lo [n,3], hi [n,3], ref [n]) -- the padded bounds and leaf
+    references of its bounded primitives, in scene order."""
+    n = lib().p3dh_build_prims(C.byref(desc), None, None, None, 0)
+    if n < 0:
+        raise P3DError("p3dh_build_prims: the scene description is inconsistent")
+    lo, hi, ref = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32), np.zeros(n, np.uint32)
+    lib().p3dh_build_prims(C.byref(desc), lo.ctypes.data, hi.ctypes.data, ref.ctypes.data, n)
+    return lo, hi, ref
+
+
+def device_bvh(lo, hi, ref, device=0):
+    """The device builder's tree (p3d_debug_lbvh_build) over n >= 4 build primitives: dict(nodes [L-1,16] u32 view, refs [n],
+    n_nodes, n_leaves, n_leaf_refs, max_depth, sah_cost) with L = (n + 1) // 2, laid out like host_bvh()'s."""
+    lo = np.ascontiguousarray(lo, np.float32).reshape(-1, 3)
+    hi = np.ascontiguousarray(hi, np.float32).reshape(-1, 3)
+    ref = np.ascontiguousarray(ref, np.uint32).ravel()
+    n = len(ref)
+    assert lo.shape == hi.shape == (n, 3)
+    nodes = np.zeros((max((n + 1) // 2 - 1, 0), 16), np.uint32)
+    refs = np.zeros(n, np.uint32)
+    stats = np.zeros(4, np.uint32)
+    sah = C.c_float(0.0)
+    _check(lib().p3d_debug_lbvh_build(int(device), n, lo.ctypes.data, hi.ctypes.data, ref.ctypes.data, nodes.ctypes.data,
+                                      refs.ctypes.data, stats.ctypes.data, C.addressof(sah)), "p3d_debug_lbvh_build")
+    return {"nodes": nodes, "refs": refs, "n_nodes": int(stats[0]), "n_leaves": int(stats[1]), "n_leaf_refs": int(stats[2]),
+            "max_depth": int(stats[3]), "sah_cost": float(np.float32(sah.value))}
 
 
 def host_grid(desc):

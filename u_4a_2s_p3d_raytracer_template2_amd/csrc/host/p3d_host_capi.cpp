@@ -123,6 +123,18 @@ void p3dh_bvh_quantise(const p3dh_bvh* b, uint32_t* qnodes8, float* scale3, floa
     memcpy(scale3, Q.scale, sizeof Q.scale); memcpy(base3, Q.base, sizeof Q.base);
 }
 
+// ---- the build primitives flatten_scene hands either BVH builder for a scene (padded bounds and leaf references, scene
+// order of the bounded primitives); returns their number, or -1.  Arrays may be NULL to ask for the number only.
+int64_t p3dh_build_prims(const p3d_scene_desc* d, float* lo3, float* hi3, uint32_t* ref, uint64_t cap) {
+    p3d::FlatScene F;
+    if (!p3d::flatten_scene(*d, F).empty()) return -1;
+    for (size_t i = 0; lo3 && hi3 && ref && i < F.build_prims.size() && i < cap; i++) {
+        memcpy(lo3 + 3 * i, F.build_prims[i].lo, 12); memcpy(hi3 + 3 * i, F.build_prims[i].hi, 12);
+        ref[i] = F.build_prims[i].ref;
+    }
+    return (int64_t)F.build_prims.size();
+}
+
 // ---- the triangle normals the device shades with (computed on the host by flatten_scene), scene order of the
 // triangles; returns their number.  For the CPU-side parity test against the reference's known answers.
 int64_t p3dh_triangle_normals(const p3d_scene_desc* d, float* out3, uint64_t cap) {

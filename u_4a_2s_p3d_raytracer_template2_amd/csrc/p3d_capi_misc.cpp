@@ -262,4 +262,25 @@ int p3d_debug_schlick_kr(int device, uint32_t n, const float* ior_1, const float
     });
 }
 
+int p3d_debug_lbvh_build(int device, uint32_t n, const float* lo3, const float* hi3, const uint32_t* ref, uint32_t* nodes16,
+                         uint32_t* leaf_refs, uint32_t* stats4, float* sah_cost) {
+    if (!lo3 || !hi3 || !ref || !nodes16 || !leaf_refs || !stats4 || !sah_cost) return fail(P3D_ERR_ARG, "NULL argument");
+    if (n < 4) return fail(P3D_ERR_ARG, "the device builder needs at least 4 primitives (two leaves)");
+    std::vector<BuildPrim> prims(n);
+    for (uint32_t i = 0; i < n; i++) {
+        memcpy(prims[i].lo, lo3 + 3 * (size_t)i, 12); memcpy(prims[i].hi, hi3 + 3 * (size_t)i, 12);
+        prims[i].ref = ref[i]; prims[i].scene_id = i;
+    }
+    const size_t n_nodes = (n + 1) / 2 - 1;
+    BvhStats bs;
+    DebugArg a[2] = {{nullptr, nodes16, n_nodes * sizeof(NodePair)}, {nullptr, leaf_refs, (size_t)n * 4}};
+    int rc = debug_run("p3d_debug_lbvh_build", device, a, [&] {
+        return build_lbvh_device(prims, BvhOptions(), a[0].as<NodePair>(), a[1].as<uint32_t>(), bs, nullptr);
+    });
+    if (rc) return rc;
+    stats4[0] = bs.n_nodes; stats4[1] = bs.n_leaves; stats4[2] = bs.n_leaf_refs; stats4[3] = bs.max_depth;
+    *sah_cost = bs.sah_cost;
+    return P3D_OK;
+}
+
 }  // extern "C"

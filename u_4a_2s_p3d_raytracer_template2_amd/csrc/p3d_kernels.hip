@@ -23,6 +23,8 @@
 
 #include <algorithm>
 #include <cstring>
+#include <map>
+#include <mutex>
 #include <type_traits>
 #include <utility>
 
@@ -1317,8 +1319,27 @@ static const void* tree_kernel(const LaunchParams& P, const KernelVariant& v) {
     const int i = variant_index(canonical_tree(v, priv));
     return i < 0 ? nullptr : kernel_at<TreeKernels>(i * 3 + (priv == 36 ? 1 : priv == 84 ? 2 : 0));
 }
+// A launch with more dynamic LDS than the 64 KiB default says so first.  Any kernel can need it: the stacks grow with the
+// depth of the BVH (a device-built tree over clustered centroids is a chain of up to 96 levels, bvh_device.hip), and the
+// four waves of a workgroup that renders from an LDS copy of the scene each have one.  The limit is a maximum, so the
+// largest one set for a kernel on a device is remembered and the runtime is asked only to raise it further.
+static hipError_t allow_lds(const void* fn, size_t shmem) {
+    if (shmem <= 64 * 1024) return hipSuccess;
+    static std::mutex lock;
+    static std::map<std::pair<int, const void*>, size_t> raised;
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    std::lock_guard<std::mutex> guard(lock);
+    size_t& limit = raised[{dev, fn}];
+    if (shmem <= limit) return hipSuccess;
+    if ((e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem)) == hipSuccess) limit = shmem;
+    return e;
+}
 static hipError_t launch_by_pointer(const void* fn, const LaunchParams& P, dim3 grid, dim3 block, size_t shmem, hipStream_t stream) {
     if (!fn) return hipErrorInvalidDeviceFunction;
+    hipError_t e = allow_lds(fn, shmem);
+    if (e != hipSuccess) return e;
     LaunchParams Pc = P;
     void* args[] = {&Pc};
     return hipLaunchKernel(fn, grid, block, args, shmem, stream);
@@ -1327,8 +1348,9 @@ static hipError_t launch_by_pointer(const void* fn, const LaunchParams& P, dim3 
 static hipError_t resident_blocks(const void* fn, int block, size_t shmem, int* blocks) {
     if (!fn) return hipErrorInvalidDeviceFunction;
     int per_cu = 0, dev = 0, cus = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, block, shmem);
+    hipError_t e = allow_lds(fn, shmem);
     if (e != hipSuccess) return e;
+    if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, block, shmem)) != hipSuccess) return e;
     if ((e = hipGetDevice(&dev)) != hipSuccess) return e;
     if ((e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev)) != hipSuccess) return e;
     *blocks = (per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
@@ -1349,10 +1371,13 @@ hipError_t launch_wf_primary(const LaunchParams& P, const KernelVariant& v, hipS
 hipError_t launch_wf_rays(const LaunchParams& P, const RayStreamIO& R, const KernelVariant& v, hipStream_t stream) {
     const void* fn = level_kernel<LevelKernels<Level::Rays>>(v);
     if (!fn) return hipErrorInvalidDeviceFunction;
+    const size_t shmem = wavefront_lds_bytes(P, v.lds);
+    hipError_t e = allow_lds(fn, shmem);
+    if (e != hipSuccess) return e;
     LaunchParams Pc = P;
     RayStreamIO Rc = R;
     void* args[] = {&Pc, &Rc};
-    return hipLaunchKernel(fn, dim3((unsigned)P.wf_tile_rows), dim3(64 * P.wg_waves), args, wavefront_lds_bytes(P, v.lds), stream);
+    return hipLaunchKernel(fn, dim3((unsigned)P.wf_tile_rows), dim3(64 * P.wg_waves), args, shmem, stream);
 }
 hipError_t launch_wf_secondary(const LaunchParams& P, const KernelVariant& v, unsigned waves, hipStream_t stream) {
     return launch_by_pointer(level_kernel<LevelKernels<Level::Secondary>>(v), P, dim3((waves + P.wg_waves - 1) / P.wg_waves),
@@ -1371,13 +1396,7 @@ size_t tile_kernel_lds_bytes(const LaunchParams& P, bool lds) {
 }
 // workgroups of this variant that can be resident on the whole device (persistent grid size)
 hipError_t tile_kernel_resident_blocks(const LaunchParams& P, const KernelVariant& v, int* blocks) {
-    const void* fn = level_kernel<LevelKernels<Level::Tile>>(v);
-    const size_t shmem = tile_kernel_lds_bytes(P, v.lds);
-    if (fn && shmem > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        if (e != hipSuccess) return e;
-    }
-    return resident_blocks(fn, 256, shmem, blocks);
+    return resident_blocks(level_kernel<LevelKernels<Level::Tile>>(v), 256, tile_kernel_lds_bytes(P, v.lds), blocks);
 }
 hipError_t launch_wf_tile(const LaunchParams& P, const KernelVariant& v, unsigned blocks, hipStream_t stream) {
     return launch_by_pointer(level_kernel<LevelKernels<Level::Tile>>(v), P, dim3(blocks), dim3(256), tile_kernel_lds_bytes(P, v.lds), stream);
@@ -1430,17 +1449,6 @@ hipError_t launch_sum_samples(const LaunchParams& P, size_t first_px, size_t n_p
     if (P.n_frames > 1) hipLaunchKernelGGL(sum_samples_kernel<true>, dim3(blocks ? blocks : 1), dim3(256), 0, stream, P, first_px, n_px);
     else hipLaunchKernelGGL(sum_samples_kernel<false>, dim3(blocks ? blocks : 1), dim3(256), 0, stream, P, first_px, n_px);
     return hipGetLastError();
-}
-
-hipError_t prepare_kernels(size_t max_lds) {
-    // only the tree kernel without an LDS scene copy and with its frames in LDS can need more than the 64 KiB default
-    for (int i = 0; i < kTreeVariants; i += 3) {          // (PRIV == 0: every third position)
-        const void* fn = kernel_at<TreeKernels>(i);
-        if (!fn || variant_at(i / 3).lds) continue;
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_lds);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
 }
 
 hipError_t launch_raygen_table(float* fx, float* fy, int res_x, int res_y, hipStream_t stream) {

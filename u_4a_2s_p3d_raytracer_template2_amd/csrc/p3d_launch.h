@@ -27,7 +27,6 @@ hipError_t launch_wf_secondary(const LaunchParams& P, const KernelVariant& v, un
 hipError_t launch_wf_tile(const LaunchParams& P, const KernelVariant& v, unsigned blocks, hipStream_t stream);
 hipError_t wf_resident_waves(const LaunchParams& P, const KernelVariant& v, unsigned* waves);
 hipError_t tile_kernel_resident_blocks(const LaunchParams& P, const KernelVariant& v, int* blocks);
-hipError_t prepare_kernels(size_t max_lds);
 // (ray_stream: the builds whose level-1 nodes return to a ray stream's planes instead of a frame's pixels)
 hipError_t launch_wf_resolve(const LaunchParams& P, unsigned blocks, bool ray_stream, hipStream_t stream);
 hipError_t launch_wf_resolve_fused(const LaunchParams& P, const ResolveLevels& R, unsigned shards, bool ray_stream, hipStream_t stream);

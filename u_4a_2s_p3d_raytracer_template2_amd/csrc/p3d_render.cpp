@@ -793,10 +793,6 @@ int render_batch(p3d_scene* s, const p3d_camera* cams, int32_t n_frames, const p
                        : sched == SCHED_TILE ? tile_kernel_lds_bytes(plan.PT, plan.lds_scene)
                                              : wavefront_lds_bytes(P, plan.lds_scene);
     if (lds > kMaxLdsBytes) return fail(P3D_ERR_LIMIT, "BVH depth / max_depth need more LDS than a CU has");
-    if (lds > 64 * 1024 && sched != SCHED_TILE && !s->lds_prepared) {
-        HIP_TRY(prepare_kernels(kMaxLdsBytes));
-        s->lds_prepared = kMaxLdsBytes;
-    }
 
     if (cfg.batch() && (rc = write_frame_cams(s, cams, n_frames, P)) != P3D_OK) return rc;
     const size_t npx = (size_t)P.local_rows * cfg.res_x;

@@ -231,7 +231,6 @@ struct p3d_scene {
     p3d::RawBuf frame_cams;
     bool profile_valid = false;
     bool timer_open = false;
-    size_t lds_prepared = 0;
     int xcd_chunk = 1;
     int frame_streams = 1;               // bands of a one-sample frame run concurrently on this many streams (experiment knob)
     int resolve_blocks_per_shard = 16;   // a resolve launch is latency-bound: few nodes per thread, many threads
