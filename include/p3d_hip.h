@@ -250,7 +250,7 @@ typedef struct p3d_prim_update {
  *  - what may change: geometry, and the lights' positions and colours.  Kind, material, primitive count, material table,
  *    number of lights and background stay what they were at creation.
  *  - tree quality: the tree keeps the topology it was built with, so its quality degrades as primitives move away from
- *    where they were; frames stay equal and get slower.  Creating a new handle is the remedy.  The statistics keep
+ *    where they were; frames stay equal and get slower.  p3d_scene_rebuild (below) is the remedy.  The statistics keep
  *    creation's sah_cost; device_bytes grows by what the first update allocates (f32 nodes of scenes read from HBM, one
  *    parent and one counter word per node pair, staging for host-memory updates).
  *  - ordering: runs after everything already enqueued on the scene's stream, and returns when scene and tree are
@@ -271,6 +271,52 @@ typedef struct p3d_prim_update {
  *  - the handle's other state stays: the measured schedule choice, the learned tile orders (predictions, never results),
  *    p3d_last_schedule() and the ray-stream state.  A frame after an update measures nothing again. */
 int p3d_scene_update(p3d_scene* scene, const p3d_prim_update* update);
+
+/* What p3d_scene_rebuild did, and the tree the handle walks after it. */
+typedef struct p3d_rebuild_info {
+    uint32_t rebuilt;          /* 1 = the handle walks a new tree; 0 = nothing was changed (see below) */
+    uint32_t n_nodes, n_leaves, max_depth;   /* of the tree the handle walks after the call */
+    float    sah_cost_before;  /* SAH cost of the tree as it stood (refitted boxes), creation's units */
+    float    sah_cost_after;   /* == p3d_scene_stats::sah_cost after the call */
+} p3d_rebuild_info;
+/* The other half of "refit while the frame time holds, rebuild when it no longer does": the tree of a live handle is built
+ * again, on the device, from the primitive records the handle holds there -- no host copy of the geometry is needed (updates
+ * may have come from device memory) and no new handle is made.  info may be NULL.
+ *  - equality of frames: after the call every entry -- p3d_render, p3d_render_frames, p3d_render_aov, p3d_trace_rays; every
+ *    accel mode, schedule, flag and feature; sharding, samples -- produces, in every bit, what it produced before the call,
+ *    and hence what a handle freshly created from the current geometry produces (a closest hit is "nearest, lowest scene
+ *    index on ties" whatever the tree).  Only speed changes.
+ *  - which tree: the device builder's (Morton sort, leaves of two, Karras hierarchy: p3d_build_opts::builder == 1) over the
+ *    padded bounds of the records as they are now, the primitives enumerated in scene order with the planes left out, so
+ *    that ties between equal Morton keys break the way they do at creation.  A handle created with the host SAH builder may
+ *    be rebuilt too: it trades the SAH tree's quality for a tree that fits the moved geometry.
+ *  - what is kept: the measured schedule choice, the learned tile orders (predictions, never results), p3d_last_schedule(),
+ *    the ray-stream state, the stream, tuning, the skybox, the lights, the materials, and which primitives' points the host
+ *    lacks for GRID mode (p3d_scene_update from device memory).
+ *  - what changes: the order of the records inside the handle (leaf order of the new tree), the map from scene index to
+ *    record, leaf records, node arrays and the quantisation grid; of p3d_scene_stats n_nodes, n_leaves, n_leaf_refs,
+ *    max_depth, sah_cost and device_bytes; the refit state (the next p3d_scene_update climbs the new topology).  A built
+ *    uniform grid is dropped, as by an update: the next GRID frame builds it again.
+ *  - ordering: runs after everything already enqueued on the scene's stream, waits on the device and returns when the handle
+ *    is consistent; what the handle held before is freed only after that wait.
+ *  - stream capture: refused with P3D_ERR_STATE while the stream is being captured.  A graph captured BEFORE a rebuild must be
+ *    captured again: the scene's addresses and the quantisation grid travel in the launch parameters by value.
+ *  - a handle created with cull_never_hit is refused with P3D_ERR_STATE, as by p3d_scene_update.  P3D_ERR_ARG: NULL scene.
+ *    P3D_ERR_HIP when device memory runs out: every allocation is made before anything of the handle changes, so the handle
+ *    is then what it was.
+ *  - handles left alone: scenes served from an LDS copy, and scenes with fewer than 64 bounded primitives (which creation
+ *    builds on the host whatever the builder asked for), keep their tree: P3D_OK, rebuilt == 0, statistics unchanged,
+ *    sah_cost_before == sah_cost_after == the current cost.  Their tree is a few hundred node pairs walked from LDS; their
+ *    layout carries a record per leaf and the f32 nodes, and growing it could push the scene out of LDS and change which
+ *    kernels serve it. */
+int p3d_scene_rebuild(p3d_scene* scene, p3d_rebuild_info* info);
+/* SAH cost of the tree the handle walks NOW, in the unit of p3d_scene_stats::sah_cost: per node pair 1.2 x the area of its
+ * own box (the union of its two child boxes), per leaf the primitive count x the area of the leaf's box, both over the root's
+ * area.  After updates it tells what the refitted boxes cost; p3d_scene_stats keeps the cost of the last build.  One
+ * reduction over the f32 node pairs (float sums in no fixed order: equal to a few ulps per thousand nodes between calls); a
+ * handle read from HBM that was never updated nor rebuilt has no such pairs and has not moved: it answers creation's
+ * sah_cost.  Synchronous; refused with P3D_ERR_STATE while the stream is being captured.  P3D_ERR_ARG: NULL scene or sah_cost. */
+int p3d_scene_tree_cost(p3d_scene* scene, float* sah_cost);
 
 /* Rows of the compact per-rank tile buffer: ceil(n_row_blocks / world) * row_block, the
  * same on every rank so that the gather moves equal-sized buffers (rows past the image are

@@ -92,6 +92,12 @@ class PrimUpdate(C.Structure):
     _fields_ = [("n", C.c_uint32), ("index", C.c_void_p), ("prim_data", C.c_void_p), ("memory", C.c_int32), ("lights", C.c_void_p)]
 
 
+class RebuildInfo(C.Structure):
+    """p3d_rebuild_info: whether p3d_scene_rebuild made a new tree, that tree's shape, and the SAH cost before and after."""
+    _fields_ = [("rebuilt", C.c_uint32), ("n_nodes", C.c_uint32), ("n_leaves", C.c_uint32), ("max_depth", C.c_uint32),
+                ("sah_cost_before", C.c_float), ("sah_cost_after", C.c_float)]
+
+
 class SceneStats(C.Structure):
     _fields_ = [("n_nodes", C.c_uint32), ("n_leaves", C.c_uint32), ("max_depth", C.c_uint32),
                 ("n_leaf_refs", C.c_uint32), ("n_spheres", C.c_uint32), ("n_triangles", C.c_uint32),
@@ -104,7 +110,7 @@ class SceneStats(C.Structure):
 
 # every symbol include/p3d_hip.h declares (tests check that the library exports them all)
 C_ABI_SYMBOLS = ["p3d_abi_version", "p3d_last_error", "p3d_device_count", "p3d_scene_create",
-                 "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_scene_update", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_render_aov", "p3d_trace_rays", "p3d_sync",
+                 "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_scene_update", "p3d_scene_rebuild", "p3d_scene_tree_cost", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_render_aov", "p3d_trace_rays", "p3d_sync",
                  "p3d_get_counters", "p3d_get_profile", "p3d_last_schedule", "p3d_set_tuning", "p3d_set_primary_tiles", "p3d_last_primary_tiles", "p3d_set_stream", "p3d_timer_begin", "p3d_timer_end", "p3d_deinterleave_frames",
                  "p3d_deinterleave", "p3d_debug_intersect", "p3d_debug_powf", "p3d_debug_pow", "p3d_debug_schlick_kr", "p3d_debug_check_rcp", "p3d_debug_check_rcp_len", "p3d_debug_lbvh_build", "p3d_tune_schedule", "p3d_debug_set_stamps", "p3d_debug_set_stamp_level",
                  "p3d_comm_unique_id", "p3d_comm_create", "p3d_comm_create_all", "p3d_comm_destroy", "p3d_comm_info",
@@ -147,6 +153,8 @@ def lib():
     L.p3d_scene_set_skybox.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.p3d_scene_get_stats.argtypes = [C.c_void_p, C.POINTER(SceneStats)]
     L.p3d_scene_update.argtypes = [C.c_void_p, C.POINTER(PrimUpdate)]
+    L.p3d_scene_rebuild.argtypes = [C.c_void_p, C.POINTER(RebuildInfo)]
+    L.p3d_scene_tree_cost.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.p3d_local_rows.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     L.p3d_render.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(Outputs)]
     L.p3d_render_frames.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.POINTER(RenderParams), C.POINTER(Outputs)]
@@ -441,6 +449,19 @@ class DeviceScene:
         scene indices or 0 for primitives 0 .. n-1."""
         u = PrimUpdate(int(n), index_ptr or None, prim_ptr or None, 1, None)
         _check(lib().p3d_scene_update(self.h, C.byref(u)), "p3d_scene_update")
+
+    def rebuild(self):
+        """p3d_scene_rebuild: the device builder's tree over the primitives where they are now, in place.  Frames stay what
+        they were, bit for bit.  Returns p3d_rebuild_info as a dict (rebuilt == 0: a scene served from LDS, left alone)."""
+        info = RebuildInfo()
+        _check(lib().p3d_scene_rebuild(self.h, C.byref(info)), "p3d_scene_rebuild")
+        return {n: getattr(info, n) for n, _ in info._fields_}
+
+    def tree_cost(self):
+        """p3d_scene_tree_cost: SAH cost of the tree as it stands (after updates: of the refitted boxes)."""
+        v = C.c_float(0)
+        _check(lib().p3d_scene_tree_cost(self.h, C.byref(v)), "p3d_scene_tree_cost")
+        return v.value
 
     def set_skybox(self, faces):
         """Six uint8 arrays [H, W, 3 or 4]: right, left, top, bottom, front, back; row 0 = bottom row (Scene::LoadSkybox)."""

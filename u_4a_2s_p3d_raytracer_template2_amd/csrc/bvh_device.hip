@@ -225,59 +225,103 @@ __global__ void lbvh_emit_kernel(int n_leaves, uint32_t n_prims, const int2* chi
 
 }  // namespace
 
-// Builds the tree of `prims` (host array, padded bounds) into device memory: nodes[n_leaves - 1],
-// refs[n].  n >= 2 * kLeafPrims.  Synchronous (returns when the tree is complete).
-hipError_t build_lbvh_device(const std::vector<BuildPrim>& prims, const BvhOptions& opt, NodePair* d_nodes,
-                             uint32_t* d_refs, BvhStats& stats, hipStream_t stream) {
-    const uint32_t n = (uint32_t)prims.size();
+// The scratch a build of n primitives carves out of one allocation (after the caller's own `head` bytes).
+struct LbvhLayout {
+    size_t keys, keys2, vals, vals2, lkeys, lbox, nbox, child, pin, pleaf, arr, misc, sort, sort_bytes, total;
+};
+static hipError_t lbvh_layout(uint32_t n, size_t head, LbvhLayout& Y, hipStream_t stream) {
+    const uint32_t L = (n + kLeafPrims - 1) / kLeafPrims;
+    size_t off = head;
+    auto carve = [&](size_t bytes) { size_t at = off; off = (off + bytes + 255) & ~(size_t)255; return at; };
+    Y.keys = carve((size_t)n * 8); Y.keys2 = carve((size_t)n * 8);
+    Y.vals = carve((size_t)n * 4); Y.vals2 = carve((size_t)n * 4);
+    Y.lkeys = carve((size_t)L * 8); Y.lbox = carve((size_t)L * sizeof(Box6)); Y.nbox = carve((size_t)L * sizeof(Box6));
+    Y.child = carve((size_t)L * 8); Y.pin = carve((size_t)L * 4); Y.pleaf = carve((size_t)L * 4);
+    Y.arr = carve((size_t)L * 4); Y.misc = carve(64);
+    Y.sort_bytes = 0;
+    hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, Y.sort_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr,
+                                                      (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0, 63, stream);
+    if (e != hipSuccess) return e;
+    Y.sort = carve(Y.sort_bytes);
+    Y.total = off;
+    return hipSuccess;
+}
+
+hipError_t lbvh_scratch_bytes(uint32_t n, size_t* bytes, hipStream_t stream) {
+    LbvhLayout Y;
+    hipError_t e = lbvh_layout(n, 0, Y, stream);
+    if (e == hipSuccess) *bytes = Y.total;
+    return e;
+}
+
+// The build itself over `d_prims` (device array, padded bounds), enqueued on `stream`: nodes[n_leaves - 1], refs[n].
+// `pool` is the allocation Y was laid out for; it must live until the stream has passed.  The tree's depth (levels of
+// inner nodes) and SAH cost are left in the two words at *d_result.
+static hipError_t lbvh_enqueue_at(const BuildPrim* d_prims, uint32_t n, const BvhOptions& opt, NodePair* d_nodes, uint32_t* d_refs,
+                                  char* pool, const LbvhLayout& Y, uint32_t** d_result, hipStream_t stream) {
     const uint32_t L = (n + kLeafPrims - 1) / kLeafPrims;
     hipError_t e;
-    char* pool = nullptr;
-    // one scratch allocation, carved up
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t at = off; off = (off + bytes + 255) & ~(size_t)255; return at; };
-    const size_t o_prims = carve((size_t)n * sizeof(BuildPrim));
-    const size_t o_keys = carve((size_t)n * 8), o_keys2 = carve((size_t)n * 8);
-    const size_t o_vals = carve((size_t)n * 4), o_vals2 = carve((size_t)n * 4);
-    const size_t o_lkeys = carve((size_t)L * 8), o_lbox = carve((size_t)L * sizeof(Box6)), o_nbox = carve((size_t)L * sizeof(Box6));
-    const size_t o_child = carve((size_t)L * 8), o_pin = carve((size_t)L * 4), o_pleaf = carve((size_t)L * 4);
-    const size_t o_arr = carve((size_t)L * 4), o_misc = carve(64);
-    size_t sort_bytes = 0;
-    e = hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr,
-                                           (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0, 63, stream);
-    if (e != hipSuccess) return e;
-    const size_t o_sort = carve(sort_bytes);
-    if ((e = hipMalloc((void**)&pool, off)) != hipSuccess) return e;
-    auto done = [&](hipError_t rc) { (void)hipFree(pool); return rc; };
-    BuildPrim* d_prims = (BuildPrim*)(pool + o_prims);
-    uint64_t *keys = (uint64_t*)(pool + o_keys), *keys2 = (uint64_t*)(pool + o_keys2), *lkeys = (uint64_t*)(pool + o_lkeys);
-    uint32_t *vals = (uint32_t*)(pool + o_vals), *vals2 = (uint32_t*)(pool + o_vals2);
-    Box6 *lbox = (Box6*)(pool + o_lbox), *nbox = (Box6*)(pool + o_nbox);
-    int2* child = (int2*)(pool + o_child);
-    int *pin = (int*)(pool + o_pin), *pleaf = (int*)(pool + o_pleaf);
-    uint32_t *arrived = (uint32_t*)(pool + o_arr), *misc = (uint32_t*)(pool + o_misc);   // misc: bounds[6], depth, sah
-    if ((e = hipMemcpyAsync(d_prims, prims.data(), (size_t)n * sizeof(BuildPrim), hipMemcpyHostToDevice, stream)) != hipSuccess) return done(e);
+    uint64_t *keys = (uint64_t*)(pool + Y.keys), *keys2 = (uint64_t*)(pool + Y.keys2), *lkeys = (uint64_t*)(pool + Y.lkeys);
+    uint32_t *vals = (uint32_t*)(pool + Y.vals), *vals2 = (uint32_t*)(pool + Y.vals2);
+    Box6 *lbox = (Box6*)(pool + Y.lbox), *nbox = (Box6*)(pool + Y.nbox);
+    int2* child = (int2*)(pool + Y.child);
+    int *pin = (int*)(pool + Y.pin), *pleaf = (int*)(pool + Y.pleaf);
+    uint32_t *arrived = (uint32_t*)(pool + Y.arr), *misc = (uint32_t*)(pool + Y.misc);   // misc: bounds[6], depth, sah
     const uint32_t init[8] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, 0u, 0u};
-    if ((e = hipMemcpyAsync(misc, init, sizeof init, hipMemcpyHostToDevice, stream)) != hipSuccess) return done(e);
-    if ((e = hipMemsetAsync(arrived, 0, (size_t)L * 4, stream)) != hipSuccess) return done(e);
+    if ((e = hipMemcpyAsync(misc, init, sizeof init, hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(arrived, 0, (size_t)L * 4, stream)) != hipSuccess) return e;
     const unsigned T = 256;
     hipLaunchKernelGGL(lbvh_bounds_kernel, dim3(std::min<unsigned>((n + T - 1) / T, 2048)), dim3(T), 0, stream, d_prims, n, misc);
     hipLaunchKernelGGL(lbvh_morton_kernel, dim3((n + T - 1) / T), dim3(T), 0, stream, d_prims, n, misc, keys, vals);
-    e = hipcub::DeviceRadixSort::SortPairs(pool + o_sort, sort_bytes, keys, keys2, vals, vals2, (int)n, 0, 63, stream);
-    if (e != hipSuccess) return done(e);
+    size_t sort_bytes = Y.sort_bytes;
+    e = hipcub::DeviceRadixSort::SortPairs(pool + Y.sort, sort_bytes, keys, keys2, vals, vals2, (int)n, 0, 63, stream);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(lbvh_leaves_kernel, dim3((L + T - 1) / T), dim3(T), 0, stream, d_prims, n, L, keys2, vals2, d_refs, lkeys, lbox);
     hipLaunchKernelGGL(lbvh_hierarchy_kernel, dim3((L + T - 1) / T), dim3(T), 0, stream, lkeys, (int)L, child, pin, pleaf);
     hipLaunchKernelGGL(lbvh_refit_kernel, dim3((L + T - 1) / T), dim3(T), 0, stream, (int)L, child, pin, pleaf, lbox, nbox, arrived, misc + 6);
     hipLaunchKernelGGL(lbvh_emit_kernel, dim3((L + T - 1) / T), dim3(T), 0, stream, (int)L, n, child, lbox, nbox, d_nodes,
                        opt.cost_traverse, opt.cost_intersect, (float*)(misc + 7));
-    if ((e = hipGetLastError()) != hipSuccess) return done(e);
-    uint32_t back[8];
-    if ((e = hipMemcpyAsync(back, misc, sizeof back, hipMemcpyDeviceToHost, stream)) != hipSuccess) return done(e);
-    if ((e = hipStreamSynchronize(stream)) != hipSuccess) return done(e);
+    *d_result = misc + 6;
+    return hipGetLastError();
+}
+
+hipError_t lbvh_enqueue(const BuildPrim* d_prims, uint32_t n, const BvhOptions& opt, NodePair* d_nodes, uint32_t* d_refs,
+                        void* scratch, uint32_t** d_result, hipStream_t stream) {
+    LbvhLayout Y;
+    hipError_t e = lbvh_layout(n, 0, Y, stream);
+    if (e != hipSuccess) return e;
+    return lbvh_enqueue_at(d_prims, n, opt, d_nodes, d_refs, (char*)scratch, Y, d_result, stream);
+}
+
+void lbvh_stats(uint32_t n, const uint32_t result[2], BvhStats& stats) {
+    const uint32_t L = (n + kLeafPrims - 1) / kLeafPrims;
     stats = BvhStats();
     stats.n_nodes = L - 1; stats.n_leaves = L; stats.n_leaf_refs = n;
-    stats.max_depth = back[6] + 1;            // + the leaf level, like the host builder's count
-    memcpy(&stats.sah_cost, &back[7], 4);
+    stats.max_depth = result[0] + 1;          // + the leaf level, like the host builder's count
+    memcpy(&stats.sah_cost, &result[1], 4);
+}
+
+// Builds the tree of `prims` (host array, padded bounds) into device memory: nodes[n_leaves - 1],
+// refs[n].  n >= 2 * kLeafPrims.  Synchronous (returns when the tree is complete).
+hipError_t build_lbvh_device(const std::vector<BuildPrim>& prims, const BvhOptions& opt, NodePair* d_nodes,
+                             uint32_t* d_refs, BvhStats& stats, hipStream_t stream) {
+    const uint32_t n = (uint32_t)prims.size();
+    hipError_t e;
+    char* pool = nullptr;
+    // one scratch allocation, carved up: the uploaded primitives lead it
+    LbvhLayout Y;
+    const size_t head = ((size_t)n * sizeof(BuildPrim) + 255) & ~(size_t)255;
+    if ((e = lbvh_layout(n, head, Y, stream)) != hipSuccess) return e;
+    if ((e = hipMalloc((void**)&pool, Y.total)) != hipSuccess) return e;
+    auto done = [&](hipError_t rc) { (void)hipFree(pool); return rc; };
+    BuildPrim* d_prims = (BuildPrim*)pool;
+    if ((e = hipMemcpyAsync(d_prims, prims.data(), (size_t)n * sizeof(BuildPrim), hipMemcpyHostToDevice, stream)) != hipSuccess) return done(e);
+    uint32_t* d_result = nullptr;
+    if ((e = lbvh_enqueue_at(d_prims, n, opt, d_nodes, d_refs, pool, Y, &d_result, stream)) != hipSuccess) return done(e);
+    uint32_t back[2];
+    if ((e = hipMemcpyAsync(back, d_result, sizeof back, hipMemcpyDeviceToHost, stream)) != hipSuccess) return done(e);
+    if ((e = hipStreamSynchronize(stream)) != hipSuccess) return done(e);
+    lbvh_stats(n, back, stats);
     return done(hipSuccess);
 }
 

@@ -52,6 +52,13 @@ hipError_t launch_debug_intersect(uint32_t n, const uint32_t* type, const float*
 // ---- bvh_device.hip
 hipError_t build_lbvh_device(const std::vector<BuildPrim>& prims, const BvhOptions& opt, NodePair* d_nodes,
                              uint32_t* d_refs, BvhStats& stats, hipStream_t stream);
+// ... the same build over primitives already on the device, for p3d_scene_rebuild: only enqueued.  `scratch` holds
+// lbvh_scratch_bytes(n) bytes and lives until the stream has passed; the two words at *d_result (inside it), read back,
+// are what lbvh_stats() turns into the tree's statistics.
+hipError_t lbvh_scratch_bytes(uint32_t n, size_t* bytes, hipStream_t stream);
+hipError_t lbvh_enqueue(const BuildPrim* d_prims, uint32_t n, const BvhOptions& opt, NodePair* d_nodes, uint32_t* d_refs,
+                        void* scratch, uint32_t** d_result, hipStream_t stream);
+void lbvh_stats(uint32_t n, const uint32_t result[2], BvhStats& stats);
 hipError_t sort_tiles_by_cost(const uint32_t* cost, uint32_t* cost_sorted, uint32_t* iota, uint32_t* order, uint32_t n,
                               void* temp, size_t& temp_bytes, hipStream_t stream);
 

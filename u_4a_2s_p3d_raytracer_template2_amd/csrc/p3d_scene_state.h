@@ -1,5 +1,5 @@
 // p3d_scene_state.h -- the scene handle behind the C-ABI of include/p3d_hip.h, shared by the files that implement it
-// (p3d_scene_create.cpp, p3d_scene_update.cpp, p3d_render.cpp, p3d_capi_misc.cpp).  Internal: not installed with include/.
+// (p3d_scene_create.cpp, p3d_scene_update.cpp, p3d_scene_rebuild.cpp, p3d_render.cpp, p3d_capi_misc.cpp).  Internal: not installed with include/.
 // Every device resource in it is owned by a member that frees it: deleting a p3d_scene releases all of them.
 #ifndef P3D_SCENE_STATE_H
 #define P3D_SCENE_STATE_H
@@ -142,7 +142,8 @@ struct p3d_scene {
     p3d::DevBuf<uint32_t> grid_cells, grid_items;
     p3d::GridHost grid_info; bool grid_ready = false;
     // p3d_scene_update: where each primitive's record sits (scene index -> kind << 30 | index in the kind's leaf-ordered
-    // array; planes index their own), and what the refit needs next to the scene, allocated by the first update
+    // array; planes index their own), and what the refit needs next to the scene, allocated by the first update.
+    // p3d_scene_rebuild replaces the map with the new tree's, and the refit state with that tree's f32 pairs and parents
     p3d::DevBuf<uint32_t> prim_map;
     struct Refit {
         p3d::RawBuf nodes;                   // f32 node pairs of a scene that carries quantised ones only (else: the blob's)
