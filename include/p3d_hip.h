@@ -105,7 +105,8 @@ typedef struct p3d_render_params {
                                 with thin lens, summed and divided by 16   */
     const float* samples;    /* spp>0: HOST array [res_y][res_x][spp*spp][4] =
                                 pixel sample x, y, lens x, lens y in reference RNG order
-                                (RT/main.cpp:776-801); uploaded by the call              */
+                                (RT/main.cpp:776-801); uploaded by the call.  p3d_generate_samples
+                                makes the same array on the device (P3D_FLAG_DEVICE_SAMPLES) */
     /* image-space sharding: this device renders the row blocks b with
      * b % world == rank, row_block rows each, into a COMPACT buffer of
      * p3d_local_rows() rows.  world = 1 renders the whole frame. */
@@ -384,6 +385,35 @@ typedef struct p3d_aov_outputs {   /* every plane may be NULL; memory as p3d_out
  *  - after p3d_scene_update the planes follow the moved geometry like everything else. */
 int p3d_render_aov(p3d_scene* scene, const p3d_camera* cams, int32_t n, const p3d_render_params* params,
                    const p3d_outputs* out, const p3d_aov_outputs* aov);
+/* Replaces the sample draws of renderScene() (set_rand_seed, RT/main.cpp:747; pixel jitter :781-782;
+ * sampleUnitDisk() * aperture, :723-730, :790) for one frame: writes [res_y][res_x][spp*spp][4] floats,
+ * every bit what generate_samples(seed, res_x, res_y, spp, aperture, out) of the host layer writes with
+ * this machine's C library -- the serial srand() / rand() stream, produced in parallel on the device
+ * (csrc/p3d_rand.h, csrc/sample_stream.hip): a new seed, a render-again loop or a frame batch no longer
+ * pays a host thread and an upload per frame.
+ *  - output: memory == 1: a device pointer on the scene's device; the array is exactly what
+ *    P3D_FLAG_DEVICE_SAMPLES reads.  A batch for p3d_render_frames is n calls at out + f * per_frame
+ *    floats (per_frame = res_x * res_y * spp * spp * 4) with the caller's seeds and apertures; the host
+ *    layer uses seed + f and cams[f].aperture.  memory == 0: the array is staged in the handle's sample
+ *    buffer (where p3d_render stages a host sample array) and copied back.
+ *  - exactness: how many draws a frame consumes depends on the draws (rejection sampling), so the call
+ *    provisions a pass from the expected consumption and reads back the count of completed samples;
+ *    while that count is short it continues the stream where the pass stopped -- position, machine
+ *    state and sample index carry over.  Every seed gives the whole array; no sample is approximated.
+ *  - synchronous, like p3d_scene_update: it runs after everything already enqueued on the scene's
+ *    stream and WAITS for its own passes (one wait in all but astronomically rare cases), so the array
+ *    is complete on return, in either memory.
+ *  - stream capture: refused with P3D_ERR_STATE while the stream is being captured.
+ *  - P3D_ERR_ARG: NULL scene or out; res_x, res_y or spp < 1; memory outside 0 and 1.  P3D_ERR_LIMIT,
+ *    before anything is allocated, when res_x * res_y * spp * spp does not fit 31 bits.
+ *  - scratch: jump tables (34 KiB) and 8 bytes per 496 pairs of draws of a pass plus 16 per 63488 --
+ *    2.5 MB for 4096 x 4096 at 2 x 2 -- never the draws themselves; owned by the handle, counted in
+ *    p3d_scene_stats::device_bytes when allocated, kept for the next call.
+ *  - handle state: nothing else changes -- the measured schedule choice, the learned tile orders,
+ *    p3d_last_schedule() and the ray-stream state are what they were. */
+int p3d_generate_samples(p3d_scene* scene, uint32_t seed, int32_t res_x, int32_t res_y, int32_t spp,
+                         float aperture, float* out, int32_t memory /* 0 host, 1 device */);
+
 /* A stream of rays the caller supplies, and what comes back for each.  Ray i is (origin[i], dir[i]); its results sit at
  * index i of every plane -- no image conventions: no clamp, no quantisation, no bottom-up rows, no "/ 16". */
 typedef struct p3d_rays {
@@ -582,6 +612,16 @@ int p3d_debug_check_rcp_len(int device, uint32_t first_bits, uint64_t count, uin
  * primitives are built on the host by p3d_scene_create; that threshold is not this entry's). */
 int p3d_debug_lbvh_build(int device, uint32_t n, const float* lo3, const float* hi3, const uint32_t* ref, uint32_t* nodes16,
                          uint32_t* leaf_refs, uint32_t* stats4, float* sah_cost);
+
+/* Unit-level probes of p3d_generate_samples (csrc/p3d_rand.h, csrc/sample_stream.hip); host arrays, synchronous.
+ * p3d_debug_rand: out[i] = the device's restatement of the value number first + i that the host C library's rand()
+ * returns after srand(seed), i < n; every device thread reaches its own position by a jump (first is 64-bit: positions
+ * no serial loop reaches).  p3d_debug_sample_stream: the generator itself into a host array, with every pass forced to read
+ * pairs_per_pass pairs of draws (0 = the entry's own sizing); *passes = how many passes ran, so that a test can take the
+ * continuation path on purpose -- with 2, a pass can end between a sample's jitter and its lens pair. */
+int p3d_debug_rand(int device, uint32_t seed, uint64_t first, uint32_t n, uint32_t* out);
+int p3d_debug_sample_stream(int device, uint32_t seed, int32_t res_x, int32_t res_y, int32_t spp, float aperture,
+                            uint64_t pairs_per_pass, float* out, int32_t* passes);
 
 #ifdef __cplusplus
 }

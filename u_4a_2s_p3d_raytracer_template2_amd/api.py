@@ -22,6 +22,9 @@ FLAG_DEVICE_SAMPLES = 128
 FLAG_PACKET_WALK = 256
 FEATURE_SOFT_SHADOW, FEATURE_FUZZY_REFLECTION, FEATURE_SKYBOX = 1, 2, 4
 FEATURE_SCHLICK = 8          # the reference's SCHLICK_APPROX (RT/main.cpp:99), bit-exact
+# p3d_generate_samples: pairs of draws one device thread reads, and threads (chunks) per workgroup -- kSampleChunkPairs and
+# kSampleChunkThreads of csrc/sample_stream.h (tests/test_rand_port.py keeps them equal); tests size their shapes from these
+SAMPLE_CHUNK_PAIRS, SAMPLE_WORKGROUP_CHUNKS = 496, 128
 
 
 class P3DError(RuntimeError):
@@ -110,9 +113,9 @@ class SceneStats(C.Structure):
 
 # every symbol include/p3d_hip.h declares (tests check that the library exports them all)
 C_ABI_SYMBOLS = ["p3d_abi_version", "p3d_last_error", "p3d_device_count", "p3d_scene_create",
-                 "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_scene_update", "p3d_scene_rebuild", "p3d_scene_tree_cost", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_render_aov", "p3d_trace_rays", "p3d_sync",
+                 "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_scene_update", "p3d_scene_rebuild", "p3d_scene_tree_cost", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_render_aov", "p3d_generate_samples", "p3d_trace_rays", "p3d_sync",
                  "p3d_get_counters", "p3d_get_profile", "p3d_last_schedule", "p3d_set_tuning", "p3d_set_primary_tiles", "p3d_last_primary_tiles", "p3d_set_stream", "p3d_timer_begin", "p3d_timer_end", "p3d_deinterleave_frames",
-                 "p3d_deinterleave", "p3d_debug_intersect", "p3d_debug_powf", "p3d_debug_pow", "p3d_debug_schlick_kr", "p3d_debug_check_rcp", "p3d_debug_check_rcp_len", "p3d_debug_lbvh_build", "p3d_tune_schedule", "p3d_debug_set_stamps", "p3d_debug_set_stamp_level",
+                 "p3d_deinterleave", "p3d_debug_intersect", "p3d_debug_powf", "p3d_debug_pow", "p3d_debug_schlick_kr", "p3d_debug_check_rcp", "p3d_debug_check_rcp_len", "p3d_debug_lbvh_build", "p3d_debug_rand", "p3d_debug_sample_stream", "p3d_tune_schedule", "p3d_debug_set_stamps", "p3d_debug_set_stamp_level",
                  "p3d_comm_unique_id", "p3d_comm_create", "p3d_comm_create_all", "p3d_comm_destroy", "p3d_comm_info",
                  "p3d_gather", "p3d_gather_all", "p3d_device_alloc", "p3d_device_free", "p3d_upload", "p3d_download"]
 
@@ -160,6 +163,7 @@ def lib():
     L.p3d_render_frames.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.POINTER(RenderParams), C.POINTER(Outputs)]
     L.p3d_render_aov.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.POINTER(RenderParams), C.POINTER(Outputs),
                                  C.POINTER(AovOutputs)]
+    L.p3d_generate_samples.argtypes = [C.c_void_p, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_int32]
     L.p3d_trace_rays.argtypes = [C.c_void_p, C.POINTER(Rays), C.POINTER(RenderParams), C.POINTER(RayOutputs)]
     L.p3d_sync.argtypes = [C.c_void_p]
     L.p3d_get_counters.argtypes = [C.c_void_p, C.POINTER(Counters)]
@@ -195,6 +199,9 @@ def lib():
     L.p3d_debug_check_rcp.argtypes = [C.c_int, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
     L.p3d_debug_check_rcp_len.argtypes = [C.c_int, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
     L.p3d_debug_lbvh_build.argtypes = [C.c_int, C.c_uint32] + [C.c_void_p] * 7
+    L.p3d_debug_rand.argtypes = [C.c_int, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p]
+    L.p3d_debug_sample_stream.argtypes = [C.c_int, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_uint64, C.c_void_p,
+                                          C.POINTER(C.c_int32)]
     L.p3d_tune_schedule.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     # host shim
     L.p3dh_scene_load.restype = C.c_void_p
@@ -462,6 +469,20 @@ class DeviceScene:
         v = C.c_float(0)
         _check(lib().p3d_scene_tree_cost(self.h, C.byref(v)), "p3d_scene_tree_cost")
         return v.value
+
+    def generate_samples(self, seed, res_x, res_y, spp, aperture):
+        """p3d_generate_samples into a numpy array (res_y, res_x, spp*spp, 4): the bits HostScene.samples / the host layer's
+        generate_samples() gives for (seed, aperture), made on the device."""
+        out = np.zeros((int(res_y), int(res_x), int(spp) * int(spp), 4), np.float32)
+        _check(lib().p3d_generate_samples(self.h, int(seed) & 0xFFFFFFFF, int(res_x), int(res_y), int(spp), float(aperture),
+                                          out.ctypes.data if out.size else None, 0), "p3d_generate_samples")
+        return out
+
+    def generate_samples_device(self, ptr, seed, res_x, res_y, spp, aperture):
+        """p3d_generate_samples into a caller-owned DEVICE buffer (raw pointer) of res_y * res_x * spp*spp * 4 floats: what
+        render_device(..., samples_ptr=ptr) reads.  Returns when the array is complete."""
+        _check(lib().p3d_generate_samples(self.h, int(seed) & 0xFFFFFFFF, int(res_x), int(res_y), int(spp), float(aperture),
+                                          C.c_void_p(int(ptr) or None), 1), "p3d_generate_samples")
 
     def set_skybox(self, faces):
         """Six uint8 arrays [H, W, 3 or 4]: right, left, top, bottom, front, back; row 0 = bottom row (Scene::LoadSkybox)."""
@@ -790,6 +811,23 @@ def debug_powf(x, y, device=0):
     out = np.zeros_like(x)
     _check(lib().p3d_debug_powf(int(device), len(x), x.ctypes.data, y.ctypes.data, out.ctypes.data), "p3d_debug_powf")
     return out
+
+
+def debug_rand(seed, first, n, device=0):
+    """The device's restatement of libc's rand() (csrc/p3d_rand.h): values number first .. first + n - 1 after srand(seed)."""
+    out = np.zeros(int(n), np.uint32)
+    _check(lib().p3d_debug_rand(int(device), int(seed) & 0xFFFFFFFF, int(first), int(n), out.ctypes.data if n else None), "p3d_debug_rand")
+    return out
+
+
+def debug_sample_stream(seed, res_x, res_y, spp, aperture, pairs_per_pass=0, device=0):
+    """The generator of p3d_generate_samples with every pass forced to pairs_per_pass pairs of draws (0: its own sizing).
+    -> (samples (res_y, res_x, spp*spp, 4), passes that ran)."""
+    out = np.zeros((int(res_y), int(res_x), int(spp) * int(spp), 4), np.float32)
+    passes = C.c_int32(0)
+    _check(lib().p3d_debug_sample_stream(int(device), int(seed) & 0xFFFFFFFF, int(res_x), int(res_y), int(spp), float(aperture),
+                                         int(pairs_per_pass), out.ctypes.data if out.size else None, C.byref(passes)), "p3d_debug_sample_stream")
+    return out, int(passes.value)
 
 
 def debug_pow(x, y, device=0):

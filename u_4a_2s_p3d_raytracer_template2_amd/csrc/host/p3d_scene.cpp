@@ -462,6 +462,19 @@ int upload_skybox(const Scene& scene, p3d_scene* dev) {
     }
     return p3d_scene_set_skybox(dev, faces, rx, ry, bpp);
 }
+
+// The sample arrays of n frames -- frame f from seed + f and cams[f].aperture: the reference draws new rand() samples per
+// frame -- made on the device by p3d_generate_samples, in the bits generate_samples() gives, into a buffer that prm then reads
+// with P3D_FLAG_DEVICE_SAMPLES: no host loop and no upload.  *buf is the caller's to p3d_device_free after the frames.
+int device_samples(p3d_scene* dev, unsigned seed, const p3d_camera* cams, int n, p3d_render_params& prm, void** buf) {
+    const size_t per = (size_t)cams[0].res_x * cams[0].res_y * prm.spp * prm.spp * 4;
+    int rc = p3d_device_alloc(dev, (uint64_t)per * n * sizeof(float), buf);
+    for (int f = 0; f < n && !rc; f++)
+        rc = p3d_generate_samples(dev, seed + (unsigned)f, cams[0].res_x, cams[0].res_y, prm.spp, cams[f].aperture, (float*)*buf + per * f, 1);
+    if (rc) return rc;
+    prm.samples = (const float*)*buf; prm.flags |= P3D_FLAG_DEVICE_SAMPLES;
+    return P3D_OK;
+}
 }  // namespace
 
 int renderScene(const Scene& scene, const RenderOptions& opt, bool want_colors, bool want_hit, RenderResult& out,
@@ -488,13 +501,13 @@ int renderScene(const Scene& scene, const RenderOptions& opt, bool want_colors, 
         prm.features |= P3D_FEATURE_SKYBOX;
     }
     prm.seed = opt.seed;
-    std::vector<float> samples;
-    if (prm.spp > 0) {
-        samples.resize((size_t)cam.res_x * cam.res_y * prm.spp * prm.spp * 4);
-        generate_samples(opt.seed, cam.res_x, cam.res_y, prm.spp, cam.aperture, samples.data());
-        prm.samples = samples.data();
-    }
-    if (opt.gpus > 1) {
+    if (opt.gpus > 1) {                // every rank uploads the one host array: the serial yardstick below
+        std::vector<float> samples;
+        if (prm.spp > 0) {
+            samples.resize((size_t)cam.res_x * cam.res_y * prm.spp * prm.spp * 4);
+            generate_samples(opt.seed, cam.res_x, cam.res_y, prm.spp, cam.aperture, samples.data());
+            prm.samples = samples.data();
+        }
         int rc = render_multi_gpu(flat, cam, prm, opt, want_colors, want_hit, out);
         return rc ? bad(rc) : P3D_OK;
     }
@@ -502,6 +515,9 @@ int renderScene(const Scene& scene, const RenderOptions& opt, bool want_colors, 
     int rc = p3d_scene_create(&flat.desc, nullptr, opt.device, &dev);
     if (rc) return bad(rc);
     if (opt.SKYBOX && (rc = upload_skybox(scene, dev)) != 0) { p3d_scene_destroy(dev); return bad(rc); }
+    void* sample_buf = nullptr;
+    auto done = [&](int code) { if (code) bad(code); if (sample_buf) p3d_device_free(dev, sample_buf); p3d_scene_destroy(dev); return code; };
+    if (prm.spp > 0 && (rc = device_samples(dev, opt.seed, &cam, 1, prm, &sample_buf)) != 0) return done(rc);
     size_t npx = (size_t)cam.res_x * cam.res_y;
     out.img_Data.assign(npx * 3, 0);
     if (want_colors) out.colors.assign(npx * 3, 0.0f);
@@ -518,9 +534,7 @@ int renderScene(const Scene& scene, const RenderOptions& opt, bool want_colors, 
     if (!rc) rc = opt.want_aov ? p3d_render_aov(dev, &cam, 1, &prm, &o, &a) : p3d_render(dev, &cam, &prm, &o);
     if (!rc) rc = p3d_timer_end(dev, &out.kernel_ms);
     if (!rc && opt.counters) rc = p3d_get_counters(dev, &out.counters);
-    if (rc) { bad(rc); p3d_scene_destroy(dev); return rc; }
-    p3d_scene_destroy(dev);
-    return P3D_OK;
+    return done(rc);
 }
 
 std::vector<Vector> orbit_eyes(Vector eye, int n, float step_deg, float d_beta_deg) {
@@ -567,17 +581,14 @@ int renderFrames(const Scene& scene, const RenderOptions& opt, const std::vector
     }
     prm.seed = opt.seed;
     const size_t npx = (size_t)cams[0].res_x * cams[0].res_y;
-    std::vector<float> samples;
-    if (prm.spp > 0) {                 // the reference draws new rand() samples per frame: frame f from seed + f
-        const size_t per = npx * prm.spp * prm.spp * 4;
-        samples.resize(per * n);
-        for (int f = 0; f < n; f++) generate_samples(opt.seed + (unsigned)f, cams[0].res_x, cams[0].res_y, prm.spp, cams[f].aperture, samples.data() + per * f);
-        prm.samples = samples.data();
-    }
     p3d_scene* dev = nullptr;
     int rc = p3d_scene_create(&flat.desc, nullptr, opt.device, &dev);
     if (rc) return bad(rc);
     if (opt.SKYBOX && (rc = upload_skybox(scene, dev)) != 0) { p3d_scene_destroy(dev); return bad(rc); }
+    // the reference draws new rand() samples per frame: frame f from seed + f
+    void* sample_buf = nullptr;
+    auto done = [&](int code) { if (code) bad(code); if (sample_buf) p3d_device_free(dev, sample_buf); p3d_scene_destroy(dev); return code; };
+    if (prm.spp > 0 && (rc = device_samples(dev, opt.seed, cams.data(), n, prm, &sample_buf)) != 0) return done(rc);
     out.img_Data.assign(npx * 3 * n, 0);
     if (want_colors) out.colors.assign(npx * 3 * n, 0.0f);
     if (want_hit) out.hit_id.assign(npx * n, -1);
@@ -588,9 +599,7 @@ int renderFrames(const Scene& scene, const RenderOptions& opt, const std::vector
     if (!rc) rc = p3d_render_frames(dev, cams.data(), n, &prm, &o);
     if (!rc) rc = p3d_timer_end(dev, &out.kernel_ms);
     if (!rc && opt.counters) rc = p3d_get_counters(dev, &out.counters);
-    if (rc) { bad(rc); p3d_scene_destroy(dev); return rc; }
-    p3d_scene_destroy(dev);
-    return P3D_OK;
+    return done(rc);
 }
 
 int traceRays(const Scene& scene, const RenderOptions& opt, const std::vector<Ray>& rays, TraceResult& out, std::string* err) {

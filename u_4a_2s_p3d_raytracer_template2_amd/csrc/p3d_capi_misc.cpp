@@ -283,4 +283,25 @@ int p3d_debug_lbvh_build(int device, uint32_t n, const float* lo3, const float* 
     return P3D_OK;
 }
 
+int p3d_debug_rand(int device, uint32_t seed, uint64_t first, uint32_t n, uint32_t* out) {
+    if (!out) return fail(P3D_ERR_ARG, "NULL argument");
+    if (n == 0) return P3D_OK;
+    DebugArg a[1] = {{nullptr, out, (size_t)n * 4}};
+    return debug_run("p3d_debug_rand", device, a, [&] { return launch_debug_rand(seed, first, n, a[0].as<uint32_t>(), nullptr); });
+}
+
+int p3d_debug_sample_stream(int device, uint32_t seed, int32_t res_x, int32_t res_y, int32_t spp, float aperture, uint64_t pairs_per_pass,
+                            float* out, int32_t* passes) {
+    if (!out || !passes) return fail(P3D_ERR_ARG, "NULL argument");
+    if (res_x < 1 || res_y < 1 || spp < 1) return fail(P3D_ERR_ARG, "res_x, res_y and spp must be at least 1");
+    const uint64_t pixels = (uint64_t)res_x * (uint64_t)res_y, per_pixel = (uint64_t)spp * (uint64_t)spp;
+    if (pixels > kMaxStackedPixels || per_pixel > kMaxStackedPixels || pixels * per_pixel > kMaxStackedPixels)
+        return fail(P3D_ERR_LIMIT, "res_x * res_y * spp * spp does not fit 31 bits");
+    SampleStreamScratch scratch;             // freed on every path
+    DebugArg a[1] = {{nullptr, out, (size_t)(pixels * per_pixel) * 4 * sizeof(float)}};
+    return debug_run("p3d_debug_sample_stream", device, a, [&] {
+        return generate_sample_stream(scratch, seed, res_x, res_y, spp, aperture, a[0].as<float>(), pairs_per_pass, passes, nullptr);
+    });
+}
+
 }  // extern "C"

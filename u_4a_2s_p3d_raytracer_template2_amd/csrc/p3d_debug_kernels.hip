@@ -6,6 +6,8 @@
 #include <stdint.h>
 
 #include "p3d_launch.h"
+#include "p3d_rand.h"
+#include "sample_stream.h"
 #include "p3d_shade.h"
 
 namespace p3d {
@@ -116,6 +118,27 @@ hipError_t launch_debug_intersect(uint32_t n, const uint32_t* type, const float*
                                   const float* dir, int32_t* hit, float* t, float* normal, hipStream_t stream) {
     hipLaunchKernelGGL(debug_intersect_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, type, prim12,
                        origin, dir, hit, t, normal);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ the restated rand(), 31 values per thread (p3d_rand.h)
+struct RandWindow { uint32_t w[2 * kRandDeg - 1]; };               // s[0 .. 60]: the seed state and the 30 words after it
+
+__global__ void __launch_bounds__(256) debug_rand_kernel(RandWindow seed_window, uint64_t first, uint32_t n, uint32_t* __restrict__ out) {
+    const uint32_t at = (blockIdx.x * 256u + threadIdx.x) * (uint32_t)kRandDeg;
+    if (at >= n) return;
+    uint32_t c[kRandDeg], st[kRandDeg];
+    rand_poly_pow((uint64_t)kRandFirstDraw + first + at, c);
+    rand_poly_apply(c, seed_window.w, kRandDeg, st);
+    for (uint32_t i = 0; i < (uint32_t)kRandDeg && at + i < n; i++) out[at + i] = st[i] >> 1;
+}
+
+hipError_t launch_debug_rand(uint32_t seed, uint64_t first, uint32_t n, uint32_t* out, hipStream_t stream) {
+    RandWindow w;
+    rand_seed_state(seed, w.w);
+    rand_extend(w.w, kRandDeg, 2 * kRandDeg - 1);
+    const uint32_t threads = (n + (uint32_t)kRandDeg - 1) / (uint32_t)kRandDeg;
+    hipLaunchKernelGGL(debug_rand_kernel, dim3((threads + 255) / 256), dim3(256), 0, stream, w, first, n, out);
     return hipGetLastError();
 }
 

@@ -1,5 +1,5 @@
 // p3d_scene_state.h -- the scene handle behind the C-ABI of include/p3d_hip.h, shared by the files that implement it
-// (p3d_scene_create.cpp, p3d_scene_update.cpp, p3d_scene_rebuild.cpp, p3d_render.cpp, p3d_capi_misc.cpp).  Internal: not installed with include/.
+// (p3d_scene_create.cpp, p3d_scene_update.cpp, p3d_scene_rebuild.cpp, p3d_render.cpp, p3d_generate_samples.cpp, p3d_capi_misc.cpp).  Internal: not installed with include/.
 // Every device resource in it is owned by a member that frees it: deleting a p3d_scene releases all of them.
 #ifndef P3D_SCENE_STATE_H
 #define P3D_SCENE_STATE_H
@@ -17,6 +17,7 @@
 #include "p3d_device_types.h"
 #include "p3d_frame_config.h"
 #include "p3d_launch.h"
+#include "sample_stream.h"
 
 extern "C" int p3d_internal_set_error(int code, const char* msg);   // p3d_capi_misc.cpp: the thread's p3d_last_error()
 
@@ -218,6 +219,8 @@ struct p3d_scene {
         p3d::RawBuf origin, dir, rgb32f, hit_id, t, normal;
         size_t budget_avail = 0; p3d::Keyed<p3d::RayStreamKey> key;
     } rays;
+    // p3d_generate_samples: jump tables and the summaries of the pass in flight (counted in device_bytes as they grow)
+    p3d::SampleStreamScratch sample_stream;
     p3d::RawBuf d_counters;              // one DeviceCounters
     bool counters_valid = false;
     p3d::TimingEvent ev0, ev1;
