@@ -449,6 +449,8 @@ typedef struct p3d_ray_outputs {  /* every plane may be NULL */
  *  - a scene created with cull_never_hit is refused with P3D_ERR_STATE: that shortcut rests on |dir| <= sqrt(2), which a
  *    caller's ray does not promise.
  *  - results for non-finite origins or directions are unspecified (the call still returns).
+ *  - the staging of host-memory rays and planes is owned by the handle, counted in p3d_scene_stats::device_bytes as it
+ *    grows and kept for the next call.
  *  - the workspace obeys the p3d_set_tuning() budget: streams that need more run in bands of rays, the way frames run in
  *    bands of rows.  A stream of 2^31 rays or more is refused with P3D_ERR_LIMIT before anything is allocated.
  *  - the handle's frame state is not touched: the measured schedule choice, the learned tile orders, p3d_last_schedule()
@@ -456,6 +458,46 @@ typedef struct p3d_ray_outputs {  /* every plane may be NULL */
  *    the frame it would have been without it. */
 int p3d_trace_rays(p3d_scene* scene, const p3d_rays* rays, const p3d_render_params* params,
                    const p3d_ray_outputs* out);
+/* Where the answers of p3d_occluded go. */
+typedef struct p3d_occlusion_outputs {
+    uint8_t* occluded;   /* [n] 1 = the shadow query answers "in shadow", 0 = not; may be NULL (the call then only validates) */
+    int32_t  memory;     /* as p3d_ray_outputs::memory: 0 = copy back and return when done, 1 = enqueue only */
+} p3d_occlusion_outputs;
+
+/* Replaces the shadow query of processLight() (RT/main.cpp:476-510) -- the other traversal of both accelerators,
+ * BVH::Traverse(Ray&) (RT/bvh.cpp:348) and Grid::Traverse(Ray&) (RT/grid.cpp:313) -- for segments the caller supplies: line
+ * of sight, light baking, ambient occlusion, portal and audio probes.  Segment i is Ray(origin[i], dir[i]) of `segments`,
+ * the "Ray(precise_hit_point, L)" processLight() builds: it ends at origin + dir.  occluded[i] is what the switch on
+ * Accel_Struct would set insideShadow to for that ray:
+ *    P3D_ACCEL_NONE  true if any primitive's intercepts() accepts the ray: the direction is used as given and there is NO
+ *                    distance bound -- a primitive beyond the segment's end occludes it
+ *    P3D_ACCEL_BVH   length = |dir|, the direction is normalised, true if a primitive is hit with t < length
+ *    P3D_ACCEL_GRID  the same bound over the reference's own grid, with its rule that a ray for which Init_Traverse fails
+ *                    -- one that misses the grid's box -- is IN SHADOW (RT/grid.cpp:327-328).  The grid is built by the
+ *                    first GRID call of a scene, this entry's included, under the rules of the first GRID frame: refused
+ *                    with P3D_ERR_STATE while the stream is being captured and after updates from device memory.
+ *   There is no L.N > 0 test: that test decides whether processLight() asks at all, and every segment here is asked.
+ *   Planes: the reference's accelerators bound a plane as [-1, 1]^3, and so do the tree and the grid here.
+ *   In BVH and GRID mode a plane occludes only where the walk reaches that box: a segment that crosses the plane away
+ *   from it is reported NOT occluded, as the reference's shadow rays are.  NONE mode tests every plane as it is.
+ *  - params: only accel and flags are read.  P3D_FLAG_NO_LDS_SCENE and P3D_FLAG_PRIVATE_WALK are honoured, P3D_FLAG_WAVEFRONT
+ *    is accepted and does nothing; every other flag is P3D_ERR_ARG.  features != 0, spp != 0, samples != NULL, world > 1
+ *    and rank != 0 are P3D_ERR_ARG.  max_depth is not read.
+ *  - P3D_ERR_ARG also for a NULL scene, segments, params or out, a NULL origin or dir with n > 0, and a memory field
+ *    outside 0 and 1.
+ *  - n >= 2^31 is P3D_ERR_LIMIT before anything is allocated; n == 0 does nothing and returns P3D_OK.
+ *  - a scene created with cull_never_hit is served in accel BVH, whose rays are unit length; NONE and GRID are
+ *    P3D_ERR_STATE (on the option itself, whatever it culled).
+ *  - asynchronous on the scene's stream; with p3d_occlusion_outputs::memory == 0 it copies back and waits, and with
+ *    p3d_rays::memory == 0 it uploads the segments first, through staging the handle owns (shared with p3d_trace_rays;
+ *    counted in p3d_scene_stats::device_bytes as either entry grows it, and kept for the next call).
+ *  - one launch, no ray queues and no workspace: the p3d_set_tuning() budget does not apply.
+ *  - results for non-finite inputs, and for a zero-length dir in BVH or GRID mode, are unspecified (the call still returns).
+ *  - the handle's frame state is not touched: the measured schedule choice, the learned tile orders, p3d_last_schedule(),
+ *    p3d_last_primary_tiles() and the ray-stream state are what they were.
+ *  - after p3d_scene_update or p3d_scene_rebuild the answers follow the moved geometry, like everything else. */
+int p3d_occluded(p3d_scene* scene, const p3d_rays* segments, const p3d_render_params* params,
+                 const p3d_occlusion_outputs* out);
 int p3d_sync(p3d_scene* scene);
 /* counters of the most recent render made with P3D_FLAG_COUNTERS (waits for it) */
 int p3d_get_counters(p3d_scene* scene, p3d_counters* out);

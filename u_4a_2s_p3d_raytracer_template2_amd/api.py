@@ -89,6 +89,11 @@ class RayOutputs(C.Structure):
                 ("memory", C.c_int32)]
 
 
+class OcclusionOutputs(C.Structure):
+    """p3d_occlusion_outputs: occluded [n] bytes (may be NULL: the call then only validates), host or device memory."""
+    _fields_ = [("occluded", C.c_void_p), ("memory", C.c_int32)]
+
+
 class PrimUpdate(C.Structure):
     """p3d_prim_update: n primitives to replace ([n][12] floats, optionally [n] scene indices) on the host (memory 0) or the
     scene's device (memory 1); lights: NULL or [n_lights][6] on the host."""
@@ -113,7 +118,7 @@ class SceneStats(C.Structure):
 
 # every symbol include/p3d_hip.h declares (tests check that the library exports them all)
 C_ABI_SYMBOLS = ["p3d_abi_version", "p3d_last_error", "p3d_device_count", "p3d_scene_create",
-                 "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_scene_update", "p3d_scene_rebuild", "p3d_scene_tree_cost", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_render_aov", "p3d_generate_samples", "p3d_trace_rays", "p3d_sync",
+                 "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_scene_update", "p3d_scene_rebuild", "p3d_scene_tree_cost", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_render_aov", "p3d_generate_samples", "p3d_trace_rays", "p3d_occluded", "p3d_sync",
                  "p3d_get_counters", "p3d_get_profile", "p3d_last_schedule", "p3d_set_tuning", "p3d_set_primary_tiles", "p3d_last_primary_tiles", "p3d_set_stream", "p3d_timer_begin", "p3d_timer_end", "p3d_deinterleave_frames",
                  "p3d_deinterleave", "p3d_debug_intersect", "p3d_debug_powf", "p3d_debug_pow", "p3d_debug_schlick_kr", "p3d_debug_check_rcp", "p3d_debug_check_rcp_len", "p3d_debug_lbvh_build", "p3d_debug_rand", "p3d_debug_sample_stream", "p3d_tune_schedule", "p3d_debug_set_stamps", "p3d_debug_set_stamp_level",
                  "p3d_comm_unique_id", "p3d_comm_create", "p3d_comm_create_all", "p3d_comm_destroy", "p3d_comm_info",
@@ -165,6 +170,7 @@ def lib():
                                  C.POINTER(AovOutputs)]
     L.p3d_generate_samples.argtypes = [C.c_void_p, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_int32]
     L.p3d_trace_rays.argtypes = [C.c_void_p, C.POINTER(Rays), C.POINTER(RenderParams), C.POINTER(RayOutputs)]
+    L.p3d_occluded.argtypes = [C.c_void_p, C.POINTER(Rays), C.POINTER(RenderParams), C.POINTER(OcclusionOutputs)]
     L.p3d_sync.argtypes = [C.c_void_p]
     L.p3d_get_counters.argtypes = [C.c_void_p, C.POINTER(Counters)]
     L.p3d_set_stream.argtypes = [C.c_void_p, C.c_void_p]
@@ -217,6 +223,7 @@ def lib():
     L.p3dh_primary_ray.argtypes = [C.c_void_p, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.p3dh_trace_rays.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.p3dh_occluded.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
     L.p3dh_generate_samples.argtypes = [C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p]
     L.p3dh_bvh_build.restype = C.c_void_p
     L.p3dh_bvh_build.argtypes = [C.POINTER(SceneDesc), C.c_uint32]
@@ -334,6 +341,13 @@ class HostScene:
         out = _ray_planes(n, RAY_PLANES)
         _check(lib().p3dh_trace_rays(self.h, n, o.ctypes.data, d.ctypes.data, int(max_depth), int(accel), 1 if soft_shadow else 0,
                                      int(device), *[out[k].ctypes.data for k in RAY_PLANES]), "traceRays")
+        return out
+
+    def occluded(self, origins, dirs, accel=ACCEL_BVH, device=0):
+        """occluded() of the C++ host layer: processLight()'s shadow query per segment on one GPU -> (n,) uint8, 1 = in shadow."""
+        o, d, n = _ray_arrays(origins, dirs)
+        out = np.zeros(n, np.uint8)
+        _check(lib().p3dh_occluded(self.h, n, o.ctypes.data, d.ctypes.data, int(accel), int(device), out.ctypes.data), "occluded")
         return out
 
     def arrays(self):
@@ -678,6 +692,26 @@ class DeviceScene:
         ro = RayOutputs(rgb32f_ptr or None, hit_ptr or None, t_ptr or None, normal_ptr or None, 1)
         p = self._ray_params(max_depth, accel, no_lds, private_walk, soft_shadow)
         _check(lib().p3d_trace_rays(self.h, C.byref(r), C.byref(p), C.byref(ro)), "p3d_trace_rays")
+
+    def occluded(self, origins, dirs, accel=ACCEL_BVH, no_lds=False, private_walk=False):
+        """p3d_occluded on host arrays: segment i = the Ray(origins[i], dirs[i]) of processLight(), ending at origins[i] +
+        dirs[i].  Returns (n,) uint8: 1 where the shadow query of `accel` answers "in shadow" (NONE: direction as given, no
+        distance bound; BVH and GRID: t < |dir|; GRID: a segment that misses the grid's box is in shadow)."""
+        o, d, n = _ray_arrays(origins, dirs)
+        out = np.zeros(n, np.uint8)
+        r = Rays(n, o.ctypes.data if n else None, d.ctypes.data if n else None, 0)
+        oo = OcclusionOutputs(out.ctypes.data if n else None, 0)
+        p = self._ray_params(1, accel, no_lds, private_walk, False)
+        _check(lib().p3d_occluded(self.h, C.byref(r), C.byref(p), C.byref(oo)), "p3d_occluded")
+        return out
+
+    def occluded_device(self, n, origin_ptr, dir_ptr, out_ptr, accel=ACCEL_BVH, no_lds=False, private_walk=False):
+        """Enqueue p3d_occluded on caller-owned DEVICE buffers (raw pointers): n segments in, n bytes out; asynchronous on
+        the scene's stream."""
+        r = Rays(int(n), origin_ptr or None, dir_ptr or None, 1)
+        oo = OcclusionOutputs(out_ptr or None, 1)
+        p = self._ray_params(1, accel, no_lds, private_walk, False)
+        _check(lib().p3d_occluded(self.h, C.byref(r), C.byref(p), C.byref(oo)), "p3d_occluded")
 
     def deinterleave_frames(self, gathered_ptr, frames_ptr, res_x, res_y, row_block, world, bpp, n_frames,
                             rank_stride_bytes=0, tile_stride_bytes=0, frame_stride_bytes=0):

@@ -82,6 +82,22 @@ int p3dh_trace_rays(const p3dh_scene* h, uint32_t n, const float* origin3, const
     return rc;
 }
 
+// occluded() of the host layer on n segments (origin3 / dir3: n x 3 floats) into out[n].  Returns its status.
+int p3dh_occluded(const p3dh_scene* h, uint32_t n, const float* origin3, const float* dir3, int32_t accel, int32_t device, uint8_t* out) {
+    std::vector<Ray> segments(n);
+    for (uint32_t i = 0; i < n; i++) {
+        segments[i].origin = Vector(origin3[3 * i], origin3[3 * i + 1], origin3[3 * i + 2]);
+        segments[i].direction = Vector(dir3[3 * i], dir3[3 * i + 1], dir3[3 * i + 2]);
+    }
+    RenderOptions opt;
+    opt.accel = accel; opt.device = device;
+    std::vector<uint8_t> res;
+    const int rc = occluded(h->scene, opt, segments, res, nullptr);
+    if (rc) return rc;
+    if (out && n) memcpy(out, res.data(), n);
+    return rc;
+}
+
 // ---- host-only BVH build, for tests that run without a GPU
 struct p3dh_bvh {
     std::vector<p3d::NodePair> nodes;

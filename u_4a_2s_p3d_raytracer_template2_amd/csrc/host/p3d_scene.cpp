@@ -635,4 +635,36 @@ int traceRays(const Scene& scene, const RenderOptions& opt, const std::vector<Ra
     return rc;
 }
 
+int occluded(const Scene& scene, const RenderOptions& opt, const std::vector<Ray>& segments, std::vector<uint8_t>& out, std::string* err) {
+    auto bad = [&](int rc) { if (err) *err = p3d_last_error(); return rc; };
+    const size_t n = segments.size();
+    if (n > 0xFFFFFFFFull) { if (err) *err = "too many segments"; return P3D_ERR_LIMIT; }
+    Scene::Flat flat;
+    scene.flatten(flat);
+    p3d_render_params prm;
+    memset(&prm, 0, sizeof prm);
+    prm.accel = opt.accel < 0 ? (int)scene.GetAccelStruct() : opt.accel;
+    prm.world = 1;
+    prm.flags = opt.counters ? P3D_FLAG_COUNTERS : 0;           // (refused by the library, like the switches below)
+    prm.features = (opt.SOFT_SHADOW ? P3D_FEATURE_SOFT_SHADOW : 0u) | (opt.FUZZY_REFLECTION ? P3D_FEATURE_FUZZY_REFLECTION : 0u) |
+                   (opt.SCHLICK_APPROX ? P3D_FEATURE_SCHLICK : 0u) | (opt.SKYBOX ? P3D_FEATURE_SKYBOX : 0u);
+    std::vector<float> origin(3 * n), dir(3 * n);
+    for (size_t i = 0; i < n; i++) {
+        origin[3 * i] = segments[i].origin.x; origin[3 * i + 1] = segments[i].origin.y; origin[3 * i + 2] = segments[i].origin.z;
+        dir[3 * i] = segments[i].direction.x; dir[3 * i + 1] = segments[i].direction.y; dir[3 * i + 2] = segments[i].direction.z;
+    }
+    out.assign(n, 0);
+    p3d_scene* dev = nullptr;
+    int rc = p3d_scene_create(&flat.desc, nullptr, opt.device, &dev);
+    if (rc) return bad(rc);
+    p3d_rays r;
+    r.n = (uint32_t)n; r.origin = origin.data(); r.dir = dir.data(); r.memory = 0;
+    p3d_occlusion_outputs o;
+    o.occluded = out.data(); o.memory = 0;
+    rc = p3d_occluded(dev, &r, &prm, &o);
+    if (rc) bad(rc);
+    p3d_scene_destroy(dev);
+    return rc;
+}
+
 }  // namespace p3d_host

@@ -275,5 +275,12 @@ struct TraceResult {
 };
 int traceRays(const Scene& scene, const RenderOptions& opt, const std::vector<Ray>& rays, TraceResult& out, std::string* err = nullptr);
 
+// The shadow query of processLight() (RT/main.cpp:476-510) as one call: segment i of `segments` is the
+// Ray(precise_hit_point, L) it builds -- it ends at origin + direction -- and out[i] is 1 where the switch on Accel_Struct
+// would set insideShadow, through p3d_occluded on one device.  From opt: accel (NONE: direction as given, no distance bound;
+// BVH and GRID: normalised, t < |L|; GRID: a segment that misses the grid's box is in shadow) and device; the feature
+// switches and counters are refused as p3d_occluded refuses them.
+int occluded(const Scene& scene, const RenderOptions& opt, const std::vector<Ray>& segments, std::vector<uint8_t>& out, std::string* err = nullptr);
+
 }  // namespace p3d_host
 #endif

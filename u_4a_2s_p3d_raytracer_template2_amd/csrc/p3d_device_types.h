@@ -209,6 +209,14 @@ struct RayStreamIO {
     uint32_t count;
 };
 
+// The segments of p3d_occluded and where their answers go (wf_occlusion_kernel), next to the launch parameters like a ray
+// stream's: segment i is origin / dir record i (12 bytes each), occluded[i] one byte, 1 = in shadow.
+struct OcclusionIO {
+    const float* origin; const float* dir;
+    uint8_t* occluded;
+    uint32_t count;
+};
+
 // Every level of a pass for the fused resolve launch (small frames / shards, wf_resolve_fused_kernel): level l's
 // parked nodes (shard s at nodes[l] + s * cap[l]) and their per-shard counts; levels top .. 1 are combined.
 struct ResolveLevels { NodeRec* nodes[18]; const uint32_t* ncount[18]; uint32_t cap[18]; int32_t top; };

@@ -27,9 +27,10 @@ struct KernelVariant {
     }
 };
 
-// The level kernels: wf_primary_kernel, wf_secondary_kernel (no BATCH: the deeper levels are shared), wf_tile_kernel, and
-// wf_rays_kernel: level 1 of a ray stream (p3d_trace_rays).
-enum class Level { Primary, Secondary, Tile, Rays };
+// The level kernels: wf_primary_kernel, wf_secondary_kernel (no BATCH: the deeper levels are shared), wf_tile_kernel,
+// wf_rays_kernel: level 1 of a ray stream (p3d_trace_rays), and wf_occlusion_kernel: the shadow query on the caller's
+// segments (p3d_occluded).
+enum class Level { Primary, Secondary, Tile, Rays, Occlusion };
 constexpr int kMaxPrimaryTiles = 3;
 // what a handle asks for until p3d_set_primary_tiles() says otherwise: 2 measured 2.4 % faster than 1 on the 1080p frame of
 // mount_low with four frames in flight, 3 measured 1.6 % (profiles/r06_primary_tiles.txt)
@@ -49,11 +50,13 @@ constexpr bool has_aov(Level k) { return k == Level::Primary || k == Level::Tile
 // The ray-stream level-1 kernel is built per scene placement and walk and nothing else: the per-lane, grid and shared walks
 // (a packet request gets the per-lane walk), at the register budget frames run their level kernels at by default.
 constexpr int kRaysOcc = 6;
+// The occlusion kernel is built by the same rule: five builds, LDS x {lane, grid} and HBM x {lane, shared, grid}.
+constexpr bool caller_rays(Level k) { return k == Level::Rays || k == Level::Occlusion; }
 // the build of level kernel k that serves request v
 constexpr KernelVariant canonical_level(KernelVariant v, Level k) {
     if (k == Level::Secondary) v.batch = false;
     if (!has_aov(k)) v.aov = false;
-    if (k == Level::Rays) {
+    if (caller_rays(k)) {
         v.count = v.stoch = v.schlick = v.batch = false;
         v.occ = kRaysOcc;
         if (v.walk == WALK_PACKET) v.walk = WALK_LANE;
@@ -68,7 +71,7 @@ constexpr KernelVariant canonical_level(KernelVariant v, Level k) {
 constexpr bool built_level(const KernelVariant& v, Level k) {
     if (v.batch && k == Level::Secondary) return false;
     if (v.aov && !has_aov(k)) return false;
-    if (k == Level::Rays && (v.count || v.stoch || v.schlick || v.batch || v.walk == WALK_PACKET || v.occ != (v.walk == WALK_GRID ? 1 : kRaysOcc)))
+    if (caller_rays(k) && (v.count || v.stoch || v.schlick || v.batch || v.walk == WALK_PACKET || v.occ != (v.walk == WALK_GRID ? 1 : kRaysOcc)))
         return false;
     if (v.walk == WALK_SHARED && v.lds) return false;
     if (v.tiles != 1 && (v.tiles < 2 || v.tiles > kMaxPrimaryTiles || !has_primary_tiles(v, k))) return false;

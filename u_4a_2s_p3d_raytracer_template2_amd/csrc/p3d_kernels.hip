@@ -609,6 +609,34 @@ __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void wf_rays_kernel(co
     emit<true>(P, sh, 1, valid, i, 1.0f, o);
 }
 
+// The shadow query of processLight() on segments the caller supplies (p3d_occluded): segment i is Ray(origin[i], dir[i]), the
+// "Ray(precise_hit_point, L)" of RT/main.cpp:478, and occluded[i] what the switch below it sets insideShadow to.  The query is
+// the frames' own: shadow_segment() and light_occluded() of p3d_shade.h, with "the lane has a segment" as need (the L.N > 0
+// test is the caller's).  One segment per lane, consecutive 12-byte records as in wf_rays_kernel, one byte written per
+// segment; no queues, no control words, no counters, nothing of a frame.  Workgroup b takes the blockDim.x consecutive
+// segments from b * blockDim.x on.  Lanes past the last segment neither read nor write; they stay for the wave-wide walk.
+// One build per scene placement and walk (p3d_kernel_variant.h: Level::Occlusion).
+// (A workgroup looping over several batches, on a grid sized from the resident workgroups, so that a scene served from LDS
+//  is copied once per workgroup and not once per 256 segments, was measured and dropped: no faster at 2 and 4 x the resident
+//  workgroups, 1 - 3 % slower at 1 x; profiles/occlusion_cost.txt.)
+template <bool LDS, int WALK, int OCC>
+__global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void wf_occlusion_kernel(const LaunchParams P, const OcclusionIO R) {
+    const typename View<LDS>::type sv = View<LDS>::make(P);
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;    // (the host keeps n below 2^31)
+    const bool valid = i < R.count;
+    if (__ballot(valid) == 0) return;                            // no barrier follows the scene copy's
+    const TravCtx tc = wave_stack<LDS>(P, 0);
+    Ctr ctr = {0, 0, 0, 0, 0, 0, 0};
+    V3 o = mk(0.0f, 0.0f, 0.0f), L = mk(1.0f, 0.0f, 0.0f);
+    if (valid) {
+        const float* po = R.origin + 3 * (size_t)i;
+        const float* pd = R.dir + 3 * (size_t)i;
+        o = mk(po[0], po[1], po[2]); L = mk(pd[0], pd[1], pd[2]);
+    }
+    const bool occluded = light_occluded<false, WALK>(P, sv, shadow_segment(L), o, valid, tc, ctr);
+    if (valid) R.occluded[i] = occluded ? 1 : 0;
+}
+
 // Lanes a wave of a deeper level uses: a short queue is spread over ALL the shard's waves with
 // fewer rays each instead of filling 64-wide waves.  Deeper levels hold few, incoherent rays and
 // are bound by the latency of one wave's ray step, not by issue slots: narrow waves diverge less
@@ -1247,6 +1275,7 @@ constexpr bool variants_are_consistent(int first, int last) {
             v.tiles = kMaxPrimaryTiles;                 // (only the level-1 kernel has the variant)
             if (!built_level(canonical_level(v, Level::Tile), Level::Tile) || !built_level(canonical_level(v, Level::Secondary), Level::Secondary)) return false;
             if (!built_level(canonical_level(v, Level::Rays), Level::Rays)) return false;
+            if (!built_level(canonical_level(v, Level::Occlusion), Level::Occlusion)) return false;
             for (int tiles = 0; tiles <= kMaxPrimaryTiles + 1; tiles++) {
                 v.tiles = tiles;
                 if (!built_level(canonical_level(v, Level::Primary), Level::Primary)) return false;
@@ -1257,7 +1286,7 @@ constexpr bool variants_are_consistent(int first, int last) {
         }
         KernelVariant v = variant_at(i);
         for (v.tiles = kMaxPrimaryTiles; v.tiles >= 1; v.tiles--)
-            for (Level k : {Level::Primary, Level::Secondary, Level::Tile, Level::Rays})
+            for (Level k : {Level::Primary, Level::Secondary, Level::Tile, Level::Rays, Level::Occlusion})
                 if (built_level(v, k) && !(canonical_level(v, k) == v)) return false;
         v.tiles = 1;
         for (int priv : kPrivs)
@@ -1272,8 +1301,9 @@ P3D_VARIANTS_CONSISTENT(0); P3D_VARIANTS_CONSISTENT(1); P3D_VARIANTS_CONSISTENT(
 #undef P3D_VARIANTS_CONSISTENT
 
 using RaysKernelFn = void (*)(const LaunchParams, const RayStreamIO);
+using OcclusionKernelFn = void (*)(const LaunchParams, const OcclusionIO);
 template <Level KERNEL> struct LevelKernels {       // position: variant_index * per_variant + (TILES - 1)
-    using Fn = std::conditional_t<KERNEL == Level::Rays, RaysKernelFn, KernelFn>;
+    using Fn = std::conditional_t<KERNEL == Level::Rays, RaysKernelFn, std::conditional_t<KERNEL == Level::Occlusion, OcclusionKernelFn, KernelFn>>;
     static constexpr Level level = KERNEL;
     static constexpr int per_variant = KERNEL == Level::Primary ? kMaxPrimaryTiles : 1;
     static constexpr int n = kLevelVariants * per_variant;
@@ -1285,6 +1315,7 @@ template <Level KERNEL> struct LevelKernels {       // position: variant_index *
         else if constexpr (KERNEL == Level::Primary) return wf_primary_kernel<v.count, v.lds, v.walk, v.occ, v.stoch, v.schlick, v.batch, v.aov>;
         else if constexpr (KERNEL == Level::Secondary) return wf_secondary_kernel<v.count, v.lds, v.walk, v.occ, v.stoch, v.schlick>;
         else if constexpr (KERNEL == Level::Rays) return wf_rays_kernel<v.lds, v.walk, v.occ>;
+        else if constexpr (KERNEL == Level::Occlusion) return wf_occlusion_kernel<v.lds, v.walk, v.occ>;
         else return wf_tile_kernel<v.count, v.lds, v.walk, v.occ, v.stoch, v.schlick, v.batch, v.aov>;
     }
 };
@@ -1378,6 +1409,19 @@ hipError_t launch_wf_rays(const LaunchParams& P, const RayStreamIO& R, const Ker
     RayStreamIO Rc = R;
     void* args[] = {&Pc, &Rc};
     return hipLaunchKernel(fn, dim3((unsigned)P.wf_tile_rows), dim3(64 * P.wg_waves), args, shmem, stream);
+}
+// p3d_occluded: one workgroup per 64 * wg_waves segments (wf_occlusion_kernel)
+hipError_t launch_wf_occlusion(const LaunchParams& P, const OcclusionIO& R, const KernelVariant& v, hipStream_t stream) {
+    const void* fn = level_kernel<LevelKernels<Level::Occlusion>>(v);
+    if (!fn) return hipErrorInvalidDeviceFunction;
+    const size_t shmem = wavefront_lds_bytes(P, v.lds);
+    hipError_t e = allow_lds(fn, shmem);
+    if (e != hipSuccess) return e;
+    LaunchParams Pc = P;
+    OcclusionIO Rc = R;
+    void* args[] = {&Pc, &Rc};
+    const unsigned per_batch = 64u * (unsigned)P.wg_waves;
+    return hipLaunchKernel(fn, dim3((R.count + per_batch - 1) / per_batch), dim3(per_batch), args, shmem, stream);
 }
 hipError_t launch_wf_secondary(const LaunchParams& P, const KernelVariant& v, unsigned waves, hipStream_t stream) {
     return launch_by_pointer(level_kernel<LevelKernels<Level::Secondary>>(v), P, dim3((waves + P.wg_waves - 1) / P.wg_waves),

@@ -23,6 +23,7 @@ size_t tile_kernel_lds_bytes(const LaunchParams& P, bool lds);
 hipError_t launch_tree(const LaunchParams& P, const KernelVariant& v, hipStream_t stream);
 hipError_t launch_wf_primary(const LaunchParams& P, const KernelVariant& v, hipStream_t stream);
 hipError_t launch_wf_rays(const LaunchParams& P, const RayStreamIO& R, const KernelVariant& v, hipStream_t stream);
+hipError_t launch_wf_occlusion(const LaunchParams& P, const OcclusionIO& R, const KernelVariant& v, hipStream_t stream);
 hipError_t launch_wf_secondary(const LaunchParams& P, const KernelVariant& v, unsigned waves, hipStream_t stream);
 hipError_t launch_wf_tile(const LaunchParams& P, const KernelVariant& v, unsigned blocks, hipStream_t stream);
 hipError_t wf_resident_waves(const LaunchParams& P, const KernelVariant& v, unsigned* waves);

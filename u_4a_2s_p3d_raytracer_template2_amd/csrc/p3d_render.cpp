@@ -1,5 +1,5 @@
-// p3d_render.cpp -- p3d_render, p3d_render_frames, p3d_render_aov, p3d_trace_rays and p3d_tune_schedule of include/p3d_hip.h: a frame (or a
-// batch of frames, or a stream of the caller's rays) as a sequence of steps -- validate the request, fill the launch
+// p3d_render.cpp -- p3d_render, p3d_render_frames, p3d_render_aov, p3d_trace_rays, p3d_occluded and p3d_tune_schedule of include/p3d_hip.h: a frame (or a
+// batch of frames, or a stream of the caller's rays, or their shadow queries) as a sequence of steps -- validate the request, fill the launch
 // parameters, size the workspaces, choose the schedule, enqueue it.  The kernels are those of p3d_kernels.hip (p3d_launch.h).
 #include <chrono>
 #include <cstdio>
@@ -826,6 +826,16 @@ int render_batch(p3d_scene* s, const p3d_camera* cams, int32_t n_frames, const p
     return P3D_OK;
 }
 
+// A staging buffer of the ray-stream state (p3d_scene::rays), counted in p3d_scene_stats::device_bytes at whatever size it
+// has after the call: p3d_trace_rays and p3d_occluded share origin / dir, so both grow them here and the count does not
+// depend on which came first (a failed allocation leaves the buffer empty and counted as such).
+hipError_t ensure_counted(p3d_scene* s, RawBuf& b, size_t bytes) {
+    s->stats.device_bytes -= b.cap;
+    const hipError_t e = b.ensure(bytes);
+    s->stats.device_bytes += b.cap;
+    return e;
+}
+
 // rayTracing(ray, 1, 1.0) on n rays of the caller's: the wavefront schedule with wf_rays_kernel as its level 1.  The same
 // steps as render_batch -- the scene into the launch parameters, a workspace plan, run_wavefront -- without a camera, a
 // schedule choice, a tile order or anything else a frame remembers: what a stream keeps between calls is in s->rays.
@@ -856,7 +866,7 @@ int trace_rays(p3d_scene* s, const p3d_rays* rays, const p3d_render_params* prm,
     io.count = rays->n; io.origin = rays->origin; io.dir = rays->dir; io.t = nullptr; io.normal = nullptr;
     plan.rays = &io;
     if (rays->memory != 1) {
-        HIP_TRY(rs.origin.ensure(n * 12)); HIP_TRY(rs.dir.ensure(n * 12));
+        HIP_TRY(ensure_counted(s, rs.origin, n * 12)); HIP_TRY(ensure_counted(s, rs.dir, n * 12));
         HIP_TRY(hipMemcpyAsync(rs.origin.p, rays->origin, n * 12, hipMemcpyHostToDevice, s->stream));
         HIP_TRY(hipMemcpyAsync(rs.dir.p, rays->dir, n * 12, hipMemcpyHostToDevice, s->stream));
         io.origin = (const float*)rs.origin.p; io.dir = (const float*)rs.dir.p;
@@ -864,10 +874,10 @@ int trace_rays(p3d_scene* s, const p3d_rays* rays, const p3d_render_params* prm,
     if (out->memory == 1) {
         P.rgb32f = out->rgb32f; P.hit_id = out->hit_id; io.t = out->t; io.normal = out->normal;
     } else {
-        if (out->rgb32f) { HIP_TRY(rs.rgb32f.ensure(n * 12)); P.rgb32f = (float*)rs.rgb32f.p; }
-        if (out->hit_id) { HIP_TRY(rs.hit_id.ensure(n * 4)); P.hit_id = (int32_t*)rs.hit_id.p; }
-        if (out->t) { HIP_TRY(rs.t.ensure(n * 4)); io.t = (float*)rs.t.p; }
-        if (out->normal) { HIP_TRY(rs.normal.ensure(n * 12)); io.normal = (float*)rs.normal.p; }
+        if (out->rgb32f) { HIP_TRY(ensure_counted(s, rs.rgb32f, n * 12)); P.rgb32f = (float*)rs.rgb32f.p; }
+        if (out->hit_id) { HIP_TRY(ensure_counted(s, rs.hit_id, n * 4)); P.hit_id = (int32_t*)rs.hit_id.p; }
+        if (out->t) { HIP_TRY(ensure_counted(s, rs.t, n * 4)); io.t = (float*)rs.t.p; }
+        if (out->normal) { HIP_TRY(ensure_counted(s, rs.normal, n * 12)); io.normal = (float*)rs.normal.p; }
     }
     if ((rc = run_wavefront(s, cfg, plan, n, false, nullptr)) != P3D_OK) return rc;
     if (out->memory != 1) {
@@ -880,9 +890,76 @@ int trace_rays(p3d_scene* s, const p3d_rays* rays, const p3d_render_params* prm,
     return P3D_OK;
 }
 
+// All argument checks of p3d_occluded, in the order include/p3d_hip.h lists them; cfg is the normalised request: a depth-1
+// configuration without features, of which fill_scene_params() reads accel and flags.
+int validate_occlusion_request(const p3d_scene* s, const p3d_rays* seg, const p3d_render_params* prm, const p3d_occlusion_outputs* out,
+                               FrameConfig& cfg) {
+    if (!s || !seg || !prm || !out) return fail(P3D_ERR_ARG, "NULL argument");
+    if (seg->n > 0 && (!seg->origin || !seg->dir)) return fail(P3D_ERR_ARG, "origin / dir is NULL with n > 0");
+    if (seg->memory != 0 && seg->memory != 1) return fail(P3D_ERR_ARG, "p3d_rays::memory must be 0 (host) or 1 (device)");
+    if (out->memory != 0 && out->memory != 1) return fail(P3D_ERR_ARG, "p3d_occlusion_outputs::memory must be 0 (host) or 1 (device)");
+    if (prm->accel < 0 || prm->accel > 2) return fail(P3D_ERR_ARG, "accel must be 0, 1 or 2");
+    if (prm->flags & ~kRayStreamFlags)
+        return fail(P3D_ERR_ARG, "an occlusion query accepts P3D_FLAG_NO_LDS_SCENE, _PRIVATE_WALK and _WAVEFRONT only");
+    if (prm->features != 0) return fail(P3D_ERR_ARG, "an occlusion query has no features: a caller who wants the 4x4 sub-lights supplies 16 segments");
+    if (prm->spp != 0) return fail(P3D_ERR_ARG, "an occlusion query has no pixel samples: spp must be 0");
+    if (prm->samples) return fail(P3D_ERR_ARG, "an occlusion query has no pixel samples: samples must be NULL");
+    if (prm->world > 1 || prm->rank != 0) return fail(P3D_ERR_ARG, "an occlusion query is not sharded: world must be 0 or 1 and rank 0");
+    if ((uint64_t)seg->n > kMaxStackedPixels) return fail(P3D_ERR_LIMIT, "an occlusion query must stay below 2^31 segments");
+    // a culled scene answers unit-length rays only: BVH mode normalises the direction, NONE uses it as given, and GRID walks
+    // the reference's grid over ALL primitives.  Refused on the option, like ray streams, not on what it happened to cull.
+    if (s->cull_never_hit && prm->accel != P3D_ACCEL_BVH)
+        return fail(P3D_ERR_STATE, "scene was built with cull_never_hit: occlusion queries are served in accel BVH only (unit-length rays)");
+    cfg.max_depth = 1; cfg.accel = prm->accel; cfg.spp = 0;
+    cfg.flags = prm->flags & kConfigFlags; cfg.features = 0;
+    return P3D_OK;
+}
+
+// processLight()'s shadow query on n segments of the caller's: the scene into the launch parameters as for any entry, then
+// ONE launch of wf_occlusion_kernel, a workgroup per 64 * wg_waves segments.  No ray queues, no workspace, no schedule: of
+// the handle it touches the ray-stream staging (host memory only) and the grid of the first GRID call.
+int occluded(p3d_scene* s, const p3d_rays* seg, const p3d_render_params* prm, const p3d_occlusion_outputs* out) {
+    FrameConfig cfg;
+    int rc = validate_occlusion_request(s, seg, prm, out, cfg);
+    if (rc) return rc;
+    const size_t n = seg->n;
+    if (n == 0 || !out->occluded) return P3D_OK;
+    HIP_TRY(hipSetDevice(s->device));
+
+    FramePlan plan;
+    plan.s = s;
+    if ((rc = fill_scene_params(s, cfg, prm, plan)) != P3D_OK) return rc;
+    const LaunchParams& P = plan.P;
+    if (wavefront_lds_bytes(P, plan.lds_scene) > kMaxLdsBytes) return fail(P3D_ERR_LIMIT, "BVH depth needs more LDS than a CU has");
+
+    p3d_scene::RayStream& rs = s->rays;
+    OcclusionIO io;
+    io.count = seg->n; io.origin = seg->origin; io.dir = seg->dir; io.occluded = out->occluded;
+    if (seg->memory != 1) {
+        HIP_TRY(ensure_counted(s, rs.origin, n * 12)); HIP_TRY(ensure_counted(s, rs.dir, n * 12));
+        HIP_TRY(hipMemcpyAsync(rs.origin.p, seg->origin, n * 12, hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(hipMemcpyAsync(rs.dir.p, seg->dir, n * 12, hipMemcpyHostToDevice, s->stream));
+        io.origin = (const float*)rs.origin.p; io.dir = (const float*)rs.dir.p;
+    }
+    if (out->memory != 1) {
+        HIP_TRY(ensure_counted(s, rs.occluded, n));
+        io.occluded = (uint8_t*)rs.occluded.p;
+    }
+    HIP_TRY(launch_wf_occlusion(P, io, plan.kv, s->stream));
+    if (out->memory != 1) {
+        HIP_TRY(hipMemcpyAsync(out->occluded, io.occluded, n, hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+    }
+    return P3D_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int p3d_occluded(p3d_scene* s, const p3d_rays* segments, const p3d_render_params* prm, const p3d_occlusion_outputs* out) {
+    return occluded(s, segments, prm, out);
+}
 
 int p3d_trace_rays(p3d_scene* s, const p3d_rays* rays, const p3d_render_params* prm, const p3d_ray_outputs* out) {
     return trace_rays(s, rays, prm, out);

@@ -212,11 +212,12 @@ struct p3d_scene {
     // configuration changes, so that several scene handles, or a framework holding most of the HBM, shrink the
     // bands / fall back to another schedule instead of failing in hipMalloc
     size_t budget_avail = 0; p3d::Keyed<p3d::BudgetKey> budget_key;
-    // Ray streams (p3d_trace_rays) keep their state apart from the frames': staging for host rays and host outputs, and their
-    // own reading of the budget.  Nothing above is keyed on, or changed by, a stream (the workspaces ws[0] are scratch that
+    // Ray streams (p3d_trace_rays) keep their state apart from the frames': staging for host rays and host outputs (counted
+    // in device_bytes as it grows), and their own reading of the budget.  Nothing above is keyed on, or changed by, a stream (the workspaces ws[0] are scratch that
     // only grows; the occupancy cache wf_occ is keyed by the build it describes).
     struct RayStream {
         p3d::RawBuf origin, dir, rgb32f, hit_id, t, normal;
+        p3d::RawBuf occluded;                // p3d_occluded stages host segments in origin / dir and host answers here
         size_t budget_avail = 0; p3d::Keyed<p3d::RayStreamKey> key;
     } rays;
     // p3d_generate_samples: jump tables and the summaries of the pass in flight (counted in device_bytes as they grow)

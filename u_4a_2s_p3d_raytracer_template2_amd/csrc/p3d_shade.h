@@ -84,15 +84,26 @@ __device__ __forceinline__ Hit find_closest(const LaunchParams& P, const SV& sv,
     return h;
 }
 
-// Shadow query of processLight() (RT/main.cpp:476-510).  `need` = this lane builds a shadow
-// ray (L.N > 0).  NONE: un-normalised direction L, no distance bound; BVH/GRID: normalised
-// direction Ln and t < len = |L| (BVH::Traverse(Ray&), RT/bvh.cpp:351-352).
+// The segment of a shadow query, Ray(point, L) of processLight(): L as given, |L| and L / |L| once.  The frames' light loop
+// (shade_hit) and the caller's segments (p3d_occluded: wf_occlusion_kernel) both form it here.
+struct ShadowSeg { V3 L; float len; V3 Ln; };
+__device__ __forceinline__ ShadowSeg shadow_segment(V3 L) {
+    ShadowSeg g; g.L = L;
+    g.len = vlen(L);
+    g.Ln = mul(L, rcp_len(g.len));                                   // normalized(L)
+    return g;
+}
+// Shadow query of processLight() (RT/main.cpp:476-510) for the segment g that starts at `precise`.  `need` = this lane
+// builds a shadow ray (frames: L.N > 0; p3d_occluded: the lane has a segment).  NONE: un-normalised direction L, no distance
+// bound; BVH/GRID: normalised direction Ln and t < len = |L| (BVH::Traverse(Ray&), RT/bvh.cpp:351-352).
+// (g by value: taken by reference, every frame kernel with the per-lane walk came out of the compiler ten instructions
+//  shorter and otherwise ordered -- and the frame kernels are to stay the builds the registered profiles describe)
 template <bool COUNT, int WALK, class SV>
-__device__ __forceinline__ bool light_occluded(const LaunchParams& P, const SV& sv, V3 L, V3 Ln, float len, V3 precise, bool need,
+__device__ __forceinline__ bool light_occluded(const LaunchParams& P, const SV& sv, const ShadowSeg g, V3 precise, bool need,
                                                const TravCtx& tc, Ctr& ctr) {
     const bool bounded = WALK == WALK_GRID || P.accel != 0;
-    Ray sr; sr.o = precise; sr.d = bounded ? Ln : L;
-    const float length = bounded ? len : 0.0f;
+    Ray sr; sr.o = precise; sr.d = bounded ? g.Ln : g.L;
+    const float length = bounded ? g.len : 0.0f;
     if (WALK == WALK_PACKET) return any_hit_packet<COUNT>(P, sv, sr, need, bounded, length, tc.wave, ctr);
     if (WALK == WALK_SHARED) return any_shared<COUNT>(P, sv, sr, need, bounded, length, tc, ctr);
     if (WALK == WALK_GRID) return need ? grid_any<COUNT>(P, sv, sr, length, ctr) : false;   // Grid::Traverse(Ray&), RT/grid.cpp:313
@@ -244,18 +255,16 @@ __device__ __forceinline__ NodeOut shade_hit(const LaunchParams& P, const SV& sv
     for (uint32_t i = 0; i < P.n_lights; i++) {
         const float4* lp = reinterpret_cast<const float4*>(P.lights + i);
         const float4 lpos = lp[0];
-        const V3 L = sub(light_position<STOCH>(P, lpos, i, rng, sample), hit_point);
-        const float len = vlen(L);
-        const V3 Ln = mul(L, rcp_len(len));                               // normalized(L)
+        const ShadowSeg g = shadow_segment(sub(light_position<STOCH>(P, lpos, i, rng, sample), hit_point));
 #ifdef P3D_DEBUG_SKIP
-        const bool need = hit && dot(L, normal) > 0.0f && P.dbg_skip != 2u;
+        const bool need = hit && dot(g.L, normal) > 0.0f && P.dbg_skip != 2u;
 #else
-        const bool need = hit && dot(L, normal) > 0.0f;                  // RT/main.cpp:476
+        const bool need = hit && dot(g.L, normal) > 0.0f;                // RT/main.cpp:476
 #endif
-        const bool occluded = light_occluded<COUNT, WALK>(P, sv, L, Ln, len, precise, need, tc, ctr);
+        const bool occluded = light_occluded<COUNT, WALK>(P, sv, g, precise, need, tc, ctr);
         if (hit && !occluded) {
             const float4 lcol = lp[1];
-            light_term(sv, Ln, mk(lcol.x, lcol.y, lcol.z), color, load_material(sv, h.mat), ray, normal);
+            light_term(sv, g.Ln, mk(lcol.x, lcol.y, lcol.z), color, load_material(sv, h.mat), ray, normal);
         }
     }
     if (!hit) {
