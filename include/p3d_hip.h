@@ -253,7 +253,9 @@ typedef struct p3d_prim_update {
  *  - tree quality: the tree keeps the topology it was built with, so its quality degrades as primitives move away from
  *    where they were; frames stay equal and get slower.  p3d_scene_rebuild (below) is the remedy.  The statistics keep
  *    creation's sah_cost; device_bytes grows by what the first update allocates (f32 nodes of scenes read from HBM, one
- *    parent and one counter word per node pair, staging for host-memory updates).
+ *    parent and one counter word per node pair, staging for host-memory updates).  The first update from DEVICE memory also
+ *    allocates GRID mode's box of every primitive, 24 bytes each (what p3d_scene_build_grid builds from); every update
+ *    after it, from either memory, keeps those boxes current in the kernel that writes the records.
  *  - ordering: runs after everything already enqueued on the scene's stream, and returns when scene and tree are
  *    consistent; it waits on the device (the root's boxes come back to set the quantisation grid).
  *  - stream capture: refused with P3D_ERR_STATE while the stream is being captured.  A graph captured BEFORE an update
@@ -267,7 +269,8 @@ typedef struct p3d_prim_update {
  *  - GRID mode: the uniform grid's shape is observable (RT/grid.cpp:265-309), so the update drops the built grid and the
  *    next GRID frame builds it again from the new points, under the rule of the first GRID frame (p3d_scene_create).
  *    The host needs the points for that: after an update from DEVICE memory, GRID-mode frames and ray streams are refused
- *    with P3D_ERR_STATE until updates from host memory have covered those primitives.  BVH and NONE mode have no such limit.
+ *    with P3D_ERR_STATE until updates from host memory have covered those primitives, or call p3d_scene_build_grid (below),
+ *    which builds the grid on the device.  BVH and NONE mode have no such limit.
  *  - lights: all of them are replaced; the 4x4 sub-lights of P3D_FEATURE_SOFT_SHADOW follow on next use.
  *  - the handle's other state stays: the measured schedule choice, the learned tile orders (predictions, never results),
  *    p3d_last_schedule() and the ray-stream state.  A frame after an update measures nothing again. */
@@ -297,7 +300,8 @@ typedef struct p3d_rebuild_info {
  *  - what changes: the order of the records inside the handle (leaf order of the new tree), the map from scene index to
  *    record, leaf records, node arrays and the quantisation grid; of p3d_scene_stats n_nodes, n_leaves, n_leaf_refs,
  *    max_depth, sah_cost and device_bytes; the refit state (the next p3d_scene_update climbs the new topology).  A built
- *    uniform grid is dropped, as by an update: the next GRID frame builds it again.
+ *    uniform grid is dropped, as by an update: the next GRID frame builds it again (after updates from device memory it is
+ *    refused as before the rebuild: cover those primitives from host memory, or call p3d_scene_build_grid).
  *  - ordering: runs after everything already enqueued on the scene's stream, waits on the device and returns when the handle
  *    is consistent; what the handle held before is freed only after that wait.
  *  - stream capture: refused with P3D_ERR_STATE while the stream is being captured.  A graph captured BEFORE a rebuild must be
@@ -318,6 +322,44 @@ int p3d_scene_rebuild(p3d_scene* scene, p3d_rebuild_info* info);
  * handle read from HBM that was never updated nor rebuilt has no such pairs and has not moved: it answers creation's
  * sah_cost.  Synchronous; refused with P3D_ERR_STATE while the stream is being captured.  P3D_ERR_ARG: NULL scene or sah_cost. */
 int p3d_scene_tree_cost(p3d_scene* scene, float* sah_cost);
+
+/* What p3d_scene_build_grid did, and the grid the handle holds after it. */
+typedef struct p3d_grid_info {
+    uint32_t built;            /* 1 = this call built the grid; 0 = the handle already had one (nothing done) */
+    int32_t  n[3];             /* cells per axis, Grid::Build's nx ny nz */
+    float    mn[3], mx[3];     /* the grid's box (scene bounds -/+ EPSILON) */
+    uint64_t n_cells, n_items; /* cells, and primitive references over all cells */
+} p3d_grid_info;
+/* GRID mode's half of "move on the device, never go back to the host": the reference's uniform grid (Grid::Build,
+ * RT/grid.cpp:30-98) is built on the device from what the handle holds there.  Opt-in: without this call the grid is built
+ * lazily on the host by the first GRID call, with the refusals described under p3d_scene_update.  info may be NULL.
+ *  - resulting state: the handle has the grid the host build would make of the current geometry -- the same cells per axis,
+ *    the same box, and the same two arrays in every word (the grid's shape is observable: hits are accepted per cell,
+ *    RT/grid.cpp:265-309), its items references in the handle's current numbering, in scene order inside every cell.  GRID-mode
+ *    p3d_render, p3d_render_frames, p3d_render_aov, p3d_trace_rays and p3d_occluded then run, also while primitives updated
+ *    from device memory are still unknown to the host.  A handle that already has a grid (built lazily, or by an earlier
+ *    call) is left alone: P3D_OK, built == 0, info describes the grid it has.
+ *  - the host's knowledge is NOT refreshed: the next p3d_scene_update or p3d_scene_rebuild drops the grid as it always does,
+ *    and the lazy path refuses again as before; calling p3d_scene_build_grid again is the remedy.
+ *  - where the boxes come from: the reference's per-primitive grid boxes (RT/scene.cpp:26-39, 180-196) cannot be recovered from
+ *    the device records (a triangle is kept as p0, e1, e2, and p0 + (p1 - p0) is not p1 in float), so the handle keeps them in
+ *    an array of its own, 24 bytes per primitive, in scene order: made of the creation-time description at the first update
+ *    from device memory or the first call of this entry, whichever comes first, and kept current by every update after that.
+ *  - ordering: synchronous.  Runs after everything already enqueued on the scene's stream and waits for it, then for the
+ *    bounds of all boxes, for the item total and for the finished arrays.
+ *  - stream capture: refused with P3D_ERR_STATE while the stream is being captured.  A GRID frame issued AFTER the call can be
+ *    captured: it finds the grid built.
+ *  - P3D_ERR_ARG: NULL scene.  P3D_ERR_STATE: a handle created with cull_never_hit, as for GRID frames.  P3D_ERR_LIMIT, before
+ *    either grid array is allocated: the reference's formula asks for more than 2^31 - 1 cells (the host build's rule), or the
+ *    references over all cells do not fit 32 bits.  P3D_ERR_HIP when device memory runs out: the handle keeps the grid state
+ *    it had (no grid); the box array, if this call made it, stays and is counted.
+ *  - what is kept: everything else -- the measured schedule choice, the learned tile orders, p3d_last_schedule(), the
+ *    ray-stream state, the refit state and the tree.
+ *  - memory: p3d_scene_stats::device_bytes grows by the two grid arrays (4 bytes per cell plus 4, 4 bytes per reference) and,
+ *    once, by the box array (24 bytes per primitive); an update or rebuild gives the grid arrays back, so update / build
+ *    rounds settle.  Sort and scan temporaries and the (cell, primitive) pairs are freed before the call returns and are not
+ *    counted. */
+int p3d_scene_build_grid(p3d_scene* scene, p3d_grid_info* info);
 
 /* Rows of the compact per-rank tile buffer: ceil(n_row_blocks / world) * row_block, the
  * same on every rank so that the gather moves equal-sized buffers (rows past the image are
@@ -475,7 +517,9 @@ typedef struct p3d_occlusion_outputs {
  *    P3D_ACCEL_GRID  the same bound over the reference's own grid, with its rule that a ray for which Init_Traverse fails
  *                    -- one that misses the grid's box -- is IN SHADOW (RT/grid.cpp:327-328).  The grid is built by the
  *                    first GRID call of a scene, this entry's included, under the rules of the first GRID frame: refused
- *                    with P3D_ERR_STATE while the stream is being captured and after updates from device memory.
+ *                    with P3D_ERR_STATE while the stream is being captured and after updates from device memory (update
+ *                    those primitives from host memory, or call p3d_scene_build_grid first: a handle that has a built
+ *                    grid is served).
  *   There is no L.N > 0 test: that test decides whether processLight() asks at all, and every segment here is asked.
  *   Planes: the reference's accelerators bound a plane as [-1, 1]^3, and so do the tree and the grid here.
  *   In BVH and GRID mode a plane occludes only where the walk reaches that box: a segment that crosses the plane away
@@ -654,6 +698,16 @@ int p3d_debug_check_rcp_len(int device, uint32_t first_bits, uint64_t count, uin
  * primitives are built on the host by p3d_scene_create; that threshold is not this entry's). */
 int p3d_debug_lbvh_build(int device, uint32_t n, const float* lo3, const float* hi3, const uint32_t* ref, uint32_t* nodes16,
                          uint32_t* leaf_refs, uint32_t* stats4, float* sah_cost);
+
+/* The device grid build of p3d_scene_build_grid (csrc/grid_device.hip), run by the same function over host arrays: n boxes
+ * lo3[n*3], hi3[n*3] in scene order and the reference ref[n] each is listed under (n == 0: the arrays may be NULL).  Returns
+ * dims3 (cells per axis), mn3 / mx3 (the grid's box), *n_cells, *n_items, and -- unless cell_start or items is NULL, which
+ * asks for the sizes only -- the first min(cell_cap, n_cells + 1) words of cell_start and min(item_cap, n_items) words of
+ * items: what the host build (p3dh_grid_dump) makes of the same boxes, in every word.  P3D_ERR_LIMIT as for
+ * p3d_scene_build_grid; P3D_ERR_ARG for a NULL size output or NULL boxes with n > 0. */
+int p3d_debug_grid_build(int device, uint32_t n, const float* lo3, const float* hi3, const uint32_t* ref, int32_t* dims3,
+                         float* mn3, float* mx3, uint64_t* n_cells, uint64_t* n_items, uint32_t* cell_start, uint64_t cell_cap,
+                         uint32_t* items, uint64_t item_cap);
 
 /* Unit-level probes of p3d_generate_samples (csrc/p3d_rand.h, csrc/sample_stream.hip); host arrays, synchronous.
  * p3d_debug_rand: out[i] = the device's restatement of the value number first + i that the host C library's rand()

@@ -106,6 +106,12 @@ class RebuildInfo(C.Structure):
                 ("sah_cost_before", C.c_float), ("sah_cost_after", C.c_float)]
 
 
+class GridInfo(C.Structure):
+    """p3d_grid_info: whether p3d_scene_build_grid built the grid, and the grid the handle holds after the call."""
+    _fields_ = [("built", C.c_uint32), ("n", C.c_int32 * 3), ("mn", C.c_float * 3), ("mx", C.c_float * 3),
+                ("n_cells", C.c_uint64), ("n_items", C.c_uint64)]
+
+
 class SceneStats(C.Structure):
     _fields_ = [("n_nodes", C.c_uint32), ("n_leaves", C.c_uint32), ("max_depth", C.c_uint32),
                 ("n_leaf_refs", C.c_uint32), ("n_spheres", C.c_uint32), ("n_triangles", C.c_uint32),
@@ -118,9 +124,9 @@ class SceneStats(C.Structure):
 
 # every symbol include/p3d_hip.h declares (tests check that the library exports them all)
 C_ABI_SYMBOLS = ["p3d_abi_version", "p3d_last_error", "p3d_device_count", "p3d_scene_create",
-                 "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_scene_update", "p3d_scene_rebuild", "p3d_scene_tree_cost", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_render_aov", "p3d_generate_samples", "p3d_trace_rays", "p3d_occluded", "p3d_sync",
+                 "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_scene_update", "p3d_scene_rebuild", "p3d_scene_tree_cost", "p3d_scene_build_grid", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_render_aov", "p3d_generate_samples", "p3d_trace_rays", "p3d_occluded", "p3d_sync",
                  "p3d_get_counters", "p3d_get_profile", "p3d_last_schedule", "p3d_set_tuning", "p3d_set_primary_tiles", "p3d_last_primary_tiles", "p3d_set_stream", "p3d_timer_begin", "p3d_timer_end", "p3d_deinterleave_frames",
-                 "p3d_deinterleave", "p3d_debug_intersect", "p3d_debug_powf", "p3d_debug_pow", "p3d_debug_schlick_kr", "p3d_debug_check_rcp", "p3d_debug_check_rcp_len", "p3d_debug_lbvh_build", "p3d_debug_rand", "p3d_debug_sample_stream", "p3d_tune_schedule", "p3d_debug_set_stamps", "p3d_debug_set_stamp_level",
+                 "p3d_deinterleave", "p3d_debug_intersect", "p3d_debug_powf", "p3d_debug_pow", "p3d_debug_schlick_kr", "p3d_debug_check_rcp", "p3d_debug_check_rcp_len", "p3d_debug_lbvh_build", "p3d_debug_grid_build", "p3d_debug_rand", "p3d_debug_sample_stream", "p3d_tune_schedule", "p3d_debug_set_stamps", "p3d_debug_set_stamp_level",
                  "p3d_comm_unique_id", "p3d_comm_create", "p3d_comm_create_all", "p3d_comm_destroy", "p3d_comm_info",
                  "p3d_gather", "p3d_gather_all", "p3d_device_alloc", "p3d_device_free", "p3d_upload", "p3d_download"]
 
@@ -163,6 +169,7 @@ def lib():
     L.p3d_scene_update.argtypes = [C.c_void_p, C.POINTER(PrimUpdate)]
     L.p3d_scene_rebuild.argtypes = [C.c_void_p, C.POINTER(RebuildInfo)]
     L.p3d_scene_tree_cost.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+    L.p3d_scene_build_grid.argtypes = [C.c_void_p, C.POINTER(GridInfo)]
     L.p3d_local_rows.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     L.p3d_render.argtypes = [C.c_void_p, C.POINTER(Camera), C.POINTER(RenderParams), C.POINTER(Outputs)]
     L.p3d_render_frames.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.POINTER(RenderParams), C.POINTER(Outputs)]
@@ -205,6 +212,7 @@ def lib():
     L.p3d_debug_check_rcp.argtypes = [C.c_int, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
     L.p3d_debug_check_rcp_len.argtypes = [C.c_int, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
     L.p3d_debug_lbvh_build.argtypes = [C.c_int, C.c_uint32] + [C.c_void_p] * 7
+    L.p3d_debug_grid_build.argtypes = [C.c_int, C.c_uint32] + [C.c_void_p] * 8 + [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]
     L.p3d_debug_rand.argtypes = [C.c_int, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p]
     L.p3d_debug_sample_stream.argtypes = [C.c_int, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_uint64, C.c_void_p,
                                           C.POINTER(C.c_int32)]
@@ -231,6 +239,8 @@ def lib():
     L.p3dh_bvh_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
     L.p3dh_bvh_dump.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.p3dh_bvh_quantise.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.p3dh_grid_dump.restype = C.c_int64
+    L.p3dh_grid_dump.argtypes = [C.POINTER(SceneDesc), C.c_uint32] + [C.c_void_p] * 7 + [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]
     L.p3dh_build_prims.restype = C.c_int64
     L.p3dh_build_prims.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
     L.p3d_pt_create.argtypes = [C.c_int, C.POINTER(C.c_void_p)]
@@ -477,6 +487,15 @@ class DeviceScene:
         info = RebuildInfo()
         _check(lib().p3d_scene_rebuild(self.h, C.byref(info)), "p3d_scene_rebuild")
         return {n: getattr(info, n) for n, _ in info._fields_}
+
+    def build_grid(self):
+        """p3d_scene_build_grid: GRID mode's grid built on the device from what the handle holds there (after updates from
+        device memory too).  Returns p3d_grid_info as a dict: built (0: the handle already had a grid), n [3] int32, mn / mx
+        [3] float32, n_cells, n_items."""
+        info = GridInfo()
+        _check(lib().p3d_scene_build_grid(self.h, C.byref(info)), "p3d_scene_build_grid")
+        return {"built": int(info.built), "n": np.array(list(info.n), np.int32), "mn": np.array(list(info.mn), np.float32),
+                "mx": np.array(list(info.mx), np.float32), "n_cells": int(info.n_cells), "n_items": int(info.n_items)}
 
     def tree_cost(self):
         """p3d_scene_tree_cost: SAH cost of the tree as it stands (after updates: of the refitted boxes)."""
@@ -967,6 +986,51 @@ def host_grid(desc):
     counts = np.zeros(n, np.uint32)
     L.p3dh_grid_build(C.byref(desc), dims, counts.ctypes.data, n)
     return np.array(list(dims), np.int32), counts
+
+
+def _grid_boxes(lo, hi, ref):
+    lo = np.ascontiguousarray(lo, np.float32).reshape(-1, 3)
+    hi = np.ascontiguousarray(hi, np.float32).reshape(-1, 3)
+    ref = np.ascontiguousarray(ref, np.uint32).ravel()
+    assert lo.shape == hi.shape == (len(ref), 3)
+    return lo, hi, ref
+
+
+def _grid_dict(dims, mn, mx, cell_start, items):
+    return {"dims": dims, "mn": mn, "mx": mx, "cell_start": cell_start, "items": items}
+
+
+def host_grid_arrays(desc=None, lo=None, hi=None, ref=None):
+    """The whole of the host grid build (p3dh_grid_dump, no GPU), over a scene description or over boxes lo / hi [n, 3] listed
+    under ref [n]: dict(dims [3] int32, mn / mx [3] float32, cell_start [cells + 1] uint32, items uint32)."""
+    if desc is None:
+        lo, hi, ref = _grid_boxes(lo, hi, ref)
+    dims, mn, mx, n_items = np.zeros(3, np.int32), np.zeros(3, np.float32), np.zeros(3, np.float32), C.c_uint64(0)
+    head = (C.byref(desc) if desc is not None else None, 0 if desc is not None else len(ref),
+            None if desc is not None else lo.ctypes.data, None if desc is not None else hi.ctypes.data,
+            None if desc is not None else ref.ctypes.data, dims.ctypes.data, mn.ctypes.data, mx.ctypes.data, C.addressof(n_items))
+    cells = lib().p3dh_grid_dump(*head, None, 0, None, 0)
+    if cells < 0:
+        raise P3DError("p3dh_grid_dump: the reference's grid formula asks for more than 2^31 cells")
+    cell_start, items = np.zeros(cells + 1, np.uint32), np.zeros(n_items.value, np.uint32)
+    lib().p3dh_grid_dump(*head, cell_start.ctypes.data, len(cell_start), items.ctypes.data, len(items))
+    return _grid_dict(dims, mn, mx, cell_start, items)
+
+
+def debug_grid_build(lo, hi, ref, device=0):
+    """The device grid build (p3d_debug_grid_build) over boxes lo / hi [n, 3] listed under ref [n]: the dict of
+    host_grid_arrays, made by the function p3d_scene_build_grid runs."""
+    lo, hi, ref = _grid_boxes(lo, hi, ref)
+    n = len(ref)
+    dims, mn, mx = np.zeros(3, np.int32), np.zeros(3, np.float32), np.zeros(3, np.float32)
+    n_cells, n_items = C.c_uint64(0), C.c_uint64(0)
+    head = (int(device), n, lo.ctypes.data if n else None, hi.ctypes.data if n else None, ref.ctypes.data if n else None,
+            dims.ctypes.data, mn.ctypes.data, mx.ctypes.data, C.addressof(n_cells), C.addressof(n_items))
+    _check(lib().p3d_debug_grid_build(*head, None, 0, None, 0), "p3d_debug_grid_build")
+    cell_start, items = np.zeros(n_cells.value + 1, np.uint32), np.zeros(max(n_items.value, 1), np.uint32)
+    _check(lib().p3d_debug_grid_build(*head, cell_start.ctypes.data, len(cell_start), items.ctypes.data, n_items.value),
+           "p3d_debug_grid_build")
+    return _grid_dict(dims, mn, mx, cell_start, items[:n_items.value])
 
 
 class PathTracer:

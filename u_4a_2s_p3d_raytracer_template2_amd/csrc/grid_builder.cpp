@@ -8,28 +8,7 @@
 
 namespace p3d {
 
-static const float kEps = 0.001f;                                        // RT/macros.h:1
-
-void grid_prim_bounds(uint32_t type, const float* v, GridPrim& g) {
-    switch (type) {
-    case P3D_SPHERE:                                                 // RT/scene.cpp:180-186
-        for (int a = 0; a < 3; a++) { g.lo[a] = v[a] - v[3]; g.hi[a] = v[a] + v[3]; }
-        break;
-    case P3D_TRIANGLE:                                               // RT/scene.cpp:26-39: min/max, then -= / += EPSILON
-        for (int a = 0; a < 3; a++) {
-            float lo = std::min(std::min(v[a], v[3 + a]), v[6 + a]);
-            float hi = std::max(std::max(v[a], v[3 + a]), v[6 + a]);
-            g.lo[a] = lo - kEps; g.hi[a] = hi + kEps;
-        }
-        break;
-    case P3D_BOX:                                                    // RT/scene.cpp:194-196
-        for (int a = 0; a < 3; a++) { g.lo[a] = v[a]; g.hi[a] = v[3 + a]; }
-        break;
-    default:                                                         // Plane: Object::GetBoundingBox(), RT/scene.h:75
-        for (int a = 0; a < 3; a++) { g.lo[a] = -1.0f; g.hi[a] = 1.0f; }
-        break;
-    }
-}
+void grid_prim_bounds(uint32_t type, const float* v, GridPrim& g) { grid_box_rule(type, v, g.lo, g.hi); }
 
 void grid_prims_from_desc(const p3d_scene_desc& d, std::vector<GridPrim>& out) {
     out.clear();
@@ -46,6 +25,25 @@ void grid_prims_from_desc(const p3d_scene_desc& d, std::vector<GridPrim>& out) {
 
 static inline double dclamp(double x, double mn, double mx) { return x < mn ? mn : (x > mx ? mx : x); }   // RT/maths.h:50-53
 
+GridShape grid_shape(size_t n_prims, const float lo[3], const float hi[3], GridHost& G) {     // RT/grid.cpp:30-56
+    float mn[3], mx[3];
+    for (int a = 0; a < 3; a++) { mn[a] = lo[a] - kGridEps; mx[a] = hi[a] + kGridEps; G.mn[a] = mn[a]; G.mx[a] = mx[a]; }
+    const double wx = mx[0] - mn[0], wy = mx[1] - mn[1], wz = mx[2] - mn[2];
+    const double s = pow((int)n_prims / (wx * wy * wz), 0.3333333);
+    const float m = 2.0f;                                                // RT/rayAccelerator.h:29
+    const double fx = m * wx * s + 1, fy = m * wy * s + 1, fz = m * wz * s + 1;
+    // No primitives (the box is still inverted: widths of -inf, s = 0, NaN counts) or coordinates that are not
+    // numbers: the reference's int conversion of such a count is undefined behaviour.  Here: ONE empty cell and the
+    // box as it stands -- an inverted box is missed by every ray (grid_init), which is what an empty grid amounts to.
+    if (n_prims == 0 || !(fx >= 1.0 && fy >= 1.0 && fz >= 1.0) || !std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(fz)) {
+        G.n[0] = G.n[1] = G.n[2] = 1;
+        return kGridShapeEmpty;
+    }
+    if (fx * fy * fz > 2147483647.0) return kGridShapeTooLarge;          // more cells than the device's 32-bit cell index
+    G.n[0] = (int)fx; G.n[1] = (int)fy; G.n[2] = (int)fz;
+    return kGridShapeCells;
+}
+
 bool build_grid(const std::vector<GridPrim>& prims, GridHost& G) {       // RT/grid.cpp:30-98
     float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
     for (const GridPrim& p : prims)
@@ -53,23 +51,15 @@ bool build_grid(const std::vector<GridPrim>& prims, GridHost& G) {       // RT/g
             if (mn[a] > p.lo[a]) mn[a] = p.lo[a];
             if (mx[a] < p.hi[a]) mx[a] = p.hi[a];
         }
-    for (int a = 0; a < 3; a++) { mn[a] -= kEps; mx[a] += kEps; G.mn[a] = mn[a]; G.mx[a] = mx[a]; }
-    const double wx = mx[0] - mn[0], wy = mx[1] - mn[1], wz = mx[2] - mn[2];
-    const double s = pow((int)prims.size() / (wx * wy * wz), 0.3333333);
-    const float m = 2.0f;                                                // RT/rayAccelerator.h:29
-    const double fx = m * wx * s + 1, fy = m * wy * s + 1, fz = m * wz * s + 1;
-    // No primitives (the box is still inverted: widths of -inf, s = 0, NaN counts) or coordinates that are not
-    // numbers: the reference's int conversion of such a count is undefined behaviour.  Here: ONE empty cell and the
-    // box as it stands -- an inverted box is missed by every ray (grid_init), which is what an empty grid amounts to.
-    if (prims.empty() || !(fx >= 1.0 && fy >= 1.0 && fz >= 1.0) || !std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(fz)) {
-        G.n[0] = G.n[1] = G.n[2] = 1;
+    const GridShape shape = grid_shape(prims.size(), mn, mx, G);
+    if (shape == kGridShapeEmpty) {
         G.cell_start.assign(2, 0u);
         G.items.clear();
         return true;
     }
-    if (fx * fy * fz > 2147483647.0) return false;                       // more cells than the device's 32-bit cell index
-    const int nx = (int)fx, ny = (int)fy, nz = (int)fz;
-    G.n[0] = nx; G.n[1] = ny; G.n[2] = nz;
+    if (shape == kGridShapeTooLarge) return false;
+    for (int a = 0; a < 3; a++) { mn[a] = G.mn[a]; mx[a] = G.mx[a]; }
+    const int nx = G.n[0], ny = G.n[1], nz = G.n[2];
     const size_t cells = (size_t)nx * ny * nz;
     struct Range { int x0, x1, y0, y1, z0, z1; };
     std::vector<Range> rng(prims.size());

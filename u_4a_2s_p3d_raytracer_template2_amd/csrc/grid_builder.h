@@ -8,9 +8,12 @@
 #include <cstdint>
 #include <vector>
 
+#include "p3d_device_types.h"
 #include "p3d_hip.h"
 
 namespace p3d {
+
+constexpr float kGridEps = 0.001f;                                       // EPSILON, RT/macros.h:1
 
 struct GridHost {
     int32_t n[3] = {0, 0, 0};
@@ -24,11 +27,42 @@ struct GridHost {
 // primitive's device reference
 struct GridPrim { float lo[3], hi[3]; uint32_t ref; };
 
-// lo / hi of one primitive of kind `type` (P3D_*; anything else: a plane) from its 12 floats, with the reference's float
-// arithmetic; g.ref is left alone
+// The box rule, stated once: lo / hi of one primitive of kind `type` (P3D_*; anything else: a plane) from its 12 floats, with
+// the reference's float arithmetic.  The host (grid_prim_bounds) and the device (update_records_kernel, which keeps the
+// handle's grid_bounds current) both call it; min and max are std::min's and std::max's selections written out.
+P3D_HD inline void grid_box_rule(uint32_t type, const float* v, float* lo, float* hi) {
+    switch (type) {
+    case P3D_SPHERE:                                                 // RT/scene.cpp:180-186
+        for (int a = 0; a < 3; a++) { lo[a] = v[a] - v[3]; hi[a] = v[a] + v[3]; }
+        break;
+    case P3D_TRIANGLE:                                               // RT/scene.cpp:26-39: min/max, then -= / += EPSILON
+        for (int a = 0; a < 3; a++) {
+            float mn = v[3 + a] < v[a] ? v[3 + a] : v[a], mx = v[a] < v[3 + a] ? v[3 + a] : v[a];
+            mn = v[6 + a] < mn ? v[6 + a] : mn; mx = mx < v[6 + a] ? v[6 + a] : mx;
+            lo[a] = mn - kGridEps; hi[a] = mx + kGridEps;
+        }
+        break;
+    case P3D_BOX:                                                    // RT/scene.cpp:194-196
+        for (int a = 0; a < 3; a++) { lo[a] = v[a]; hi[a] = v[3 + a]; }
+        break;
+    default:                                                         // Plane: Object::GetBoundingBox(), RT/scene.h:75
+        for (int a = 0; a < 3; a++) { lo[a] = -1.0f; hi[a] = 1.0f; }
+        break;
+    }
+}
+// grid_box_rule into g.lo / g.hi; g.ref is left alone
 void grid_prim_bounds(uint32_t type, const float* prim12, GridPrim& g);
 // bounding boxes of a scene description in scene order, with the reference's float arithmetic
 void grid_prims_from_desc(const p3d_scene_desc& d, std::vector<GridPrim>& out);
+// The shape rule (RT/grid.cpp:30-56) from the bounds of all boxes (mn / mx as AABB::extend leaves them: FLT_MAX / -FLT_MAX
+// for no primitives) and the primitive count: out.mn / out.mx (the bounds -/+ EPSILON) and out.n.  Shared by build_grid and the
+// device build (grid_device.hip), which gets the bounds from a reduction on the device.
+enum GridShape {
+    kGridShapeCells = 0,      // a grid of out.n cells to fill
+    kGridShapeEmpty = 1,      // no primitives, or a count that is no number: ONE empty cell, the box as it stands
+    kGridShapeTooLarge = 2    // more than 2^31 - 1 cells: nothing is built
+};
+GridShape grid_shape(size_t n_prims, const float mn[3], const float mx[3], GridHost& out);
 // false: the reference's cell-count formula asks for more than 2^31 cells (nothing is built)
 bool build_grid(const std::vector<GridPrim>& prims, GridHost& out);
 

@@ -2,6 +2,7 @@
 // test / bench harness (ctypes) can drive the same loader, camera and sample generator the
 // C++ front end uses.  These p3dh_* functions are conveniences ABOVE the drop-in boundary;
 // the boundary itself is include/p3d_hip.h.
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -171,6 +172,29 @@ int64_t p3dh_grid_build(const p3d_scene_desc* d, int32_t* dims, uint32_t* counts
     const size_t cells = g.cell_start.size() - 1;
     if (counts) for (size_t c = 0; c < cells && c < counts_cap; c++) counts[c] = g.cell_start[c + 1] - g.cell_start[c];
     return (int64_t)cells;
+}
+
+
+// ---- the whole of build_grid()'s output, for the device build to be compared with: over a scene description (d != NULL), or
+// over n boxes lo3 / hi3 [n*3] with the references ref[n] they are listed under, as p3d_debug_grid_build takes them.
+// dims3, mn3, mx3, *n_items; cell_start / items (may be NULL): the first cell_cap / item_cap words.  Returns the number of
+// cells, or -1 when the formula asks for more than 2^31 of them.
+int64_t p3dh_grid_dump(const p3d_scene_desc* d, uint32_t n, const float* lo3, const float* hi3, const uint32_t* ref, int32_t* dims3,
+                       float* mn3, float* mx3, uint64_t* n_items, uint32_t* cell_start, uint64_t cell_cap, uint32_t* items,
+                       uint64_t item_cap) {
+    std::vector<p3d::GridPrim> prims;
+    if (d) p3d::grid_prims_from_desc(*d, prims);
+    else {
+        prims.resize(n);
+        for (size_t i = 0; i < n; i++) { memcpy(prims[i].lo, lo3 + 3 * i, 12); memcpy(prims[i].hi, hi3 + 3 * i, 12); prims[i].ref = ref[i]; }
+    }
+    p3d::GridHost g;
+    if (!p3d::build_grid(prims, g)) return -1;
+    for (int a = 0; a < 3; a++) { dims3[a] = g.n[a]; mn3[a] = g.mn[a]; mx3[a] = g.mx[a]; }
+    *n_items = g.items.size();
+    if (cell_start) memcpy(cell_start, g.cell_start.data(), std::min<size_t>(cell_cap, g.cell_start.size()) * 4);
+    if (items) memcpy(items, g.items.data(), std::min<size_t>(item_cap, g.items.size()) * 4);
+    return (int64_t)g.cell_start.size() - 1;
 }
 
 }  // extern "C"

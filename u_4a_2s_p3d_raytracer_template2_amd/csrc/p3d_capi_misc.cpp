@@ -2,6 +2,7 @@
 // profile and timers, de-interleaving, device memory for callers, and the debug entries that run one device function.
 #include <cstring>
 
+#include "grid_device.h"
 #include "p3d_scene_state.h"
 
 using namespace p3d;
@@ -280,6 +281,36 @@ int p3d_debug_lbvh_build(int device, uint32_t n, const float* lo3, const float* 
     if (rc) return rc;
     stats4[0] = bs.n_nodes; stats4[1] = bs.n_leaves; stats4[2] = bs.n_leaf_refs; stats4[3] = bs.max_depth;
     *sah_cost = bs.sah_cost;
+    return P3D_OK;
+}
+
+int p3d_debug_grid_build(int device, uint32_t n, const float* lo3, const float* hi3, const uint32_t* ref, int32_t* dims3,
+                         float* mn3, float* mx3, uint64_t* n_cells, uint64_t* n_items, uint32_t* cell_start, uint64_t cell_cap,
+                         uint32_t* items, uint64_t item_cap) {
+    if (!dims3 || !mn3 || !mx3 || !n_cells || !n_items || (n > 0 && (!lo3 || !hi3 || !ref))) return fail(P3D_ERR_ARG, "NULL argument");
+    std::vector<float> rows(6 * (size_t)n);
+    for (size_t i = 0; i < n; i++) { memcpy(&rows[6 * i], lo3 + 3 * i, 12); memcpy(&rows[6 * i + 3], hi3 + 3 * i, 12); }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(P3D_ERR_NO_DEVICE, "no HIP device visible");
+    DevBuf<float> d_rows; DevBuf<uint32_t> d_ref, cells, refs;           // freed on every path
+    GridDeviceOut G;
+    GridDeviceLimit limit = kGridFits;
+    const bool sizes_only = !cell_start || !items;
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = d_rows.upload(rows);
+    if (e == hipSuccess) e = d_ref.upload(std::vector<uint32_t>(ref, ref + n));
+    if (e == hipSuccess) e = build_grid_device(d_rows.p, d_ref.p, n, sizes_only, nullptr, G, &limit);
+    cells.p = G.cell_start; refs.p = G.items;
+    if (e == hipSuccess && limit == kGridFits && !sizes_only) {
+        e = hipMemcpy(cell_start, G.cell_start, (size_t)std::min<uint64_t>(cell_cap, G.n_cells + 1) * 4, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && std::min<uint64_t>(item_cap, G.n_items) > 0)
+            e = hipMemcpy(items, G.items, (size_t)std::min<uint64_t>(item_cap, G.n_items) * 4, hipMemcpyDeviceToHost);
+    }
+    if (e != hipSuccess) return fail(P3D_ERR_HIP, std::string("p3d_debug_grid_build: ") + hipGetErrorString(e));
+    for (int a = 0; a < 3; a++) { dims3[a] = G.n[a]; mn3[a] = G.mn[a]; mx3[a] = G.mx[a]; }
+    *n_cells = G.n_cells; *n_items = G.n_items;
+    if (limit == kGridTooManyCells) return fail(P3D_ERR_LIMIT, "the reference's grid formula asks for more than 2^31 cells");
+    if (limit == kGridTooManyItems) return fail(P3D_ERR_LIMIT, "the grid's cells hold more than 2^32 - 1 primitive references");
     return P3D_OK;
 }
 

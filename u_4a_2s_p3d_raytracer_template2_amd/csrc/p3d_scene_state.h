@@ -1,5 +1,5 @@
 // p3d_scene_state.h -- the scene handle behind the C-ABI of include/p3d_hip.h, shared by the files that implement it
-// (p3d_scene_create.cpp, p3d_scene_update.cpp, p3d_scene_rebuild.cpp, p3d_render.cpp, p3d_generate_samples.cpp, p3d_capi_misc.cpp).  Internal: not installed with include/.
+// (p3d_scene_create.cpp, p3d_scene_update.cpp, p3d_scene_rebuild.cpp, p3d_scene_build_grid.cpp, p3d_render.cpp, p3d_generate_samples.cpp, p3d_capi_misc.cpp).  Internal: not installed with include/.
 // Every device resource in it is owned by a member that frees it: deleting a p3d_scene releases all of them.
 #ifndef P3D_SCENE_STATE_H
 #define P3D_SCENE_STATE_H
@@ -154,6 +154,10 @@ struct p3d_scene {
     } refit;
     // primitives whose grid_src entry predates an update from device memory: GRID mode is refused while there are any
     std::vector<uint8_t> grid_stale; size_t grid_stale_count = 0;
+    // p3d_scene_build_grid: GRID mode's box of every primitive ([n_prims][6], scene order), made of grid_src by the first
+    // update from device memory or the first device build (grid_device.h: ensure_grid_bounds) and kept current by every
+    // update from then on (update_records_kernel); empty until then
+    p3d::DevBuf<float> grid_bounds;
     p3d::DevBuf<p3d::LightRec> soft_lights;     // 16 sub-lights per light, built on first use (SOFT_SHADOW, spp == 0)
     p3d::DevBuf<uint8_t> sky;                   // cube map of P3D_FEATURE_SKYBOX: the six faces back to back
     uint32_t sky_off[6] = {0, 0, 0, 0, 0, 0}, sky_w[6] = {0, 0, 0, 0, 0, 0}, sky_h[6] = {0, 0, 0, 0, 0, 0}, sky_bpp[6] = {0, 0, 0, 0, 0, 0};

@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "grid_device.h"
 #include "p3d_scene_state.h"
 #include "scene_flatten.h"
 #include "scene_update.h"
@@ -62,6 +63,8 @@ extern "C" int p3d_scene_update(p3d_scene* s, const p3d_prim_update* u) {
     if (u->n > 0) {
         int rc = prepare_refit(s, n_nodes);
         if (rc) return rc;
+        // from the first update the host cannot follow on, the device keeps GRID mode's boxes (p3d_scene_build_grid)
+        if (!host && (rc = ensure_grid_bounds(s))) return rc;
         const float* d_prims = u->prim_data; const uint32_t* d_index = u->index;
         if (host) {      // one code path: host data is staged and takes the kernel device data takes
             if ((rc = ensure_staging(s, s->refit.stage_prims, (size_t)u->n * 12 * sizeof(float)))) return rc;
@@ -79,7 +82,7 @@ extern "C" int p3d_scene_update(p3d_scene* s, const p3d_prim_update* u) {
         S.planes = s->planes.p; S.prim_map = s->prim_map.p; S.n_prims = n_prims;
         uint32_t* status = (uint32_t*)s->refit.status.p;
         HIP_TRY(hipMemsetAsync(status, 0, kStatusWords * sizeof(uint32_t), s->stream));
-        HIP_TRY(launch_update_records(S, u->n, d_index, d_prims, status, s->stream));
+        HIP_TRY(launch_update_records(S, u->n, d_index, d_prims, status, s->grid_bounds.p, s->stream));
         // LDS-capable scenes carry their f32 nodes in the blob: the LDS walk reads them there
         NodePair* nodes = s->lds_capable ? (NodePair*)(s->blob.p + 4 * (size_t)s->off_nodes) : (NodePair*)s->refit.nodes.p;
         HIP_TRY(launch_refit(S, nodes, (const int32_t*)s->refit.parent.p, (uint32_t*)s->refit.arrived.p, n_nodes, status, s->stream));

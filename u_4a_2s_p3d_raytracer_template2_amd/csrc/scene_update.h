@@ -26,8 +26,10 @@ constexpr uint32_t kStatusRootFloats = 12, kStatusBadIndex = 12, kStatusWords = 
 
 // One thread per entry: primitive index[i] (nullptr: i) gets the record made of prim12[12 i ..], with flatten_scene's float
 // operations.  Entries whose index is >= n_prims are skipped and counted in status[kStatusBadIndex].
+// grid_bounds (nullptr: the handle has none yet): [n_prims][6] in scene order, the primitive's GRID-mode box
+// (grid_builder.h: grid_box_rule) goes to its row.
 hipError_t launch_update_records(const SceneRecords& S, uint32_t n, const uint32_t* index, const float* prim12,
-                                 uint32_t* status, hipStream_t stream);
+                                 uint32_t* status, float* grid_bounds, hipStream_t stream);
 // f32 node pairs of a scene that carries quantised ones only (nodes == nullptr: they exist) and every node's parent,
 // from the child references of the quantised nodes.  Boxes are left to the refit.
 hipError_t launch_refit_prepare(const QNode* qnodes, uint32_t n_nodes, NodePair* nodes, int32_t* parent, hipStream_t stream);

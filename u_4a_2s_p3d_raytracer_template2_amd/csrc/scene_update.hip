@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "grid_builder.h"
 #include "scene_bounds.h"
 #include "scene_update.h"
 
@@ -21,7 +22,8 @@ namespace {
 
 constexpr unsigned kThreads = 256;
 
-__global__ void update_records_kernel(SceneRecords S, uint32_t n, const uint32_t* index, const float* prim12, uint32_t* status) {
+__global__ void update_records_kernel(SceneRecords S, uint32_t n, const uint32_t* index, const float* prim12, uint32_t* status,
+                                      float* grid_bounds) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const uint32_t prim = index ? index[i] : i;
@@ -48,6 +50,10 @@ __global__ void update_records_kernel(SceneRecords S, uint32_t n, const uint32_t
         for (int a = 0; a < 3; a++) { b[a] = v[a]; b[4 + a] = v[3 + a]; }
     } else {
         S.planes[k] = PlaneRec{v[0], v[1], v[2], v[3]};
+    }
+    if (grid_bounds) {                                             // GRID mode's box of the primitive (grid_builder.h), scene order
+        float* g = grid_bounds + 6 * (size_t)prim;
+        grid_box_rule(kind, v, g, g + 3);
     }
 }
 
@@ -141,9 +147,9 @@ unsigned blocks_for(uint64_t n) { return (unsigned)((n + kThreads - 1) / kThread
 }  // namespace
 
 hipError_t launch_update_records(const SceneRecords& S, uint32_t n, const uint32_t* index, const float* prim12,
-                                 uint32_t* status, hipStream_t stream) {
+                                 uint32_t* status, float* grid_bounds, hipStream_t stream) {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(update_records_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, stream, S, n, index, prim12, status);
+    hipLaunchKernelGGL(update_records_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, stream, S, n, index, prim12, status, grid_bounds);
     return hipGetLastError();
 }
 
