@@ -75,7 +75,13 @@ typedef struct p3d_build_opts {
     uint32_t builder;         /* 0 = binned SAH on the host (default); 1 = linear BVH built on the
                                  device (Morton sort + Karras hierarchy + refit): a tree of lower
                                  quality in a fraction of the time, for scene-reload loops and
-                                 scenes of millions of primitives. Same images either way.     */
+                                 scenes of millions of primitives. 2 = built on the device by local
+                                 clustering over builder 1's sorted leaves (csrc/bvh_ploc.hip): a tree
+                                 near the SAH tree's cost, at builder 1's node and leaf counts; when the
+                                 clustering does not finish in 95 rounds the tree is builder 1's
+                                 (p3d_scene_last_builder tells). Above 2: P3D_ERR_ARG. Scenes of fewer
+                                 than 64 bounded primitives are built on the host whatever this says.
+                                 Same images either way.                                       */
     uint32_t cull_never_hit;  /* 1 = leave out of the BVH every triangle the reference's own test can
                                  never accept: Triangle::intercepts rejects |det| < 1e-3
                                  (RT/scene.cpp:66-67) and |det| <= |d| * |e1 x e2|, so a
@@ -315,6 +321,18 @@ typedef struct p3d_rebuild_info {
  *    layout carries a record per leaf and the f32 nodes, and growing it could push the scene out of LDS and change which
  *    kernels serve it. */
 int p3d_scene_rebuild(p3d_scene* scene, p3d_rebuild_info* info);
+/* p3d_scene_rebuild with the device builder named: builder == 1 is p3d_scene_rebuild exactly (which is a call of this entry);
+ * builder == 2 builds the clustered tree of p3d_build_opts::builder == 2 over the same sorted leaves.  Anything else is
+ * P3D_ERR_ARG: builder 0 needs the host's geometry.  Every rule above carries over -- equal frames, what is kept and what
+ * changes, the refusals, every allocation before any change, the handles left alone (rebuilt == 0) -- with one difference:
+ * builder 2 waits on the device once per clustering round (about 50 to 60 short waits on a real scene, 95 at the most)
+ * instead of twice in all.  When the clustering does not finish in 95 rounds the tree is builder 1's; rebuilt is 1 then too
+ * and p3d_scene_last_builder answers 1. */
+int p3d_scene_rebuild_with(p3d_scene* scene, uint32_t builder, p3d_rebuild_info* info);
+/* The builder whose tree the handle walks now: 0 = host SAH (also every scene under 64 bounded primitives), 1 = device LBVH
+ * (also a builder-2 request that fell back), 2 = the clustered tree.  A handle a rebuild left alone keeps its value.
+ * P3D_ERR_ARG: NULL argument. */
+int p3d_scene_last_builder(const p3d_scene* scene, int32_t* builder);
 /* SAH cost of the tree the handle walks NOW, in the unit of p3d_scene_stats::sah_cost: per node pair 1.2 x the area of its
  * own box (the union of its two child boxes), per leaf the primitive count x the area of the leaf's box, both over the root's
  * area.  After updates it tells what the refitted boxes cost; p3d_scene_stats keeps the cost of the last build.  One
@@ -698,6 +716,11 @@ int p3d_debug_check_rcp_len(int device, uint32_t first_bits, uint64_t count, uin
  * primitives are built on the host by p3d_scene_create; that threshold is not this entry's). */
 int p3d_debug_lbvh_build(int device, uint32_t n, const float* lo3, const float* hi3, const uint32_t* ref, uint32_t* nodes16,
                          uint32_t* leaf_refs, uint32_t* stats4, float* sah_cost);
+/* The same for builder 2 (csrc/bvh_ploc.hip), run by the function p3d_scene_create and p3d_scene_rebuild_with call: the same
+ * leaves and leaf_refs; node 0 is the root and every inner child's index is above its parent's.  *rounds = clustering rounds
+ * run (at most 95); *fell_back = 1 when clusters were left after them and everything returned is builder 1's tree. */
+int p3d_debug_ploc_build(int device, uint32_t n, const float* lo3, const float* hi3, const uint32_t* ref, uint32_t* nodes16,
+                         uint32_t* leaf_refs, uint32_t* stats4, float* sah_cost, int32_t* rounds, int32_t* fell_back);
 
 /* The device grid build of p3d_scene_build_grid (csrc/grid_device.hip), run by the same function over host arrays: n boxes
  * lo3[n*3], hi3[n*3] in scene order and the reference ref[n] each is listed under (n == 0: the arrays may be NULL).  Returns

@@ -124,9 +124,9 @@ class SceneStats(C.Structure):
 
 # every symbol include/p3d_hip.h declares (tests check that the library exports them all)
 C_ABI_SYMBOLS = ["p3d_abi_version", "p3d_last_error", "p3d_device_count", "p3d_scene_create",
-                 "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_scene_update", "p3d_scene_rebuild", "p3d_scene_tree_cost", "p3d_scene_build_grid", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_render_aov", "p3d_generate_samples", "p3d_trace_rays", "p3d_occluded", "p3d_sync",
+                 "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_scene_update", "p3d_scene_rebuild", "p3d_scene_rebuild_with", "p3d_scene_last_builder", "p3d_scene_tree_cost", "p3d_scene_build_grid", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_render_aov", "p3d_generate_samples", "p3d_trace_rays", "p3d_occluded", "p3d_sync",
                  "p3d_get_counters", "p3d_get_profile", "p3d_last_schedule", "p3d_set_tuning", "p3d_set_primary_tiles", "p3d_last_primary_tiles", "p3d_set_stream", "p3d_timer_begin", "p3d_timer_end", "p3d_deinterleave_frames",
-                 "p3d_deinterleave", "p3d_debug_intersect", "p3d_debug_powf", "p3d_debug_pow", "p3d_debug_schlick_kr", "p3d_debug_check_rcp", "p3d_debug_check_rcp_len", "p3d_debug_lbvh_build", "p3d_debug_grid_build", "p3d_debug_rand", "p3d_debug_sample_stream", "p3d_tune_schedule", "p3d_debug_set_stamps", "p3d_debug_set_stamp_level",
+                 "p3d_deinterleave", "p3d_debug_intersect", "p3d_debug_powf", "p3d_debug_pow", "p3d_debug_schlick_kr", "p3d_debug_check_rcp", "p3d_debug_check_rcp_len", "p3d_debug_lbvh_build", "p3d_debug_ploc_build", "p3d_debug_grid_build", "p3d_debug_rand", "p3d_debug_sample_stream", "p3d_tune_schedule", "p3d_debug_set_stamps", "p3d_debug_set_stamp_level",
                  "p3d_comm_unique_id", "p3d_comm_create", "p3d_comm_create_all", "p3d_comm_destroy", "p3d_comm_info",
                  "p3d_gather", "p3d_gather_all", "p3d_device_alloc", "p3d_device_free", "p3d_upload", "p3d_download"]
 
@@ -168,6 +168,8 @@ def lib():
     L.p3d_scene_get_stats.argtypes = [C.c_void_p, C.POINTER(SceneStats)]
     L.p3d_scene_update.argtypes = [C.c_void_p, C.POINTER(PrimUpdate)]
     L.p3d_scene_rebuild.argtypes = [C.c_void_p, C.POINTER(RebuildInfo)]
+    L.p3d_scene_rebuild_with.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(RebuildInfo)]
+    L.p3d_scene_last_builder.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     L.p3d_scene_tree_cost.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.p3d_scene_build_grid.argtypes = [C.c_void_p, C.POINTER(GridInfo)]
     L.p3d_local_rows.argtypes = [C.c_int32, C.c_int32, C.c_int32]
@@ -212,6 +214,7 @@ def lib():
     L.p3d_debug_check_rcp.argtypes = [C.c_int, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
     L.p3d_debug_check_rcp_len.argtypes = [C.c_int, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]
     L.p3d_debug_lbvh_build.argtypes = [C.c_int, C.c_uint32] + [C.c_void_p] * 7
+    L.p3d_debug_ploc_build.argtypes = [C.c_int, C.c_uint32] + [C.c_void_p] * 9
     L.p3d_debug_grid_build.argtypes = [C.c_int, C.c_uint32] + [C.c_void_p] * 8 + [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]
     L.p3d_debug_rand.argtypes = [C.c_int, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p]
     L.p3d_debug_sample_stream.argtypes = [C.c_int, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_uint64, C.c_void_p,
@@ -431,7 +434,7 @@ class DeviceScene:
     """p3d_scene on one GPU."""
 
     def __init__(self, desc, device=0, leaf_max=0, keepalive=None, builder=0, cull_never_hit=False):
-        """builder: 0 = host SAH, 1 = device LBVH; cull_never_hit: see p3d_build_opts in p3d_hip.h."""
+        """builder: 0 = host SAH, 1 = device LBVH, 2 = device clustering (near SAH quality); cull_never_hit: see p3d_build_opts in p3d_hip.h."""
         self._keep = keepalive
         self.h = C.c_void_p()
         opts = BuildOpts(leaf_max, 0, builder, 1 if cull_never_hit else 0)
@@ -481,12 +484,19 @@ class DeviceScene:
         u = PrimUpdate(int(n), index_ptr or None, prim_ptr or None, 1, None)
         _check(lib().p3d_scene_update(self.h, C.byref(u)), "p3d_scene_update")
 
-    def rebuild(self):
-        """p3d_scene_rebuild: the device builder's tree over the primitives where they are now, in place.  Frames stay what
-        they were, bit for bit.  Returns p3d_rebuild_info as a dict (rebuilt == 0: a scene served from LDS, left alone)."""
+    def rebuild(self, builder=1):
+        """p3d_scene_rebuild_with: a device builder's tree (1 = LBVH, what p3d_scene_rebuild makes; 2 = clustering) over the
+        primitives where they are now, in place.  Frames stay what they were, bit for bit.  Returns p3d_rebuild_info as a
+        dict (rebuilt == 0: a scene served from LDS, left alone)."""
         info = RebuildInfo()
-        _check(lib().p3d_scene_rebuild(self.h, C.byref(info)), "p3d_scene_rebuild")
+        _check(lib().p3d_scene_rebuild_with(self.h, int(builder), C.byref(info)), "p3d_scene_rebuild_with")
         return {n: getattr(info, n) for n, _ in info._fields_}
+
+    def last_builder(self):
+        """p3d_scene_last_builder: whose tree the handle walks now (0 host SAH, 1 device LBVH, 2 device clustering)."""
+        v = C.c_int32(-1)
+        _check(lib().p3d_scene_last_builder(self.h, C.byref(v)), "p3d_scene_last_builder")
+        return v.value
 
     def build_grid(self):
         """p3d_scene_build_grid: GRID mode's grid built on the device from what the handle holds there (after updates from
@@ -974,6 +984,26 @@ def device_bvh(lo, hi, ref, device=0):
                                       refs.ctypes.data, stats.ctypes.data, C.addressof(sah)), "p3d_debug_lbvh_build")
     return {"nodes": nodes, "refs": refs, "n_nodes": int(stats[0]), "n_leaves": int(stats[1]), "n_leaf_refs": int(stats[2]),
             "max_depth": int(stats[3]), "sah_cost": float(np.float32(sah.value))}
+
+
+def ploc_build(lo, hi, ref, device=0):
+    """Builder 2's tree (p3d_debug_ploc_build) over n >= 4 build primitives: device_bvh()'s dict plus rounds and fell_back."""
+    lo = np.ascontiguousarray(lo, np.float32).reshape(-1, 3)
+    hi = np.ascontiguousarray(hi, np.float32).reshape(-1, 3)
+    ref = np.ascontiguousarray(ref, np.uint32).ravel()
+    n = len(ref)
+    assert lo.shape == hi.shape == (n, 3)
+    nodes = np.zeros((max((n + 1) // 2 - 1, 0), 16), np.uint32)
+    refs = np.zeros(n, np.uint32)
+    stats = np.zeros(4, np.uint32)
+    sah = C.c_float(0.0)
+    rounds, fell_back = C.c_int32(0), C.c_int32(0)
+    _check(lib().p3d_debug_ploc_build(int(device), n, lo.ctypes.data, hi.ctypes.data, ref.ctypes.data, nodes.ctypes.data,
+                                      refs.ctypes.data, stats.ctypes.data, C.addressof(sah), C.addressof(rounds),
+                                      C.addressof(fell_back)), "p3d_debug_ploc_build")
+    return {"nodes": nodes, "refs": refs, "n_nodes": int(stats[0]), "n_leaves": int(stats[1]), "n_leaf_refs": int(stats[2]),
+            "max_depth": int(stats[3]), "sah_cost": float(np.float32(sah.value)), "rounds": rounds.value,
+            "fell_back": fell_back.value}
 
 
 def host_grid(desc):

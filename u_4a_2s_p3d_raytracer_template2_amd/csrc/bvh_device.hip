@@ -16,6 +16,8 @@
 //   5. Karras' parallel hierarchy over the leaf keys              (HPG 2012; ties broken by index)
 //   6. bottom-up box refit with one atomic counter per inner node (second arriver continues)
 //   7. NodePair records (a node holds its CHILDREN's boxes), tree depth, SAH cost
+// Builder 2 (p3d_build_opts::builder == 2) shares steps 1-4 and 7 and puts the clustering rounds of bvh_ploc.hip in the place
+// of 5-6; when those rounds do not finish within their bound, 5-6 run after all and the tree is builder 1's.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <stdint.h>
@@ -25,6 +27,7 @@
 #include <vector>
 
 #include "bvh_builder.h"
+#include "bvh_ploc.h"
 #include "p3d_device_types.h"
 #include "p3d_launch.h"
 
@@ -33,8 +36,6 @@ namespace p3d {
 namespace {
 
 constexpr uint32_t kLeafPrims = 2;
-
-struct Box6 { float lo[3], hi[3]; };
 
 __device__ __forceinline__ uint32_t ordered(float f) {          // monotone float -> uint map
     uint32_t u = __float_as_uint(f);
@@ -257,32 +258,79 @@ hipError_t lbvh_scratch_bytes(uint32_t n, size_t* bytes, hipStream_t stream) {
 // The build itself over `d_prims` (device array, padded bounds), enqueued on `stream`: nodes[n_leaves - 1], refs[n].
 // `pool` is the allocation Y was laid out for; it must live until the stream has passed.  The tree's depth (levels of
 // inner nodes) and SAH cost are left in the two words at *d_result.
+struct LbvhArrays {
+    uint64_t *keys, *keys2, *lkeys;
+    uint32_t *vals, *vals2, *arrived, *misc;              // misc: bounds[6], depth, sah
+    Box6 *lbox, *nbox;
+    int2* child;
+    int *pin, *pleaf;
+    LbvhArrays(char* pool, const LbvhLayout& Y)
+        : keys((uint64_t*)(pool + Y.keys)), keys2((uint64_t*)(pool + Y.keys2)), lkeys((uint64_t*)(pool + Y.lkeys)),
+          vals((uint32_t*)(pool + Y.vals)), vals2((uint32_t*)(pool + Y.vals2)), arrived((uint32_t*)(pool + Y.arr)),
+          misc((uint32_t*)(pool + Y.misc)), lbox((Box6*)(pool + Y.lbox)), nbox((Box6*)(pool + Y.nbox)), child((int2*)(pool + Y.child)),
+          pin((int*)(pool + Y.pin)), pleaf((int*)(pool + Y.pleaf)) {}
+};
+constexpr unsigned T = 256;
+
+// steps 1-4: sorted references in d_refs, leaf keys and leaf boxes in the scratch
+static hipError_t lbvh_enqueue_leaves(const BuildPrim* d_prims, uint32_t n, uint32_t* d_refs, char* pool, const LbvhLayout& Y, hipStream_t stream) {
+    const uint32_t L = (n + kLeafPrims - 1) / kLeafPrims;
+    const LbvhArrays A(pool, Y);
+    hipError_t e;
+    const uint32_t init[8] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, 0u, 0u};
+    if ((e = hipMemcpyAsync(A.misc, init, sizeof init, hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(A.arrived, 0, (size_t)L * 4, stream)) != hipSuccess) return e;
+    hipLaunchKernelGGL(lbvh_bounds_kernel, dim3(std::min<unsigned>((n + T - 1) / T, 2048)), dim3(T), 0, stream, d_prims, n, A.misc);
+    hipLaunchKernelGGL(lbvh_morton_kernel, dim3((n + T - 1) / T), dim3(T), 0, stream, d_prims, n, A.misc, A.keys, A.vals);
+    size_t sort_bytes = Y.sort_bytes;
+    e = hipcub::DeviceRadixSort::SortPairs(pool + Y.sort, sort_bytes, A.keys, A.keys2, A.vals, A.vals2, (int)n, 0, 63, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(lbvh_leaves_kernel, dim3((L + T - 1) / T), dim3(T), 0, stream, d_prims, n, L, A.keys2, A.vals2, d_refs, A.lkeys, A.lbox);
+    return hipGetLastError();
+}
+// steps 5-6: Karras' hierarchy and the refit
+static hipError_t lbvh_enqueue_hierarchy(uint32_t n, char* pool, const LbvhLayout& Y, hipStream_t stream) {
+    const uint32_t L = (n + kLeafPrims - 1) / kLeafPrims;
+    const LbvhArrays A(pool, Y);
+    hipLaunchKernelGGL(lbvh_hierarchy_kernel, dim3((L + T - 1) / T), dim3(T), 0, stream, A.lkeys, (int)L, A.child, A.pin, A.pleaf);
+    hipLaunchKernelGGL(lbvh_refit_kernel, dim3((L + T - 1) / T), dim3(T), 0, stream, (int)L, A.child, A.pin, A.pleaf, A.lbox, A.nbox, A.arrived, A.misc + 6);
+    return hipGetLastError();
+}
+// step 7
+static hipError_t lbvh_enqueue_emit(uint32_t n, const BvhOptions& opt, NodePair* d_nodes, char* pool, const LbvhLayout& Y,
+                                    uint32_t** d_result, hipStream_t stream) {
+    const uint32_t L = (n + kLeafPrims - 1) / kLeafPrims;
+    const LbvhArrays A(pool, Y);
+    hipLaunchKernelGGL(lbvh_emit_kernel, dim3((L + T - 1) / T), dim3(T), 0, stream, (int)L, n, A.child, A.lbox, A.nbox, d_nodes,
+                       opt.cost_traverse, opt.cost_intersect, (float*)(A.misc + 7));
+    *d_result = A.misc + 6;
+    return hipGetLastError();
+}
+
+// The build itself over `d_prims` (device array, padded bounds), enqueued on `stream`: nodes[n_leaves - 1], refs[n].
+// `pool` is the allocation Y was laid out for; it must live until the stream has passed.  The tree's depth (levels of
+// inner nodes) and SAH cost are left in the two words at *d_result.
 static hipError_t lbvh_enqueue_at(const BuildPrim* d_prims, uint32_t n, const BvhOptions& opt, NodePair* d_nodes, uint32_t* d_refs,
                                   char* pool, const LbvhLayout& Y, uint32_t** d_result, hipStream_t stream) {
-    const uint32_t L = (n + kLeafPrims - 1) / kLeafPrims;
     hipError_t e;
-    uint64_t *keys = (uint64_t*)(pool + Y.keys), *keys2 = (uint64_t*)(pool + Y.keys2), *lkeys = (uint64_t*)(pool + Y.lkeys);
-    uint32_t *vals = (uint32_t*)(pool + Y.vals), *vals2 = (uint32_t*)(pool + Y.vals2);
-    Box6 *lbox = (Box6*)(pool + Y.lbox), *nbox = (Box6*)(pool + Y.nbox);
-    int2* child = (int2*)(pool + Y.child);
-    int *pin = (int*)(pool + Y.pin), *pleaf = (int*)(pool + Y.pleaf);
-    uint32_t *arrived = (uint32_t*)(pool + Y.arr), *misc = (uint32_t*)(pool + Y.misc);   // misc: bounds[6], depth, sah
-    const uint32_t init[8] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0u, 0u, 0u, 0u, 0u};
-    if ((e = hipMemcpyAsync(misc, init, sizeof init, hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(arrived, 0, (size_t)L * 4, stream)) != hipSuccess) return e;
-    const unsigned T = 256;
-    hipLaunchKernelGGL(lbvh_bounds_kernel, dim3(std::min<unsigned>((n + T - 1) / T, 2048)), dim3(T), 0, stream, d_prims, n, misc);
-    hipLaunchKernelGGL(lbvh_morton_kernel, dim3((n + T - 1) / T), dim3(T), 0, stream, d_prims, n, misc, keys, vals);
-    size_t sort_bytes = Y.sort_bytes;
-    e = hipcub::DeviceRadixSort::SortPairs(pool + Y.sort, sort_bytes, keys, keys2, vals, vals2, (int)n, 0, 63, stream);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(lbvh_leaves_kernel, dim3((L + T - 1) / T), dim3(T), 0, stream, d_prims, n, L, keys2, vals2, d_refs, lkeys, lbox);
-    hipLaunchKernelGGL(lbvh_hierarchy_kernel, dim3((L + T - 1) / T), dim3(T), 0, stream, lkeys, (int)L, child, pin, pleaf);
-    hipLaunchKernelGGL(lbvh_refit_kernel, dim3((L + T - 1) / T), dim3(T), 0, stream, (int)L, child, pin, pleaf, lbox, nbox, arrived, misc + 6);
-    hipLaunchKernelGGL(lbvh_emit_kernel, dim3((L + T - 1) / T), dim3(T), 0, stream, (int)L, n, child, lbox, nbox, d_nodes,
-                       opt.cost_traverse, opt.cost_intersect, (float*)(misc + 7));
-    *d_result = misc + 6;
-    return hipGetLastError();
+    if ((e = lbvh_enqueue_leaves(d_prims, n, d_refs, pool, Y, stream)) != hipSuccess) return e;
+    if ((e = lbvh_enqueue_hierarchy(n, pool, Y, stream)) != hipSuccess) return e;
+    return lbvh_enqueue_emit(n, opt, d_nodes, pool, Y, d_result, stream);
+}
+// Builder 2: the clustered hierarchy between the same leaves and the same emit step.  Waits on the stream once per round
+// (bvh_ploc.h).  `ploc_pool` holds ploc_cluster_scratch_bytes(n_leaves) bytes.  info = {rounds, fell_back}.
+static hipError_t ploc_enqueue_at(const BuildPrim* d_prims, uint32_t n, const BvhOptions& opt, NodePair* d_nodes, uint32_t* d_refs,
+                                  char* pool, const LbvhLayout& Y, char* ploc_pool, uint32_t** d_result, PlocInfo* info, hipStream_t stream) {
+    const uint32_t L = (n + kLeafPrims - 1) / kLeafPrims;
+    const LbvhArrays A(pool, Y);
+    hipError_t e;
+    if ((e = lbvh_enqueue_leaves(d_prims, n, d_refs, pool, Y, stream)) != hipSuccess) return e;
+    int rounds = 0;
+    bool finished = false;
+    if ((e = ploc_cluster(A.lbox, L, A.child, A.nbox, A.misc + 6, ploc_pool, &rounds, &finished, stream)) != hipSuccess) return e;
+    if (!finished && (e = lbvh_enqueue_hierarchy(n, pool, Y, stream)) != hipSuccess) return e;
+    if (info) { info->rounds = rounds; info->fell_back = finished ? 0 : 1; }
+    return lbvh_enqueue_emit(n, opt, d_nodes, pool, Y, d_result, stream);
 }
 
 hipError_t lbvh_enqueue(const BuildPrim* d_prims, uint32_t n, const BvhOptions& opt, NodePair* d_nodes, uint32_t* d_refs,
@@ -291,6 +339,32 @@ hipError_t lbvh_enqueue(const BuildPrim* d_prims, uint32_t n, const BvhOptions& 
     hipError_t e = lbvh_layout(n, 0, Y, stream);
     if (e != hipSuccess) return e;
     return lbvh_enqueue_at(d_prims, n, opt, d_nodes, d_refs, (char*)scratch, Y, d_result, stream);
+}
+
+// the two halves of builder 2's scratch: builder 1's layout, then that of the clustering rounds
+static hipError_t ploc_layout_both(uint32_t n, size_t head, LbvhLayout& Y, size_t* ploc_at, size_t* total, hipStream_t stream) {
+    hipError_t e = lbvh_layout(n, head, Y, stream);
+    if (e != hipSuccess) return e;
+    size_t bytes = 0;
+    if ((e = ploc_cluster_scratch_bytes((n + kLeafPrims - 1) / kLeafPrims, &bytes, stream)) != hipSuccess) return e;
+    *ploc_at = Y.total;
+    *total = Y.total + bytes;
+    return hipSuccess;
+}
+
+hipError_t ploc_scratch_bytes(uint32_t n, size_t* bytes, hipStream_t stream) {
+    LbvhLayout Y;
+    size_t at = 0;
+    return ploc_layout_both(n, 0, Y, &at, bytes, stream);
+}
+
+hipError_t ploc_enqueue(const BuildPrim* d_prims, uint32_t n, const BvhOptions& opt, NodePair* d_nodes, uint32_t* d_refs,
+                        void* scratch, uint32_t** d_result, PlocInfo* info, hipStream_t stream) {
+    LbvhLayout Y;
+    size_t at = 0, total = 0;
+    hipError_t e = ploc_layout_both(n, 0, Y, &at, &total, stream);
+    if (e != hipSuccess) return e;
+    return ploc_enqueue_at(d_prims, n, opt, d_nodes, d_refs, (char*)scratch, Y, (char*)scratch + at, d_result, info, stream);
 }
 
 void lbvh_stats(uint32_t n, const uint32_t result[2], BvhStats& stats) {
@@ -302,27 +376,39 @@ void lbvh_stats(uint32_t n, const uint32_t result[2], BvhStats& stats) {
 }
 
 // Builds the tree of `prims` (host array, padded bounds) into device memory: nodes[n_leaves - 1],
-// refs[n].  n >= 2 * kLeafPrims.  Synchronous (returns when the tree is complete).
-hipError_t build_lbvh_device(const std::vector<BuildPrim>& prims, const BvhOptions& opt, NodePair* d_nodes,
-                             uint32_t* d_refs, BvhStats& stats, hipStream_t stream) {
+// refs[n].  n >= 2 * kLeafPrims.  Synchronous (returns when the tree is complete).  builder 1: the LBVH; 2: the clustered
+// tree, *info telling how many rounds it took and whether the LBVH was made after all.
+hipError_t build_bvh_device(uint32_t builder, const std::vector<BuildPrim>& prims, const BvhOptions& opt, NodePair* d_nodes,
+                            uint32_t* d_refs, BvhStats& stats, PlocInfo* info, hipStream_t stream) {
     const uint32_t n = (uint32_t)prims.size();
     hipError_t e;
     char* pool = nullptr;
     // one scratch allocation, carved up: the uploaded primitives lead it
     LbvhLayout Y;
     const size_t head = ((size_t)n * sizeof(BuildPrim) + 255) & ~(size_t)255;
-    if ((e = lbvh_layout(n, head, Y, stream)) != hipSuccess) return e;
-    if ((e = hipMalloc((void**)&pool, Y.total)) != hipSuccess) return e;
+    size_t ploc_at = 0, total = 0;
+    if (builder == 2) e = ploc_layout_both(n, head, Y, &ploc_at, &total, stream);
+    else { e = lbvh_layout(n, head, Y, stream); total = Y.total; }
+    if (e != hipSuccess) return e;
+    if ((e = hipMalloc((void**)&pool, total)) != hipSuccess) return e;
     auto done = [&](hipError_t rc) { (void)hipFree(pool); return rc; };
     BuildPrim* d_prims = (BuildPrim*)pool;
     if ((e = hipMemcpyAsync(d_prims, prims.data(), (size_t)n * sizeof(BuildPrim), hipMemcpyHostToDevice, stream)) != hipSuccess) return done(e);
     uint32_t* d_result = nullptr;
-    if ((e = lbvh_enqueue_at(d_prims, n, opt, d_nodes, d_refs, pool, Y, &d_result, stream)) != hipSuccess) return done(e);
+    if (info) *info = PlocInfo();
+    if (builder == 2) e = ploc_enqueue_at(d_prims, n, opt, d_nodes, d_refs, pool, Y, pool + ploc_at, &d_result, info, stream);
+    else e = lbvh_enqueue_at(d_prims, n, opt, d_nodes, d_refs, pool, Y, &d_result, stream);
+    if (e != hipSuccess) return done(e);
     uint32_t back[2];
     if ((e = hipMemcpyAsync(back, d_result, sizeof back, hipMemcpyDeviceToHost, stream)) != hipSuccess) return done(e);
     if ((e = hipStreamSynchronize(stream)) != hipSuccess) return done(e);
     lbvh_stats(n, back, stats);
     return done(hipSuccess);
+}
+
+hipError_t build_lbvh_device(const std::vector<BuildPrim>& prims, const BvhOptions& opt, NodePair* d_nodes,
+                             uint32_t* d_refs, BvhStats& stats, hipStream_t stream) {
+    return build_bvh_device(1, prims, opt, d_nodes, d_refs, stats, nullptr, stream);
 }
 
 // ------------------------------------------------------------------ tile order of the persistent tile schedule

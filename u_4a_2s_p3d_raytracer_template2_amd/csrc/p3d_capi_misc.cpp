@@ -85,6 +85,12 @@ int p3d_get_profile(p3d_scene* s, float* frame_ms, float* kernel_ms) {
     return P3D_OK;
 }
 
+int p3d_scene_last_builder(const p3d_scene* s, int32_t* builder) {
+    if (!s || !builder) return fail(P3D_ERR_ARG, "NULL argument");
+    *builder = s->builder;
+    return P3D_OK;
+}
+
 int p3d_last_schedule(p3d_scene* s, int32_t* schedule) {
     if (!s || !schedule) return fail(P3D_ERR_ARG, "NULL argument");
     if (s->last_schedule < 0) return fail(P3D_ERR_STATE, "no render yet");
@@ -263,8 +269,8 @@ int p3d_debug_schlick_kr(int device, uint32_t n, const float* ior_1, const float
     });
 }
 
-int p3d_debug_lbvh_build(int device, uint32_t n, const float* lo3, const float* hi3, const uint32_t* ref, uint32_t* nodes16,
-                         uint32_t* leaf_refs, uint32_t* stats4, float* sah_cost) {
+static int debug_bvh_build(const char* what, uint32_t builder, int device, uint32_t n, const float* lo3, const float* hi3, const uint32_t* ref,
+                           uint32_t* nodes16, uint32_t* leaf_refs, uint32_t* stats4, float* sah_cost, PlocInfo* info) {
     if (!lo3 || !hi3 || !ref || !nodes16 || !leaf_refs || !stats4 || !sah_cost) return fail(P3D_ERR_ARG, "NULL argument");
     if (n < 4) return fail(P3D_ERR_ARG, "the device builder needs at least 4 primitives (two leaves)");
     std::vector<BuildPrim> prims(n);
@@ -275,12 +281,27 @@ int p3d_debug_lbvh_build(int device, uint32_t n, const float* lo3, const float* 
     const size_t n_nodes = (n + 1) / 2 - 1;
     BvhStats bs;
     DebugArg a[2] = {{nullptr, nodes16, n_nodes * sizeof(NodePair)}, {nullptr, leaf_refs, (size_t)n * 4}};
-    int rc = debug_run("p3d_debug_lbvh_build", device, a, [&] {
-        return build_lbvh_device(prims, BvhOptions(), a[0].as<NodePair>(), a[1].as<uint32_t>(), bs, nullptr);
+    int rc = debug_run(what, device, a, [&] {
+        return build_bvh_device(builder, prims, BvhOptions(), a[0].as<NodePair>(), a[1].as<uint32_t>(), bs, info, nullptr);
     });
     if (rc) return rc;
     stats4[0] = bs.n_nodes; stats4[1] = bs.n_leaves; stats4[2] = bs.n_leaf_refs; stats4[3] = bs.max_depth;
     *sah_cost = bs.sah_cost;
+    return P3D_OK;
+}
+
+int p3d_debug_lbvh_build(int device, uint32_t n, const float* lo3, const float* hi3, const uint32_t* ref, uint32_t* nodes16,
+                         uint32_t* leaf_refs, uint32_t* stats4, float* sah_cost) {
+    return debug_bvh_build("p3d_debug_lbvh_build", 1u, device, n, lo3, hi3, ref, nodes16, leaf_refs, stats4, sah_cost, nullptr);
+}
+
+int p3d_debug_ploc_build(int device, uint32_t n, const float* lo3, const float* hi3, const uint32_t* ref, uint32_t* nodes16,
+                         uint32_t* leaf_refs, uint32_t* stats4, float* sah_cost, int32_t* rounds, int32_t* fell_back) {
+    if (!rounds || !fell_back) return fail(P3D_ERR_ARG, "NULL argument");
+    PlocInfo info;
+    int rc = debug_bvh_build("p3d_debug_ploc_build", 2u, device, n, lo3, hi3, ref, nodes16, leaf_refs, stats4, sah_cost, &info);
+    if (rc) return rc;
+    *rounds = info.rounds; *fell_back = info.fell_back;
     return P3D_OK;
 }
 

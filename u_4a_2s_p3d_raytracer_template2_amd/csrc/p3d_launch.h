@@ -60,6 +60,16 @@ hipError_t lbvh_scratch_bytes(uint32_t n, size_t* bytes, hipStream_t stream);
 hipError_t lbvh_enqueue(const BuildPrim* d_prims, uint32_t n, const BvhOptions& opt, NodePair* d_nodes, uint32_t* d_refs,
                         void* scratch, uint32_t** d_result, hipStream_t stream);
 void lbvh_stats(uint32_t n, const uint32_t result[2], BvhStats& stats);
+// ... and builder 2 (bvh_ploc.hip between builder 1's leaves and its emit step): the same split, the same two result words.
+// ploc_enqueue WAITS on the stream once per clustering round.  fell_back: the rounds did not finish within their bound and
+// the tree is builder 1's.
+struct PlocInfo { int32_t rounds = 0, fell_back = 0; };
+hipError_t ploc_scratch_bytes(uint32_t n, size_t* bytes, hipStream_t stream);
+hipError_t ploc_enqueue(const BuildPrim* d_prims, uint32_t n, const BvhOptions& opt, NodePair* d_nodes, uint32_t* d_refs,
+                        void* scratch, uint32_t** d_result, PlocInfo* info, hipStream_t stream);
+// builder 1 or 2 over host primitives, synchronous (build_lbvh_device is builder 1)
+hipError_t build_bvh_device(uint32_t builder, const std::vector<BuildPrim>& prims, const BvhOptions& opt, NodePair* d_nodes,
+                            uint32_t* d_refs, BvhStats& stats, PlocInfo* info, hipStream_t stream);
 hipError_t sort_tiles_by_cost(const uint32_t* cost, uint32_t* cost_sorted, uint32_t* iota, uint32_t* order, uint32_t n,
                               void* temp, size_t& temp_bytes, hipStream_t stream);
 

@@ -54,9 +54,10 @@ int p3d_scene_create(const p3d_scene_desc* d, const p3d_build_opts* opts, int de
         F.build_prims.swap(kept);
     }
     std::vector<NodePair> nodes; std::vector<uint32_t> refs; BvhStats bs;
-    if (opts && opts->builder > 1) return fail(P3D_ERR_ARG, "builder must be 0 (host SAH) or 1 (device LBVH)");
-    // the device builder needs at least two leaves; tiny scenes are built on the host either way
-    const bool device_build = opts && opts->builder == 1 && F.build_prims.size() >= 64;
+    if (opts && opts->builder > 2) return fail(P3D_ERR_ARG, "builder must be 0 (host SAH), 1 (device LBVH) or 2 (device clustering)");
+    // the device builders need at least two leaves; tiny scenes are built on the host either way
+    const bool device_build = opts && opts->builder >= 1 && F.build_prims.size() >= 64;
+    PlocInfo ploc;
     if (device_build) {
         // built on the device into scratch buffers, read back: the leaves are typed and the primitive arrays put
         // into leaf order on the host (type_leaves) before anything is uploaded for rendering
@@ -65,7 +66,7 @@ int p3d_scene_create(const p3d_scene_desc* d, const p3d_build_opts* opts, int de
         NodePair* d_nodes = nullptr; uint32_t* d_refs = nullptr;
         hipError_t be = hipMalloc((void**)&d_nodes, nodes.size() * sizeof(NodePair));
         if (be == hipSuccess) be = hipMalloc((void**)&d_refs, refs.size() * sizeof(uint32_t));
-        if (be == hipSuccess) be = build_lbvh_device(F.build_prims, bo, d_nodes, d_refs, bs, nullptr);
+        if (be == hipSuccess) be = build_bvh_device(opts->builder, F.build_prims, bo, d_nodes, d_refs, bs, &ploc, nullptr);
         if (be == hipSuccess) be = hipMemcpy(nodes.data(), d_nodes, nodes.size() * sizeof(NodePair), hipMemcpyDeviceToHost);
         if (be == hipSuccess) be = hipMemcpy(refs.data(), d_refs, refs.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
         (void)hipFree(d_nodes); (void)hipFree(d_refs);
@@ -88,6 +89,7 @@ int p3d_scene_create(const p3d_scene_desc* d, const p3d_build_opts* opts, int de
 
     std::unique_ptr<p3d_scene> s(new p3d_scene());      // every early return below frees what the handle holds so far
     s->device = device;
+    s->builder = !device_build ? 0 : (opts->builder == 2 && !ploc.fell_back) ? 2 : 1;
     if (const char* e = getenv("P3D_FRAME_STREAMS")) { int v = atoi(e); if (v >= 1 && v <= kLanes) s->frame_streams = v; }
     if (const char* e = getenv("P3D_RESOLVE_BLOCKS")) { int v = atoi(e); if (v >= 1 && v <= 64) s->resolve_blocks_per_shard = v; }   // tuning experiments
     if (const char* e = getenv("P3D_FUSED_RESOLVE_PX")) { int v = atoi(e); if (v >= 0 && v <= (1 << 24)) s->fused_resolve_shard_px = v; }

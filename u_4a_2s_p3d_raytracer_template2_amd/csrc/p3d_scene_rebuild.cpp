@@ -1,6 +1,7 @@
-// p3d_scene_rebuild.cpp -- p3d_scene_rebuild and p3d_scene_tree_cost of include/p3d_hip.h: the tree of a live scene handle
-// is built again on the device (bvh_device.hip) from the primitive records the handle holds there, the leaves are typed and
-// the records put into the new leaf order on the device too (scene_rebuild.hip).  Everything is enqueued on the scene's
+// p3d_scene_rebuild.cpp -- p3d_scene_rebuild, p3d_scene_rebuild_with and p3d_scene_tree_cost of include/p3d_hip.h: the tree
+// of a live scene handle is built again on the device (bvh_device.hip; builder 2: with bvh_ploc.hip's rounds, a wait each)
+// from the primitive records the handle holds there, the leaves are typed and the records put into the new leaf order on
+// the device too (scene_rebuild.hip).  Everything is enqueued on the scene's
 // stream; the call waits for the old tree's cost (a handle that has f32 node pairs), for the number of leaf records, which
 // sizes the new blob, and for the finished handle.
 // Every allocation is made before anything of the handle changes, and what the handle held is freed after the last wait.
@@ -64,8 +65,12 @@ extern "C" int p3d_scene_tree_cost(p3d_scene* s, float* sah_cost) {
     return current_cost(s, sah_cost);
 }
 
-extern "C" int p3d_scene_rebuild(p3d_scene* s, p3d_rebuild_info* info) {
+extern "C" int p3d_scene_rebuild(p3d_scene* s, p3d_rebuild_info* info) { return p3d_scene_rebuild_with(s, 1u, info); }
+
+extern "C" int p3d_scene_rebuild_with(p3d_scene* s, uint32_t builder, p3d_rebuild_info* info) {
     if (!s) return fail(P3D_ERR_ARG, "scene is NULL");
+    if (builder != 1u && builder != 2u)
+        return fail(P3D_ERR_ARG, "builder must be 1 (device LBVH) or 2 (device clustering): the host builder needs the host's geometry");
     if (s->cull_never_hit)
         return fail(P3D_ERR_STATE, "scene was built with cull_never_hit: a moved triangle may no longer be one no ray can hit; create a new handle");
     HIP_TRY(hipSetDevice(s->device));
@@ -90,7 +95,7 @@ extern "C" int p3d_scene_rebuild(p3d_scene* s, p3d_rebuild_info* info) {
     // ---- allocations: scratch, then what the handle will hold
     size_t scan_bytes = 0, lbvh_bytes = 0;
     HIP_TRY(rebuild_scan_temp_bytes(std::max(n_prims, n), &scan_bytes, st));
-    HIP_TRY(lbvh_scratch_bytes(n, &lbvh_bytes, st));
+    HIP_TRY(builder == 2u ? ploc_scratch_bytes(n, &lbvh_bytes, st) : lbvh_scratch_bytes(n, &lbvh_bytes, st));
     size_t off = 0;
     auto carve = [&](size_t bytes) { size_t at = off; off = (off + bytes + 255) & ~(size_t)255; return at; };
     const size_t o_bounded = carve((size_t)n_prims * 4), o_pos = carve((size_t)n_prims * 4), o_prims = carve((size_t)n * sizeof(BuildPrim));
@@ -124,7 +129,9 @@ extern "C" int p3d_scene_rebuild(p3d_scene* s, p3d_rebuild_info* info) {
     const BvhOptions bo;
     uint32_t* d_result = nullptr;
     HIP_TRY(launch_rebuild_prims(S, n, W, st));
-    HIP_TRY(lbvh_enqueue(W.prims, n, bo, nodes, W.refs, base + o_lbvh, &d_result, st));
+    PlocInfo ploc;
+    if (builder == 2u) HIP_TRY(ploc_enqueue(W.prims, n, bo, nodes, W.refs, base + o_lbvh, &d_result, &ploc, st));   // waits once per round
+    else HIP_TRY(lbvh_enqueue(W.prims, n, bo, nodes, W.refs, base + o_lbvh, &d_result, st));
     HIP_TRY(launch_rebuild_type(n, W, st));
     uint32_t result[2] = {0, 0}, last_rec = 0, last_need = 0;
     float root[kStatusRootFloats];
@@ -192,6 +199,7 @@ extern "C" int p3d_scene_rebuild(p3d_scene* s, p3d_rebuild_info* info) {
     s->refit.nodes = std::move(new_nodes); s->refit.parent = std::move(new_parent); s->refit.arrived = std::move(new_arrived);
     if (!s->refit.status.p) s->refit.status = std::move(new_status);
     s->refit.ready = true;
+    s->builder = (builder == 2u && !ploc.fell_back) ? 2 : 1;
     for (uint32_t i = 0; i < n_prims; i++) s->grid_src[i].ref = map[i];
     // max_depth sizes the walk stacks: the occupancy caches (tile_occ, wf_occ) are keyed on the stack size and the LDS
     // they were asked with, and the launch parameters are filled from the handle every frame, so nothing else holds it

@@ -165,6 +165,7 @@ struct p3d_scene {
     size_t lds_scene_limit = p3d::kLdsSceneLimit;  // blobs up to this size are rendered from an LDS copy
     bool lds_capable = false;            // ... and then carry the f32 nodes the LDS walk reads
     int last_schedule = -1;
+    int32_t builder = 0;                 // whose tree the handle walks: 0 host SAH, 1 device LBVH, 2 device clustering (p3d_scene_last_builder)
     bool unit_rays_only = false;         // built with cull_never_hit: cannot serve un-normalised (NONE-mode) shadow rays
     bool cull_never_hit = false;         // ... the option itself, whether or not it found a triangle to leave out: ray streams are refused
     uint32_t packet_node_limit = 64;     // trees up to this many node pairs use the wave-wide walk
