@@ -508,7 +508,9 @@ typedef struct p3d_ray_outputs {  /* every plane may be NULL */
  *    outside 1..16.
  *  - a scene created with cull_never_hit is refused with P3D_ERR_STATE: that shortcut rests on |dir| <= sqrt(2), which a
  *    caller's ray does not promise.
- *  - results for non-finite origins or directions are unspecified (the call still returns).
+ *  - a ray with a NaN or an infinity in its origin or direction, or whose largest direction component lies outside
+ *    [2^-60, 2^60], is tested against every primitive, as the reference's loop over the scene does (accel NONE and BVH;
+ *    in GRID mode the reference converts such a ray's cell coordinate to int, which is undefined, and so are the results).
  *  - the staging of host-memory rays and planes is owned by the handle, counted in p3d_scene_stats::device_bytes as it
  *    grows and kept for the next call.
  *  - the workspace obeys the p3d_set_tuning() budget: streams that need more run in bands of rays, the way frames run in
@@ -531,7 +533,10 @@ typedef struct p3d_occlusion_outputs {
  * Accel_Struct would set insideShadow to for that ray:
  *    P3D_ACCEL_NONE  true if any primitive's intercepts() accepts the ray: the direction is used as given and there is NO
  *                    distance bound -- a primitive beyond the segment's end occludes it
- *    P3D_ACCEL_BVH   length = |dir|, the direction is normalised, true if a primitive is hit with t < length
+ *    P3D_ACCEL_BVH   length = |dir|, the direction is normalised, true if a primitive is hit with t < length.  (The
+ *                    reference's own tree answers false for a segment that starts exactly ON a primitive's bounding box and
+ *                    does not enter it -- its box test rejects the node although intercepts() accepts the primitive at
+ *                    t = 0.  The answer here is the primitive's: true.  tests/test_gpu_edge_rays.py keeps such segments.)
  *    P3D_ACCEL_GRID  the same bound over the reference's own grid, with its rule that a ray for which Init_Traverse fails
  *                    -- one that misses the grid's box -- is IN SHADOW (RT/grid.cpp:327-328).  The grid is built by the
  *                    first GRID call of a scene, this entry's included, under the rules of the first GRID frame: refused
@@ -554,7 +559,9 @@ typedef struct p3d_occlusion_outputs {
  *    p3d_rays::memory == 0 it uploads the segments first, through staging the handle owns (shared with p3d_trace_rays;
  *    counted in p3d_scene_stats::device_bytes as either entry grows it, and kept for the next call).
  *  - one launch, no ray queues and no workspace: the p3d_set_tuning() budget does not apply.
- *  - results for non-finite inputs, and for a zero-length dir in BVH or GRID mode, are unspecified (the call still returns).
+ *  - non-finite inputs, a zero-length dir and a dir whose largest component lies outside [2^-60, 2^60] are tested against
+ *    every primitive in NONE and BVH mode (the rules above, no tree in between); in GRID mode the reference converts such a
+ *    segment's cell coordinate to int, which is undefined, and so are the results (the call still returns).
  *  - the handle's frame state is not touched: the measured schedule choice, the learned tile orders, p3d_last_schedule(),
  *    p3d_last_primary_tiles() and the ray-stream state are what they were.
  *  - after p3d_scene_update or p3d_scene_rebuild the answers follow the moved geometry, like everything else. */
@@ -682,7 +689,9 @@ int p3d_debug_set_stamp_level(p3d_scene* scene, int32_t level);
 /* Unit-level probe used by the parity tests: intersect n rays with one primitive each using
  * the DEVICE intersectors (Sphere/Triangle/aaBox/Plane::intercepts, RT/scene.cpp:55-283).
  * Host arrays: type[n], prim12[n*12] (plane = PN,D), origin[n*3], dir[n*3] -> hit[n], t[n],
- * normal[n*3] (getNormal(hit point).normalize()). */
+ * normal[n*3] (getNormal(hit point).normalize()).  type: 0 sphere, 1 triangle, 2 box, 3 plane, and 4 = a triangle
+ * through the reciprocal form of the test (1 / det by csrc/p3d_device_math.h's frcp()) that scenes read from HBM use:
+ * the same bits as type 1 on every input. */
 int p3d_debug_intersect(int device, uint32_t n, const uint32_t* type, const float* prim12,
                         const float* origin, const float* dir, int32_t* hit, float* t,
                         float* normal);

@@ -851,7 +851,9 @@ def gather_all(comms, scenes, tile_ptrs, gathered_ptr, tile_bytes):
 
 
 def debug_intersect(ptype, prim12, origin, direction, device=0):
-    """Device intersectors on n (ray, primitive) pairs -> (hit[n] bool, t[n], normal[n,3])."""
+    """Device intersectors on n (ray, primitive) pairs -> (hit[n] bool, t[n], normal[n,3]).  ptype: 0 sphere, 1 triangle,
+    2 box, 3 plane (prim12 = unit normal, D), 4 = a triangle through hit_triangle<true>, the frcp() form of the test that
+    scenes read from HBM use."""
     ptype = np.ascontiguousarray(ptype, np.uint32)
     prim12 = np.ascontiguousarray(prim12, np.float32).reshape(-1, 12)
     origin = np.ascontiguousarray(origin, np.float32).reshape(-1, 3)

@@ -29,10 +29,11 @@ __global__ void debug_intersect_kernel(uint32_t n, const uint32_t* type, const f
         if (h) { V3 hp = add(r.o, mul(r.d, tt)); nn = normalized(normalized(sub(hp, c))); }
         break;
     }
-    case 1: {
+    case 1:
+    case 4: {    // 4: the same triangle through hit_triangle<true>, the frcp() form every scene read from HBM tests with
         V3 p0 = mk(d[0], d[1], d[2]), p1 = mk(d[3], d[4], d[5]), p2 = mk(d[6], d[7], d[8]);
         V3 e1 = sub(p1, p0), e2 = sub(p2, p0);
-        h = hit_triangle(r, p0, e1, e2, tt);
+        h = type[i] == 4 ? hit_triangle<true>(r, p0, e1, e2, tt) : hit_triangle<false>(r, p0, e1, e2, tt);
         if (h) {     // the host-side statement of this lives in scene_flatten.cpp; the probe keeps the device arithmetic
             V3 m = mk((e1.y * e2.z) - (e1.z * e2.y), (e1.z * e2.x) - (e1.x * e2.z), (e1.x * e2.y) - (e1.y * e2.x));
             nn = normalized(normalized(m));

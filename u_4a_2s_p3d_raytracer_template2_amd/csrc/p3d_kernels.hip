@@ -404,7 +404,7 @@ __device__ __forceinline__ TravCtx wave_stack(const LaunchParams& P, uint32_t ex
     uint32_t* base = p3d_lds + View<LDS>::scene_dwords(P) + wave * (P.trav_stack_dwords + extra_dwords_per_wave);
     if (wave_base) *wave_base = base;
     TravCtx tc;
-    tc.lane.region = base; tc.lane.lane = threadIdx.x & 63; tc.lane.slots = P.trav_stack_entries;
+    tc.lane.region = base; tc.lane.lane = threadIdx.x & 63; tc.lane.slots = P.trav_stack_entries; tc.lane.walk_all = false;
     tc.wave.base = reinterpret_cast<int32_t*>(base);     // the two walks never run in the same launch
     tc.share = base + P.trav_stack_dwords - kShareDwords; // work-sharing walk: the last kShareDwords of the wave's region (host: p3d_render)
     return tc;
@@ -586,7 +586,7 @@ __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void wf_rays_kernel(co
     const bool valid = i < R.count;
     if (__ballot(valid) == 0) return;
     const Shard sh = shard_of(P, blockIdx.x % kWfShards, par);
-    const TravCtx tc = wave_stack<LDS>(P, 0);
+    TravCtx tc = wave_stack<LDS>(P, 0);
     Ctr ctr = {0, 0, 0, 0, 0, 0, 0};
     Ray ray; ray.o = mk(0.0f, 0.0f, 0.0f); ray.d = mk(1.0f, 0.0f, 0.0f);
     if (valid) {                                                 // Ray(origin[i], dir[i]): the direction is NOT normalised
@@ -594,6 +594,7 @@ __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void wf_rays_kernel(co
         const float* pd = R.dir + 3 * (size_t)i;
         ray.o = mk(po[0], po[1], po[2]); ray.d = mk(pd[0], pd[1], pd[2]);
     }
+    tc.lane.walk_all = !slab_can_cull(ray);                      // a caller's ray: p3d_traverse.h, slab_can_cull (its shadow rays too)
     const Hit h = find_closest<false, WALK>(P, sv, ray, valid, tc, ctr);
     if (P.hit_id || R.t || R.normal) {                           // wave-uniform
         const bool hit = valid && h.ref != 0xFFFFFFFFu;
@@ -625,7 +626,7 @@ __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void wf_occlusion_kern
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;    // (the host keeps n below 2^31)
     const bool valid = i < R.count;
     if (__ballot(valid) == 0) return;                            // no barrier follows the scene copy's
-    const TravCtx tc = wave_stack<LDS>(P, 0);
+    TravCtx tc = wave_stack<LDS>(P, 0);
     Ctr ctr = {0, 0, 0, 0, 0, 0, 0};
     V3 o = mk(0.0f, 0.0f, 0.0f), L = mk(1.0f, 0.0f, 0.0f);
     if (valid) {
@@ -633,6 +634,7 @@ __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void wf_occlusion_kern
         const float* pd = R.dir + 3 * (size_t)i;
         o = mk(po[0], po[1], po[2]); L = mk(pd[0], pd[1], pd[2]);
     }
+    { Ray given; given.o = o; given.d = L; tc.lane.walk_all = !slab_can_cull(given); }   // a caller's segment, as given: p3d_traverse.h
     const bool occluded = light_occluded<false, WALK>(P, sv, shadow_segment(L), o, valid, tc, ctr);
     if (valid) R.occluded[i] = occluded ? 1 : 0;
 }

@@ -107,6 +107,7 @@ template <class SV> __device__ __forceinline__ void sv_mat(const SV& sv, uint32_
 struct TravStack {
     uint32_t* region;    // this wave's stack region
     uint32_t lane, slots;
+    bool walk_all;       // the lane's walk culls nothing (make_slab): set where a caller's ray enters, false in every frame kernel
 };
 constexpr uint32_t kWideStackDwords = 128, kSlimStackDwords = 96;    // per slot per wave
 
@@ -195,22 +196,41 @@ __device__ __forceinline__ float slab_rcp(float d) {
     return __builtin_amdgcn_fmed3f(__builtin_amdgcn_rcpf(d), -1e30f, 1e30f);
 #endif
 }
+// Rays the slab test cannot cull for: a NaN or an infinity in the origin or the direction, and a direction whose largest
+// component lies outside [2^-60, 2^60] (a zero direction included).  The reference has no tree in front of its closest-hit
+// loop or its NONE-mode shadow loop, and on such rays its intersectors accept primitives that no box test would reach:
+// aaBox::intercepts ignores an axis whose distances are NaN, Sphere::intercepts reports EVERY sphere once d.d overflows or
+// underflows (delta is NaN or b * b), and the +-1e30 that stands in for 1 / 0 above is no longer beyond every hit
+// distance.  For them the slab constants are all zero: every box then passes (t0 = 0 <= t1 = 1e-30), the walk visits every
+// primitive, and the answer is the reference's loop over all of them.  tests/test_gpu_edge_rays.py: scale, nonfinite.
+// Only a caller's ray can be one (p3d_trace_rays, p3d_occluded): the kernels that read those evaluate this once per ray
+// and pass it on as TravStack::walk_all.  Frame kernels pass a constant false, and their code is what it was without it:
+// a camera ray and a reflected or refracted one is normalised, and a ray that is NaN in every component
+// misses every box and every primitive alike.
+__device__ __forceinline__ bool slab_can_cull(const Ray& r) {
+    const float m = fmaxf(fmaxf(fabsf(r.d.x), fabsf(r.d.y)), fabsf(r.d.z));
+    const float sum = fabsf(r.o.x) + fabsf(r.o.y) + fabsf(r.o.z) + fabsf(r.d.x) + fabsf(r.d.y) + fabsf(r.d.z);
+    const uint32_t e = __float_as_uint(m) >> 23;                         // m >= 0 (fmaxf drops NaNs: `sum` sees those)
+    return (e - 67u <= 120u) && (sum < __builtin_inff());               // 2^-60 <= m < 2^61, everything finite
+}
 // Scenes in LDS: f32 boxes, plane distance = fma(plane, i, -o * i)
-__device__ __forceinline__ SlabRay make_slab(const LdsScene&, const Ray& r) {
+__device__ __forceinline__ SlabRay make_slab(const LdsScene&, const Ray& r, bool walk_all) {
     SlabRay s;
     // 1-ulp hardware reciprocals are enough here: the slab test only has to be conservative
     // (boxes are padded by >= 1e-3, far above a relative 1e-7), it never decides a hit
     s.ix = slab_rcp(r.d.x); s.iy = slab_rcp(r.d.y); s.iz = slab_rcp(r.d.z);
     s.kx = -r.o.x * s.ix; s.ky = -r.o.y * s.iy; s.kz = -r.o.z * s.iz;
+    if (walk_all) { s.ix = 0.0f; s.iy = 0.0f; s.iz = 0.0f; s.kx = 0.0f; s.ky = 0.0f; s.kz = 0.0f; }
     return s;
 }
 // Scenes read from HBM: 16-bit plane codes, plane = qb + code * qs, so the distance is fma(code, qs * i, (qb - o) * i):
 // the same one FMA per plane, with the de-quantisation folded into the per-ray constants
-__device__ __forceinline__ SlabRay make_slab(const GlobalScene& g, const Ray& r) {
+__device__ __forceinline__ SlabRay make_slab(const GlobalScene& g, const Ray& r, bool walk_all) {
     SlabRay s;
     const float ix = slab_rcp(r.d.x), iy = slab_rcp(r.d.y), iz = slab_rcp(r.d.z);
     s.ix = g.qs[0] * ix; s.iy = g.qs[1] * iy; s.iz = g.qs[2] * iz;
     s.kx = (g.qb[0] - r.o.x) * ix; s.ky = (g.qb[1] - r.o.y) * iy; s.kz = (g.qb[2] - r.o.z) * iz;
+    if (walk_all) { s.ix = 0.0f; s.iy = 0.0f; s.iz = 0.0f; s.kx = 0.0f; s.ky = 0.0f; s.kz = 0.0f; }
     return s;
 }
 // conservative slab test against a padded box; returns entry distance in tn.  One fused multiply-add per plane
@@ -227,8 +247,9 @@ __device__ __forceinline__ bool slab(const SlabRay& s, float lx, float ly, float
     t1 = t1 * 1.0000005f + 1e-30f;
     tn = t0;
     // (t0 <= t1 && t0 <= tlimit) as ONE comparison against min(t1, tlimit): a mask AND on the scalar unit less per child.
-    // t0 itself stays in the comparison, so a ray with NaNs in it (t0 and t1 both NaN) still misses every box -- folding
-    // t1 >= 0 in as max(t0, 0) would not: fmax drops the NaN (profiles/r02_experiments_traversal.txt).
+    // t0 itself stays in the comparison, so a frame's ray that is NaN in every component (t0 and t1 both NaN) still misses
+    // every box -- folding t1 >= 0 in as max(t0, 0) would not: fmax drops the NaN (profiles/r02_experiments_traversal.txt).
+    // (A caller's ray with a NaN in it has all-zero constants instead, make_slab's walk_all: t0 = 0, every box passes.)
     return (t0 <= fminf(t1, tlimit)) && (t1 >= 0.0f);
 }
 
@@ -322,7 +343,7 @@ __device__ __forceinline__ Hit closest_hit(const LaunchParams& P, const SV& sv, 
             }
         }
     }
-    SlabRay s = make_slab(sv, r);
+    SlabRay s = make_slab(sv, r, region.walk_all);
     typename StackOf<SV>::type st(region);
     int32_t cur = 0;
     if (FlatWalk<SV>::value) {
@@ -424,7 +445,7 @@ __device__ __forceinline__ bool any_hit(const LaunchParams& P, const SV& sv, con
             }
         }
     }
-    SlabRay s = make_slab(sv, r);
+    SlabRay s = make_slab(sv, r, region.walk_all);
     float tlimit = bounded ? tmax : 3.402823466e+38f;
     typename StackOf<SV>::type st(region);
     int32_t cur = 0;
@@ -487,7 +508,8 @@ __device__ __forceinline__ bool any_hit(const LaunchParams& P, const SV& sv, con
 // may test a box the owner would have pruned a moment later).
 //
 // Per-wave LDS ("share region", behind the wave's stack region): [0,64) donor table of a steal round, [64,192) the
-// owners' best keys (u64: t bits << 32 | scene id), [192,320) ref + material of the key's holder, [320,384) any-hit flags.
+// owners' best keys (u64: t bits << 32 | scene id), [192,320) ref + material of the key's holder, [320,384) any-hit flags
+// (during a closest-hit query: the holder's t, bit for bit).
 constexpr unsigned long long kShareNoHit = 0x7F7FFFFFFFFFFFFFull;      // t = FLT_MAX, id = none
 
 __device__ __forceinline__ void wave_lds_fence() {
@@ -547,8 +569,12 @@ __device__ __forceinline__ void share_publish(uint32_t* share, uint32_t owner, c
     unsigned long long* keys = reinterpret_cast<unsigned long long*>(share + 64);
     const unsigned long long key = share_key(h);
     atomicMin(&keys[owner], key);
-    if (reinterpret_cast<volatile unsigned long long*>(keys)[owner] == key)
+    if (reinterpret_cast<volatile unsigned long long*>(keys)[owner] == key) {
         reinterpret_cast<volatile unsigned long long*>(share + 192)[owner] = (unsigned long long)h.ref | ((unsigned long long)h.mat << 32);
+        // t as the intersector returned it: the key holds t + 0.0f, and a sphere left from its own surface gives t = -0.0f
+        // (the any-hit flags' slot is free during a closest-hit query)
+        reinterpret_cast<volatile uint32_t*>(share + 320)[owner] = __float_as_uint(h.t);
+    }
 }
 
 // closest hit, work shared among the lanes of the wave.  Must be called by all 64 lanes together; `active` = this lane
@@ -573,7 +599,7 @@ __device__ __forceinline__ Hit closest_hit_shared(const LaunchParams& P, const G
     }
     const uint32_t lane = region.lane;
     Ray r = ray;
-    SlabRay s = make_slab(sv, r);
+    SlabRay s = make_slab(sv, r, region.walk_all);
     uint32_t* refs = region.region + lane;
     int sp = 0, bot = 0;
     int32_t cur = active ? 0 : P3D_DONE;
@@ -631,7 +657,8 @@ __device__ __forceinline__ Hit closest_hit_shared(const LaunchParams& P, const G
         const unsigned long long aq = reinterpret_cast<volatile unsigned long long*>(share + 192)[lane];
         const uint2 a = make_uint2((uint32_t)aq, (uint32_t)(aq >> 32));
         best.t = 3.402823466e+38f; best.ref = 0xFFFFFFFFu; best.sid = 0xFFFFFFFFu; best.mat = 0;
-        if (active && k != kShareNoHit) { best.t = __uint_as_float((uint32_t)(k >> 32)); best.sid = (uint32_t)k; best.ref = a.x; best.mat = a.y; }
+        const uint32_t t_bits = reinterpret_cast<volatile uint32_t*>(share + 320)[lane];
+        if (active && k != kShareNoHit) { best.t = __uint_as_float(t_bits); best.sid = (uint32_t)k; best.ref = a.x; best.mat = a.y; }
         wave_lds_fence();
     }
     return best;
@@ -659,7 +686,7 @@ __device__ __forceinline__ bool any_hit_shared(const LaunchParams& P, const Glob
     }
     const uint32_t lane = region.lane;
     Ray r = ray;
-    SlabRay s = make_slab(sv, r);
+    SlabRay s = make_slab(sv, r, region.walk_all);
     float limit = bounded ? tmax : 3.402823466e+38f;
     uint32_t* refs = region.region + lane;
     int sp = 0, bot = 0;
@@ -925,7 +952,7 @@ __device__ __forceinline__ Hit closest_hit_packet(const LaunchParams& P, const S
         }
     }
     if (__ballot(active) == 0) return best;
-    SlabRay s = make_slab(sv, r);
+    SlabRay s = make_slab(sv, r, false);
     int sp = 0;
     int32_t cur = 0;
     for (;;) {
@@ -972,7 +999,7 @@ __device__ __forceinline__ bool any_hit_packet(const LaunchParams& P, const SV& 
         }
     }
     if (__ballot(active && !occ) == 0) return occ;
-    SlabRay s = make_slab(sv, r);
+    SlabRay s = make_slab(sv, r, false);
     const float tlimit = bounded ? tmax : 3.402823466e+38f;
     int sp = 0;
     int32_t cur = 0;
