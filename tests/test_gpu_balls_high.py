@@ -6,7 +6,9 @@ Frames are compared with tests/golden/balls_high_frames.npz (rendered by oracle/
 and with live oracle renders, at the project's bar: rgb32f bit for bit (conftest.RGB_TOL = 0), rgb8 equal, primary hit
 ids equal, closest / shadow query counts and ray counts equal.  Everything goes through the C-ABI.
 
-A handle is never rendered with two row_block values: the heaviest-tile-first order cache does not key on it.
+Every test here makes a fresh handle per configuration (or repeats one configuration).  One handle rendered with several
+row_block values, resolutions, worlds, depths and accel modes -- the tile-order key holds row_block since the keys were
+named (csrc/p3d_frame_config.h) -- is tests/test_gpu_handle_walks.py.
 """
 import json
 import os
@@ -16,6 +18,7 @@ import pytest
 
 from conftest import GOLDEN, RGB_TOL, assert_rgb8_equal
 from extra_scenes import scene_path
+from handle_walks import stitch
 from oracle import oracle_py as O
 import u_4a_2s_p3d_raytracer_template2_amd as P
 
@@ -145,23 +148,6 @@ def test_forced_schedule_repeated_frames_keep_the_reference_frame(schedule, priv
 
 # ---- shards of the frame (row blocks dealt round robin over ranks)
 
-def stitch(parts, H, W, world, rb):
-    st = {"rgb8": np.zeros((H, W, 3), np.uint8), "rgb32f": np.zeros((H, W, 3), np.float32),
-          "hit_id": np.full((H, W), -2, np.int32)}
-    for r, part in enumerate(parts):
-        rows = part["rgb8"].shape[0]
-        assert rows == P.local_rows(H, rb, world)
-        for lb in range(rows // rb):
-            y0 = (lb * world + r) * rb
-            if y0 >= H:
-                continue
-            n = min(rb, H - y0)
-            for k in st:
-                st[k][y0:y0 + n] = part[k][lb * rb:lb * rb + n]
-    st["counters"] = {k: sum(p["counters"][k] for p in parts) for k in ("closest_queries", "shadow_queries", "rays", "pixels")}
-    return st
-
-
 def shards(name, world, rb, **over):
     m = CASES[name]
     hs, ds = handle(m["res"])
@@ -170,6 +156,7 @@ def shards(name, world, rb, **over):
     for r in range(world):
         kw["rank"] = r
         parts.append(ds.render(hs.camera(), **kw))
+        assert parts[-1]["rgb8"].shape[0] == P.local_rows(m["res"][1], rb, world)
     ds.close()
     return stitch(parts, m["res"][1], m["res"][0], world, rb)
 
