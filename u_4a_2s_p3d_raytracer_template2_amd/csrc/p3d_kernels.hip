@@ -677,6 +677,25 @@ __device__ __forceinline__ void queued_ray_step(const LaunchParams& P, const typ
     stamp_wave(P, wave_id, 4, st1);
 }
 
+// Inclusive prefix sum over the 64 lanes of a wave, all of them active, in six vector adds on the data-parallel
+// primitives: row shifts by 1, 2, 4 and 8 sum within each row of 16 lanes, then the last lane of rows 0 and 2 is
+// broadcast into rows 1 and 3, and lane 31 into rows 2 and 3.  A lane with no source, and a row the mask leaves out,
+// adds zero.  Needs a 64-lane wave with every lane enabled (a disabled lane would neither pass its value on nor take
+// one) and the row broadcasts of the gfx9 family (gfx950 has them; gfx10 and later do not).
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ uint32_t dpp_or_zero(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, false);
+}
+__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v) {
+    v += dpp_or_zero<0x111, 0xf>(v);     // row_shr:1
+    v += dpp_or_zero<0x112, 0xf>(v);     // row_shr:2
+    v += dpp_or_zero<0x114, 0xf>(v);     // row_shr:4
+    v += dpp_or_zero<0x118, 0xf>(v);     // row_shr:8
+    v += dpp_or_zero<0x142, 0xa>(v);     // row_bcast:15 into rows 1 and 3
+    v += dpp_or_zero<0x143, 0xc>(v);     // row_bcast:31 into rows 2 and 3
+    return v;
+}
+
 // level >= 2: one queued ray per lane, persistent waves striding over the queue
 template <bool COUNT, bool LDS, int WALK, int OCC, bool STOCH = false, bool SCHLICK = false>
 __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void wf_secondary_kernel(const LaunchParams P) {
@@ -694,23 +713,31 @@ __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void wf_secondary_kern
         // wave owning at most one batch whichever shard it is in, the level costs one ray step instead of two.
         const uint32_t c = (uint32_t)lane < S ? counts_in[lane] : 0u;
         const uint32_t nb = (c + 63u) >> 6;
-        uint32_t incl = nb;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const uint32_t t = __shfl_up(incl, d); if (lane >= d) incl += t; }
-        const uint32_t total = __shfl(incl, 63);
+        const uint32_t incl = wave_inclusive_scan(nb);
+        const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
         if (((blockIdx.x * blockDim.x) >> 6) >= total) return;      // workgroup-uniform, before the scene copy's barrier
         const typename View<LDS>::type sv = View<LDS>::make_shading(P);
         const TravCtx tc = wave_stack<LDS>(P, 0);
         Ctr ctr = {0, 0, 0, 0, 0, 0, 0};
         uint32_t n_batches = 0;
+        // Read once per wave, above: parity, counts and their scan, the scene view, the stack.  Everything else a batch
+        // reads of the launch parameters it reads through a pointer the compiler cannot see through, for the reason given
+        // in wf_primary_kernel_tiles: read from P they are all invariant in this loop, are hoisted out of it and stay live,
+        // spilled into lanes of vector registers, across both walks of every batch.  The kernel's one argument IS the
+        // kernarg segment:
+        static_assert(std::is_same_v<decltype(&wf_secondary_kernel<COUNT, LDS, WALK, OCC, STOCH, SCHLICK>), void (*)(const LaunchParams)>,
+                      "Q below reads the kernarg segment as the kernel's only argument, a LaunchParams at offset 0");
         for (uint32_t b = wave_id; b < total; b += n_waves, n_batches++) {
+            auto args = __builtin_amdgcn_kernarg_segment_ptr();
+            asm volatile("" : "+s"(args));
+            const LaunchParams& Q = *(const LaunchParams*)args;
             const bool st1 = n_batches == 0;
-            stamp_wave(P, wave_id, 0, st1);
+            stamp_wave(Q, wave_id, 0, st1);
             const int s = (int)__builtin_ctzll(__ballot(incl > b));  // the shard batch b belongs to
-            const uint32_t first = __shfl(incl - nb, s);             // batches in the shards before it
-            const Shard sh = shard_of(P, (uint32_t)s, par);
+            const uint32_t first = (uint32_t)__builtin_amdgcn_readlane((int)(incl - nb), s);   // batches in the shards before it
+            const Shard sh = shard_of(Q, (uint32_t)s, par);
             const uint32_t i = (b - first) * 64u + lane;
-            queued_ray_step<COUNT, LDS, WALK, STOCH, SCHLICK>(P, sv, sh, tc, ctr, i, i < sh.count_in, wave_id, st1);
+            queued_ray_step<COUNT, LDS, WALK, STOCH, SCHLICK>(Q, sv, sh, tc, ctr, i, i < sh.count_in, wave_id, st1);
         }
         if (stamps_on(P) && n_batches) { stamp_wave(P, wave_id, 5); P.dbg_stamps[(size_t)wave_id * 8 + 6] = n_batches; }
         flush_counters<COUNT>(P, ctr, 0u);
