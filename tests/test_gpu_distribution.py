@@ -75,7 +75,8 @@ def mean_and_var(frames):
     return a.mean(0), a.var(0, ddof=1)
 
 
-@pytest.mark.parametrize("feature,spp", [("fuzzy_reflection", 0), ("soft_shadow", 2), ("both", 2)])
+@pytest.mark.parametrize("feature,spp", [("fuzzy_reflection", 0), ("soft_shadow", 2), ("both", 2),
+                                         ("soft_shadow", 3), ("both", 3)])
 def test_random_features_match_oracle_statistically(feature, spp):
     K = 24
     sc, hs, ds = load("balls_low")
