@@ -567,6 +567,60 @@ typedef struct p3d_occlusion_outputs {
  *  - after p3d_scene_update or p3d_scene_rebuild the answers follow the moved geometry, like everything else. */
 int p3d_occluded(p3d_scene* scene, const p3d_rays* segments, const p3d_render_params* params,
                  const p3d_occlusion_outputs* out);
+
+/* The consumer of p3d_render_aov's planes: an edge-stopping filter for frames that are noisy by design -- jittered soft
+ * shadows, fuzzy reflections, the thin lens at low spp. */
+typedef struct p3d_denoise_params {
+    int32_t res_x, res_y, n_frames;          /* n_frames >= 1: planes hold the frames back to back, as p3d_render_aov writes them */
+    int32_t iterations;                      /* 0..6 */
+    float   sigma_depth, sigma_albedo, sigma_color;
+    int32_t normal_power_log2;               /* 0..8 */
+} p3d_denoise_params;
+typedef struct p3d_denoise_inputs { const float *rgb32f, *depth, *normal, *albedo; int32_t memory; } p3d_denoise_inputs;
+/* An a-trous edge-avoiding wavelet filter (Dammertz et al. 2010) over the colour of n_frames frames, guided by their depth,
+ * normal and albedo planes.  The reference has no denoiser; the result is DEFINED here, in float32 IEEE-754 basic
+ * operations in a fixed order (no fused multiply-add, correctly rounded division, no exp and no pow), and the device, the
+ * host layer (p3dh_denoise) and tests/denoise_reference.py agree on it in every bit.
+ *  - the filter: pass i (0 <= i < iterations) has step s = 2^i, reads the previous pass's colour (pass 0 the input) and the
+ *    unchanged depth Z, normal N and albedo A.  With k1 = {0.375, 0.25, 0.0625}, inv_a = 1 / sigma_albedo and, when
+ *    sigma_color > 0, inv_c = 1 / (sigma_color * 2^-i):
+ *      a pixel is VALID when its Z is finite and > 0.  A centre p that is not (a miss: +inf; t == 0; NaN) is copied.
+ *      Else inv_z = 1 / (sigma_depth * Z_p), lum(c) = (0.2126 c.r + 0.7152 c.g) + 0.0722 c.b, and the taps
+ *      q = (x + dx s, y + dy s) run dy = -2..2 (outer), dx = -2..2 (inner); a tap outside the frame or not valid
+ *      contributes nothing; for the others
+ *        h  = k1[|dx|] * k1[|dy|]
+ *        wz = tz * tz,  tz = max(0, 1 - |Z_q - Z_p| * inv_z)
+ *        wn = max(0, (N_p.x N_q.x + N_p.y N_q.y) + N_p.z N_q.z), then wn = wn * wn, normal_power_log2 times
+ *        wa = ta * ta,  ta = max(0, 1 - ((|A_q.r - A_p.r| + |A_q.g - A_p.g|) + |A_q.b - A_p.b|) * inv_a)
+ *        wc = tc * tc,  tc = max(0, 1 - |lum(C_q) - lum(C_p)| * inv_c)      (sigma_color > 0 only)
+ *        w  = ((h * wz) * wn) * wa, then w = w * wc;  sum += w * C_q per channel (a product, then a sum);  sw += w
+ *      out_p = sw > 0 ? sum / sw per channel : in_p.  max(0, v) is v > 0 ? v : 0.
+ *    rgb32f receives the last pass's colour (the input when iterations == 0) and rgb8 its u8fromfloat(clamp01()), the
+ *    quantisation of a frame (RT/maths.h:113-117).  NaN colours give unspecified results.  Frames of a batch are filtered
+ *    independently: no tap crosses from one into the next.
+ *  - planes: res_y rows of res_x pixels, bottom row first, frame f starting f * res_x * res_y pixels in -- what
+ *    p3d_render_aov writes with world == 1.  Every input plane is needed.  out->rgb32f and out->rgb8 may each be NULL;
+ *    out->hit_id must be NULL.  in->memory and out->memory are 0 (host) or 1 (device), independently; host planes are
+ *    staged in buffers the handle owns and copied back before the call returns, as in p3d_trace_rays.
+ *  - ordering: with all planes in device memory the call only enqueues on the scene's stream: one launch per pass, all
+ *    frames in it (iterations == 0: one copy-and-quantise launch).
+ *  - aliasing: out->rgb32f == in->rgb32f in device memory is allowed for every iterations.  No pass writes a buffer it
+ *    reads: the colour alternates between two scratch buffers of the handle and the last pass writes the destination (a
+ *    single in-place pass reads a copy).  Partial overlap is unspecified.
+ *  - handle-owned memory: the scratch (12 bytes per pixel each, as many as the pass count needs) and the staging of
+ *    host planes are counted in p3d_scene_stats::device_bytes as they grow, kept for the next call and freed with the handle.
+ *  - stream capture: a call that has to allocate while the stream is being captured is refused with P3D_ERR_STATE, and
+ *    so is one with a plane in host memory (it would have to wait); the capture survives.  After a call of the same
+ *    shape made before the capture, the captured call is accepted and the graph replays.
+ *  - P3D_ERR_ARG: a NULL scene, params or in; any NULL input plane; a NULL out; a non-NULL out->hit_id; res_x, res_y or
+ *    n_frames below 1; iterations outside 0..6; normal_power_log2 outside 0..8; sigma_depth or sigma_albedo not finite or
+ *    not positive; sigma_color not finite or negative (0 switches the colour stop off); a memory field outside 0 and 1.
+ *    P3D_ERR_LIMIT, before anything is allocated, when n_frames * res_x * res_y does not fit 31 bits.
+ *  - shards: the compact shards of world > 1 are not frames -- their rows are not neighbours in the image.  Stitch them with
+ *    p3d_deinterleave[_frames] first and denoise the result.
+ *  - handle state: nothing of the handle's frame state changes -- the measured schedule choice, the learned tile orders,
+ *    p3d_last_schedule(), p3d_last_primary_tiles() and the ray-stream state are what they were. */
+int p3d_denoise(p3d_scene* scene, const p3d_denoise_params* params, const p3d_denoise_inputs* in, const p3d_outputs* out);
 int p3d_sync(p3d_scene* scene);
 /* counters of the most recent render made with P3D_FLAG_COUNTERS (waits for it) */
 int p3d_get_counters(p3d_scene* scene, p3d_counters* out);
@@ -750,6 +804,12 @@ int p3d_debug_grid_build(int device, uint32_t n, const float* lo3, const float* 
 int p3d_debug_rand(int device, uint32_t seed, uint64_t first, uint32_t n, uint32_t* out);
 int p3d_debug_sample_stream(int device, uint32_t seed, int32_t res_x, int32_t res_y, int32_t spp, float aperture,
                             uint64_t pairs_per_pass, float* out, int32_t* passes);
+
+/* The launches of p3d_denoise (csrc/denoise.hip) run by the same function over HOST planes, without a scene: params and
+ * in as p3d_denoise reads them with in->memory == 0, out->rgb32f / out->rgb8 (each may be NULL) with out->memory == 0.
+ * Synchronous; scratch is allocated for the call and freed.  Refusals as p3d_denoise (in->memory or out->memory other than
+ * 0: P3D_ERR_ARG). */
+int p3d_debug_denoise(int device, const p3d_denoise_params* params, const p3d_denoise_inputs* in, const p3d_outputs* out);
 
 #ifdef __cplusplus
 }

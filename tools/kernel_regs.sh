@@ -1,13 +1,15 @@
 #!/bin/bash
 # Register / spill / scratch use of every kernel of p3d_kernels.hip (CPU-only: device-only compile + readelf notes).
 # usage: tools/kernel_regs.sh [name filter regex] [extra hipcc flags...]
+# P3D_KERNEL_SRC=denoise.hip (any kernel file of csrc/) reads that file instead.
 set -e
+src=${P3D_KERNEL_SRC:-p3d_kernels.hip}
 here=$(cd "$(dirname "$0")/.." && pwd)
 cs=$here/u_4a_2s_p3d_raytracer_template2_amd/csrc
 filt=${1:-.}; shift || true
 out=$(mktemp -d)
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -fno-slp-vectorize \
-  -fhip-fp32-correctly-rounded-divide-sqrt -fno-gpu-rdc -I$here/include -I$cs --cuda-device-only --no-gpu-bundle-output -c $cs/p3d_kernels.hip -o $out/k.co "$@"
+  -fhip-fp32-correctly-rounded-divide-sqrt -fno-gpu-rdc -I$here/include -I$cs --cuda-device-only --no-gpu-bundle-output -c $cs/$src -o $out/k.co "$@"
 /opt/rocm/lib/llvm/bin/llvm-readelf --notes $out/k.co | python3 -c '
 import re, sys, subprocess
 txt = sys.stdin.read()

@@ -94,6 +94,27 @@ class OcclusionOutputs(C.Structure):
     _fields_ = [("occluded", C.c_void_p), ("memory", C.c_int32)]
 
 
+class DenoiseParams(C.Structure):
+    """p3d_denoise_params: n_frames frames of res_x x res_y back to back, iterations 0..6 passes, the three sigmas
+    (sigma_color 0: no colour stop) and normal_power_log2 0..8 squarings of the normal weight."""
+    _fields_ = [("res_x", C.c_int32), ("res_y", C.c_int32), ("n_frames", C.c_int32), ("iterations", C.c_int32),
+                ("sigma_depth", C.c_float), ("sigma_albedo", C.c_float), ("sigma_color", C.c_float),
+                ("normal_power_log2", C.c_int32)]
+
+
+class DenoiseInputs(C.Structure):
+    """p3d_denoise_inputs: the colour and the AOV planes of p3d_render_aov, on the host (memory 0) or the scene's device (1)."""
+    _fields_ = [("rgb32f", C.c_void_p), ("depth", C.c_void_p), ("normal", C.c_void_p), ("albedo", C.c_void_p), ("memory", C.c_int32)]
+
+
+# p3d_denoise's defaults (DESIGN "Denoising" says how they were chosen)
+DENOISE_ITERATIONS = 4
+DENOISE_SIGMA_DEPTH = 0.05
+DENOISE_SIGMA_ALBEDO = 0.25
+DENOISE_SIGMA_COLOR = 0.15
+DENOISE_NORMAL_POWER_LOG2 = 5
+
+
 class PrimUpdate(C.Structure):
     """p3d_prim_update: n primitives to replace ([n][12] floats, optionally [n] scene indices) on the host (memory 0) or the
     scene's device (memory 1); lights: NULL or [n_lights][6] on the host."""
@@ -124,9 +145,9 @@ class SceneStats(C.Structure):
 
 # every symbol include/p3d_hip.h declares (tests check that the library exports them all)
 C_ABI_SYMBOLS = ["p3d_abi_version", "p3d_last_error", "p3d_device_count", "p3d_scene_create",
-                 "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_scene_update", "p3d_scene_rebuild", "p3d_scene_rebuild_with", "p3d_scene_last_builder", "p3d_scene_tree_cost", "p3d_scene_build_grid", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_render_aov", "p3d_generate_samples", "p3d_trace_rays", "p3d_occluded", "p3d_sync",
+                 "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_scene_update", "p3d_scene_rebuild", "p3d_scene_rebuild_with", "p3d_scene_last_builder", "p3d_scene_tree_cost", "p3d_scene_build_grid", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_render_aov", "p3d_generate_samples", "p3d_trace_rays", "p3d_occluded", "p3d_denoise", "p3d_sync",
                  "p3d_get_counters", "p3d_get_profile", "p3d_last_schedule", "p3d_set_tuning", "p3d_set_primary_tiles", "p3d_last_primary_tiles", "p3d_set_stream", "p3d_timer_begin", "p3d_timer_end", "p3d_deinterleave_frames",
-                 "p3d_deinterleave", "p3d_debug_intersect", "p3d_debug_powf", "p3d_debug_pow", "p3d_debug_schlick_kr", "p3d_debug_check_rcp", "p3d_debug_check_rcp_len", "p3d_debug_lbvh_build", "p3d_debug_ploc_build", "p3d_debug_grid_build", "p3d_debug_rand", "p3d_debug_sample_stream", "p3d_tune_schedule", "p3d_debug_set_stamps", "p3d_debug_set_stamp_level",
+                 "p3d_deinterleave", "p3d_debug_intersect", "p3d_debug_powf", "p3d_debug_pow", "p3d_debug_schlick_kr", "p3d_debug_check_rcp", "p3d_debug_check_rcp_len", "p3d_debug_lbvh_build", "p3d_debug_ploc_build", "p3d_debug_grid_build", "p3d_debug_rand", "p3d_debug_sample_stream", "p3d_debug_denoise", "p3d_tune_schedule", "p3d_debug_set_stamps", "p3d_debug_set_stamp_level",
                  "p3d_comm_unique_id", "p3d_comm_create", "p3d_comm_create_all", "p3d_comm_destroy", "p3d_comm_info",
                  "p3d_gather", "p3d_gather_all", "p3d_device_alloc", "p3d_device_free", "p3d_upload", "p3d_download"]
 
@@ -180,6 +201,9 @@ def lib():
     L.p3d_generate_samples.argtypes = [C.c_void_p, C.c_uint32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_int32]
     L.p3d_trace_rays.argtypes = [C.c_void_p, C.POINTER(Rays), C.POINTER(RenderParams), C.POINTER(RayOutputs)]
     L.p3d_occluded.argtypes = [C.c_void_p, C.POINTER(Rays), C.POINTER(RenderParams), C.POINTER(OcclusionOutputs)]
+    L.p3d_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(DenoiseInputs), C.POINTER(Outputs)]
+    L.p3d_debug_denoise.argtypes = [C.c_int, C.POINTER(DenoiseParams), C.POINTER(DenoiseInputs), C.POINTER(Outputs)]
+    L.p3dh_denoise.argtypes = [C.POINTER(DenoiseParams)] + [C.c_void_p] * 6
     L.p3d_sync.argtypes = [C.c_void_p]
     L.p3d_get_counters.argtypes = [C.c_void_p, C.POINTER(Counters)]
     L.p3d_set_stream.argtypes = [C.c_void_p, C.c_void_p]
@@ -742,6 +766,27 @@ class DeviceScene:
         p = self._ray_params(1, accel, no_lds, private_walk, False)
         _check(lib().p3d_occluded(self.h, C.byref(r), C.byref(p), C.byref(oo)), "p3d_occluded")
 
+    def denoise(self, rgb32f, depth, normal, albedo, **kw):
+        """p3d_denoise on host arrays: rgb32f / normal / albedo (n, H, W, 3) or (H, W, 3), depth (n, H, W) or (H, W), as
+        render_aov returns them.  Keywords: iterations, sigma_depth, sigma_albedo, sigma_color (0: no colour stop),
+        normal_power_log2 (defaults: the DENOISE_* constants).  Returns {"rgb32f", "rgb8"} in the shape of rgb32f."""
+        p, planes, shape = _denoise_request(rgb32f, depth, normal, albedo, **kw)
+        out = {"rgb32f": np.zeros(shape, np.float32), "rgb8": np.zeros(shape, np.uint8)}
+        i = DenoiseInputs(*[a.ctypes.data for a in planes], 0)
+        o = Outputs(out["rgb8"].ctypes.data, out["rgb32f"].ctypes.data, None, 0)
+        _check(lib().p3d_denoise(self.h, C.byref(p), C.byref(i), C.byref(o)), "p3d_denoise")
+        return out
+
+    def denoise_device(self, res_x, res_y, rgb32f_ptr, depth_ptr, normal_ptr, albedo_ptr, out_rgb32f_ptr=0, out_rgb8_ptr=0,
+                       n_frames=1, iterations=DENOISE_ITERATIONS, sigma_depth=DENOISE_SIGMA_DEPTH, sigma_albedo=DENOISE_SIGMA_ALBEDO,
+                       sigma_color=DENOISE_SIGMA_COLOR, normal_power_log2=DENOISE_NORMAL_POWER_LOG2):
+        """Enqueue p3d_denoise on caller-owned DEVICE buffers (raw pointers; an output of 0 = no such plane); asynchronous on
+        the scene's stream.  out_rgb32f_ptr may equal rgb32f_ptr."""
+        p = DenoiseParams(int(res_x), int(res_y), int(n_frames), int(iterations), sigma_depth, sigma_albedo, sigma_color, int(normal_power_log2))
+        i = DenoiseInputs(rgb32f_ptr or None, depth_ptr or None, normal_ptr or None, albedo_ptr or None, 1)
+        o = Outputs(out_rgb8_ptr or None, out_rgb32f_ptr or None, None, 1)
+        _check(lib().p3d_denoise(self.h, C.byref(p), C.byref(i), C.byref(o)), "p3d_denoise")
+
     def deinterleave_frames(self, gathered_ptr, frames_ptr, res_x, res_y, row_block, world, bpp, n_frames,
                             rank_stride_bytes=0, tile_stride_bytes=0, frame_stride_bytes=0):
         L = lib()
@@ -893,6 +938,42 @@ def debug_sample_stream(seed, res_x, res_y, spp, aperture, pairs_per_pass=0, dev
     _check(lib().p3d_debug_sample_stream(int(device), int(seed) & 0xFFFFFFFF, int(res_x), int(res_y), int(spp), float(aperture),
                                          int(pairs_per_pass), out.ctypes.data if out.size else None, C.byref(passes)), "p3d_debug_sample_stream")
     return out, int(passes.value)
+
+
+def _denoise_request(rgb32f, depth, normal, albedo, iterations=DENOISE_ITERATIONS, sigma_depth=DENOISE_SIGMA_DEPTH,
+                     sigma_albedo=DENOISE_SIGMA_ALBEDO, sigma_color=DENOISE_SIGMA_COLOR, normal_power_log2=DENOISE_NORMAL_POWER_LOG2):
+    """Host planes of one frame (H, W[, 3]) or n frames (n, H, W[, 3]) -> (DenoiseParams, contiguous float32 planes, shape of rgb32f)."""
+    c = np.ascontiguousarray(rgb32f, np.float32)
+    if c.ndim not in (3, 4) or c.shape[-1] != 3:
+        raise ValueError("rgb32f must be (H, W, 3) or (n, H, W, 3)")
+    n, (h, w) = (1 if c.ndim == 3 else c.shape[0]), c.shape[-3:-1]
+    z = np.ascontiguousarray(depth, np.float32)
+    nr = np.ascontiguousarray(normal, np.float32)
+    al = np.ascontiguousarray(albedo, np.float32)
+    if z.size != n * h * w or nr.size != c.size or al.size != c.size:
+        raise ValueError("depth, normal and albedo must match rgb32f")
+    p = DenoiseParams(w, h, n, int(iterations), sigma_depth, sigma_albedo, sigma_color, int(normal_power_log2))
+    return p, (c, z, nr, al), c.shape
+
+
+def host_denoise(rgb32f, depth, normal, albedo, **kw):
+    """p3dh_denoise: the host layer's restatement of p3d_denoise, every bit of it, on host arrays (no GPU).  Arguments and
+    result as DeviceScene.denoise."""
+    p, planes, shape = _denoise_request(rgb32f, depth, normal, albedo, **kw)
+    out = {"rgb32f": np.zeros(shape, np.float32), "rgb8": np.zeros(shape, np.uint8)}
+    lib().p3dh_denoise(C.byref(p), *[a.ctypes.data for a in planes], out["rgb32f"].ctypes.data, out["rgb8"].ctypes.data)
+    return out
+
+
+def debug_denoise(rgb32f, depth, normal, albedo, device=0, **kw):
+    """p3d_debug_denoise: the launches of p3d_denoise over host arrays, without a scene.  Arguments and result as
+    DeviceScene.denoise."""
+    p, planes, shape = _denoise_request(rgb32f, depth, normal, albedo, **kw)
+    out = {"rgb32f": np.zeros(shape, np.float32), "rgb8": np.zeros(shape, np.uint8)}
+    i = DenoiseInputs(*[a.ctypes.data for a in planes], 0)
+    o = Outputs(out["rgb8"].ctypes.data, out["rgb32f"].ctypes.data, None, 0)
+    _check(lib().p3d_debug_denoise(int(device), C.byref(p), C.byref(i), C.byref(o)), "p3d_debug_denoise")
+    return out
 
 
 def debug_pow(x, y, device=0):

@@ -11,6 +11,7 @@
 #include "../bvh_builder.h"
 #include "../scene_flatten.h"
 #include "../grid_builder.h"
+#include "denoise_host.h"
 #include "p3d_scene.h"
 
 using namespace p3d_host;
@@ -97,6 +98,13 @@ int p3dh_occluded(const p3dh_scene* h, uint32_t n, const float* origin3, const f
     if (rc) return rc;
     if (out && n) memcpy(out, res.data(), n);
     return rc;
+}
+
+// denoise() of the host layer (denoise_host.cpp): p3d_denoise's result on host planes, every bit.  out_rgb32f / out_rgb8
+// may each be NULL.  The caller keeps params inside the ranges p3d_denoise accepts.
+void p3dh_denoise(const p3d_denoise_params* params, const float* rgb32f, const float* depth, const float* normal, const float* albedo,
+                  float* out_rgb32f, uint8_t* out_rgb8) {
+    denoise(*params, rgb32f, depth, normal, albedo, out_rgb32f, out_rgb8);
 }
 
 // ---- host-only BVH build, for tests that run without a GPU

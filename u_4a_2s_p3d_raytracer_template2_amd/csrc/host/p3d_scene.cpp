@@ -482,6 +482,7 @@ int renderScene(const Scene& scene, const RenderOptions& opt, bool want_colors, 
     auto bad = [&](int rc) { if (err) *err = p3d_last_error(); return rc; };
     if (!scene.GetCamera()) { if (err) *err = "scene has no camera"; return P3D_ERR_ARG; }
     if (opt.gpus < 1 || opt.gpus > 64) { if (err) *err = "gpus must be in 1..64"; return P3D_ERR_ARG; }
+    if (opt.denoise >= 0 && opt.gpus > 1) { if (err) *err = "the denoiser is served on one GPU (shards are not frames)"; return P3D_ERR_ARG; }
     Scene::Flat flat;
     scene.flatten(flat);
     p3d_camera cam;
@@ -519,19 +520,29 @@ int renderScene(const Scene& scene, const RenderOptions& opt, bool want_colors, 
     auto done = [&](int code) { if (code) bad(code); if (sample_buf) p3d_device_free(dev, sample_buf); p3d_scene_destroy(dev); return code; };
     if (prm.spp > 0 && (rc = device_samples(dev, opt.seed, &cam, 1, prm, &sample_buf)) != 0) return done(rc);
     size_t npx = (size_t)cam.res_x * cam.res_y;
+    const bool denoised = opt.denoise >= 0, planes = opt.want_aov || denoised;   // the filter reads the float colour and the planes
     out.img_Data.assign(npx * 3, 0);
-    if (want_colors) out.colors.assign(npx * 3, 0.0f);
+    if (want_colors || denoised) out.colors.assign(npx * 3, 0.0f);
     if (want_hit) out.hit_id.assign(npx, -1);
     p3d_outputs o;
-    o.rgb8 = out.img_Data.data(); o.rgb32f = want_colors ? out.colors.data() : nullptr;
+    o.rgb8 = out.img_Data.data(); o.rgb32f = (want_colors || denoised) ? out.colors.data() : nullptr;
     o.hit_id = want_hit ? out.hit_id.data() : nullptr; o.memory = 0;
     p3d_aov_outputs a = {nullptr, nullptr, nullptr};
-    if (opt.want_aov) {
+    if (planes) {
         out.depth.assign(npx, 0.0f); out.normal.assign(npx * 3, 0.0f); out.albedo.assign(npx * 3, 0.0f);
         a.depth = out.depth.data(); a.normal = out.normal.data(); a.albedo = out.albedo.data();
     }
     rc = p3d_timer_begin(dev);
-    if (!rc) rc = opt.want_aov ? p3d_render_aov(dev, &cam, 1, &prm, &o, &a) : p3d_render(dev, &cam, &prm, &o);
+    if (!rc) rc = planes ? p3d_render_aov(dev, &cam, 1, &prm, &o, &a) : p3d_render(dev, &cam, &prm, &o);
+    if (!rc && denoised) {             // img_Data and colors become the filtered frame
+        const p3d_denoise_params dp = {cam.res_x, cam.res_y, 1, opt.denoise, opt.denoise_sigma_depth, opt.denoise_sigma_albedo,
+                                       opt.denoise_sigma_color, opt.denoise_normal_power_log2};
+        const p3d_denoise_inputs di = {out.colors.data(), out.depth.data(), out.normal.data(), out.albedo.data(), 0};
+        const p3d_outputs filtered = {out.img_Data.data(), out.colors.data(), nullptr, 0};
+        rc = p3d_denoise(dev, &dp, &di, &filtered);
+        if (!want_colors) out.colors.clear();
+        if (!opt.want_aov) { out.depth.clear(); out.normal.clear(); out.albedo.clear(); }
+    }
     if (!rc) rc = p3d_timer_end(dev, &out.kernel_ms);
     if (!rc && opt.counters) rc = p3d_get_counters(dev, &out.counters);
     return done(rc);

@@ -233,6 +233,12 @@ struct RenderOptions {
     // renderScene() also fills RenderResult::depth / normal / albedo (p3d_render_aov: the primary hit's t, normal and
     // diffuse colour, written by the frame's own launches); with gpus > 1 they are gathered like hit_id
     bool want_aov = false;
+    // renderScene() on one GPU: >= 0 filters the frame with p3d_denoise, that many passes, before it is returned -- img_Data
+    // (and colors) then hold the filtered frame; the planes it reads are rendered whether or not want_aov asks for them.
+    // The defaults are those of the Python binding (api.py, DENOISE_*; DESIGN "Denoising" says how they were chosen)
+    int denoise = -1;
+    float denoise_sigma_depth = 0.05f, denoise_sigma_albedo = 0.25f, denoise_sigma_color = 0.15f;
+    int denoise_normal_power_log2 = 5;
 };
 struct RenderResult {
     std::vector<uint8_t> img_Data;   // RGB8, bottom row first (RT/main.cpp:76)

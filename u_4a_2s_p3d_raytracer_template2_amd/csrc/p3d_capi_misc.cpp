@@ -2,6 +2,7 @@
 // profile and timers, de-interleaving, device memory for callers, and the debug entries that run one device function.
 #include <cstring>
 
+#include "denoise.h"
 #include "grid_device.h"
 #include "p3d_scene_state.h"
 
@@ -353,6 +354,22 @@ int p3d_debug_sample_stream(int device, uint32_t seed, int32_t res_x, int32_t re
     DebugArg a[1] = {{nullptr, out, (size_t)(pixels * per_pixel) * 4 * sizeof(float)}};
     return debug_run("p3d_debug_sample_stream", device, a, [&] {
         return generate_sample_stream(scratch, seed, res_x, res_y, spp, aperture, a[0].as<float>(), pairs_per_pass, passes, nullptr);
+    });
+}
+
+int p3d_debug_denoise(int device, const p3d_denoise_params* params, const p3d_denoise_inputs* in, const p3d_outputs* out) {
+    const char* why = "";
+    if (const int rc = denoise_check_request(params, in, out, &why)) return fail(rc, why);
+    if (in->memory != 0 || out->memory != 0) return fail(P3D_ERR_ARG, "p3d_debug_denoise takes host planes: memory must be 0");
+    const size_t px = (size_t)params->n_frames * (size_t)params->res_x * (size_t)params->res_y;
+    const int n_scratch = denoise_scratch_buffers(params->iterations, false);
+    // a plane that is not wanted (or a scratch buffer that is not needed) is one byte that nothing touches
+    DebugArg a[8] = {{in->rgb32f, nullptr, px * 12}, {in->depth, nullptr, px * 4}, {in->normal, nullptr, px * 12}, {in->albedo, nullptr, px * 12},
+                     {nullptr, nullptr, n_scratch > 0 ? px * 12 : 1}, {nullptr, nullptr, n_scratch > 1 ? px * 12 : 1},
+                     {nullptr, out->rgb32f, out->rgb32f ? px * 12 : 1}, {nullptr, out->rgb8, out->rgb8 ? px * 3 : 1}};
+    return debug_run("p3d_debug_denoise", device, a, [&] {
+        return launch_denoise(*params, a[0].as<float>(), a[1].as<float>(), a[2].as<float>(), a[3].as<float>(), a[4].as<float>(), a[5].as<float>(),
+                              out->rgb32f ? a[6].as<float>() : nullptr, out->rgb8 ? a[7].as<uint8_t>() : nullptr, nullptr);
     });
 }
 
