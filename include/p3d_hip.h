@@ -621,6 +621,89 @@ typedef struct p3d_denoise_inputs { const float *rgb32f, *depth, *normal, *albed
  *  - handle state: nothing of the handle's frame state changes -- the measured schedule choice, the learned tile orders,
  *    p3d_last_schedule(), p3d_last_primary_tiles() and the ray-stream state are what they were. */
 int p3d_denoise(p3d_scene* scene, const p3d_denoise_params* params, const p3d_denoise_inputs* in, const p3d_outputs* out);
+
+/* The temporal half of that pipeline: frames of a SEQUENCE from a moving camera (p3d_render_frames, p3d_render --orbit,
+ * the render-again loop after SetEye, RT/main.cpp:740) are blended with what the previous frame accumulated at the same
+ * surface point, found by reprojecting the pixel's primary hit into the previous camera. */
+typedef struct p3d_accumulate_params {
+    int32_t res_x, res_y, n_frames;   /* n_frames >= 1: a SEQUENCE, planes back to back as p3d_render_aov writes them (world == 1) */
+    float   depth_tolerance;          /* finite, > 0: relative */
+    float   normal_min;               /* in [-1, 1] */
+    float   max_history;              /* finite, >= 1: cap of the history length, i.e. floor of the blend weight 1 / length */
+} p3d_accumulate_params;
+typedef struct p3d_accumulate_frames {  /* the frames to accumulate */
+    const float *rgb32f, *depth, *normal;   /* needed */
+    const int32_t* hit_id;                  /* may be NULL */
+    const p3d_camera* cams;                 /* HOST array of n_frames cameras, always; res_x / res_y must equal params' */
+    int32_t memory;                         /* 0 host, 1 device: the planes */
+} p3d_accumulate_frames;
+typedef struct p3d_accumulate_history { /* what frame 0 looks back at; the whole struct may be NULL = frame 0 has no history */
+    const float *rgb32f, *depth, *normal, *length;   /* one frame each; all needed */
+    const int32_t* hit_id;                            /* may be NULL */
+    const p3d_camera* cam;                            /* HOST, the camera those planes were seen through */
+    int32_t memory;
+} p3d_accumulate_history;
+typedef struct p3d_accumulate_outputs { float* rgb32f; float* length; int32_t memory; } p3d_accumulate_outputs;  /* either may be NULL, not both */
+/* Temporal reprojection of history over the AOV planes of a sequence.  The reference has nothing like it; the result is
+ * DEFINED here, in float32 IEEE-754 basic operations in a fixed order (no fused multiply-add, correctly rounded division
+ * and square root), and the device, the host layer (p3dh_accumulate) and tests/accumulate_reference.py agree on it in
+ * every bit.
+ *  - history across the sequence: frame 0 looks back at `history` (at nothing when it is NULL); frame f > 0 looks back at
+ *    frame f-1: its OUTPUT colour and length, its INPUT depth, normal and hit_id, and cams[f-1].  A caller running frame by
+ *    frame feeds the previous call's outputs (and the previous frame's depth, normal, hit_id and camera) back as `history`
+ *    and gets the bits of the whole sequence in one call.  The handle keeps no history: the entry is a pure function of
+ *    its arguments.
+ *  - the definition, for pixel (x, y) of frame f with colour C, depth Z, normal N and hit id I; primed values belong to the
+ *    frame it looks back at, seen through the camera eye', u', v', n', w', h', plane_dist'.  A depth is VALID when it is
+ *    finite and > 0 (the denoiser's rule).  "No history" means out = C and length = 1.
+ *      0. the frame has nothing to look back at, or Z is not valid: no history.
+ *      1. d = the direction of Camera::PrimaryRay((x + 0.5, y + 0.5)) of cams[f] (RT/camera.h:91-108) -- the bits of the
+ *         spp == 0 frame kernels: fx = ((float)x + 0.5) / (float)res_x - 0.5, fy likewise,
+ *         D = ((u * w) * fx + (v * h) * fy) + n * -plane_dist per component, l = 1 / sqrt((D.x^2 + D.y^2) + D.z^2),
+ *         d = D * l.  P = eye + d * Z, per component a product and then a sum.
+ *      2. q = P - eye';  a = (q.x u'.x + q.y u'.y) + q.z u'.z, b the same with v', c = -((q.x n'.x + q.y n'.y) + q.z n'.z).
+ *         !(c > 0): no history.  s = c / plane_dist', fx' = a / (w' * s), fy' = b / (h' * s),
+ *         px = (fx' + 0.5) * (float)res_x - 0.5, py = (fy' + 0.5) * (float)res_y - 0.5.
+ *         !(px > -1 && px < (float)res_x && py > -1 && py < (float)res_y): no history (this also catches NaN).
+ *         x0 = floor(px), tx = px - x0, y0 = floor(py), ty = py - y0.
+ *         dist = sqrt((q.x^2 + q.y^2) + q.z^2), lim = depth_tolerance * dist.
+ *      3. the taps (x0, y0), (x0+1, y0), (x0, y0+1), (x0+1, y0+1), in this order, with the weights (1-tx)*(1-ty),
+ *         tx*(1-ty), (1-tx)*ty, tx*ty.  A tap contributes when it is inside the frame, Z' is valid, |Z' - dist| <= lim,
+ *         (N.x N'.x + N.y N'.y) + N.z N'.z >= normal_min and, when both hit_id planes exist, I' == I.  For each of them,
+ *         with weight wgt and history length L':  sum += wgt * C' per channel, sl += wgt * L', sw += wgt.
+ *      4. !(sw > 0): no history.  Else H = sum / sw, hl = sl / sw, len = hl + 1, len = max_history if len > max_history,
+ *         alpha = 1 / len, out = H + (C - H) * alpha per channel, length = len.
+ *    NaN colours give unspecified results.
+ *  - depth counts from the ray's origin.  For one-sample pinhole frames (spp == 0) the planes are exact geometry along
+ *    exactly the ray of step 1.  For spp > 0 the planes describe sample 0's jittered lens ray; the pinhole ray through the
+ *    pixel centre then approximates it within a pixel (and within the aperture).  The definition does not change.
+ *  - planes: res_y rows of res_x pixels, bottom row first, frame f starting f * res_x * res_y pixels in: rgb32f and normal
+ *    3 floats per pixel, depth and length 1 float, hit_id 1 int32.  `length` is the history length: 1 where no history was
+ *    taken, else up to max_history.  The compact shards of world > 1 are not frames: stitch them first
+ *    (p3d_deinterleave[_frames]).
+ *  - memory: frames->memory, history->memory and out->memory are 0 (host) or 1 (device), independently.  Host planes are
+ *    staged in buffers the handle owns (counted in p3d_scene_stats::device_bytes as they grow, kept for the next call,
+ *    freed with the handle); the call copies back and waits.  With everything in device memory the call only enqueues on
+ *    the scene's stream: one launch per frame, in stream order; both cameras travel in the launch arguments by value, so
+ *    a captured graph replays the cameras it was captured with.  An output plane that is NULL while n_frames > 1 is kept
+ *    in two frame-sized buffers of the handle, since the next frame reads it.
+ *  - aliasing: out->rgb32f == frames->rgb32f is allowed (a pixel reads only its own current colour before it writes).
+ *    An output plane equal to any plane of `history`, to frames->depth, frames->normal or frames->hit_id, to the other
+ *    output plane, or out->length == frames->rgb32f: P3D_ERR_ARG.  Partial overlap is unspecified.
+ *  - stream capture: a call that has to allocate while the stream is being captured, or that has a plane in host memory,
+ *    is refused with P3D_ERR_STATE; the capture survives.  After a call of the same shape made before the capture, the
+ *    captured call is accepted and the graph replays.
+ *  - P3D_ERR_ARG: a NULL scene, params, frames or out; a NULL frames->rgb32f, depth, normal or cams; a non-NULL history
+ *    with a NULL rgb32f, depth, normal, length or cam; both output planes NULL; res_x, res_y or n_frames below 1; a camera
+ *    whose res_x / res_y differ from params'; depth_tolerance not finite or not positive; normal_min outside [-1, 1] (or
+ *    NaN); max_history not finite or below 1; a memory field outside 0 and 1; the aliases above.  P3D_ERR_LIMIT, before
+ *    anything is allocated, when n_frames * res_x * res_y does not fit 31 bits.
+ *  - handle state: nothing of the handle's frame state changes -- the measured schedule choice, the learned tile orders,
+ *    p3d_last_schedule(), p3d_last_primary_tiles() and the ray-stream state are what they were.
+ *  - after p3d_scene_update the reprojection still sees a static world: there are no motion vectors; the hit_id, depth and
+ *    normal tests drop what moved. */
+int p3d_accumulate(p3d_scene* scene, const p3d_accumulate_params* params, const p3d_accumulate_frames* frames,
+                   const p3d_accumulate_history* history, const p3d_accumulate_outputs* out);
 int p3d_sync(p3d_scene* scene);
 /* counters of the most recent render made with P3D_FLAG_COUNTERS (waits for it) */
 int p3d_get_counters(p3d_scene* scene, p3d_counters* out);
@@ -810,6 +893,12 @@ int p3d_debug_sample_stream(int device, uint32_t seed, int32_t res_x, int32_t re
  * Synchronous; scratch is allocated for the call and freed.  Refusals as p3d_denoise (in->memory or out->memory other than
  * 0: P3D_ERR_ARG). */
 int p3d_debug_denoise(int device, const p3d_denoise_params* params, const p3d_denoise_inputs* in, const p3d_outputs* out);
+
+/* The launches of p3d_accumulate (csrc/accumulate.hip) run by the same function over HOST planes, without a scene: the
+ * four structs as p3d_accumulate reads them, every memory field 0.  Synchronous; scratch is allocated for the call and
+ * freed.  Refusals as p3d_accumulate (a memory field other than 0: P3D_ERR_ARG). */
+int p3d_debug_accumulate(int device, const p3d_accumulate_params* params, const p3d_accumulate_frames* frames,
+                         const p3d_accumulate_history* history, const p3d_accumulate_outputs* out);
 
 #ifdef __cplusplus
 }

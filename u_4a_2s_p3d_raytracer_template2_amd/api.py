@@ -115,6 +115,37 @@ DENOISE_SIGMA_COLOR = 0.15
 DENOISE_NORMAL_POWER_LOG2 = 5
 
 
+class AccumulateParams(C.Structure):
+    """p3d_accumulate_params: a sequence of n_frames frames of res_x x res_y back to back; the relative depth tolerance, the
+    least normal agreement and the cap of the history length."""
+    _fields_ = [("res_x", C.c_int32), ("res_y", C.c_int32), ("n_frames", C.c_int32), ("depth_tolerance", C.c_float),
+                ("normal_min", C.c_float), ("max_history", C.c_float)]
+
+
+class AccumulateFrames(C.Structure):
+    """p3d_accumulate_frames: colour, depth, normal and (optionally) hit_id of the frames, on the host (memory 0) or the scene's
+    device (1), and their cameras, always on the host."""
+    _fields_ = [("rgb32f", C.c_void_p), ("depth", C.c_void_p), ("normal", C.c_void_p), ("hit_id", C.c_void_p),
+                ("cams", C.POINTER(Camera)), ("memory", C.c_int32)]
+
+
+class AccumulateHistory(C.Structure):
+    """p3d_accumulate_history: what frame 0 looks back at -- one frame of accumulated colour and length, the depth, normal and
+    (optionally) hit_id they were rendered with, and that frame's camera (host)."""
+    _fields_ = [("rgb32f", C.c_void_p), ("depth", C.c_void_p), ("normal", C.c_void_p), ("length", C.c_void_p), ("hit_id", C.c_void_p),
+                ("cam", C.POINTER(Camera)), ("memory", C.c_int32)]
+
+
+class AccumulateOutputs(C.Structure):
+    _fields_ = [("rgb32f", C.c_void_p), ("length", C.c_void_p), ("memory", C.c_int32)]
+
+
+# p3d_accumulate's defaults: conveniences, not measured
+ACCUMULATE_DEPTH_TOLERANCE = 0.05
+ACCUMULATE_NORMAL_MIN = 0.9
+ACCUMULATE_MAX_HISTORY = 32.0
+
+
 class PrimUpdate(C.Structure):
     """p3d_prim_update: n primitives to replace ([n][12] floats, optionally [n] scene indices) on the host (memory 0) or the
     scene's device (memory 1); lights: NULL or [n_lights][6] on the host."""
@@ -145,9 +176,9 @@ class SceneStats(C.Structure):
 
 # every symbol include/p3d_hip.h declares (tests check that the library exports them all)
 C_ABI_SYMBOLS = ["p3d_abi_version", "p3d_last_error", "p3d_device_count", "p3d_scene_create",
-                 "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_scene_update", "p3d_scene_rebuild", "p3d_scene_rebuild_with", "p3d_scene_last_builder", "p3d_scene_tree_cost", "p3d_scene_build_grid", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_render_aov", "p3d_generate_samples", "p3d_trace_rays", "p3d_occluded", "p3d_denoise", "p3d_sync",
+                 "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_scene_update", "p3d_scene_rebuild", "p3d_scene_rebuild_with", "p3d_scene_last_builder", "p3d_scene_tree_cost", "p3d_scene_build_grid", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_render_aov", "p3d_generate_samples", "p3d_trace_rays", "p3d_occluded", "p3d_denoise", "p3d_accumulate", "p3d_sync",
                  "p3d_get_counters", "p3d_get_profile", "p3d_last_schedule", "p3d_set_tuning", "p3d_set_primary_tiles", "p3d_last_primary_tiles", "p3d_set_stream", "p3d_timer_begin", "p3d_timer_end", "p3d_deinterleave_frames",
-                 "p3d_deinterleave", "p3d_debug_intersect", "p3d_debug_powf", "p3d_debug_pow", "p3d_debug_schlick_kr", "p3d_debug_check_rcp", "p3d_debug_check_rcp_len", "p3d_debug_lbvh_build", "p3d_debug_ploc_build", "p3d_debug_grid_build", "p3d_debug_rand", "p3d_debug_sample_stream", "p3d_debug_denoise", "p3d_tune_schedule", "p3d_debug_set_stamps", "p3d_debug_set_stamp_level",
+                 "p3d_deinterleave", "p3d_debug_intersect", "p3d_debug_powf", "p3d_debug_pow", "p3d_debug_schlick_kr", "p3d_debug_check_rcp", "p3d_debug_check_rcp_len", "p3d_debug_lbvh_build", "p3d_debug_ploc_build", "p3d_debug_grid_build", "p3d_debug_rand", "p3d_debug_sample_stream", "p3d_debug_denoise", "p3d_debug_accumulate", "p3d_tune_schedule", "p3d_debug_set_stamps", "p3d_debug_set_stamp_level",
                  "p3d_comm_unique_id", "p3d_comm_create", "p3d_comm_create_all", "p3d_comm_destroy", "p3d_comm_info",
                  "p3d_gather", "p3d_gather_all", "p3d_device_alloc", "p3d_device_free", "p3d_upload", "p3d_download"]
 
@@ -204,6 +235,11 @@ def lib():
     L.p3d_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(DenoiseInputs), C.POINTER(Outputs)]
     L.p3d_debug_denoise.argtypes = [C.c_int, C.POINTER(DenoiseParams), C.POINTER(DenoiseInputs), C.POINTER(Outputs)]
     L.p3dh_denoise.argtypes = [C.POINTER(DenoiseParams)] + [C.c_void_p] * 6
+    _acc = [C.POINTER(AccumulateParams), C.POINTER(AccumulateFrames), C.POINTER(AccumulateHistory)]
+    L.p3d_accumulate.argtypes = [C.c_void_p] + _acc + [C.POINTER(AccumulateOutputs)]
+    L.p3d_debug_accumulate.argtypes = [C.c_int] + _acc + [C.POINTER(AccumulateOutputs)]
+    L.p3dh_accumulate.argtypes = _acc + [C.c_void_p, C.c_void_p]
+    L.p3dh_accumulate.restype = None
     L.p3d_sync.argtypes = [C.c_void_p]
     L.p3d_get_counters.argtypes = [C.c_void_p, C.POINTER(Counters)]
     L.p3d_set_stream.argtypes = [C.c_void_p, C.c_void_p]
@@ -787,6 +823,34 @@ class DeviceScene:
         o = Outputs(out_rgb8_ptr or None, out_rgb32f_ptr or None, None, 1)
         _check(lib().p3d_denoise(self.h, C.byref(p), C.byref(i), C.byref(o)), "p3d_denoise")
 
+    def accumulate(self, rgb32f, depth, normal, cams, hit_id=None, history=None, **kw):
+        """p3d_accumulate on host arrays: the frames of a sequence, rgb32f / normal (n, H, W, 3) or (H, W, 3), depth and hit_id
+        (n, H, W) or (H, W) as render_aov returns them, cams one Camera per frame.  history: None, or a dict with rgb32f,
+        depth, normal, length and cam (optionally hit_id) of the frame before frame 0 -- the previous call's outputs and
+        that frame's planes.  Keywords: depth_tolerance, normal_min, max_history (defaults: the ACCUMULATE_* constants).
+        Returns {"rgb32f", "length"}: the accumulated colour in the shape of rgb32f and the history length per pixel."""
+        p, fr, hi, out, keep = _accumulate_request(rgb32f, depth, normal, cams, hit_id, history, **kw)
+        o = AccumulateOutputs(out["rgb32f"].ctypes.data, out["length"].ctypes.data, 0)
+        _check(lib().p3d_accumulate(self.h, C.byref(p), C.byref(fr), C.byref(hi) if hi else None, C.byref(o)), "p3d_accumulate")
+        return out
+
+    def accumulate_device(self, res_x, res_y, cams, rgb32f_ptr, depth_ptr, normal_ptr, hit_ptr=0, out_rgb32f_ptr=0, out_length_ptr=0,
+                          history=None, depth_tolerance=ACCUMULATE_DEPTH_TOLERANCE, normal_min=ACCUMULATE_NORMAL_MIN,
+                          max_history=ACCUMULATE_MAX_HISTORY):
+        """Enqueue p3d_accumulate on caller-owned DEVICE buffers (raw pointers; 0 = no such plane) holding len(cams) frames;
+        asynchronous on the scene's stream.  history: None, or a dict of device pointers rgb32f, depth, normal, length
+        (optionally hit_id) and the host Camera cam.  out_rgb32f_ptr may equal rgb32f_ptr."""
+        arr, n = _camera_array(cams)
+        p = AccumulateParams(int(res_x), int(res_y), n, depth_tolerance, normal_min, max_history)
+        fr = AccumulateFrames(rgb32f_ptr or None, depth_ptr or None, normal_ptr or None, hit_ptr or None, arr, 1)
+        hi = None
+        if history is not None:
+            hcam = (Camera * 1)(history["cam"])
+            hi = AccumulateHistory(history["rgb32f"] or None, history["depth"] or None, history["normal"] or None, history["length"] or None,
+                                   history.get("hit_id") or None, hcam, 1)
+        o = AccumulateOutputs(out_rgb32f_ptr or None, out_length_ptr or None, 1)
+        _check(lib().p3d_accumulate(self.h, C.byref(p), C.byref(fr), C.byref(hi) if hi else None, C.byref(o)), "p3d_accumulate")
+
     def deinterleave_frames(self, gathered_ptr, frames_ptr, res_x, res_y, row_block, world, bpp, n_frames,
                             rank_stride_bytes=0, tile_stride_bytes=0, frame_stride_bytes=0):
         L = lib()
@@ -973,6 +1037,55 @@ def debug_denoise(rgb32f, depth, normal, albedo, device=0, **kw):
     i = DenoiseInputs(*[a.ctypes.data for a in planes], 0)
     o = Outputs(out["rgb8"].ctypes.data, out["rgb32f"].ctypes.data, None, 0)
     _check(lib().p3d_debug_denoise(int(device), C.byref(p), C.byref(i), C.byref(o)), "p3d_debug_denoise")
+    return out
+
+
+def _accumulate_request(rgb32f, depth, normal, cams, hit_id=None, history=None, depth_tolerance=ACCUMULATE_DEPTH_TOLERANCE,
+                        normal_min=ACCUMULATE_NORMAL_MIN, max_history=ACCUMULATE_MAX_HISTORY):
+    """Host planes of one frame (H, W[, 3]) or n frames (n, H, W[, 3]) and their cameras -> (AccumulateParams, AccumulateFrames,
+    AccumulateHistory or None, the zeroed outputs {"rgb32f", "length"}, what must stay alive while the structs are used)."""
+    c = np.ascontiguousarray(rgb32f, np.float32)
+    if c.ndim not in (3, 4) or c.shape[-1] != 3:
+        raise ValueError("rgb32f must be (H, W, 3) or (n, H, W, 3)")
+    n, (h, w) = (1 if c.ndim == 3 else c.shape[0]), c.shape[-3:-1]
+    z = np.ascontiguousarray(depth, np.float32)
+    nr = np.ascontiguousarray(normal, np.float32)
+    hid = None if hit_id is None else np.ascontiguousarray(hit_id, np.int32)
+    if z.size != n * h * w or nr.size != c.size or (hid is not None and hid.size != z.size):
+        raise ValueError("depth, normal and hit_id must match rgb32f")
+    arr, n_cams = _camera_array([cams] if isinstance(cams, Camera) else cams)
+    if n_cams != n:
+        raise ValueError("one camera per frame: %d frames, %d cameras" % (n, n_cams))
+    p = AccumulateParams(w, h, n, depth_tolerance, normal_min, max_history)
+    fr = AccumulateFrames(c.ctypes.data, z.ctypes.data, nr.ctypes.data, None if hid is None else hid.ctypes.data, arr, 0)
+    keep = [c, z, nr, hid, arr]
+    hi = None
+    if history is not None:
+        hp = [np.ascontiguousarray(history[k], np.float32) for k in ("rgb32f", "depth", "normal", "length")]
+        hh = None if history.get("hit_id") is None else np.ascontiguousarray(history["hit_id"], np.int32)
+        if hp[0].size != 3 * h * w or hp[1].size != h * w or hp[2].size != 3 * h * w or hp[3].size != h * w or (hh is not None and hh.size != h * w):
+            raise ValueError("the history is one frame of the frames' resolution")
+        hcam = (Camera * 1)(history["cam"])
+        hi = AccumulateHistory(*[a.ctypes.data for a in hp], None if hh is None else hh.ctypes.data, hcam, 0)
+        keep += hp + [hh, hcam]
+    out = {"rgb32f": np.zeros(c.shape, np.float32), "length": np.zeros(c.shape[:-1], np.float32)}
+    return p, fr, hi, out, keep
+
+
+def host_accumulate(rgb32f, depth, normal, cams, hit_id=None, history=None, **kw):
+    """p3dh_accumulate: the host layer's restatement of p3d_accumulate, every bit of it, on host arrays (no GPU).  Arguments
+    and result as DeviceScene.accumulate."""
+    p, fr, hi, out, keep = _accumulate_request(rgb32f, depth, normal, cams, hit_id, history, **kw)
+    lib().p3dh_accumulate(C.byref(p), C.byref(fr), C.byref(hi) if hi else None, out["rgb32f"].ctypes.data, out["length"].ctypes.data)
+    return out
+
+
+def debug_accumulate(rgb32f, depth, normal, cams, hit_id=None, history=None, device=0, **kw):
+    """p3d_debug_accumulate: the launches of p3d_accumulate over host arrays, without a scene.  Arguments and result as
+    DeviceScene.accumulate."""
+    p, fr, hi, out, keep = _accumulate_request(rgb32f, depth, normal, cams, hit_id, history, **kw)
+    o = AccumulateOutputs(out["rgb32f"].ctypes.data, out["length"].ctypes.data, 0)
+    _check(lib().p3d_debug_accumulate(int(device), C.byref(p), C.byref(fr), C.byref(hi) if hi else None, C.byref(o)), "p3d_debug_accumulate")
     return out
 
 

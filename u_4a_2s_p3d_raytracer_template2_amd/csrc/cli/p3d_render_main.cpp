@@ -2,7 +2,7 @@
 // (RT/main.cpp:949-976: init_scene -> renderScene -> save image) on an MI355X.
 //   p3d_render <scene.p3f> [--res W H] [--accel 0|1|2] [--depth D] [--spp N] [--seed S]
 //              [--device K | --gpus N] [--out image.png|image.ppm] [--counters] [--soft-shadow] [--fuzzy-reflection]
-//              [--aov PREFIX] [--denoise K [--denoise-sigmas Z A C]]
+//              [--aov PREFIX] [--denoise K [--denoise-sigmas Z A C]] [--accumulate [--accumulate-params TOL NMIN MAXLEN]]
 // --gpus N: devices 0..N-1 each render every N-th block of 16 rows, one RCCL gather to device 0.
 // --orbit N STEP_DEG: N frames of the reference's mouse orbit (alpha advancing by STEP_DEG per frame, RT/main.cpp:339-341,
 // 419-421) in ONE p3d_render_frames call; --out then takes a %d pattern (e.g. frame_%03d.png) for the frame number.
@@ -10,7 +10,11 @@
 // PREFIX_depth.npy (H, W), PREFIX_normal.npy and PREFIX_albedo.npy (H, W, 3), bottom row first like img_Data.
 // --denoise K: the frame is filtered by p3d_denoise (K passes, 0..6) before it is written to --out; --denoise-sigmas Z A C sets
 // sigma_depth, sigma_albedo and sigma_color (C = 0: no colour stop).  Combines with --aov, --soft-shadow, --fuzzy-reflection and
-// --spp; one frame on one GPU: not with --orbit, and not with --gpus N (a rank's shard is not a frame).
+// --spp; one frame on one GPU: not with --orbit (but see --accumulate), and not with --gpus N (a rank's shard is not a frame).
+// --orbit N STEP --accumulate: the orbit's frames are a sequence -- each is blended with the history reprojected from the
+// frame before it (p3d_accumulate) before it is written; --accumulate-params TOL NMIN MAXLEN sets depth_tolerance,
+// normal_min and max_history.  With it --denoise K is legal together with --orbit and filters every accumulated frame (one
+// p3d_denoise call over all N).  One GPU; needs --orbit.
 // Defaults are the reference's: resolution / accel / spp from the file, MAX_DEPTH 4.
 #include <chrono>
 #include <cstdio>
@@ -52,8 +56,9 @@ int main(int argc, char** argv) {
     if (argc < 2) {
         fprintf(stderr, "usage: %s scene.p3f [--res W H] [--accel A] [--depth D] [--spp N] [--seed S] "
                         "[--device K | --gpus N] [--out file.ppm] [--orbit N STEP_DEG] [--counters] [--soft-shadow] [--fuzzy-reflection] [--schlick] [--aov PREFIX] "
-                        "[--denoise K [--denoise-sigmas Z A C]]\n"
-                        "  --denoise filters one frame on one GPU: not with --orbit, not with --gpus N\n", argv[0]);
+                        "[--denoise K [--denoise-sigmas Z A C]] [--accumulate [--accumulate-params TOL NMIN MAXLEN]]\n"
+                        "  --denoise filters one frame on one GPU: not with --orbit, not with --gpus N\n"
+                        "  --accumulate blends the frames of --orbit over time on one GPU; with it --denoise filters every accumulated frame\n", argv[0]);
         return 2;
     }
     RenderOptions opt;
@@ -80,6 +85,8 @@ int main(int argc, char** argv) {
         else if (a == "--aov") { need(1); aov = argv[++i]; opt.want_aov = true; }
         else if (a == "--denoise") { need(1); opt.denoise = atoi(argv[++i]); if (opt.denoise < 0 || opt.denoise > 6) { fprintf(stderr, "--denoise needs K in 0..6\n"); return 2; } }
         else if (a == "--denoise-sigmas") { need(3); opt.denoise_sigma_depth = (float)atof(argv[++i]); opt.denoise_sigma_albedo = (float)atof(argv[++i]); opt.denoise_sigma_color = (float)atof(argv[++i]); }
+        else if (a == "--accumulate") opt.accumulate = true;
+        else if (a == "--accumulate-params") { need(3); opt.accumulate_depth_tolerance = (float)atof(argv[++i]); opt.accumulate_normal_min = (float)atof(argv[++i]); opt.accumulate_max_history = (float)atof(argv[++i]); }
         else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     Scene scene;
@@ -94,7 +101,8 @@ int main(int argc, char** argv) {
         return save_png(path.c_str(), img, W, H);
     };
     if (orbit_n > 0 && opt.want_aov) { fprintf(stderr, "--aov writes the planes of one frame: not with --orbit\n"); return 2; }
-    if (opt.denoise >= 0 && (orbit_n > 0 || opt.gpus > 1)) { fprintf(stderr, "--denoise filters one frame on one GPU: not with --orbit or --gpus N\n"); return 2; }
+    if (opt.accumulate && (orbit_n < 1 || opt.gpus > 1)) { fprintf(stderr, "--accumulate blends the frames of --orbit N STEP on one GPU: it needs --orbit, not --gpus N\n"); return 2; }
+    if (opt.denoise >= 0 && ((orbit_n > 0 && !opt.accumulate) || opt.gpus > 1)) { fprintf(stderr, "--denoise filters one frame on one GPU: not with --orbit or --gpus N\n"); return 2; }
     if (orbit_n > 0) {
         {   // exactly one conversion, %d or %0Nd: the pattern is handed to snprintf
             const size_t pc = out.find('%');

@@ -11,6 +11,7 @@
 #include "../bvh_builder.h"
 #include "../scene_flatten.h"
 #include "../grid_builder.h"
+#include "accumulate_host.h"
 #include "denoise_host.h"
 #include "p3d_scene.h"
 
@@ -105,6 +106,13 @@ int p3dh_occluded(const p3dh_scene* h, uint32_t n, const float* origin3, const f
 void p3dh_denoise(const p3d_denoise_params* params, const float* rgb32f, const float* depth, const float* normal, const float* albedo,
                   float* out_rgb32f, uint8_t* out_rgb8) {
     denoise(*params, rgb32f, depth, normal, albedo, out_rgb32f, out_rgb8);
+}
+
+// accumulate() of the host layer (accumulate_host.cpp): p3d_accumulate's result on host planes, every bit.  history may be
+// NULL; out_rgb32f / out_length may each be NULL.  The caller keeps params inside the ranges p3d_accumulate accepts.
+void p3dh_accumulate(const p3d_accumulate_params* params, const p3d_accumulate_frames* frames, const p3d_accumulate_history* history,
+                     float* out_rgb32f, float* out_length) {
+    accumulate(*params, *frames, history, out_rgb32f, out_length);
 }
 
 // ---- host-only BVH build, for tests that run without a GPU

@@ -600,14 +600,36 @@ int renderFrames(const Scene& scene, const RenderOptions& opt, const std::vector
     void* sample_buf = nullptr;
     auto done = [&](int code) { if (code) bad(code); if (sample_buf) p3d_device_free(dev, sample_buf); p3d_scene_destroy(dev); return code; };
     if (prm.spp > 0 && (rc = device_samples(dev, opt.seed, cams.data(), n, prm, &sample_buf)) != 0) return done(rc);
+    const bool acc = opt.accumulate;      // reads the float colour, the planes and the hit ids of every frame
     out.img_Data.assign(npx * 3 * n, 0);
-    if (want_colors) out.colors.assign(npx * 3 * n, 0.0f);
-    if (want_hit) out.hit_id.assign(npx * n, -1);
+    if (want_colors || acc) out.colors.assign(npx * 3 * n, 0.0f);
+    if (want_hit || acc) out.hit_id.assign(npx * n, -1);
     p3d_outputs o;
-    o.rgb8 = out.img_Data.data(); o.rgb32f = want_colors ? out.colors.data() : nullptr;
-    o.hit_id = want_hit ? out.hit_id.data() : nullptr; o.memory = 0;
+    o.rgb8 = out.img_Data.data(); o.rgb32f = (want_colors || acc) ? out.colors.data() : nullptr;
+    o.hit_id = (want_hit || acc) ? out.hit_id.data() : nullptr; o.memory = 0;
+    p3d_aov_outputs a = {nullptr, nullptr, nullptr};
+    if (acc) {
+        out.depth.assign(npx * n, 0.0f); out.normal.assign(npx * 3 * n, 0.0f); out.albedo.assign(npx * 3 * n, 0.0f);
+        a.depth = out.depth.data(); a.normal = out.normal.data(); a.albedo = out.albedo.data();
+    }
     rc = p3d_timer_begin(dev);
-    if (!rc) rc = p3d_render_frames(dev, cams.data(), n, &prm, &o);
+    if (!rc) rc = acc ? p3d_render_aov(dev, cams.data(), n, &prm, &o, &a) : p3d_render_frames(dev, cams.data(), n, &prm, &o);
+    if (!rc && acc) {                  // img_Data and colors become the accumulated (and filtered) frames
+        const p3d_accumulate_params ap = {cams[0].res_x, cams[0].res_y, n, opt.accumulate_depth_tolerance, opt.accumulate_normal_min,
+                                          opt.accumulate_max_history};
+        const p3d_accumulate_frames af = {out.colors.data(), out.depth.data(), out.normal.data(), out.hit_id.data(), cams.data(), 0};
+        const p3d_accumulate_outputs ao = {out.colors.data(), nullptr, 0};
+        rc = p3d_accumulate(dev, &ap, &af, nullptr, &ao);
+        // one p3d_denoise call over all frames; 0 passes quantise the accumulated colour and filter nothing
+        const p3d_denoise_params dp = {cams[0].res_x, cams[0].res_y, n, opt.denoise >= 0 ? opt.denoise : 0, opt.denoise_sigma_depth,
+                                       opt.denoise_sigma_albedo, opt.denoise_sigma_color, opt.denoise_normal_power_log2};
+        const p3d_denoise_inputs di = {out.colors.data(), out.depth.data(), out.normal.data(), out.albedo.data(), 0};
+        const p3d_outputs filtered = {out.img_Data.data(), out.colors.data(), nullptr, 0};
+        if (!rc) rc = p3d_denoise(dev, &dp, &di, &filtered);
+        if (!want_colors) out.colors.clear();
+        if (!want_hit) out.hit_id.clear();
+        out.depth.clear(); out.normal.clear(); out.albedo.clear();
+    }
     if (!rc) rc = p3d_timer_end(dev, &out.kernel_ms);
     if (!rc && opt.counters) rc = p3d_get_counters(dev, &out.counters);
     return done(rc);

@@ -239,6 +239,11 @@ struct RenderOptions {
     int denoise = -1;
     float denoise_sigma_depth = 0.05f, denoise_sigma_albedo = 0.25f, denoise_sigma_color = 0.15f;
     int denoise_normal_power_log2 = 5;
+    // renderFrames(): the frames are a sequence -- each is blended with the history reprojected from the frame before it
+    // (p3d_accumulate; frame 0 has none) before it is returned; with it, denoise >= 0 filters every accumulated frame (one
+    // p3d_denoise call over all of them).  The defaults are those of the Python binding (api.py, ACCUMULATE_*)
+    bool accumulate = false;
+    float accumulate_depth_tolerance = 0.05f, accumulate_normal_min = 0.9f, accumulate_max_history = 32.0f;
 };
 struct RenderResult {
     std::vector<uint8_t> img_Data;   // RGB8, bottom row first (RT/main.cpp:76)

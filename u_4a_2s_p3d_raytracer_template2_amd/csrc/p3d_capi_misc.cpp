@@ -2,6 +2,7 @@
 // profile and timers, de-interleaving, device memory for callers, and the debug entries that run one device function.
 #include <cstring>
 
+#include "accumulate.h"
 #include "denoise.h"
 #include "grid_device.h"
 #include "p3d_scene_state.h"
@@ -370,6 +371,33 @@ int p3d_debug_denoise(int device, const p3d_denoise_params* params, const p3d_de
     return debug_run("p3d_debug_denoise", device, a, [&] {
         return launch_denoise(*params, a[0].as<float>(), a[1].as<float>(), a[2].as<float>(), a[3].as<float>(), a[4].as<float>(), a[5].as<float>(),
                               out->rgb32f ? a[6].as<float>() : nullptr, out->rgb8 ? a[7].as<uint8_t>() : nullptr, nullptr);
+    });
+}
+
+int p3d_debug_accumulate(int device, const p3d_accumulate_params* params, const p3d_accumulate_frames* frames,
+                         const p3d_accumulate_history* history, const p3d_accumulate_outputs* out) {
+    const char* why = "";
+    if (const int rc = accumulate_check_request(params, frames, history, out, &why)) return fail(rc, why);
+    if (frames->memory != 0 || (history && history->memory != 0) || out->memory != 0)
+        return fail(P3D_ERR_ARG, "p3d_debug_accumulate takes host planes: every memory field must be 0");
+    const size_t fr = (size_t)params->res_x * (size_t)params->res_y, px = fr * (size_t)params->n_frames;
+    const bool many = params->n_frames > 1;
+    const p3d_accumulate_history none = {};
+    const p3d_accumulate_history& h = history ? *history : none;
+    // a plane that is not there (or a spare that is not needed) is one byte that nothing touches
+    DebugArg a[13] = {{frames->rgb32f, nullptr, px * 12}, {frames->depth, nullptr, px * 4}, {frames->normal, nullptr, px * 12},
+                      {frames->hit_id, nullptr, frames->hit_id ? px * 4 : 1},
+                      {h.rgb32f, nullptr, history ? fr * 12 : 1}, {h.depth, nullptr, history ? fr * 4 : 1}, {h.normal, nullptr, history ? fr * 12 : 1},
+                      {h.length, nullptr, history ? fr * 4 : 1}, {h.hit_id, nullptr, h.hit_id ? fr * 4 : 1},
+                      {nullptr, out->rgb32f, out->rgb32f ? px * 12 : 1}, {nullptr, out->length, out->length ? px * 4 : 1},
+                      {nullptr, nullptr, many && !out->rgb32f ? 2 * fr * 12 : 1}, {nullptr, nullptr, many && !out->length ? 2 * fr * 4 : 1}};
+    return debug_run("p3d_debug_accumulate", device, a, [&] {
+        const AccumulatePlanes P = {a[0].as<float>(), a[1].as<float>(), a[2].as<float>(), frames->hit_id ? a[3].as<int32_t>() : nullptr,
+                                    history ? a[4].as<float>() : nullptr, a[5].as<float>(), a[6].as<float>(), a[7].as<float>(),
+                                    h.hit_id ? a[8].as<int32_t>() : nullptr,
+                                    out->rgb32f ? a[9].as<float>() : nullptr, out->length ? a[10].as<float>() : nullptr,
+                                    a[11].as<float>(), a[12].as<float>()};
+        return launch_accumulate(*params, P, frames->cams, h.cam, nullptr);
     });
 }
 
