@@ -704,6 +704,73 @@ typedef struct p3d_accumulate_outputs { float* rgb32f; float* length; int32_t me
  *    normal tests drop what moved. */
 int p3d_accumulate(p3d_scene* scene, const p3d_accumulate_params* params, const p3d_accumulate_frames* frames,
                    const p3d_accumulate_history* history, const p3d_accumulate_outputs* out);
+
+/* Ambient occlusion over the planes of p3d_render_aov: hemisphere any-hit queries fused per pixel.  What a caller of
+ * p3d_occluded would build as res_x * res_y * samples segments, upload and count is made in the lanes of one launch from
+ * the depth and normal planes; the segments never exist in memory. */
+typedef struct p3d_ao_params {
+    int32_t  samples;    /* 1, 2, 4, 8, 16, 32 or 64 segments per pixel */
+    float    radius;     /* finite, > 0: the segments' length */
+    float    bias;       /* finite, >= 0: the origin is moved this far along the normal that faces the eye */
+    uint32_t seed;       /* frame f keys its random streams with seed + f */
+} p3d_ao_params;
+typedef struct p3d_ao_inputs {
+    const float *depth, *normal;   /* needed */
+    const float* rgb32f;           /* may be NULL */
+    int32_t memory;                /* 0 host, 1 device */
+} p3d_ao_inputs;
+typedef struct p3d_ao_outputs { float* ao; float* rgb32f; int32_t memory; } p3d_ao_outputs;   /* either may be NULL, not both */
+/* The reference has no ambient occlusion; the result is DEFINED here, in float32 IEEE-754 basic operations in a fixed
+ * order (no fused multiply-add, correctly rounded division and square root), and the device, the host layer
+ * (p3dh_ao_segments, p3dh_ao_resolve) and tests/ao_reference.py agree on it in every bit.  One part is anchored to what the
+ * reference pins: whether a sample counts as occluded is what p3d_occluded answers for its segment.
+ *  - planes: res_y rows of res_x pixels, bottom row first, n frames back to back, as p3d_render_aov writes them with
+ *    world == 1: depth and ao 1 float per pixel, normal and rgb32f 3.  Frame f is seen through cams[f] (HOST array of n
+ *    cameras); all cameras share res_x / res_y.
+ *  - the definition, for pixel (x, y) of frame f with depth Z and normal N.  normalized(a) is the project's:
+ *    l = 1 / sqrt((a.x^2 + a.y^2) + a.z^2), a * l per component.  rng_mix(a, b) is, in uint32 arithmetic,
+ *    h = (a ^ 0x9E3779B9) * 0x85EBCA6B + b; h ^= h >> 16; h *= 0x7FEB352D; h ^= h >> 15; h *= 0x846CA68B; h ^= h >> 16; and
+ *    rng_u01(key, k) = (float)(rng_mix(key, k) >> 8) * 2^-24 (the random streams of the frames' stochastic features).
+ *      1. validity: Z is VALID when it is finite and > 0 (the denoiser's rule).  Otherwise the pixel has no query and ao = 1.
+ *      2. hit point: d = the direction of Camera::PrimaryRay((x + 0.5, y + 0.5)) of cams[f], exactly as step 1 of
+ *         p3d_accumulate forms it; P = eye + d * Z, per component a product and then a sum.
+ *      3. face-forward: Ns = -N if (N.x d.x + N.y d.y) + N.z d.z > 0, else N.  The origin is O = P + Ns * bias, per
+ *         component a product and then a sum.
+ *      4. keys: pk = rng_mix(seed + f, y * res_x + x); sample s = 0 .. samples - 1 has the key k = rng_mix(pk, s).  The
+ *         keys do not depend on `samples`: sample s is the same segment at every sample count.
+ *      5. a uniform point on the sphere by rejection: tries j = 0 .. 31 draw c_i = 2 * rng_u01(k, 3 j + i) - 1 for
+ *         i = 0, 1, 2; q = (c_0^2 + c_1^2) + c_2^2.  The first try with q <= 1 && q >= 2^-20 is accepted and
+ *         v = normalized(c).  If none of the 32 tries is accepted, v = Ns (the rule bounds the loop).
+ *      6. cosine-weighted direction: w = Ns + v; if !((w.x^2 + w.y^2) + w.z^2 >= 2^-20) then w = Ns.
+ *         L = normalized(w) * radius.
+ *      7. the query: sample s is occluded iff p3d_occluded answers 1 for the segment (O, L) under params->accel -- NONE
+ *         mode's "no distance bound", GRID's "misses the grid's box = in shadow" and the accelerators' plane rule included.
+ *      8. with occ the number of occluded samples, ao = (float)(samples - occ) / (float)samples.  out->rgb32f is ao * c per
+ *         channel of in->rgb32f when that is given, else (ao, ao, ao) -- a plane p3d_denoise takes as its colour.
+ *    A normal that is not unit length, zero or not finite goes through the same operations; step 7's answer for a segment
+ *    that is not finite is p3d_occluded's.
+ *  - params: only accel and flags are read, with p3d_occluded's rules: P3D_FLAG_NO_LDS_SCENE and P3D_FLAG_PRIVATE_WALK are
+ *    honoured, P3D_FLAG_WAVEFRONT is accepted and does nothing; every other flag is P3D_ERR_ARG, and so are features != 0,
+ *    spp != 0, samples != NULL, world > 1 and rank != 0.  The GRID-mode lazy build and the cull_never_hit refusals
+ *    (P3D_ERR_STATE) are p3d_occluded's.
+ *  - P3D_ERR_ARG also for a NULL scene, cams, params, ao, in or out; n < 1; cameras whose res_x / res_y are below 1 or
+ *    differ; ao->samples not one of 1, 2, 4, 8, 16, 32, 64; radius or bias not finite, radius <= 0, bias < 0; a NULL depth or
+ *    normal; both output planes NULL; an output plane that is an input plane or the other output plane; a memory field
+ *    outside 0 and 1.  P3D_ERR_LIMIT, before anything is allocated, when n * res_y * res_x * samples does not fit 31 bits.
+ *  - memory: in->memory and out->memory are 0 (host) or 1 (device), independently.  Host planes are staged in buffers the
+ *    handle owns (counted in p3d_scene_stats::device_bytes as they grow, kept for the next call, freed with the handle);
+ *    the call copies back and waits.  With everything in device memory the call only enqueues on the scene's stream: one
+ *    small launch that writes the n cameras into a buffer of the handle (they travel in that launch's arguments, so a
+ *    captured graph replays the cameras it was captured with) and ONE launch for all n frames.
+ *  - stream capture: a call that has to allocate while the stream is being captured, or that has a plane in host memory,
+ *    is refused with P3D_ERR_STATE; the capture survives.  After a call of the same shape made before the capture, the
+ *    captured call is accepted and the graph replays.
+ *  - handle state: nothing of the handle's frame state changes -- the measured schedule choice, the learned tile orders,
+ *    p3d_last_schedule(), p3d_last_primary_tiles() and the ray-stream state are what they were.
+ *  - after p3d_scene_update or p3d_scene_rebuild the queries follow the moved geometry; the planes are the caller's.
+ *  - on every refusal the outputs are untouched. */
+int p3d_ambient_occlusion(p3d_scene* scene, const p3d_camera* cams, int32_t n, const p3d_render_params* params,
+                          const p3d_ao_params* ao, const p3d_ao_inputs* in, const p3d_ao_outputs* out);
 int p3d_sync(p3d_scene* scene);
 /* counters of the most recent render made with P3D_FLAG_COUNTERS (waits for it) */
 int p3d_get_counters(p3d_scene* scene, p3d_counters* out);

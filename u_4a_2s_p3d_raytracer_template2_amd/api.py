@@ -146,6 +146,27 @@ ACCUMULATE_NORMAL_MIN = 0.9
 ACCUMULATE_MAX_HISTORY = 32.0
 
 
+class AoParams(C.Structure):
+    """p3d_ao_params: samples (1, 2, 4, .. 64) segments of length radius per pixel, their origin moved bias along the normal
+    that faces the eye; frame f keys its random streams with seed + f."""
+    _fields_ = [("samples", C.c_int32), ("radius", C.c_float), ("bias", C.c_float), ("seed", C.c_uint32)]
+
+
+class AoInputs(C.Structure):
+    """p3d_ao_inputs: depth, normal and (optionally) colour planes as p3d_render_aov writes them, host (memory 0) or device (1)."""
+    _fields_ = [("depth", C.c_void_p), ("normal", C.c_void_p), ("rgb32f", C.c_void_p), ("memory", C.c_int32)]
+
+
+class AoOutputs(C.Structure):
+    _fields_ = [("ao", C.c_void_p), ("rgb32f", C.c_void_p), ("memory", C.c_int32)]
+
+
+# p3d_ambient_occlusion's defaults: conveniences, not measured (bias: the reference's EPSILON, RT/macros.h:1)
+AO_SAMPLES = 8
+AO_RADIUS = 0.5
+AO_BIAS = 0.001
+
+
 class PrimUpdate(C.Structure):
     """p3d_prim_update: n primitives to replace ([n][12] floats, optionally [n] scene indices) on the host (memory 0) or the
     scene's device (memory 1); lights: NULL or [n_lights][6] on the host."""
@@ -176,7 +197,7 @@ class SceneStats(C.Structure):
 
 # every symbol include/p3d_hip.h declares (tests check that the library exports them all)
 C_ABI_SYMBOLS = ["p3d_abi_version", "p3d_last_error", "p3d_device_count", "p3d_scene_create",
-                 "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_scene_update", "p3d_scene_rebuild", "p3d_scene_rebuild_with", "p3d_scene_last_builder", "p3d_scene_tree_cost", "p3d_scene_build_grid", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_render_aov", "p3d_generate_samples", "p3d_trace_rays", "p3d_occluded", "p3d_denoise", "p3d_accumulate", "p3d_sync",
+                 "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_scene_update", "p3d_scene_rebuild", "p3d_scene_rebuild_with", "p3d_scene_last_builder", "p3d_scene_tree_cost", "p3d_scene_build_grid", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_render_aov", "p3d_generate_samples", "p3d_trace_rays", "p3d_occluded", "p3d_denoise", "p3d_accumulate", "p3d_ambient_occlusion", "p3d_sync",
                  "p3d_get_counters", "p3d_get_profile", "p3d_last_schedule", "p3d_set_tuning", "p3d_set_primary_tiles", "p3d_last_primary_tiles", "p3d_set_stream", "p3d_timer_begin", "p3d_timer_end", "p3d_deinterleave_frames",
                  "p3d_deinterleave", "p3d_debug_intersect", "p3d_debug_powf", "p3d_debug_pow", "p3d_debug_schlick_kr", "p3d_debug_check_rcp", "p3d_debug_check_rcp_len", "p3d_debug_lbvh_build", "p3d_debug_ploc_build", "p3d_debug_grid_build", "p3d_debug_rand", "p3d_debug_sample_stream", "p3d_debug_denoise", "p3d_debug_accumulate", "p3d_tune_schedule", "p3d_debug_set_stamps", "p3d_debug_set_stamp_level",
                  "p3d_comm_unique_id", "p3d_comm_create", "p3d_comm_create_all", "p3d_comm_destroy", "p3d_comm_info",
@@ -240,6 +261,12 @@ def lib():
     L.p3d_debug_accumulate.argtypes = [C.c_int] + _acc + [C.POINTER(AccumulateOutputs)]
     L.p3dh_accumulate.argtypes = _acc + [C.c_void_p, C.c_void_p]
     L.p3dh_accumulate.restype = None
+    L.p3d_ambient_occlusion.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.POINTER(RenderParams), C.POINTER(AoParams),
+                                        C.POINTER(AoInputs), C.POINTER(AoOutputs)]
+    L.p3dh_ao_segments.argtypes = [C.POINTER(AoParams), C.POINTER(Camera), C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 5
+    L.p3dh_ao_segments.restype = None
+    L.p3dh_ao_resolve.argtypes = [C.c_int32, C.c_uint64] + [C.c_void_p] * 4
+    L.p3dh_ao_resolve.restype = None
     L.p3d_sync.argtypes = [C.c_void_p]
     L.p3d_get_counters.argtypes = [C.c_void_p, C.POINTER(Counters)]
     L.p3d_set_stream.argtypes = [C.c_void_p, C.c_void_p]
@@ -851,6 +878,40 @@ class DeviceScene:
         o = AccumulateOutputs(out_rgb32f_ptr or None, out_length_ptr or None, 1)
         _check(lib().p3d_accumulate(self.h, C.byref(p), C.byref(fr), C.byref(hi) if hi else None, C.byref(o)), "p3d_accumulate")
 
+    def ambient_occlusion(self, cam_or_cams, depth, normal, rgb32f=None, samples=AO_SAMPLES, radius=AO_RADIUS, bias=AO_BIAS, seed=0,
+                          accel=ACCEL_BVH, no_lds=False, private_walk=False, want=("ao", "rgb32f")):
+        """p3d_ambient_occlusion on host arrays: depth (n, H, W) or (H, W) and normal (n, H, W, 3) or (H, W, 3) as render_aov
+        returns them, seen through one Camera or a sequence of n; rgb32f (optional) is the colour to modulate.  Returns
+        the planes named in `want`: ao (n, H, W) and rgb32f (n, H, W, 3) -- ao * rgb32f, or (ao, ao, ao) without a colour."""
+        arr, n = _camera_array([cam_or_cams] if isinstance(cam_or_cams, Camera) else cam_or_cams)
+        H, W = arr[0].res_y, arr[0].res_x
+        depth = np.ascontiguousarray(depth, np.float32).reshape(n, H, W)
+        normal = np.ascontiguousarray(normal, np.float32).reshape(n, H, W, 3)
+        if rgb32f is not None:
+            rgb32f = np.ascontiguousarray(rgb32f, np.float32).reshape(n, H, W, 3)
+        out = {}
+        if "ao" in want:
+            out["ao"] = np.zeros((n, H, W), np.float32)
+        if "rgb32f" in want:
+            out["rgb32f"] = np.zeros((n, H, W, 3), np.float32)
+        p = self._ray_params(1, accel, no_lds, private_walk, False)
+        a = AoParams(int(samples), radius, bias, int(seed) & 0xFFFFFFFF)
+        i = AoInputs(depth.ctypes.data, normal.ctypes.data, rgb32f.ctypes.data if rgb32f is not None else None, 0)
+        o = AoOutputs(out["ao"].ctypes.data if "ao" in out else None, out["rgb32f"].ctypes.data if "rgb32f" in out else None, 0)
+        _check(lib().p3d_ambient_occlusion(self.h, arr, n, C.byref(p), C.byref(a), C.byref(i), C.byref(o)), "p3d_ambient_occlusion")
+        return out
+
+    def ambient_occlusion_device(self, cam_or_cams, depth_ptr, normal_ptr, rgb32f_ptr=0, out_ao_ptr=0, out_rgb32f_ptr=0, samples=AO_SAMPLES,
+                                 radius=AO_RADIUS, bias=AO_BIAS, seed=0, accel=ACCEL_BVH, no_lds=False, private_walk=False):
+        """Enqueue p3d_ambient_occlusion on caller-owned DEVICE buffers (raw pointers; 0 = no such plane) holding one frame per
+        camera; asynchronous on the scene's stream."""
+        arr, n = _camera_array([cam_or_cams] if isinstance(cam_or_cams, Camera) else cam_or_cams)
+        p = self._ray_params(1, accel, no_lds, private_walk, False)
+        a = AoParams(int(samples), radius, bias, int(seed) & 0xFFFFFFFF)
+        i = AoInputs(depth_ptr or None, normal_ptr or None, rgb32f_ptr or None, 1)
+        o = AoOutputs(out_ao_ptr or None, out_rgb32f_ptr or None, 1)
+        _check(lib().p3d_ambient_occlusion(self.h, arr, n, C.byref(p), C.byref(a), C.byref(i), C.byref(o)), "p3d_ambient_occlusion")
+
     def deinterleave_frames(self, gathered_ptr, frames_ptr, res_x, res_y, row_block, world, bpp, n_frames,
                             rank_stride_bytes=0, tile_stride_bytes=0, frame_stride_bytes=0):
         L = lib()
@@ -1086,6 +1147,34 @@ def debug_accumulate(rgb32f, depth, normal, cams, hit_id=None, history=None, dev
     p, fr, hi, out, keep = _accumulate_request(rgb32f, depth, normal, cams, hit_id, history, **kw)
     o = AccumulateOutputs(out["rgb32f"].ctypes.data, out["length"].ctypes.data, 0)
     _check(lib().p3d_debug_accumulate(int(device), C.byref(p), C.byref(fr), C.byref(hi) if hi else None, C.byref(o)), "p3d_debug_accumulate")
+    return out
+
+
+def host_ao_segments(cam, depth, normal, samples=AO_SAMPLES, radius=AO_RADIUS, bias=AO_BIAS, seed=0, frame=0):
+    """p3dh_ao_segments: steps 1 to 6 of p3d_ambient_occlusion's definition on the host (no GPU), for ONE frame -- depth (H, W)
+    and normal (H, W, 3) seen through cam, the frame-th of a batch.  Returns origin and dir (H, W, samples, 3), the segments
+    p3d_occluded would be asked (zeros where the pixel has no query), and valid (H, W) uint8."""
+    depth = np.ascontiguousarray(depth, np.float32)
+    H, W = depth.shape
+    normal = np.ascontiguousarray(normal, np.float32).reshape(H, W, 3)
+    S = int(samples)
+    origin = np.zeros((H, W, S, 3), np.float32)
+    direction = np.zeros((H, W, S, 3), np.float32)
+    valid = np.zeros((H, W), np.uint8)
+    a = AoParams(S, radius, bias, int(seed) & 0xFFFFFFFF)
+    lib().p3dh_ao_segments(C.byref(a), C.byref(cam), int(frame), W, H, depth.ctypes.data, normal.ctypes.data, origin.ctypes.data,
+                           direction.ctypes.data, valid.ctypes.data)
+    return origin, direction, valid
+
+
+def host_ao_resolve(occluded, samples, rgb32f=None):
+    """p3dh_ao_resolve: step 8 on the host -- occluded (...) int32 counts per pixel -> {"ao" (...), "rgb32f" (..., 3)}."""
+    occluded = np.ascontiguousarray(occluded, np.int32)
+    if rgb32f is not None:
+        rgb32f = np.ascontiguousarray(rgb32f, np.float32).reshape(occluded.shape + (3,))
+    out = {"ao": np.zeros(occluded.shape, np.float32), "rgb32f": np.zeros(occluded.shape + (3,), np.float32)}
+    lib().p3dh_ao_resolve(int(samples), occluded.size, occluded.ctypes.data, rgb32f.ctypes.data if rgb32f is not None else None,
+                          out["ao"].ctypes.data, out["rgb32f"].ctypes.data)
     return out
 
 

@@ -22,6 +22,7 @@
 
 #include "accumulate.h"
 #include "p3d_device_math.h"
+#include "p3d_pinhole.h"
 
 namespace p3d {
 
@@ -46,8 +47,6 @@ struct AccumulateFrame {
     float eye[3], uw[3], vh[3], vz[3];       // the frame's camera, as the frame kernels hold it: u * w, v * h, n * -plane_dist
     float peye[3], pu[3], pv[3], pn[3], pw, ph, ppd;     // the previous camera
 };
-
-__device__ __forceinline__ bool valid_depth(float z) { return z > 0.0f && z <= 3.402823466e+38f; }   // finite and > 0; not NaN
 
 // The tile this workgroup runs: XCD x (workgroups x, x + 8, ...) takes the x-th contiguous share of the tiles.
 __device__ __forceinline__ uint32_t logical_block() {
@@ -77,11 +76,9 @@ __device__ __forceinline__ void tap(const AccumulateFrame& F, int64_t tx, int64_
 // One pixel with a frame to look back at: DESIGN "Temporal accumulation", operation by operation.  false: no history.
 __device__ __forceinline__ bool reproject(const AccumulateFrame& F, int32_t x, int32_t y, size_t pixel, V3 C, float Z, V3& out, float& len) {
     if (!valid_depth(Z)) return false;
-    // 1. the ray of the frame kernels (primary_ray_tab of p3d_shade.h, the table entries formed here)
-    const float fx = fdiv((float)x + 0.5f, (float)F.res_x) - 0.5f, fy = fdiv((float)y + 0.5f, (float)F.res_y) - 0.5f;
-    const V3 vX = mul(mk(F.uw[0], F.uw[1], F.uw[2]), fx), vY = mul(mk(F.vh[0], F.vh[1], F.vh[2]), fy);
-    const V3 d = normalized(add(add(vX, vY), mk(F.vz[0], F.vz[1], F.vz[2])));
-    const V3 P = mk(F.eye[0] + d.x * Z, F.eye[1] + d.y * Z, F.eye[2] + d.z * Z);
+    // 1. the ray of the frame kernels and the point it reaches (p3d_pinhole.h)
+    const V3 d = pinhole_dir(F.uw, F.vh, F.vz, x, y, F.res_x, F.res_y);
+    const V3 P = pinhole_point(F.eye, d, Z);
     // 2. its hit seen through the previous camera
     const V3 q = mk(P.x - F.peye[0], P.y - F.peye[1], P.z - F.peye[2]);
     const float a = (q.x * F.pu[0] + q.y * F.pu[1]) + q.z * F.pu[2];

@@ -3,6 +3,7 @@
 //   p3d_render <scene.p3f> [--res W H] [--accel 0|1|2] [--depth D] [--spp N] [--seed S]
 //              [--device K | --gpus N] [--out image.png|image.ppm] [--counters] [--soft-shadow] [--fuzzy-reflection]
 //              [--aov PREFIX] [--denoise K [--denoise-sigmas Z A C]] [--accumulate [--accumulate-params TOL NMIN MAXLEN]]
+//              [--ao S RADIUS [--ao-out PREFIX]]
 // --gpus N: devices 0..N-1 each render every N-th block of 16 rows, one RCCL gather to device 0.
 // --orbit N STEP_DEG: N frames of the reference's mouse orbit (alpha advancing by STEP_DEG per frame, RT/main.cpp:339-341,
 // 419-421) in ONE p3d_render_frames call; --out then takes a %d pattern (e.g. frame_%03d.png) for the frame number.
@@ -15,6 +16,10 @@
 // frame before it (p3d_accumulate) before it is written; --accumulate-params TOL NMIN MAXLEN sets depth_tolerance,
 // normal_min and max_history.  With it --denoise K is legal together with --orbit and filters every accumulated frame (one
 // p3d_denoise call over all N).  One GPU; needs --orbit.
+// --ao S RADIUS: the frame is rendered with its planes, p3d_ambient_occlusion runs S (1, 2, 4, .. 64) segments of length RADIUS
+// per pixel over them and the colour is multiplied by the result before it is written.  Combines with --denoise K (the
+// modulated colour is what is filtered), with --aov and with --orbit N STEP [--accumulate]; one GPU: not with --gpus N.
+// --ao-out PREFIX also writes the plane as PREFIX_ao.npy (H, W) (with --orbit: PREFIX_ao_<frame>.npy).
 // Defaults are the reference's: resolution / accel / spp from the file, MAX_DEPTH 4.
 #include <chrono>
 #include <cstdio>
@@ -56,9 +61,10 @@ int main(int argc, char** argv) {
     if (argc < 2) {
         fprintf(stderr, "usage: %s scene.p3f [--res W H] [--accel A] [--depth D] [--spp N] [--seed S] "
                         "[--device K | --gpus N] [--out file.ppm] [--orbit N STEP_DEG] [--counters] [--soft-shadow] [--fuzzy-reflection] [--schlick] [--aov PREFIX] "
-                        "[--denoise K [--denoise-sigmas Z A C]] [--accumulate [--accumulate-params TOL NMIN MAXLEN]]\n"
+                        "[--denoise K [--denoise-sigmas Z A C]] [--accumulate [--accumulate-params TOL NMIN MAXLEN]] [--ao S RADIUS [--ao-out PREFIX]]\n"
                         "  --denoise filters one frame on one GPU: not with --orbit, not with --gpus N\n"
-                        "  --accumulate blends the frames of --orbit over time on one GPU; with it --denoise filters every accumulated frame\n", argv[0]);
+                        "  --accumulate blends the frames of --orbit over time on one GPU; with it --denoise filters every accumulated frame\n"
+                        "  --ao multiplies the colour by ambient occlusion (S segments of length RADIUS per pixel) on one GPU: not with --gpus N\n", argv[0]);
         return 2;
     }
     RenderOptions opt;
@@ -66,6 +72,7 @@ int main(int argc, char** argv) {
     float orbit_step = 0.0f;
     std::string out = "RT_Output.png";                       // the reference's file name, RT/main.cpp:968
     std::string aov;                                         // --aov PREFIX
+    std::string ao_out;                                      // --ao-out PREFIX
     for (int i = 2; i < argc; i++) {
         std::string a = argv[i];
         auto need = [&](int n) { if (i + n >= argc) { fprintf(stderr, "%s needs %d value(s)\n", a.c_str(), n); exit(2); } };
@@ -87,6 +94,12 @@ int main(int argc, char** argv) {
         else if (a == "--denoise-sigmas") { need(3); opt.denoise_sigma_depth = (float)atof(argv[++i]); opt.denoise_sigma_albedo = (float)atof(argv[++i]); opt.denoise_sigma_color = (float)atof(argv[++i]); }
         else if (a == "--accumulate") opt.accumulate = true;
         else if (a == "--accumulate-params") { need(3); opt.accumulate_depth_tolerance = (float)atof(argv[++i]); opt.accumulate_normal_min = (float)atof(argv[++i]); opt.accumulate_max_history = (float)atof(argv[++i]); }
+        else if (a == "--ao") {
+            need(2); opt.ambient_occlusion = atoi(argv[++i]); opt.ao_radius = (float)atof(argv[++i]);
+            const int S = opt.ambient_occlusion;
+            if (S < 1 || S > 64 || (S & (S - 1)) || !(opt.ao_radius > 0.0f)) { fprintf(stderr, "--ao needs S in 1, 2, 4, .. 64 and RADIUS > 0\n"); return 2; }
+        }
+        else if (a == "--ao-out") { need(1); ao_out = argv[++i]; }
         else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     Scene scene;
@@ -102,6 +115,8 @@ int main(int argc, char** argv) {
     };
     if (orbit_n > 0 && opt.want_aov) { fprintf(stderr, "--aov writes the planes of one frame: not with --orbit\n"); return 2; }
     if (opt.accumulate && (orbit_n < 1 || opt.gpus > 1)) { fprintf(stderr, "--accumulate blends the frames of --orbit N STEP on one GPU: it needs --orbit, not --gpus N\n"); return 2; }
+    if (opt.ambient_occlusion > 0 && opt.gpus > 1) { fprintf(stderr, "--ao runs on the planes of whole frames on one GPU: not with --gpus N\n"); return 2; }
+    if (!ao_out.empty() && opt.ambient_occlusion < 1) { fprintf(stderr, "--ao-out needs --ao S RADIUS\n"); return 2; }
     if (opt.denoise >= 0 && ((orbit_n > 0 && !opt.accumulate) || opt.gpus > 1)) { fprintf(stderr, "--denoise filters one frame on one GPU: not with --orbit or --gpus N\n"); return 2; }
     if (orbit_n > 0) {
         {   // exactly one conversion, %d or %0Nd: the pattern is handed to snprintf
@@ -123,6 +138,11 @@ int main(int argc, char** argv) {
             snprintf(path, sizeof path, out.c_str(), f);
             if (save(path, res.img_Data.data() + (size_t)f * W * H * 3)) { fprintf(stderr, "Error saving Image file\n"); return 1; }
             printf("Image file created: %s\n", path);
+            if (!ao_out.empty()) {
+                const std::vector<float> plane(res.ao.begin() + (size_t)f * W * H, res.ao.begin() + (size_t)(f + 1) * W * H);
+                const std::string npy = ao_out + "_ao_" + std::to_string(f) + ".npy";
+                if (save_npy(npy, plane, H, W, 1)) { fprintf(stderr, "Error saving %s\n", npy.c_str()); return 1; }
+            }
         }
         return 0;
     }
@@ -146,6 +166,10 @@ int main(int argc, char** argv) {
         return 1;
     }
     printf("Image file created: %s\n", out.c_str());
+    if (!ao_out.empty()) {
+        if (save_npy(ao_out + "_ao.npy", res.ao, H, W, 1)) { fprintf(stderr, "Error saving the ambient occlusion file\n"); return 1; }
+        printf("Ambient occlusion file created: %s_ao.npy\n", ao_out.c_str());
+    }
     if (opt.want_aov) {
         if (save_npy(aov + "_depth.npy", res.depth, H, W, 1) || save_npy(aov + "_normal.npy", res.normal, H, W, 3) ||
             save_npy(aov + "_albedo.npy", res.albedo, H, W, 3)) {

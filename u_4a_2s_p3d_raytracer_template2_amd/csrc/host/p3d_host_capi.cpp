@@ -12,6 +12,7 @@
 #include "../scene_flatten.h"
 #include "../grid_builder.h"
 #include "accumulate_host.h"
+#include "ao_host.h"
 #include "denoise_host.h"
 #include "p3d_scene.h"
 
@@ -106,6 +107,17 @@ int p3dh_occluded(const p3dh_scene* h, uint32_t n, const float* origin3, const f
 void p3dh_denoise(const p3d_denoise_params* params, const float* rgb32f, const float* depth, const float* normal, const float* albedo,
                   float* out_rgb32f, uint8_t* out_rgb8) {
     denoise(*params, rgb32f, depth, normal, albedo, out_rgb32f, out_rgb8);
+}
+
+// ao_segments() / ao_resolve() of the host layer (ao_host.cpp): steps 1 to 6 and step 8 of p3d_ambient_occlusion's definition
+// on host planes, every bit.  One frame, the frame-th of a batch: origin_out / dir_out [res_y][res_x][samples][3], valid_out
+// [res_y][res_x].  The caller keeps params inside the ranges p3d_ambient_occlusion accepts.
+void p3dh_ao_segments(const p3d_ao_params* params, const p3d_camera* cam, int32_t frame, int32_t res_x, int32_t res_y, const float* depth,
+                      const float* normal, float* origin_out, float* dir_out, uint8_t* valid_out) {
+    ao_segments(*params, *cam, frame, res_x, res_y, depth, normal, origin_out, dir_out, valid_out);
+}
+void p3dh_ao_resolve(int32_t samples, uint64_t n_pixels, const int32_t* occluded, const float* rgb32f_in, float* ao_out, float* rgb32f_out) {
+    ao_resolve(samples, (size_t)n_pixels, occluded, rgb32f_in, ao_out, rgb32f_out);
 }
 
 // accumulate() of the host layer (accumulate_host.cpp): p3d_accumulate's result on host planes, every bit.  history may be

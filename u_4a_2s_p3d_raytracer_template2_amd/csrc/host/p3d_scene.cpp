@@ -475,6 +475,21 @@ int device_samples(p3d_scene* dev, unsigned seed, const p3d_camera* cams, int n,
     prm.samples = (const float*)*buf; prm.flags |= P3D_FLAG_DEVICE_SAMPLES;
     return P3D_OK;
 }
+// RenderOptions::ambient_occlusion over n frames in host memory: out.ao gets the plane and out.colors is multiplied by it.
+int modulate_by_ao(p3d_scene* dev, const RenderOptions& opt, const p3d_camera* cams, int n, int accel, RenderResult& out) {
+    p3d_render_params prm;
+    memset(&prm, 0, sizeof prm);
+    prm.accel = accel; prm.world = 1;
+    const p3d_ao_params ap = {opt.ambient_occlusion, opt.ao_radius, opt.ao_bias, opt.seed};
+    std::vector<float> lit(out.colors.size());
+    out.ao.assign(out.depth.size(), 1.0f);
+    const p3d_ao_inputs in = {out.depth.data(), out.normal.data(), out.colors.data(), 0};
+    const p3d_ao_outputs o = {out.ao.data(), lit.data(), 0};
+    const int rc = p3d_ambient_occlusion(dev, cams, n, &prm, &ap, &in, &o);
+    if (!rc) out.colors.swap(lit);
+    return rc;
+}
+
 }  // namespace
 
 int renderScene(const Scene& scene, const RenderOptions& opt, bool want_colors, bool want_hit, RenderResult& out,
@@ -483,6 +498,7 @@ int renderScene(const Scene& scene, const RenderOptions& opt, bool want_colors, 
     if (!scene.GetCamera()) { if (err) *err = "scene has no camera"; return P3D_ERR_ARG; }
     if (opt.gpus < 1 || opt.gpus > 64) { if (err) *err = "gpus must be in 1..64"; return P3D_ERR_ARG; }
     if (opt.denoise >= 0 && opt.gpus > 1) { if (err) *err = "the denoiser is served on one GPU (shards are not frames)"; return P3D_ERR_ARG; }
+    if (opt.ambient_occlusion > 0 && opt.gpus > 1) { if (err) *err = "ambient occlusion is served on one GPU (shards are not frames)"; return P3D_ERR_ARG; }
     Scene::Flat flat;
     scene.flatten(flat);
     p3d_camera cam;
@@ -520,7 +536,9 @@ int renderScene(const Scene& scene, const RenderOptions& opt, bool want_colors, 
     auto done = [&](int code) { if (code) bad(code); if (sample_buf) p3d_device_free(dev, sample_buf); p3d_scene_destroy(dev); return code; };
     if (prm.spp > 0 && (rc = device_samples(dev, opt.seed, &cam, 1, prm, &sample_buf)) != 0) return done(rc);
     size_t npx = (size_t)cam.res_x * cam.res_y;
-    const bool denoised = opt.denoise >= 0, planes = opt.want_aov || denoised;   // the filter reads the float colour and the planes
+    const bool with_ao = opt.ambient_occlusion > 0;
+    // the filter reads the float colour and the planes, and so does ambient occlusion: 0 passes then quantise its colour
+    const bool denoised = opt.denoise >= 0 || with_ao, planes = opt.want_aov || denoised;
     out.img_Data.assign(npx * 3, 0);
     if (want_colors || denoised) out.colors.assign(npx * 3, 0.0f);
     if (want_hit) out.hit_id.assign(npx, -1);
@@ -534,8 +552,9 @@ int renderScene(const Scene& scene, const RenderOptions& opt, bool want_colors, 
     }
     rc = p3d_timer_begin(dev);
     if (!rc) rc = planes ? p3d_render_aov(dev, &cam, 1, &prm, &o, &a) : p3d_render(dev, &cam, &prm, &o);
+    if (!rc && with_ao) rc = modulate_by_ao(dev, opt, &cam, 1, prm.accel, out);
     if (!rc && denoised) {             // img_Data and colors become the filtered frame
-        const p3d_denoise_params dp = {cam.res_x, cam.res_y, 1, opt.denoise, opt.denoise_sigma_depth, opt.denoise_sigma_albedo,
+        const p3d_denoise_params dp = {cam.res_x, cam.res_y, 1, opt.denoise >= 0 ? opt.denoise : 0, opt.denoise_sigma_depth, opt.denoise_sigma_albedo,
                                        opt.denoise_sigma_color, opt.denoise_normal_power_log2};
         const p3d_denoise_inputs di = {out.colors.data(), out.depth.data(), out.normal.data(), out.albedo.data(), 0};
         const p3d_outputs filtered = {out.img_Data.data(), out.colors.data(), nullptr, 0};
@@ -600,7 +619,8 @@ int renderFrames(const Scene& scene, const RenderOptions& opt, const std::vector
     void* sample_buf = nullptr;
     auto done = [&](int code) { if (code) bad(code); if (sample_buf) p3d_device_free(dev, sample_buf); p3d_scene_destroy(dev); return code; };
     if (prm.spp > 0 && (rc = device_samples(dev, opt.seed, cams.data(), n, prm, &sample_buf)) != 0) return done(rc);
-    const bool acc = opt.accumulate;      // reads the float colour, the planes and the hit ids of every frame
+    const bool with_ao = opt.ambient_occlusion > 0;
+    const bool acc = opt.accumulate || with_ao;      // reads the float colour, the planes and the hit ids of every frame
     out.img_Data.assign(npx * 3 * n, 0);
     if (want_colors || acc) out.colors.assign(npx * 3 * n, 0.0f);
     if (want_hit || acc) out.hit_id.assign(npx * n, -1);
@@ -614,12 +634,13 @@ int renderFrames(const Scene& scene, const RenderOptions& opt, const std::vector
     }
     rc = p3d_timer_begin(dev);
     if (!rc) rc = acc ? p3d_render_aov(dev, cams.data(), n, &prm, &o, &a) : p3d_render_frames(dev, cams.data(), n, &prm, &o);
+    if (!rc && with_ao) rc = modulate_by_ao(dev, opt, cams.data(), n, prm.accel, out);
     if (!rc && acc) {                  // img_Data and colors become the accumulated (and filtered) frames
         const p3d_accumulate_params ap = {cams[0].res_x, cams[0].res_y, n, opt.accumulate_depth_tolerance, opt.accumulate_normal_min,
                                           opt.accumulate_max_history};
         const p3d_accumulate_frames af = {out.colors.data(), out.depth.data(), out.normal.data(), out.hit_id.data(), cams.data(), 0};
         const p3d_accumulate_outputs ao = {out.colors.data(), nullptr, 0};
-        rc = p3d_accumulate(dev, &ap, &af, nullptr, &ao);
+        if (opt.accumulate) rc = p3d_accumulate(dev, &ap, &af, nullptr, &ao);
         // one p3d_denoise call over all frames; 0 passes quantise the accumulated colour and filter nothing
         const p3d_denoise_params dp = {cams[0].res_x, cams[0].res_y, n, opt.denoise >= 0 ? opt.denoise : 0, opt.denoise_sigma_depth,
                                        opt.denoise_sigma_albedo, opt.denoise_sigma_color, opt.denoise_normal_power_log2};

@@ -244,6 +244,11 @@ struct RenderOptions {
     // p3d_denoise call over all of them).  The defaults are those of the Python binding (api.py, ACCUMULATE_*)
     bool accumulate = false;
     float accumulate_depth_tolerance = 0.05f, accumulate_normal_min = 0.9f, accumulate_max_history = 32.0f;
+    // renderScene() and renderFrames() on one GPU: > 0 runs p3d_ambient_occlusion with that many samples per pixel over the
+    // frames' planes (accel as the frames', seed as theirs) and multiplies the float colour by it before the accumulator and
+    // the filter read it; RenderResult::ao keeps the plane.  The defaults are those of the Python binding (api.py, AO_*)
+    int ambient_occlusion = 0;
+    float ao_radius = 0.5f, ao_bias = 0.001f;
 };
 struct RenderResult {
     std::vector<uint8_t> img_Data;   // RGB8, bottom row first (RT/main.cpp:76)
@@ -252,6 +257,7 @@ struct RenderResult {
     // RenderOptions::want_aov (renderScene only), bottom row first like the others: the primary hit's t (+inf on a miss),
     // getNormal(hit point).normalize() and its material's diffuse rgb (zeros on a miss)
     std::vector<float> depth, normal, albedo;      // [res_y][res_x], [res_y][res_x][3], [res_y][res_x][3]
+    std::vector<float> ao;                         // RenderOptions::ambient_occlusion: [frames][res_y][res_x]
     p3d_counters counters{};
     float kernel_ms = 0;
 };

@@ -217,6 +217,21 @@ struct OcclusionIO {
     uint32_t count;
 };
 
+// The planes of p3d_ambient_occlusion (wf_ao_kernel), next to the launch parameters like the segments of p3d_occluded:
+// n_frames frames of res_y rows of res_x pixels back to back, frame f seen through cams[f] (device, written by a launch of
+// the same stream).  color may be nullptr; ao and rgb may each be nullptr.  samples = 1 << log2_samples lanes per pixel;
+// row_waves = waves that cover a row (64 >> log2_samples pixels each), row_groups = workgroups of wg_waves such waves.
+struct AoIO {
+    const float* depth; const float* normal; const float* color;
+    float* ao; float* rgb;
+    const FrameCam* cams;
+    int32_t res_x, res_y, n_frames;
+    int32_t log2_samples;
+    uint32_t row_waves, row_groups;
+    float radius, bias;
+    uint32_t seed;
+};
+
 // Every level of a pass for the fused resolve launch (small frames / shards, wf_resolve_fused_kernel): level l's
 // parked nodes (shard s at nodes[l] + s * cap[l]) and their per-shard counts; levels top .. 1 are combined.
 struct ResolveLevels { NodeRec* nodes[18]; const uint32_t* ncount[18]; uint32_t cap[18]; int32_t top; };

@@ -31,6 +31,7 @@
 #include "p3d_device_types.h"
 #include "p3d_launch.h"
 #include "p3d_shade.h"
+#include "p3d_scene_view.h"
 
 namespace p3d {
 
@@ -42,9 +43,6 @@ __device__ __forceinline__ uint32_t lane_rank(uint64_t mask) {          // # set
 __device__ __forceinline__ int32_t hit_id_of(const Hit& h) { return (h.ref == 0xFFFFFFFFu) ? -1 : (int32_t)h.sid; }
 // "color / (4 * 4)" of the anti-aliased path (RT/main.cpp:800)
 __device__ __forceinline__ V3 div16(V3 c) { return mk(fdiv(c.x, 16.0f), fdiv(c.y, 16.0f), fdiv(c.z, 16.0f)); }
-__device__ __forceinline__ SceneOffsets scene_offsets(const LaunchParams& P) {
-    return SceneOffsets{P.off_nodes, P.off_leaves, P.off_spheres, P.off_sphere_meta, P.off_tris, P.off_tri_normals, P.off_boxes, P.off_mats, P.tri_quads};
-}
 
 // The AOV planes of compact pixel p (p3d_render_aov: LaunchParams::aov_*), written where hit_id is, from the primary ray and
 // its closest hit.  Only the AOV = true builds of the kernels call it (p3d_kernel_variant.h: has_aov): a frame without planes
@@ -348,36 +346,6 @@ __device__ __forceinline__ void emit(const LaunchParams& P, const Shard& sh, int
     }
 }
 
-// Scene view of this launch.  LDS variant: the workgroup first copies the blob into LDS (all
-// threads, then one barrier -- the only barrier of the launch; call before any early exit).
-template <bool LDS> struct View;
-template <> struct View<false> {
-    typedef GlobalScene type;
-    static __device__ __forceinline__ GlobalScene make(const LaunchParams& P) {
-        GlobalScene g; g.q = reinterpret_cast<const float4*>(P.blob);
-        g.o = scene_offsets(P);
-        g.qn = reinterpret_cast<const uint4*>(P.qnodes);
-        for (int a = 0; a < 3; a++) { g.qs[a] = P.q_scale[a]; g.qb[a] = P.q_base[a]; }
-        return g;
-    }
-    static __device__ __forceinline__ GlobalScene make_shading(const LaunchParams& P) { return make(P); }
-    static __device__ __forceinline__ uint32_t scene_dwords(const LaunchParams&) { return 0; }
-};
-template <> struct View<true> {
-    typedef LdsScene type;
-    static __device__ __forceinline__ LdsScene make(const LaunchParams& P) {
-        const float4* src = reinterpret_cast<const float4*>(P.blob);
-        float4* dst = reinterpret_cast<float4*>(p3d_lds);
-        for (uint32_t i = threadIdx.x; i < P.blob_quads; i += blockDim.x) dst[i] = src[i];
-        __syncthreads();
-        LdsScene l;
-        l.o = scene_offsets(P);
-        return l;
-    }
-    static __device__ __forceinline__ LdsScene make_shading(const LaunchParams& P) { return make(P); }
-    static __device__ __forceinline__ uint32_t scene_dwords(const LaunchParams& P) { return P.blob_quads * 4; }
-};
-
 // Last level in pair mode (LaunchParams::wf_pair_in): every ray of the level has returned (o.ret), lanes 2k / 2k+1 hold
 // the reflection / refraction child of one level-(D-1) node.  The even lane combines them with the node's parked record
 // -- "color += reflection_color * KR * specColor + refraction_color * (1 - KR)", RT/main.cpp:719, a never-traced child
@@ -395,19 +363,6 @@ __device__ __forceinline__ void combine_pair(const LaunchParams& P, const Shard&
     const V3 ret = resolve_node<false>(gv, sh.nodes_parent + parent, up, mine, other);
     if (P.wf_level == 2) { sink_sample(P, (size_t)up, ret); return; }
     store_return(sh.nodes_grand, up, ret);
-}
-
-// this wave's traversal stack: after the (optional) scene copy, one region per wave
-template <bool LDS>
-__device__ __forceinline__ TravCtx wave_stack(const LaunchParams& P, uint32_t extra_dwords_per_wave, uint32_t** wave_base = nullptr) {
-    const uint32_t wave = threadIdx.x >> 6;
-    uint32_t* base = p3d_lds + View<LDS>::scene_dwords(P) + wave * (P.trav_stack_dwords + extra_dwords_per_wave);
-    if (wave_base) *wave_base = base;
-    TravCtx tc;
-    tc.lane.region = base; tc.lane.lane = threadIdx.x & 63; tc.lane.slots = P.trav_stack_entries; tc.lane.walk_all = false;
-    tc.wave.base = reinterpret_cast<int32_t*>(base);     // the two walks never run in the same launch
-    tc.share = base + P.trav_stack_dwords - kShareDwords; // work-sharing walk: the last kShareDwords of the wave's region (host: p3d_render)
-    return tc;
 }
 
 // diagnostic stamps (only when a stamp buffer was set with p3d_debug_set_stamps): slot k of the
@@ -449,10 +404,6 @@ __device__ __forceinline__ void stamp_wave(const LaunchParams& P, uint32_t wave_
 // OCC = requested waves per SIMD (amdgpu_waves_per_eu): caps the VGPR allocation so that more
 // waves hide each other's latency, at the price of a few spilled registers.  Selected at run
 // time by p3d_set_tuning(); never changes results.
-#ifndef P3D_OCC_FLOOR
-#define P3D_OCC_FLOOR 1          // build-time experiment knob: minimum waves per SIMD of every ray kernel
-#endif
-#define P3D_OCC(OCC) __attribute__((amdgpu_waves_per_eu(((OCC) > P3D_OCC_FLOOR ? (OCC) : P3D_OCC_FLOOR), 8)))
 
 // One workgroup per 16 x (4 x wg_waves) tile, dispatched by the hardware.  (A persistent variant -- resident-sized
 // grid, scene copied once per workgroup, every wave drawing 16x4 tiles from device counters with the next number
@@ -1305,6 +1256,7 @@ constexpr bool variants_are_consistent(int first, int last) {
             if (!built_level(canonical_level(v, Level::Tile), Level::Tile) || !built_level(canonical_level(v, Level::Secondary), Level::Secondary)) return false;
             if (!built_level(canonical_level(v, Level::Rays), Level::Rays)) return false;
             if (!built_level(canonical_level(v, Level::Occlusion), Level::Occlusion)) return false;
+            if (!built_level(canonical_level(v, Level::AmbientOcclusion), Level::AmbientOcclusion)) return false;
             for (int tiles = 0; tiles <= kMaxPrimaryTiles + 1; tiles++) {
                 v.tiles = tiles;
                 if (!built_level(canonical_level(v, Level::Primary), Level::Primary)) return false;
@@ -1315,7 +1267,7 @@ constexpr bool variants_are_consistent(int first, int last) {
         }
         KernelVariant v = variant_at(i);
         for (v.tiles = kMaxPrimaryTiles; v.tiles >= 1; v.tiles--)
-            for (Level k : {Level::Primary, Level::Secondary, Level::Tile, Level::Rays, Level::Occlusion})
+            for (Level k : {Level::Primary, Level::Secondary, Level::Tile, Level::Rays, Level::Occlusion, Level::AmbientOcclusion})
                 if (built_level(v, k) && !(canonical_level(v, k) == v)) return false;
         v.tiles = 1;
         for (int priv : kPrivs)
@@ -1383,7 +1335,7 @@ static const void* tree_kernel(const LaunchParams& P, const KernelVariant& v) {
 // depth of the BVH (a device-built tree over clustered centroids is a chain of up to 96 levels, bvh_device.hip), and the
 // four waves of a workgroup that renders from an LDS copy of the scene each have one.  The limit is a maximum, so the
 // largest one set for a kernel on a device is remembered and the runtime is asked only to raise it further.
-static hipError_t allow_lds(const void* fn, size_t shmem) {
+hipError_t allow_lds(const void* fn, size_t shmem) {
     if (shmem <= 64 * 1024) return hipSuccess;
     static std::mutex lock;
     static std::map<std::pair<int, const void*>, size_t> raised;

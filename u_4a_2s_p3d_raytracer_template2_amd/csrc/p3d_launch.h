@@ -39,6 +39,11 @@ hipError_t launch_deinterleave(const void* gathered, void* frames, int res_x, in
                                int world, size_t rank_stride, int bpp, int n_frames, size_t in_stride,
                                size_t out_stride, hipStream_t stream);
 bool kernels_have_stamps();
+// a launch of fn with more dynamic LDS than the 64 KiB default says so first (remembered per device and kernel)
+hipError_t allow_lds(const void* fn, size_t shmem);
+
+// ---- ao.hip
+hipError_t launch_wf_ao(const LaunchParams& P, const AoIO& A, const KernelVariant& v, hipStream_t stream);
 
 // ---- p3d_debug_kernels.hip: unit probes of the device arithmetic (p3d_debug_* of include/p3d_hip.h)
 hipError_t launch_debug_check_rcp(uint32_t first, uint64_t count, unsigned long long* n_bad, uint32_t* first_bad, hipStream_t stream);

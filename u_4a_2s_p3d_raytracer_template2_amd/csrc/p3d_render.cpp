@@ -1,7 +1,8 @@
-// p3d_render.cpp -- p3d_render, p3d_render_frames, p3d_render_aov, p3d_trace_rays, p3d_occluded and p3d_tune_schedule of include/p3d_hip.h: a frame (or a
-// batch of frames, or a stream of the caller's rays, or their shadow queries) as a sequence of steps -- validate the request, fill the launch
-// parameters, size the workspaces, choose the schedule, enqueue it.  The kernels are those of p3d_kernels.hip (p3d_launch.h).
+// p3d_render.cpp -- p3d_render, p3d_render_frames, p3d_render_aov, p3d_trace_rays, p3d_occluded, p3d_ambient_occlusion and p3d_tune_schedule of include/p3d_hip.h: a frame (or a
+// batch of frames, or a stream of the caller's rays, or their shadow queries, or those of ambient occlusion) as a sequence of steps -- validate the request, fill the launch
+// parameters, size the workspaces, choose the schedule, enqueue it.  The kernels are those of p3d_kernels.hip and ao.hip (p3d_launch.h).
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 
@@ -953,9 +954,128 @@ int occluded(p3d_scene* s, const p3d_rays* seg, const p3d_render_params* prm, co
     return P3D_OK;
 }
 
+// All argument checks of p3d_ambient_occlusion, in the order include/p3d_hip.h lists them: p3d_occluded's rules for params
+// (the same normalised request), then the entry's own.
+int validate_ao_request(const p3d_scene* s, const p3d_camera* cams, int32_t n, const p3d_render_params* prm, const p3d_ao_params* ao,
+                        const p3d_ao_inputs* in, const p3d_ao_outputs* out, FrameConfig& cfg) {
+    if (!s || !cams || !prm || !ao || !in || !out) return fail(P3D_ERR_ARG, "NULL argument");
+    if (n < 1) return fail(P3D_ERR_ARG, "n must be at least 1");
+    if (prm->accel < 0 || prm->accel > 2) return fail(P3D_ERR_ARG, "accel must be 0, 1 or 2");
+    if (prm->flags & ~kRayStreamFlags)
+        return fail(P3D_ERR_ARG, "flags: ambient occlusion accepts P3D_FLAG_NO_LDS_SCENE, _PRIVATE_WALK and _WAVEFRONT only");
+    if (prm->features != 0) return fail(P3D_ERR_ARG, "features: ambient occlusion has none, features must be 0");
+    if (prm->spp != 0) return fail(P3D_ERR_ARG, "spp: ambient occlusion has no pixel samples, spp must be 0");
+    if (prm->samples) return fail(P3D_ERR_ARG, "samples: ambient occlusion has no pixel samples, p3d_render_params::samples must be NULL");
+    if (prm->world > 1 || prm->rank != 0) return fail(P3D_ERR_ARG, "world / rank: ambient occlusion is not sharded, world must be 0 or 1 and rank 0 (stitch the planes first)");
+    const int32_t S = ao->samples;
+    if (S < 1 || S > 64 || (S & (S - 1)) != 0) return fail(P3D_ERR_ARG, "p3d_ao_params::samples must be 1, 2, 4, 8, 16, 32 or 64");
+    if (!std::isfinite(ao->radius) || !(ao->radius > 0.0f)) return fail(P3D_ERR_ARG, "p3d_ao_params::radius must be finite and positive");
+    if (!std::isfinite(ao->bias) || !(ao->bias >= 0.0f)) return fail(P3D_ERR_ARG, "p3d_ao_params::bias must be finite and not negative");
+    if (!in->depth || !in->normal) return fail(P3D_ERR_ARG, "p3d_ao_inputs::depth / normal is NULL");
+    if (!out->ao && !out->rgb32f) return fail(P3D_ERR_ARG, "p3d_ao_outputs: both ao and rgb32f are NULL");
+    if (in->memory != 0 && in->memory != 1) return fail(P3D_ERR_ARG, "p3d_ao_inputs::memory must be 0 (host) or 1 (device)");
+    if (out->memory != 0 && out->memory != 1) return fail(P3D_ERR_ARG, "p3d_ao_outputs::memory must be 0 (host) or 1 (device)");
+    const void* const outs[2] = {out->ao, out->rgb32f};
+    for (const void* o : outs)
+        if (o && (o == in->depth || o == in->normal || o == in->rgb32f)) return fail(P3D_ERR_ARG, "an output plane aliases an input plane");
+    if (out->ao && (const void*)out->ao == (const void*)out->rgb32f) return fail(P3D_ERR_ARG, "p3d_ao_outputs::ao and rgb32f alias each other");
+    if (cams[0].res_x < 1 || cams[0].res_y < 1) return fail(P3D_ERR_ARG, "res_x and res_y of the cameras must be at least 1");
+    for (int f = 1; f < n; f++)
+        if (cams[f].res_x != cams[0].res_x || cams[f].res_y != cams[0].res_y) return fail(P3D_ERR_ARG, "the cameras differ in res_x / res_y");
+    // 64-bit products of 31-bit factors, compared step by step so that none of them wraps
+    const uint64_t rows = (uint64_t)n * (uint64_t)cams[0].res_y;
+    if (rows > kMaxStackedPixels || rows * (uint64_t)cams[0].res_x > kMaxStackedPixels ||
+        rows * (uint64_t)cams[0].res_x * (uint64_t)S > kMaxStackedPixels)
+        return fail(P3D_ERR_LIMIT, "n * res_y * res_x * samples does not fit 31 bits");
+    if (s->cull_never_hit && prm->accel != P3D_ACCEL_BVH)
+        return fail(P3D_ERR_STATE, "scene was built with cull_never_hit: occlusion queries are served in accel BVH only (unit-length rays)");
+    cfg.max_depth = 1; cfg.accel = prm->accel; cfg.spp = 0;
+    cfg.flags = prm->flags & kConfigFlags; cfg.features = 0;
+    return P3D_OK;
+}
+
+// The queries of p3d_occluded on segments made in lanes from the planes: the scene into the launch parameters as for any
+// entry, the cameras into the handle's buffer by a launch of the stream, then ONE launch of wf_ao_kernel (ao.hip) for all
+// frames.  Of the handle it touches the staging of s->ao and the grid of the first GRID call.
+int ambient_occlusion(p3d_scene* s, const p3d_camera* cams, int32_t n, const p3d_render_params* prm, const p3d_ao_params* ao,
+                      const p3d_ao_inputs* in, const p3d_ao_outputs* out) {
+    FrameConfig cfg;
+    int rc = validate_ao_request(s, cams, n, prm, ao, in, out, cfg);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t pixels = (size_t)n * (size_t)cams[0].res_y * (size_t)cams[0].res_x;
+    const bool host_in = in->memory == 0, host_out = out->memory == 0;
+    p3d_scene::AmbientOcclusion& B = s->ao;
+
+    // everything the call needs of the handle, sized before anything is allocated
+    struct Need { RawBuf* buf; size_t bytes; } needs[6];
+    int n_needs = 0;
+    needs[n_needs++] = {&B.cams, (size_t)n * sizeof(FrameCam)};
+    if (host_in) {
+        needs[n_needs++] = {&B.in_depth, pixels * 4}; needs[n_needs++] = {&B.in_normal, pixels * 12};
+        if (in->rgb32f) needs[n_needs++] = {&B.in_rgb32f, pixels * 12};
+    }
+    if (host_out && out->ao) needs[n_needs++] = {&B.out_ao, pixels * 4};
+    if (host_out && out->rgb32f) needs[n_needs++] = {&B.out_rgb32f, pixels * 12};
+    if (capturing(s->stream)) {
+        if (host_in || host_out)
+            return fail(P3D_ERR_STATE, "p3d_ambient_occlusion copies host planes and waits for them: not while the stream is being captured");
+        for (int i = 0; i < n_needs; i++)
+            if (needs[i].bytes > needs[i].buf->cap)
+                return fail(P3D_ERR_STATE, "p3d_ambient_occlusion has to allocate its camera buffer: make a call of this shape before the capture");
+    }
+
+    FramePlan plan;
+    plan.s = s;
+    if ((rc = fill_scene_params(s, cfg, prm, plan)) != P3D_OK) return rc;
+    const LaunchParams& P = plan.P;
+    if (wavefront_lds_bytes(P, plan.lds_scene) > kMaxLdsBytes) return fail(P3D_ERR_LIMIT, "BVH depth needs more LDS than a CU has");
+    for (int i = 0; i < n_needs; i++) HIP_TRY(ensure_counted(s, *needs[i].buf, needs[i].bytes));
+
+    AoIO io;
+    memset(&io, 0, sizeof io);
+    io.depth = in->depth; io.normal = in->normal; io.color = in->rgb32f; io.ao = out->ao; io.rgb = out->rgb32f;
+    io.res_x = cams[0].res_x; io.res_y = cams[0].res_y; io.n_frames = n;
+    for (io.log2_samples = 0; (1 << io.log2_samples) < ao->samples; io.log2_samples++) {}
+    io.radius = ao->radius; io.bias = ao->bias; io.seed = ao->seed;
+    {   // the cameras travel in the arguments of a launch of this stream: a captured call replays with its own
+        std::vector<FrameCam> fc((size_t)n);
+        for (int f = 0; f < n; f++) fc[f] = camera_record(cams[f]);
+        HIP_TRY(launch_frame_cams((FrameCam*)B.cams.p, fc.data(), n, s->stream));
+        io.cams = (const FrameCam*)B.cams.p;
+    }
+    if (host_in) {
+        HIP_TRY(hipMemcpyAsync(B.in_depth.p, in->depth, pixels * 4, hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(hipMemcpyAsync(B.in_normal.p, in->normal, pixels * 12, hipMemcpyHostToDevice, s->stream));
+        io.depth = (const float*)B.in_depth.p; io.normal = (const float*)B.in_normal.p;
+        if (in->rgb32f) {
+            HIP_TRY(hipMemcpyAsync(B.in_rgb32f.p, in->rgb32f, pixels * 12, hipMemcpyHostToDevice, s->stream));
+            io.color = (const float*)B.in_rgb32f.p;
+        }
+    }
+    if (host_out) {
+        if (out->ao) io.ao = (float*)B.out_ao.p;
+        if (out->rgb32f) io.rgb = (float*)B.out_rgb32f.p;
+    }
+    HIP_TRY(launch_wf_ao(P, io, plan.kv, s->stream));
+    if (host_out) {
+        if (out->ao) HIP_TRY(hipMemcpyAsync(out->ao, io.ao, pixels * 4, hipMemcpyDeviceToHost, s->stream));
+        if (out->rgb32f) HIP_TRY(hipMemcpyAsync(out->rgb32f, io.rgb, pixels * 12, hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+    } else if (host_in) {
+        HIP_TRY(hipStreamSynchronize(s->stream));        // the caller's host planes have been read when the call returns
+    }
+    return P3D_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int p3d_ambient_occlusion(p3d_scene* s, const p3d_camera* cams, int32_t n, const p3d_render_params* prm, const p3d_ao_params* ao,
+                          const p3d_ao_inputs* in, const p3d_ao_outputs* out) {
+    return ambient_occlusion(s, cams, n, prm, ao, in, out);
+}
 
 int p3d_occluded(p3d_scene* s, const p3d_rays* segments, const p3d_render_params* prm, const p3d_occlusion_outputs* out) {
     return occluded(s, segments, prm, out);

@@ -1,5 +1,5 @@
 // p3d_scene_state.h -- the scene handle behind the C-ABI of include/p3d_hip.h, shared by the files that implement it
-// (p3d_scene_create.cpp, p3d_scene_update.cpp, p3d_scene_rebuild.cpp, p3d_scene_build_grid.cpp, p3d_render.cpp, p3d_generate_samples.cpp, p3d_denoise.cpp, p3d_accumulate.cpp, p3d_capi_misc.cpp).  Internal: not installed with include/.
+// (p3d_scene_create.cpp, p3d_scene_update.cpp, p3d_scene_rebuild.cpp, p3d_scene_build_grid.cpp, p3d_render.cpp, p3d_generate_samples.cpp, p3d_denoise.cpp, p3d_accumulate.cpp, p3d_capi_misc.cpp; p3d_ambient_occlusion lives in p3d_render.cpp).  Internal: not installed with include/.
 // Every device resource in it is owned by a member that frees it: deleting a p3d_scene releases all of them.
 #ifndef P3D_SCENE_STATE_H
 #define P3D_SCENE_STATE_H
@@ -240,6 +240,11 @@ struct p3d_scene {
         p3d::RawBuf hist_rgb32f, hist_depth, hist_normal, hist_length, hist_hit_id;
         p3d::RawBuf out_rgb32f, out_length, spare_rgb32f, spare_length;
     } accumulate;
+    // p3d_ambient_occlusion: the staging of host planes and the frames' cameras (FrameCam records, written on the stream
+    // by every call: launch_frame_cams); all counted in device_bytes as they grow.  Apart from the frames' frame_cams.
+    struct AmbientOcclusion {
+        p3d::RawBuf in_depth, in_normal, in_rgb32f, out_ao, out_rgb32f, cams;
+    } ao;
     p3d::RawBuf d_counters;              // one DeviceCounters
     bool counters_valid = false;
     p3d::TimingEvent ev0, ev1;
