@@ -793,6 +793,30 @@ int p3d_set_primary_tiles(p3d_scene* scene, int32_t tiles);
  * (1 on the tile and tree schedules). P3D_ERR_STATE before the first render. */
 int p3d_last_primary_tiles(p3d_scene* scene, int32_t* tiles);
 
+/* Tile coverage mask of those multi-tile level-1 kernels, another switch that never changes results: on = 1 gives every
+ * eligible frame a mask of the 16x16 tiles a primitive can project onto, made by one small launch on the frame's stream in
+ * front of level 1 (camera from its arguments, primitives from the device-resident scene: it follows p3d_scene_update and
+ * p3d_scene_rebuild, copies nothing from the host and waits for nothing).  A tile outside the mask gets the background
+ * colour and hit_id -1 without a camera ray, a walk or shading; a workgroup with no tile inside it also skips its copy of
+ * the scene.  The mask is conservative: the projected vertices of a triangle and the projected corners of a sphere's or a
+ * box's bounds, per row of tiles, widened by two pixels; a primitive with a vertex or corner that is not in front of the eye
+ * marks every tile, and the frame runs as it would without a mask.
+ *  - eligible: a frame of p3d_render() whose level-1 launch is such a kernel (p3d_set_primary_tiles: tiles 2 or 3 and the
+ *    conditions listed there), with spp == 0, without P3D_FEATURE_SKYBOX, of a scene without planes.  Sharded frames
+ *    (world > 1) are eligible: a tile's rows are mapped to image rows exactly.  A frame captured into a graph takes its
+ *    pre-pass with it, unless the mask's buffer would have to be allocated during the capture.  Every other frame --
+ *    p3d_render_frames, p3d_render_aov, counters, features, samples, the other schedules -- runs exactly as before.
+ *  - default: see kDefaultSkyTiles (csrc/p3d_kernel_variant.h) and profiles/sky_tiles.txt; P3D_SKY_TILES=0 / 1 in the
+ *    environment sets it for every scene created afterwards.
+ * P3D_ERR_ARG: a NULL scene, on outside 0 and 1. */
+int p3d_set_sky_tiles(p3d_scene* scene, int32_t on);
+/* Whether the most recent p3d_render() / p3d_render_frames() / p3d_render_aov() of this scene ran with such a mask
+ * (*used = 1) and how many of the frame's tiles (this rank's, when sharded) it marked empty.  *used = 0, *empty_tiles = 0
+ * for a frame that was not eligible and for one whose mask marked every tile because a primitive was not in front of the
+ * eye.  Waits for the scene's stream (the marks are read back from the device): P3D_ERR_STATE while it is being captured,
+ * and before the first render. */
+int p3d_last_sky_tiles(p3d_scene* scene, int32_t* used, int32_t* empty_tiles);
+
 /* Elapsed device time of the most recent render made with P3D_FLAG_PROFILE (waits for it):
  * the whole frame (all launches of the call, samples and bands included) and its dominant
  * kernel alone -- wf_primary_kernel, or whitted_tree_kernel with P3D_FLAG_TREE_KERNEL -- for

@@ -198,7 +198,7 @@ class SceneStats(C.Structure):
 # every symbol include/p3d_hip.h declares (tests check that the library exports them all)
 C_ABI_SYMBOLS = ["p3d_abi_version", "p3d_last_error", "p3d_device_count", "p3d_scene_create",
                  "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_scene_update", "p3d_scene_rebuild", "p3d_scene_rebuild_with", "p3d_scene_last_builder", "p3d_scene_tree_cost", "p3d_scene_build_grid", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_render_aov", "p3d_generate_samples", "p3d_trace_rays", "p3d_occluded", "p3d_denoise", "p3d_accumulate", "p3d_ambient_occlusion", "p3d_sync",
-                 "p3d_get_counters", "p3d_get_profile", "p3d_last_schedule", "p3d_set_tuning", "p3d_set_primary_tiles", "p3d_last_primary_tiles", "p3d_set_stream", "p3d_timer_begin", "p3d_timer_end", "p3d_deinterleave_frames",
+                 "p3d_get_counters", "p3d_get_profile", "p3d_last_schedule", "p3d_set_tuning", "p3d_set_primary_tiles", "p3d_last_primary_tiles", "p3d_set_sky_tiles", "p3d_last_sky_tiles", "p3d_set_stream", "p3d_timer_begin", "p3d_timer_end", "p3d_deinterleave_frames",
                  "p3d_deinterleave", "p3d_debug_intersect", "p3d_debug_powf", "p3d_debug_pow", "p3d_debug_schlick_kr", "p3d_debug_check_rcp", "p3d_debug_check_rcp_len", "p3d_debug_lbvh_build", "p3d_debug_ploc_build", "p3d_debug_grid_build", "p3d_debug_rand", "p3d_debug_sample_stream", "p3d_debug_denoise", "p3d_debug_accumulate", "p3d_tune_schedule", "p3d_debug_set_stamps", "p3d_debug_set_stamp_level",
                  "p3d_comm_unique_id", "p3d_comm_create", "p3d_comm_create_all", "p3d_comm_destroy", "p3d_comm_info",
                  "p3d_gather", "p3d_gather_all", "p3d_device_alloc", "p3d_device_free", "p3d_upload", "p3d_download"]
@@ -275,6 +275,10 @@ def lib():
     L.p3d_set_tuning.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
     L.p3d_set_primary_tiles.argtypes = [C.c_void_p, C.c_int32]
     L.p3d_last_primary_tiles.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+    L.p3d_set_sky_tiles.argtypes = [C.c_void_p, C.c_int32]
+    L.p3d_last_sky_tiles.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.p3dh_tile_coverage.argtypes = [C.POINTER(Camera), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SceneDesc), C.c_void_p]
+    L.p3dh_tile_coverage.restype = C.c_int32
     L.p3d_timer_begin.argtypes = [C.c_void_p]
     L.p3d_timer_end.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     L.p3d_deinterleave.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
@@ -481,6 +485,16 @@ RAY_PLANES = ("rgb32f", "hit_id", "t", "normal")       # the planes of p3d_ray_o
 AOV_PLANES = ("depth", "normal", "albedo")             # the planes of p3d_aov_outputs, in its order
 
 
+def host_tile_coverage(cam, desc, tile_h=16, row_block=16, rank=0, world=1):
+    """(active [tiles_y, tiles_x] bool, fell_back): the level-1 launch's tile coverage mask of cam's frame over a scene
+    description, on the host (csrc/p3d_tile_coverage.h through host/tile_coverage_host.cpp).  fell_back: every tile was
+    marked because a primitive asked for it."""
+    tiles_x, tiles_y = (cam.res_x + 15) // 16, local_rows(cam.res_y, row_block, world) // tile_h
+    out = np.zeros((tiles_y, tiles_x), np.uint8)
+    fell = lib().p3dh_tile_coverage(C.byref(cam), int(tile_h), int(row_block), int(rank), int(world), C.byref(desc), out.ctypes.data)
+    return out.astype(bool), bool(fell)
+
+
 def _ray_arrays(origins, dirs):
     o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
     d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
@@ -639,6 +653,18 @@ class DeviceScene:
         v = C.c_int32()
         _check(lib().p3d_last_primary_tiles(self.h, C.byref(v)), "p3d_last_primary_tiles")
         return v.value
+
+    def set_sky_tiles(self, on):
+        """Tile coverage mask of the multi-tile level-1 kernels (p3d_set_sky_tiles): tiles no primitive projects onto are
+        filled with the background instead of traced.  Never changes results."""
+        _check(lib().p3d_set_sky_tiles(self.h, 1 if on else 0), "p3d_set_sky_tiles")
+
+    def last_sky_tiles(self):
+        """(used, empty_tiles) of the most recent render: whether it ran with a tile coverage mask, and how many tiles the
+        mask marked empty.  Waits for the stream."""
+        used, empty = C.c_int32(), C.c_int32()
+        _check(lib().p3d_last_sky_tiles(self.h, C.byref(used), C.byref(empty)), "p3d_last_sky_tiles")
+        return bool(used.value), empty.value
 
     def sync(self):
         _check(lib().p3d_sync(self.h), "p3d_sync")

@@ -15,6 +15,7 @@
 #include "ao_host.h"
 #include "denoise_host.h"
 #include "p3d_scene.h"
+#include "tile_coverage_host.h"
 
 using namespace p3d_host;
 
@@ -125,6 +126,14 @@ void p3dh_ao_resolve(int32_t samples, uint64_t n_pixels, const int32_t* occluded
 void p3dh_accumulate(const p3d_accumulate_params* params, const p3d_accumulate_frames* frames, const p3d_accumulate_history* history,
                      float* out_rgb32f, float* out_length) {
     accumulate(*params, *frames, history, out_rgb32f, out_length);
+}
+
+// tile_coverage() of the host layer (tile_coverage_host.cpp): the level-1 launch's tile coverage mask for cam's frame over a
+// scene description, the statements of csrc/p3d_tile_coverage.h.  active_out [tiles_y][tiles_x] bytes; returns 1 when every
+// tile was marked because a primitive asked for it.
+int32_t p3dh_tile_coverage(const p3d_camera* cam, int32_t tile_h, int32_t row_block, int32_t rank, int32_t world, const p3d_scene_desc* desc,
+                           uint8_t* active_out) {
+    return tile_coverage(*cam, tile_h, row_block, rank, world, desc->n_prims, desc->prim_type, desc->prim_data, active_out);
 }
 
 // ---- host-only BVH build, for tests that run without a GPU

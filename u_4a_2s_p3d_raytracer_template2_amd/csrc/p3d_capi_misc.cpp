@@ -107,6 +107,32 @@ int p3d_last_primary_tiles(p3d_scene* s, int32_t* tiles) {
     return P3D_OK;
 }
 
+// What the pre-pass of the most recent frame marked is on the device: it is read back here, after the stream has passed, and
+// nowhere on a frame's own path.
+int p3d_last_sky_tiles(p3d_scene* s, int32_t* used, int32_t* empty_tiles) {
+    if (!s || !used || !empty_tiles) return fail(P3D_ERR_ARG, "NULL argument");
+    if (s->last_schedule < 0) return fail(P3D_ERR_STATE, "no render yet");
+    *used = 0; *empty_tiles = 0;
+    if (!s->last_sky.on) return P3D_OK;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(s->stream, &cap);
+    if (cap != hipStreamCaptureStatusNone) return fail(P3D_ERR_STATE, "p3d_last_sky_tiles waits for the stream: not while it is being captured");
+    HIP_TRY(hipSetDevice(s->device));
+    const CoverTiles& g = s->last_sky.tiles;
+    std::vector<uint32_t> status((size_t)g.tiles_y);
+    const uint32_t* d_status = (const uint32_t*)s->sky_mask.p + (size_t)g.tiles_y * s->last_sky.row_words;
+    HIP_TRY(hipMemcpyAsync(status.data(), d_status, status.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    int64_t tiles = 0, active = 0;
+    for (int32_t ty = 0; ty < g.tiles_y; ty++) {
+        if (status[(size_t)ty] & kCoverAllFlag) return P3D_OK;            // a primitive asked for every tile: the frame ran as without a mask
+        if (cover_tile_image_row(g, ty) >= g.res_y) continue;               // rows the compact buffer pads the image with
+        tiles += g.tiles_x; active += status[(size_t)ty];
+    }
+    *used = 1; *empty_tiles = (int32_t)(tiles - active);
+    return P3D_OK;
+}
+
 int p3d_timer_begin(p3d_scene* s) {
     if (!s) return fail(P3D_ERR_ARG, "scene is NULL");
     HIP_TRY(hipSetDevice(s->device));

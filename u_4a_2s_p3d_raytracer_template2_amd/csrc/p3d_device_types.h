@@ -196,6 +196,11 @@ struct LaunchParams {
     // nullptr.  Only the AOV builds of the kernels read them (KernelVariant::aov): a frame without planes runs the builds
     // without.  They sit behind every field frames had before them, so no older field moved in the kernarg segment.
     float* aov_depth; float* aov_normal; float* aov_albedo;
+    // ---- tile coverage mask of this frame (p3d_tile_coverage.h), or nullptr: bit tx & 31 of word ty * sky_mask_row_words +
+    // (tx >> 5), ty counted from the first tile row of the rank's buffer (wf_tile_row0 + the band's own), is clear where no
+    // primitive projects onto the tile.  Written by a pre-pass on the frame's stream; read by wf_primary_kernel_tiles only,
+    // which fills such a tile with the background instead of tracing it.  Behind every older field, like the AOV planes.
+    const uint32_t* sky_mask; uint32_t sky_mask_row_words;
 };
 
 // A ray stream (p3d_trace_rays): what its level-1 launch, wf_rays_kernel, takes NEXT TO the launch parameters -- which stay

@@ -35,6 +35,9 @@ constexpr int kMaxPrimaryTiles = 3;
 // what a handle asks for until p3d_set_primary_tiles() says otherwise: 2 measured 2.4 % faster than 1 on the 1080p frame of
 // mount_low with four frames in flight, 3 measured 1.6 % (profiles/r06_primary_tiles.txt)
 constexpr int kDefaultPrimaryTiles = 2;
+// whether a handle gives the frames of those kernels a tile coverage mask (p3d_tile_coverage.h) until p3d_set_sky_tiles()
+// says otherwise; the measurement behind the value is profiles/sky_tiles.txt
+constexpr bool kDefaultSkyTiles = true;
 
 // Several tiles per workgroup are built for the level-1 kernel of scenes served from LDS, walked per lane, and there only
 // for the timed builds without features: the variant exists to spread a workgroup's fixed cost (scene copy, launch

@@ -32,6 +32,7 @@
 #include "p3d_launch.h"
 #include "p3d_shade.h"
 #include "p3d_scene_view.h"
+#include "p3d_tile_coverage.h"
 
 namespace p3d {
 
@@ -478,10 +479,35 @@ __device__ __forceinline__ void primary_tile_lds(const LaunchParams& P, const Ld
     stamp(P, tile, 4);
 }
 
+// The frame's tile coverage mask (LaunchParams::sky_mask, p3d_tile_coverage.h): is tile (tx, ty) of this band one a primitive
+// may project onto?  Wave-uniform, and read through the constant address space so that it is a scalar load whatever the
+// compiler can prove about the stores before it: the mask was written by an earlier launch of the stream and nothing in
+// this one writes it.
+__device__ __forceinline__ bool tile_may_hit(const LaunchParams& P, const uint32_t* mask, int tx, int ty) {
+    typedef const __attribute__((address_space(4))) uint32_t* ConstWords;
+    const uint32_t w = ((ConstWords)mask)[(uint32_t)(ty + P.wf_tile_row0) * P.sky_mask_row_words + ((uint32_t)tx >> 5)];
+    return ((w >> ((uint32_t)tx & 31u)) & 1u) != 0u;
+}
+// A tile the mask marks empty: every camera ray of it leaves the scene, so each valid pixel gets what such a ray's tree
+// returns -- miss_color() = bg, clamped by sink_sample(), through the same write_pixel() -- and hit_id -1.  No camera ray, no
+// shard, no walk, no shading, nothing queued (a ray that hits nothing parks no node and queues no child).
+__device__ __forceinline__ void fill_sky_tile(const LaunchParams& P, int tx, int ty) {
+    int x, y, row;
+    const bool valid = tile_pixel_at(P, tx, ty, x, y, row);
+    if (!valid) return;
+    const size_t p = (size_t)row * P.res_x + x;
+    write_pixel(P, p, clampc(mk(P.bg[0], P.bg[1], P.bg[2])));
+    if (P.hit_id && P.wf_sample == 0) P.hit_id[p] = -1;
+}
+
 // Workgroup (bx, by) runs the tiles of column bx in tile rows by, by + gridDim.y, by + 2 gridDim.y one after the other.
 // Once per workgroup: the parity read, the first-block clearing, the scene copy and its barrier, the wave's stack.
 // Per tile: tile -> pixel, shard_of(), the camera ray, find_closest(), shade_hit(), emit() -- and the launch parameters
 // those read, see below.  The loop carries nothing but its wave-uniform counter from one tile to the next.
+// With a coverage mask (sky_mask != nullptr; the host decides which frames have one, p3d_render.cpp): a tile whose bit is
+// clear is filled by fill_sky_tile() and the loop goes on, and a workgroup none of whose tiles has its bit set fills them
+// and returns before the scene copy and its barrier -- the test is on blockIdx and the mask alone, so the whole workgroup
+// takes the same side.  The first block's clearing above it stays unconditional.
 template <int WALK, int OCC, int TILES>
 __global__ __launch_bounds__(256) P3D_OCC(OCC) void wf_primary_kernel_tiles(const LaunchParams P) {
     static_assert(TILES >= 2 && TILES <= kMaxPrimaryTiles, "one tile per workgroup is wf_primary_kernel");
@@ -492,9 +518,23 @@ __global__ __launch_bounds__(256) P3D_OCC(OCC) void wf_primary_kernel_tiles(cons
         uint32_t* other = P.wf_alt + (size_t)((1u - par) * 2u) * kWfShards;
         for (uint32_t i = threadIdx.x; i < 2u * kWfShards; i += blockDim.x) other[i] = 0u;
     }
+    const int tx = blockIdx.x;
+    if (P.sky_mask) {                                                         // (launch-uniform)
+        bool any = false;
+        for (int k = 0; k < TILES; k++) {
+            const int ty = (int)(blockIdx.y + (uint32_t)k * gridDim.y);
+            if (ty < P.wf_tile_rows && tile_may_hit(P, P.sky_mask, tx, ty)) any = true;
+        }
+        if (!any) {                                                           // workgroup-uniform, before the scene copy's barrier
+            for (int k = 0; k < TILES; k++) {
+                const int ty = (int)(blockIdx.y + (uint32_t)k * gridDim.y);
+                if (ty < P.wf_tile_rows) fill_sky_tile(P, tx, ty);
+            }
+            return;
+        }
+    }
     const LdsScene sv = View<true>::make_shading(P);
     const TravCtx tc = wave_stack<true>(P, 0);
-    const int tx = blockIdx.x;
 #pragma nounroll
     for (int k = 0; k < TILES; k++) {
         const int ty = (int)(blockIdx.y + (uint32_t)k * gridDim.y);          // wave-uniform: the loop's state stays in scalar registers
@@ -509,6 +549,9 @@ __global__ __launch_bounds__(256) P3D_OCC(OCC) void wf_primary_kernel_tiles(cons
         auto args = __builtin_amdgcn_kernarg_segment_ptr();
         asm volatile("" : "+s"(args));
         const LaunchParams& Q = *(const LaunchParams*)args;
+        if (const uint32_t* mask = Q.sky_mask) {
+            if (!tile_may_hit(Q, mask, tx, ty)) { fill_sky_tile(Q, tx, ty); continue; }
+        }
         int x, y, row;
         const bool valid = tile_pixel_at(Q, tx, ty, x, y, row);
         if (__ballot(valid) == 0) continue;
@@ -1436,6 +1479,73 @@ hipError_t launch_wf_resolve_fused(const LaunchParams& P, const ResolveLevels& R
 hipError_t launch_wf_resolve(const LaunchParams& P, unsigned blocks, bool ray_stream, hipStream_t stream) {
     if (ray_stream) hipLaunchKernelGGL(wf_resolve_kernel<true>, dim3(blocks), dim3(256), 0, stream, P);
     else hipLaunchKernelGGL(wf_resolve_kernel<false>, dim3(blocks), dim3(256), 0, stream, P);
+    return hipGetLastError();
+}
+
+// The pre-pass of a frame with a tile coverage mask (p3d_tile_coverage.h): workgroup ty makes tile row ty's words.  Lane i takes
+// primitives i, i + 64, ... of the device-resident scene blob -- so the mask follows p3d_scene_update and p3d_scene_rebuild
+// with nothing copied from the host -- and ORs the columns each can touch into the row's words in LDS; then the words are
+// stored whole: no atomics on memory, nothing to clear beforehand, and no launch of the frame before this one reads them.
+// The camera travels in the arguments, so a captured frame replays with the mask of the camera it was captured with.
+__global__ __launch_bounds__(64) void tile_coverage_kernel(const TileCoverageJob J) {
+    __shared__ uint32_t words[kCoverMaxRowWords];
+    __shared__ uint32_t all;
+    const int32_t ty = (int32_t)blockIdx.x;
+    if (threadIdx.x < kCoverMaxRowWords) words[threadIdx.x] = 0u;
+    if (threadIdx.x == 0) all = 0u;
+    __syncthreads();
+    const CoverCamera cam = cover_camera(J.eye, J.uw, J.vh, J.vz);
+    const float4* q = reinterpret_cast<const float4*>(J.blob);
+    const uint32_t n = J.n_spheres + J.n_tris + J.n_boxes;
+    for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
+        double pts[kCoverMaxPoints][3];
+        CoverRow r;
+        if (i < J.n_spheres + J.n_boxes) {
+            double lo[3], hi[3];
+            if (i < J.n_spheres) {
+                const float4 s = q[J.off_spheres + i];                          // SphereRec
+                lo[0] = (double)s.x - (double)s.w; lo[1] = (double)s.y - (double)s.w; lo[2] = (double)s.z - (double)s.w;
+                hi[0] = (double)s.x + (double)s.w; hi[1] = (double)s.y + (double)s.w; hi[2] = (double)s.z + (double)s.w;
+            } else {
+                const uint32_t b = J.off_boxes + (i - J.n_spheres) * 2u;         // BoxRec
+                const float4 mn = q[b], mx = q[b + 1];
+                lo[0] = mn.x; lo[1] = mn.y; lo[2] = mn.z; hi[0] = mx.x; hi[1] = mx.y; hi[2] = mx.z;
+            }
+            cover_box_points(lo, hi, pts);
+            r = cover_row<8>(cam, J.tiles, pts, ty);
+        } else {
+            const uint32_t t = J.off_tris + (i - J.n_spheres - J.n_boxes) * J.tri_quads;   // TriRec's test record
+            const float4 a = q[t], b = q[t + 1], c = q[t + 2];
+            const float p0[3] = {a.x, a.y, a.z}, e1[3] = {b.x, b.y, b.z}, e2[3] = {c.x, c.y, c.z};
+            cover_triangle_points(p0, e1, e2, pts);
+            r = cover_row<3>(cam, J.tiles, pts, ty);
+        }
+        if (r.all) atomicOr(&all, 1u);
+        else if (r.any)
+            for (uint32_t w = (uint32_t)(r.tx0 < 0 ? 0 : r.tx0) >> 5; w < J.row_words && (int32_t)(32u * w) <= r.tx1; w++)
+                atomicOr(&words[w], cover_word_bits(r.tx0, r.tx1, w));
+    }
+    __syncthreads();
+    const bool every = all != 0u || !cam.ok;
+    uint32_t mine = 0u;
+    if (threadIdx.x < J.row_words) {
+        const uint32_t valid = cover_word_bits(0, J.tiles.tiles_x - 1, threadIdx.x);   // the row's tiles in this word
+        mine = (every ? 0xFFFFFFFFu : words[threadIdx.x]) & valid;
+        J.mask[(size_t)ty * J.row_words + threadIdx.x] = mine;
+    }
+    __syncthreads();
+    if (threadIdx.x < kCoverMaxRowWords) words[threadIdx.x] = (uint32_t)__popc(mine);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t active = 0u;
+        for (uint32_t w = 0; w < J.row_words; w++) active += words[w];
+        J.status[ty] = active | (every ? kCoverAllFlag : 0u);
+    }
+}
+hipError_t launch_tile_coverage(const TileCoverageJob& J, hipStream_t stream) {
+    static_assert(kCoverMaxRowWords <= 64, "one lane per word of a row");
+    if (J.row_words > kCoverMaxRowWords || J.tiles.tiles_y < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(tile_coverage_kernel, dim3((unsigned)J.tiles.tiles_y), dim3(64), 0, stream, J);
     return hipGetLastError();
 }
 

@@ -32,6 +32,9 @@ hipError_t tile_kernel_resident_blocks(const LaunchParams& P, const KernelVarian
 hipError_t launch_wf_resolve(const LaunchParams& P, unsigned blocks, bool ray_stream, hipStream_t stream);
 hipError_t launch_wf_resolve_fused(const LaunchParams& P, const ResolveLevels& R, unsigned shards, bool ray_stream, hipStream_t stream);
 hipError_t launch_clear_words(uint32_t* p, uint32_t n, hipStream_t stream);
+// the pre-pass of a frame with a tile coverage mask (p3d_tile_coverage.h: TileCoverageJob): one workgroup per tile row
+struct TileCoverageJob;
+hipError_t launch_tile_coverage(const TileCoverageJob& J, hipStream_t stream);
 hipError_t launch_frame_cams(FrameCam* dst, const FrameCam* cams, int n, hipStream_t stream);
 hipError_t launch_raygen_table(float* fx, float* fy, int res_x, int res_y, hipStream_t stream);
 hipError_t launch_sum_samples(const LaunchParams& P, size_t first_px, size_t n_px, hipStream_t stream);

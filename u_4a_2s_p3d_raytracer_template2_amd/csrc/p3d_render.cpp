@@ -651,6 +651,51 @@ int run_wavefront_pass(p3d_scene* s, p3d_scene::Workspace& ws, hipStream_t strea
     return P3D_OK;
 }
 
+// ---- tile coverage mask (p3d_tile_coverage.h)
+
+// Does this frame get one?  Only frames whose level-1 launches are wf_primary_kernel_tiles -- the one kernel that reads it;
+// served_primary() holds has_primary_tiles(): an LDS scene walked per lane, no counters, no features with random draws (the
+// skybox among them), no Schlick, one frame, no AOV planes -- and whose camera rays are the pinhole's and can only meet bounded
+// primitives: spp == 0 (camera_ray() then ignores the aperture) and no plane in the scene.  Everything else runs as before.
+bool sky_tiles_eligible(const p3d_scene* s, const FrameConfig& cfg, const FramePlan& plan) {
+    const LaunchParams& P = plan.P;
+    if (!s->sky_tiles || plan.rays || cfg.spp != 0 || cfg.batch() || P.n_planes != 0 || (P.features & kFeatSky)) return false;
+    if (cover_row_words(P.tiles_x) > kCoverMaxRowWords) return false;
+    KernelVariant v = with_budget(plan.kv, s->occupancy ? s->occupancy : 6);       // what run_wavefront_pass() asks for
+    v.tiles = s->primary_tiles;
+    // (every band of the frame has the first one's columns and chunking, so all of them are served alike)
+    const int rows = (int)std::min<size_t>(plan.band_tile_rows, (size_t)P.tiles_y);
+    return served_primary(v, P.tiles_x, rows, P.tiles_x * rows, P.xcd_chunk).tiles > 1;
+}
+
+// The pre-pass of an eligible frame, on the frame's stream in front of its level-1 launches (and of the fork, when the
+// frame's bands run on several streams): one small launch that reads the camera from its arguments and the primitives from
+// the device-resident blob.  No copy from the host, no wait.  A capture that would have to allocate gets no mask.
+int sky_tiles_begin(p3d_scene* s, const FrameConfig& cfg, const FramePlan& plan, LaunchParams& P) {
+    if (plan.rays) return P3D_OK;                   // a ray stream touches nothing of the frames' state
+    s->last_sky.on = false;
+    if (!sky_tiles_eligible(s, cfg, plan)) return P3D_OK;
+    TileCoverageJob J;
+    memset(&J, 0, sizeof J);
+    memcpy(J.eye, P.eye, sizeof J.eye); memcpy(J.uw, P.uw, sizeof J.uw); memcpy(J.vh, P.vh, sizeof J.vh); memcpy(J.vz, P.vz, sizeof J.vz);
+    J.tiles.res_x = P.res_x; J.tiles.res_y = P.res_y; J.tiles.tile_h = 4 * P.wg_waves;
+    J.tiles.tiles_x = P.tiles_x; J.tiles.tiles_y = P.tiles_y;
+    J.tiles.row_block = P.row_block; J.tiles.rank = P.rank; J.tiles.world = P.world;
+    J.row_words = cover_row_words(P.tiles_x);
+    const size_t words = (size_t)P.tiles_y * J.row_words + (size_t)P.tiles_y;
+    if (s->sky_mask.cap < words * sizeof(uint32_t)) {
+        if (capturing(s->stream)) return P3D_OK;
+        HIP_TRY(s->sky_mask.ensure(words * sizeof(uint32_t)));
+    }
+    J.blob = P.blob; J.off_spheres = P.off_spheres; J.off_tris = P.off_tris; J.off_boxes = P.off_boxes; J.tri_quads = P.tri_quads;
+    J.n_spheres = s->stats.n_spheres; J.n_tris = s->stats.n_triangles; J.n_boxes = s->stats.n_boxes;
+    J.mask = (uint32_t*)s->sky_mask.p; J.status = J.mask + (size_t)P.tiles_y * J.row_words;
+    HIP_TRY(launch_tile_coverage(J, s->stream));
+    P.sky_mask = J.mask; P.sky_mask_row_words = J.row_words;
+    s->last_sky.on = true; s->last_sky.tiles = J.tiles; s->last_sky.row_words = J.row_words;
+    return P3D_OK;
+}
+
 // npx: pixels of the device planes (all frames of a batch)
 int run_wavefront(p3d_scene* s, const FrameConfig& cfg, FramePlan& plan, size_t npx, bool profile, hipEvent_t pick_begin) {
     LaunchParams& P = plan.P;
@@ -682,6 +727,7 @@ int run_wavefront(p3d_scene* s, const FrameConfig& cfg, FramePlan& plan, size_t 
         if (rc) return rc;
     }
     if (pick_begin) HIP_TRY(hipEventRecord(pick_begin, s->stream));   // after the (host-side) allocations
+    { int rc = sky_tiles_begin(s, cfg, plan, P); if (rc) return rc; }  // the tile coverage mask of an eligible frame
     if (lanes > 1) {                                   // the other lanes start after what the stream holds
         HIP_TRY(hipEventRecord(s->ev_fork, s->stream));
         for (int ln = 1; ln < lanes; ln++) HIP_TRY(hipStreamWaitEvent(s->lane_stream[ln], s->ev_fork, 0));
@@ -789,6 +835,7 @@ int render_batch(p3d_scene* s, const p3d_camera* cams, int32_t n_frames, const p
     if (sched == SCHED_TREE && plan.stochastic) return fail(P3D_ERR_LIMIT, "workspace budget too small for the schedules the features need");
     s->last_schedule = sched;
     s->last_primary_tiles = 1;          // (the wavefront schedule says what its level-1 launch ran with)
+    s->last_sky.on = false;             // (... and whether the frame had a tile coverage mask)
     LaunchParams& P = plan.P;
     const size_t lds = sched == SCHED_TREE   ? tree_kernel_lds_bytes(P, plan.lds_scene)
                        : sched == SCHED_TILE ? tile_kernel_lds_bytes(plan.PT, plan.lds_scene)

@@ -98,6 +98,7 @@ int p3d_scene_create(const p3d_scene_desc* d, const p3d_build_opts* opts, int de
     if (const char* e = getenv("P3D_TILE_LPT")) s->tile_lpt_enabled = atoi(e) != 0;
     if (const char* e = getenv("P3D_OCC")) { int v = atoi(e); if (v == 0 || v == 5 || v == 6) s->occupancy = v; }
     if (const char* e = getenv("P3D_PRIMARY_TILES")) { int v = atoi(e); if (v >= 1 && v <= kMaxPrimaryTiles) s->primary_tiles = v; }
+    if (const char* e = getenv("P3D_SKY_TILES")) s->sky_tiles = atoi(e) != 0;
     if (const char* e = getenv("P3D_TRI_STRIDE")) s->tri_quads = atoi(e) == 64 ? 4u : 3u;
     if (const char* e = getenv("P3D_SHARE_MIN_IDLE")) { int v = atoi(e); if (v >= 0 && v <= 65) s->share_min_idle = v; }
     if (const char* e = getenv("P3D_DEBUG_SKIP")) s->dbg_skip = (uint32_t)atoi(e);      // read by -DP3D_DEBUG_SKIP builds only
@@ -259,6 +260,13 @@ int p3d_set_primary_tiles(p3d_scene* s, int32_t tiles) {
     if (!s) return fail(P3D_ERR_ARG, "scene is NULL");
     if (tiles < 0 || tiles > kMaxPrimaryTiles) return fail(P3D_ERR_ARG, "tiles must be 0 (default), 1, 2 or 3");
     s->primary_tiles = tiles ? tiles : kDefaultPrimaryTiles;
+    return P3D_OK;
+}
+
+int p3d_set_sky_tiles(p3d_scene* s, int32_t on) {
+    if (!s) return fail(P3D_ERR_ARG, "scene is NULL");
+    if (on != 0 && on != 1) return fail(P3D_ERR_ARG, "on must be 0 or 1");
+    s->sky_tiles = on != 0;
     return P3D_OK;
 }
 

@@ -17,6 +17,7 @@
 #include "p3d_device_types.h"
 #include "p3d_frame_config.h"
 #include "p3d_launch.h"
+#include "p3d_tile_coverage.h"
 #include "sample_stream.h"
 
 extern "C" int p3d_internal_set_error(int code, const char* msg);   // p3d_capi_misc.cpp: the thread's p3d_last_error()
@@ -269,6 +270,12 @@ struct p3d_scene {
     int occupancy = 0;     // 0 = compiler default register budget, else 5 / 6 / 8 waves per SIMD
     int primary_tiles = p3d::kDefaultPrimaryTiles;   // 16x16 tiles a workgroup of the level-1 launch runs (p3d_set_primary_tiles)
     int last_primary_tiles = 1;                      // ... and what the most recent render's level-1 launch ran with
+    // The tile coverage mask of a frame (p3d_tile_coverage.h, p3d_set_sky_tiles): [tiles_y][row_words] mask words, then
+    // [tiles_y] status words, written by a pre-pass on the frame's stream.  last_sky: the geometry of the most recent
+    // render's mask (on = it had one); what the device marked is read back only when p3d_last_sky_tiles() asks.
+    bool sky_tiles = p3d::kDefaultSkyTiles;
+    p3d::RawBuf sky_mask;
+    struct { bool on = false; p3d::CoverTiles tiles{}; uint32_t row_words = 0; } last_sky;
     uint32_t tri_quads = 3;    // 16-byte quads per triangle test record (3; 4 = round 2's 64-byte stride, P3D_TRI_STRIDE=64)
     bool verbose = false;      // P3D_VERBOSE=1: launch geometry on stderr (diagnostic)
     int share_min_idle = 16;   // work-sharing walk of scenes read from HBM: idle lanes before a steal round (0 or > 64: private walks)
