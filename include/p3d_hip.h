@@ -700,10 +700,66 @@ typedef struct p3d_accumulate_outputs { float* rgb32f; float* length; int32_t me
  *    anything is allocated, when n_frames * res_x * res_y does not fit 31 bits.
  *  - handle state: nothing of the handle's frame state changes -- the measured schedule choice, the learned tile orders,
  *    p3d_last_schedule(), p3d_last_primary_tiles() and the ray-stream state are what they were.
- *  - after p3d_scene_update the reprojection still sees a static world: there are no motion vectors; the hit_id, depth and
- *    normal tests drop what moved. */
+ *  - after p3d_scene_update THIS entry still sees a static world: the hit_id, depth and normal tests drop what moved, or,
+ *    under a small motion, pass on the wrong surface point.  p3d_accumulate_moving (below) is the entry for sequences whose
+ *    primitives move: it reprojects through the primitive records of the two frames. */
 int p3d_accumulate(p3d_scene* scene, const p3d_accumulate_params* params, const p3d_accumulate_frames* frames,
                    const p3d_accumulate_history* history, const p3d_accumulate_outputs* out);
+
+/* The same accumulation for a sequence whose primitives move between frames (p3d_scene_update): the geometry every frame
+ * was rendered with, in the form p3d_scene_update was given it. */
+typedef struct p3d_accumulate_motion {
+    uint32_t        n_prims;             /* >= 1 */
+    const uint32_t* prim_type;           /* [n_prims] P3D_SPHERE.. as in p3d_scene_desc */
+    const float*    prim_data;           /* [n_frames][n_prims][12]: the geometry frame f was rendered with,
+                                            in p3d_scene_desc::prim_data form (what p3d_scene_update was given) */
+    const float*    history_prim_data;   /* [n_prims][12]: the geometry the history was rendered with; needed iff history != NULL */
+    int32_t         memory;              /* 0 host, 1 device: all three arrays */
+} p3d_accumulate_motion;
+typedef struct p3d_accumulate_moving_outputs { float* rgb32f; float* length; float* prev_xy; int32_t memory; } p3d_accumulate_moving_outputs;  /* not all NULL */
+/* p3d_accumulate with the hit point moved back onto where the same surface point of the same primitive was in the frame
+ * looked back at.  DEFINED here like p3d_accumulate: float32 IEEE-754 basic operations in the stated order, no fused
+ * multiply-add, correctly rounded division and square root; the device, the host layer (p3dh_accumulate_moving) and
+ * tests/accumulate_moving_reference.py agree on it in every bit.  Like p3d_accumulate it is a pure function of its
+ * arguments: the handle keeps no previous geometry and no history, it lends its stream and its staging buffers.
+ *  - the definition: steps 0, 1, 3 and 4 are p3d_accumulate's.  Step 2 starts from q = P_prev - eye' instead of
+ *    q = P - eye'; everything after that line is unchanged, the depth test of step 3 included -- dist = |q| is then the
+ *    PREVIOUS depth of the surface point, which is what Z' has to be compared with.
+ *  - P_prev, for the pixel's hit id I (frames->hit_id is needed here: the motion is looked up by it; history->hit_id may
+ *    still be NULL, which only switches the id test of step 3 off).  a = the record prim_data[f][I]; b = the record of the
+ *    frame looked back at, prim_data[f-1][I], or history_prim_data[I] for frame 0; k = prim_type[I];
+ *    dot(p, q) = (p.x q.x + p.y q.y) + p.z q.z.
+ *      static rule: if I < 0, or I >= n_prims, or the kind's meaningful floats of a and b are equal as 32-bit words (4 for a
+ *         sphere, 9 for a triangle, 6 for a box, 4 for a plane and for any kind above 3 that reaches the device), then
+ *         P_prev = P exactly.  With unchanged geometry the entry therefore returns the bits of p3d_accumulate, and ids
+ *         outside the primitives read nothing.
+ *      sphere   c, r -> c', r':  s = r' / r;  P_prev = c' + (P - c) * s per component, a product and then a sum.
+ *      triangle P0 P1 P2 -> P0' P1' P2':  e1 = P1 - P0, e2 = P2 - P0, w = P - P0;  d11 = dot(e1, e1), d12 = dot(e1, e2),
+ *         d22 = dot(e2, e2), w1 = dot(w, e1), w2 = dot(w, e2);  den = d11 * d22 - d12 * d12;
+ *         beta = (d22 * w1 - d12 * w2) / den, gamma = (d11 * w2 - d12 * w1) / den;  e1' = P1' - P0', e2' = P2' - P0';
+ *         P_prev = (P0' + e1' * beta) + e2' * gamma per component.
+ *      box      mn, mx -> mn', mx', per axis:  e = mx - mn;  t = e != 0 ? (P - mn) / e : 0;  P_prev = mn' + (mx' - mn') * t.
+ *      plane (and any kind above 3): a changed record has no point correspondence: no history.
+ *    Degenerate records (r == 0, den == 0) give an infinite or NaN P_prev; the !(c > 0) and window tests of step 2 turn that
+ *    into "no history", there is no test of its own.  The normal test of step 3 compares the CURRENT normal N with N': a
+ *    primitive that turns by more than acos(normal_min) per frame loses its history.
+ *  - out->prev_xy (optional): 2 floats per pixel, frames back to back: (px, py) of step 2 whenever the window test of step 2
+ *    passed -- whether or not a tap then contributed -- and two quiet NaNs (0x7FC00000) otherwise: a frame with nothing to
+ *    look back at, Z not valid, a changed plane, !(c > 0), a position outside the window.  It is the screen-space motion
+ *    vector (previous position; subtract the pixel's own x, y) that temporal anti-aliasing and motion blur need.
+ *  - planes, memory, the launches (one per frame in stream order, cameras by value), the spare planes, stream capture, the
+ *    shards of world > 1 and the handle's untouched frame state: as p3d_accumulate.  motion->memory is independent of the
+ *    other memory fields; host geometry is staged in buffers the handle owns (counted in device_bytes) like host planes,
+ *    and like them refuses a captured stream.  Device arrays need only the alignment of their floats.
+ *  - aliasing: out->rgb32f == frames->rgb32f is allowed.  Any other output plane equal to a plane of the frames or of the
+ *    history, to an array of the motion or to another output plane -- prev_xy included --: P3D_ERR_ARG.
+ *  - P3D_ERR_ARG: everything p3d_accumulate refuses (with "every output plane NULL" for its "both"); a NULL motion, prim_type
+ *    or prim_data; n_prims == 0; a history with a NULL history_prim_data; a NULL frames->hit_id; motion->memory outside 0
+ *    and 1; for host memory a prim_type above 3.  P3D_ERR_LIMIT, before anything is allocated, when
+ *    n_frames * res_x * res_y or n_frames * n_prims * 12 does not fit 31 bits. */
+int p3d_accumulate_moving(p3d_scene* scene, const p3d_accumulate_params* params, const p3d_accumulate_frames* frames,
+                          const p3d_accumulate_history* history, const p3d_accumulate_motion* motion,
+                          const p3d_accumulate_moving_outputs* out);
 
 /* Ambient occlusion over the planes of p3d_render_aov: hemisphere any-hit queries fused per pixel.  What a caller of
  * p3d_occluded would build as res_x * res_y * samples segments, upload and count is made in the lanes of one launch from
@@ -990,6 +1046,11 @@ int p3d_debug_denoise(int device, const p3d_denoise_params* params, const p3d_de
  * freed.  Refusals as p3d_accumulate (a memory field other than 0: P3D_ERR_ARG). */
 int p3d_debug_accumulate(int device, const p3d_accumulate_params* params, const p3d_accumulate_frames* frames,
                          const p3d_accumulate_history* history, const p3d_accumulate_outputs* out);
+/* Likewise the launches of p3d_accumulate_moving (csrc/accumulate_motion.hip) over HOST planes and HOST geometry, without a
+ * scene.  Refusals as p3d_accumulate_moving (a memory field other than 0: P3D_ERR_ARG). */
+int p3d_debug_accumulate_moving(int device, const p3d_accumulate_params* params, const p3d_accumulate_frames* frames,
+                                const p3d_accumulate_history* history, const p3d_accumulate_motion* motion,
+                                const p3d_accumulate_moving_outputs* out);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,347 @@
+"""p3d_accumulate_moving without a GPU: the host restatement (p3dh_accumulate_moving) against the NumPy restatement of the
+definition (tests/accumulate_moving_reference.py), bit for bit; the static rule against p3dh_accumulate; that the motion is
+right and not merely self-consistent; the rounding of prev_xy; degenerate records, ids outside the primitives and a changed
+plane; every refusal; the interface."""
+import ctypes as C
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import accumulate_reference as R                           # noqa: E402
+import accumulate_moving_reference as M                    # noqa: E402
+import u_4a_2s_p3d_raytracer_template2_amd as P            # noqa: E402
+from u_4a_2s_p3d_raytracer_template2_amd import api        # noqa: E402
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+F = np.float32
+KW = dict(depth_tolerance=0.1, normal_min=0.8, max_history=4.5)
+KWT = (KW["depth_tolerance"], KW["normal_min"], KW["max_history"])
+SHAPES = [(1, 1), (5, 3), (17, 33), (37, 23), (64, 48), (131, 77)]      # the shapes of test_accumulate_host.py
+ERR_ARG, ERR_LIMIT = -1, -4
+
+
+def same_bits(got, ref, what):
+    assert got.shape == ref.shape and got.dtype == ref.dtype, what
+    bad = got.view(np.uint32) != ref.view(np.uint32)
+    assert not bad.any(), "%s: %d of %d values differ, first at %s" % (what, int(bad.sum()), bad.size, np.argwhere(bad)[0])
+
+
+def same_result(got, ref, keys=("rgb32f", "length", "prev_xy")):
+    for k in keys:
+        same_bits(got[k], ref[k], k)
+
+
+@pytest.mark.parametrize("history", [False, True])
+@pytest.mark.parametrize("n_frames", [1, 2, 4])
+@pytest.mark.parametrize("shape", SHAPES)
+def test_host_equals_the_numpy_restatement(shape, n_frames, history):
+    seq = M.make_sequence(*shape, n_frames, seed=n_frames, history=history)
+    got = api.host_accumulate_moving(*M.args(seq), **KW)
+    ref = M.accumulate(*M.args(seq), *KWT)
+    same_result(got, ref)
+    same_result(api.host_accumulate_moving(*M.args(seq), prev_xy=False, **KW), ref, ("rgb32f", "length"))
+    nan = np.isnan(ref["prev_xy"]).all(-1)
+    assert (np.isnan(ref["prev_xy"]).any(-1) == nan).all(), "px and py are both there or both NaN"
+    assert (ref["prev_xy"].view(np.uint32)[nan] == 0x7FC00000).all()
+    assert not nan[ref["length"] > 1].any(), "history is only taken where prev_xy is"
+    if not history:
+        assert nan[0].all() and (ref["length"][0] == 1).all()
+    if shape in ((64, 48), (131, 77)):      # large enough to show every primitive: each moved kind takes history through its motion
+        for f in range(0 if history else 1, n_frames):
+            for k in (1, 2, 3):
+                at = seq["hit_id"][f] == k
+                assert at.sum() >= 20 and (ref["length"][f][at] > 1).mean() > 0.3, (f, k, at.sum(), (ref["length"][f][at] > 1).mean())
+            assert nan[f][seq["hit_id"][f] < 0].all(), "a miss has no previous position"
+
+
+@pytest.mark.parametrize("history", [False, True])
+@pytest.mark.parametrize("shape", [(5, 3), (37, 23), (64, 48)])
+def test_unchanged_geometry_gives_the_bits_of_p3dh_accumulate(shape, history):
+    seq = R.make_sequence(*shape, 4, seed=3, history=history)           # ids 0 and 2: the ground, 1: the sphere
+    kinds = np.array([M.PLANE, M.SPHERE, M.PLANE], np.uint32)
+    rec = np.random.default_rng(5).random((3, 12), dtype=F)             # what the records hold does not matter: they are equal
+    h = None if seq["history"] is None else dict(seq["history"], prim_data=rec)
+    got = api.host_accumulate_moving(seq["rgb32f"], seq["depth"], seq["normal"], seq["cams"], seq["hit_id"], kinds, np.stack([rec] * 4), h, **KW)
+    ref = api.host_accumulate(seq["rgb32f"], seq["depth"], seq["normal"], seq["cams"], seq["hit_id"], seq["history"], **KW)
+    same_result(got, ref, ("rgb32f", "length"))
+    assert (ref["length"] > 1).any()
+    # the unused floats of a record are not compared: a sphere's floats 4.. and a plane's may differ
+    rec2 = rec.copy()
+    rec2[:, 4:] += 1
+    moved = np.stack([rec, rec2, rec, rec2])
+    got = api.host_accumulate_moving(seq["rgb32f"], seq["depth"], seq["normal"], seq["cams"], seq["hit_id"], kinds, moved, h, **KW)
+    same_result(got, ref, ("rgb32f", "length"))
+
+
+def view_axis_sequence():
+    """A static camera on the z axis and a sphere that comes 1.0 closer along it between the history's frame and frame 0: more
+    than depth_tolerance * dist = 0.1 * 5.  Colours are the palette, noise-free; the history is 3 frames long."""
+    cam = R.look_at((0.0, 1.0, 6.0), (0.0, 1.0, 0.0), 64, 48)
+
+    def records(g):
+        rec = M.world(0)
+        rec[1, :4] = (0.0, 1.0, 1.0 + 1.0 * g, 1.0)
+        rec[2, :9] += 50                            # the triangle and the box out of sight
+        rec[3, :6] += 50
+        return rec
+    seq = M.make_sequence(64, 48, 1, history=True, noise=0.0, records=records, camera=lambda f: cam)
+    seq["history"]["length"][:] = 3.0
+    return seq
+
+
+def test_the_motion_is_right_not_merely_self_consistent():
+    seq = view_axis_sequence()
+    kw = dict(KW, max_history=32.0)
+    got = api.host_accumulate_moving(*M.args(seq), **kw)
+    hit, hhit = seq["hit_id"][0], seq["history"]["hit_id"]
+    xy = got["prev_xy"][0]
+    x0, y0 = np.floor(np.nan_to_num(xy[..., 0], nan=-9)).astype(int), np.floor(np.nan_to_num(xy[..., 1], nan=-9)).astype(int)
+    inside = (hit == 1) & (x0 >= 0) & (x0 + 1 < 64) & (y0 >= 0) & (y0 + 1 < 48)
+    xc, yc = np.clip(x0, 0, 62), np.clip(y0, 0, 46)
+    for ox, oy in ((0, 0), (1, 0), (0, 1), (1, 1)):                      # the four taps show the previous sphere
+        inside &= hhit[yc + oy, xc + ox] == 1
+    assert inside.sum() >= 20, inside.sum()
+    assert (got["length"][0][inside] > 1).all()
+    # four products, three sums, one division and one blend, each within half an ulp of values <= 1
+    assert np.abs(got["rgb32f"][0][inside] - M.PALETTE[1]).max() <= 1e-6
+    # the sphere's previous silhouette is smaller: the surface point moved towards the image centre
+    assert (np.hypot(xy[..., 0] - 31.5, xy[..., 1] - 23.5)[inside] <= np.hypot(*np.meshgrid(np.arange(64) - 31.5, np.arange(48) - 23.5))[inside] + 1e-3).all()
+    plain = api.host_accumulate(seq["rgb32f"], seq["depth"], seq["normal"], seq["cams"], seq["hit_id"], seq["history"], **kw)
+    assert (plain["length"][0][inside] == 1).all(), "p3d_accumulate drops what moved"
+
+
+def test_prev_xy_against_a_float64_evaluation():
+    """2^-10 pixel: px < 256 has an ulp of 2^-16 and the chain has about 40 roundings.  No step of it cancels for this world:
+    the differences P - c, P - P0 and P - mn are between a point ON the primitive and a point of the same primitive, so they
+    are of the primitive's size (0.7 to 2), like their operands (all coordinates are below 6); the triangle is fat
+    (den = |e1 x e2|^2 is about 0.4 of d11 * d22), so den and the numerators of beta and gamma lose no leading bits; and
+    c > 1 for everything in view (the eye is 3 or more from every primitive), so the perspective division is benign."""
+    seq = M.make_sequence(64, 48, 2, seed=2)
+    prev = dict(rgb32f=seq["rgb32f"][0], depth=seq["depth"][0], normal=seq["normal"][0], hit_id=seq["hit_id"][0], cam=seq["cams"][0],
+                length=np.ones((48, 64), F))
+    a = (seq["cams"][1], seq["rgb32f"][1], seq["depth"][1], seq["normal"][1], seq["hit_id"][1], prev, seq["prim_type"], seq["prim_data"][1],
+         seq["prim_data"][0], *KWT)
+    xy32 = M.accumulate_frame(*a)[2]
+    xy64 = M.accumulate_frame(*a, T=np.float64)[2]
+    same_bits(api.host_accumulate_moving(*M.args(seq), **KW)["prev_xy"][1], xy32, "prev_xy")
+    for k in (1, 2, 3):
+        at = (seq["hit_id"][1] == k) & ~np.isnan(xy32).any(-1) & ~np.isnan(xy64).any(-1)
+        assert at.sum() >= 50, (k, at.sum())
+        err = np.abs(xy32[at].astype(np.float64) - xy64[at]).max()
+        print("kind %d: %d pixels, max |prev_xy - float64| = %.3g pixel" % (k, at.sum(), err))
+        assert err <= 2.0 ** -10, (k, err)
+        assert np.abs(xy64[at] - np.argwhere(at)[:, ::-1]).max() > 0.25, "the primitive did move on the screen, by 250 times the bound or more"
+
+
+def damaged(seq, f, prim, values, where="cur"):
+    """The sequence with floats of primitive `prim`'s record of frame f (or of the frame before it) replaced."""
+    out = dict(seq, prim_data=seq["prim_data"].copy())
+    rec = out["prim_data"][f if where == "cur" else f - 1, prim]
+    for k, v in values.items():
+        rec[k] = v
+    return out
+
+
+def test_degenerate_records():
+    seq = M.make_sequence(64, 48, 2, seed=6)
+    good = M.accumulate(*M.args(seq), *KWT)
+    for name, prim, values in (("r == 0", 1, {3: 0.0}),
+                               ("a collinear triangle", 2, {3: 1.0, 4: 1.0, 5: 1.0, 6: 2.0, 7: 2.0, 8: 2.0, 0: 0.0, 1: 0.0, 2: 0.0})):
+        bad = damaged(seq, 1, prim, values)
+        got = api.host_accumulate_moving(*M.args(bad), **KW)
+        same_result(got, M.accumulate(*M.args(bad), *KWT))
+        at = seq["hit_id"][1] == prim
+        assert (good["length"][1][at] > 1).any(), name
+        assert (got["length"][1][at] == 1).all() and np.isnan(got["prev_xy"][1][at]).all(), name
+        same_bits(got["rgb32f"][1][at], seq["rgb32f"][1][at], name + ": copied")
+        assert not np.isnan(got["rgb32f"]).any() and not np.isnan(got["length"]).any(), name
+        same_bits(got["length"][1][~at], good["length"][1][~at], name + ": the other primitives")
+    flat = damaged(seq, 1, 3, {4: float(seq["prim_data"][1, 3, 1])})          # mx.y = mn.y: t = 0 on that axis
+    got = api.host_accumulate_moving(*M.args(flat), **KW)
+    same_result(got, M.accumulate(*M.args(flat), *KWT))
+    at = seq["hit_id"][1] == 3
+    assert not np.isnan(got["rgb32f"]).any() and not np.isnan(got["length"]).any()
+    assert not np.isnan(got["prev_xy"][1][at]).all(), "a flat axis is no reason to lose the position"
+    probe = {}
+    prev = dict(rgb32f=good["rgb32f"][0], depth=seq["depth"][0], normal=seq["normal"][0], hit_id=seq["hit_id"][0], cam=seq["cams"][0], length=good["length"][0])
+    M.accumulate_frame(seq["cams"][1], seq["rgb32f"][1], seq["depth"][1], seq["normal"][1], seq["hit_id"][1], prev, seq["prim_type"],
+                       flat["prim_data"][1], flat["prim_data"][0], *KWT, probe=probe)
+    assert (probe["Q"][1][at] == flat["prim_data"][0, 3, 1]).all(), "t = 0: the previous box's mn on the flat axis"
+
+
+@pytest.mark.parametrize("other", [-1, 4, 1000, 2 ** 31 - 1])
+def test_ids_outside_the_primitives_follow_the_static_rule(other):
+    seq = M.make_sequence(37, 23, 2, seed=8, history=True)
+    sphere = [seq["hit_id"] == 1, seq["history"]["hit_id"] == 1]
+    seq["hit_id"][sphere[0]] = other
+    seq["history"]["hit_id"][sphere[1]] = other
+    got = api.host_accumulate_moving(*M.args(seq), **KW)
+    same_result(got, M.accumulate(*M.args(seq), *KWT))
+    plain = api.host_accumulate(seq["rgb32f"], seq["depth"], seq["normal"], seq["cams"], seq["hit_id"], seq["history"], **KW)
+    # frame 0 looks back at the history, which both entries read alike: there the sphere's pixels are p3d_accumulate's
+    assert sphere[0][0].sum() > 20 and (plain["length"][0][sphere[0][0]] > 1).any()
+    same_bits(got["rgb32f"][0][sphere[0][0]], plain["rgb32f"][0][sphere[0][0]], "rgb32f")
+    same_bits(got["length"][0][sphere[0][0]], plain["length"][0][sphere[0][0]], "length")
+
+
+def test_a_changed_plane_has_no_history():
+    seq = M.make_sequence(37, 23, 2, seed=9)
+    good = api.host_accumulate_moving(*M.args(seq), **KW)
+    ground = seq["hit_id"][1] == 0
+    assert (good["length"][1][ground] > 1).mean() > 0.5
+    for k, v in ((3, 1e-6), (1, np.nextafter(F(1), F(2)))):
+        bad = damaged(seq, 1, 0, {k: v})
+        got = api.host_accumulate_moving(*M.args(bad), **KW)
+        same_result(got, M.accumulate(*M.args(bad), *KWT))
+        assert (got["length"][1][ground] == 1).all() and np.isnan(got["prev_xy"][1][ground]).all()
+        same_bits(got["rgb32f"][1][ground], seq["rgb32f"][1][ground], "copied")
+        same_bits(got["length"][1][~ground], good["length"][1][~ground], "the other primitives")
+
+
+def test_one_call_equals_frame_by_frame_with_the_outputs_fed_back():
+    seq = M.make_sequence(37, 23, 4, seed=5, history=True)
+    whole = api.host_accumulate_moving(*M.args(seq), **KW)
+    h = seq["history"]
+    for f in range(4):
+        one = api.host_accumulate_moving(seq["rgb32f"][f], seq["depth"][f], seq["normal"][f], seq["cams"][f], seq["hit_id"][f], seq["prim_type"],
+                                         seq["prim_data"][f], h, **KW)
+        for k in ("rgb32f", "length", "prev_xy"):
+            same_bits(one[k].reshape(whole[k][f].shape), whole[k][f], "frame %d %s" % (f, k))
+        h = dict(rgb32f=one["rgb32f"], length=one["length"], depth=seq["depth"][f], normal=seq["normal"][f], cam=seq["cams"][f],
+                 hit_id=seq["hit_id"][f], prim_data=seq["prim_data"][f])
+
+
+# ---- the interface
+def test_the_symbols_are_exported_declared_and_listed():
+    dyn = subprocess.check_output(["nm", "-D", "--defined-only", api.LIB_PATH]).decode()
+    for name in ("p3d_accumulate_moving", "p3d_debug_accumulate_moving", "p3dh_accumulate_moving"):
+        assert re.search(r"\bT %s$" % name, dyn, re.M), "libp3d_hip.so does not export " + name
+        assert hasattr(P.lib(), name)
+    header = open(os.path.join(REPO, "include", "p3d_hip.h")).read()
+    assert re.search(r"\bint p3d_accumulate_moving\(p3d_scene\* scene, const p3d_accumulate_params\* params, const p3d_accumulate_frames\* frames,\s*"
+                     r"const p3d_accumulate_history\* history, const p3d_accumulate_motion\* motion,\s*const p3d_accumulate_moving_outputs\* out\);", header)
+    assert re.search(r"\bint p3d_debug_accumulate_moving\(int device, const p3d_accumulate_params\* params,", header)
+    for name in ("p3d_accumulate_motion", "p3d_accumulate_moving_outputs"):
+        assert "} %s;" % name in header
+    assert "p3d_accumulate_moving" in api.C_ABI_SYMBOLS and "p3d_debug_accumulate_moving" in api.C_ABI_SYMBOLS
+    assert re.search(r"#define\s+P3D_ABI_VERSION\s+4\b", header) and P.lib().p3d_abi_version() == 4
+    mo, ou = api.AccumulateMotion, api.AccumulateMovingOutputs
+    assert C.sizeof(mo) == 40 and (mo.n_prims.offset, mo.prim_type.offset, mo.prim_data.offset, mo.history_prim_data.offset, mo.memory.offset) == (0, 8, 16, 24, 32)
+    assert C.sizeof(ou) == 32 and (ou.rgb32f.offset, ou.length.offset, ou.prev_xy.offset, ou.memory.offset) == (0, 8, 16, 24)
+    for name in ("accumulate_moving", "accumulate_moving_device"):
+        assert hasattr(P.DeviceScene, name)
+    assert hasattr(P, "host_accumulate_moving") and hasattr(P, "debug_accumulate_moving")
+
+
+def refusal_cases():
+    """(name, expected status, keyword changes of call()): the new refusals, then those inherited from p3d_accumulate."""
+    good = (5, 3, 1, 0.1, 0.8, 4.0)
+    cases = [("motion NULL", ERR_ARG, dict(motion=False)), ("prim_type NULL", ERR_ARG, dict(motion_null="prim_type")),
+             ("prim_data NULL", ERR_ARG, dict(motion_null="prim_data")), ("n_prims == 0", ERR_ARG, dict(n_prims=0)),
+             ("a history without history_prim_data", ERR_ARG, dict(motion_null="history_prim_data")),
+             ("frames->hit_id NULL", ERR_ARG, dict(frames_null="hit_id")), ("a prim_type of 4", ERR_ARG, dict(kind=4)),
+             ("a prim_type of 2^31", ERR_ARG, dict(kind=1 << 31))]
+    for v in (2, -1):
+        cases.append(("motion->memory = %d" % v, ERR_ARG, dict(memory={"motion": v})))
+    for k in ("rgb32f", "depth", "normal", "hit_id"):
+        cases.append(("out->prev_xy == frames->%s" % k, ERR_ARG, dict(alias=("prev_xy", "frames", k))))
+    for k in ("rgb32f", "depth", "normal", "length", "hit_id"):
+        cases.append(("out->prev_xy == history->%s" % k, ERR_ARG, dict(alias=("prev_xy", "history", k))))
+    for k in ("prim_type", "prim_data", "history_prim_data"):
+        cases.append(("out->prev_xy == motion->%s" % k, ERR_ARG, dict(alias=("prev_xy", "motion", k))))
+    for k in ("rgb32f", "length"):
+        cases.append(("out->prev_xy == out->%s" % k, ERR_ARG, dict(alias=("prev_xy", "out", k))))
+    cases.append(("n_frames * n_prims * 12 = 2^31", ERR_LIMIT, dict(n_prims=(1 << 31) // 12 + 1)))
+    cases.append(("n_frames * n_prims = 2^32 - 1", ERR_LIMIT, dict(n_prims=(1 << 32) - 1)))
+    # inherited
+    cases += [("params NULL", ERR_ARG, dict(params=None)), ("frames NULL", ERR_ARG, dict(frames=False)), ("out NULL", ERR_ARG, dict(out=False))]
+    for k in ("rgb32f", "depth", "normal", "cams"):
+        cases.append(("frames->%s NULL" % k, ERR_ARG, dict(frames_null=k)))
+    for k in ("rgb32f", "depth", "normal", "length", "cam"):
+        cases.append(("history->%s NULL" % k, ERR_ARG, dict(history_null=k)))
+    cases.append(("every output NULL", ERR_ARG, dict(out_planes=(False, False, False))))
+    for bad in ((0, 3, 1), (5, 0, 1), (5, 3, 0), (-5, 3, 1)):
+        cases.append(("shape %s" % (bad,), ERR_ARG, dict(params=bad + good[3:])))
+    for field, values in ((3, (0.0, -1.0, np.inf, np.nan)), (4, (-1.5, 1.5, np.nan, np.inf)), (5, (0.5, 0.0, -2.0, np.inf, np.nan))):
+        for v in values:
+            cases.append(("params[%d] = %r" % (field, v), ERR_ARG, dict(params=good[:field] + (v,) + good[field + 1:])))
+    for where in ("frames", "history", "out"):
+        for v in (2, -1):
+            cases.append(("%s->memory = %d" % (where, v), ERR_ARG, dict(memory={where: v})))
+    cases.append(("a camera of another resolution", ERR_ARG, dict(cam_res=(6, 3))))
+    cases.append(("the history's camera of another resolution", ERR_ARG, dict(hist_cam_res=(5, 4))))
+    for o in ("rgb32f", "length"):
+        for k in ("depth", "normal", "hit_id"):
+            cases.append(("out->%s == frames->%s" % (o, k), ERR_ARG, dict(alias=(o, "frames", k))))
+        for k in ("rgb32f", "depth", "normal", "length", "hit_id"):
+            cases.append(("out->%s == history->%s" % (o, k), ERR_ARG, dict(alias=(o, "history", k))))
+    cases.append(("out->length == frames->rgb32f", ERR_ARG, dict(alias=("length", "frames", "rgb32f"))))
+    cases.append(("out->rgb32f == out->length", ERR_ARG, dict(alias=("length", "out", "rgb32f"))))
+    cases.append(("46341 x 46341", ERR_LIMIT, dict(params=(46341, 46341, 1) + good[3:])))
+    cases.append(("2 x 2 x 2^30", ERR_LIMIT, dict(params=(2, 2, 1 << 30) + good[3:])))
+    return cases
+
+
+def make_call(entry):
+    """call(**changes) -> (the status of `entry` on a good 5 x 3 request with the changes of refusal_cases() applied, whether
+    every array of the request -- the outputs above all -- still holds what it held)."""
+    seq = M.make_sequence(5, 3, 1, seed=7, history=True)
+    hist = seq["history"]
+    outs = dict(rgb32f=np.full((3, 5, 3), 7.25, F), length=np.full((3, 5), 7.25, F), prev_xy=np.full((3, 5, 2), 7.25, F))
+
+    def call(params=(5, 3, 1, 0.1, 0.8, 4.0), frames=True, out=True, motion=True, frames_null=None, history_null=None, motion_null=None,
+             out_planes=(True, True, True), memory={}, cam_res=None, hist_cam_res=None, alias=None, n_prims=4, kind=None):
+        cam, hcam = (api.Camera * 1)(seq["cams"][0]), (api.Camera * 1)(hist["cam"])
+        if cam_res:
+            cam[0].res_x, cam[0].res_y = cam_res
+        if hist_cam_res:
+            hcam[0].res_x, hcam[0].res_y = hist_cam_res
+        kinds = seq["prim_type"].copy()
+        if kind is not None:
+            kinds[2] = kind
+        arrays = [seq[k] for k in ("rgb32f", "depth", "normal", "hit_id", "prim_data")] + [hist[k] for k in ("rgb32f", "depth", "normal", "length", "hit_id", "prim_data")]
+        before = [a.copy() for a in arrays]
+        ptr = dict(frames={k: seq[k].ctypes.data for k in ("rgb32f", "depth", "normal", "hit_id")},
+                   history={k: hist[k].ctypes.data for k in ("rgb32f", "depth", "normal", "length", "hit_id")},
+                   motion=dict(prim_type=kinds.ctypes.data, prim_data=seq["prim_data"].ctypes.data, history_prim_data=hist["prim_data"].ctypes.data),
+                   out={k: outs[k].ctypes.data if on else None for k, on in zip(("rgb32f", "length", "prev_xy"), out_planes)})
+        ptr["frames"]["cams"], ptr["history"]["cam"] = cam, hcam
+        for group, name in (("frames", frames_null), ("history", history_null), ("motion", motion_null)):
+            if name:
+                ptr[group][name] = None
+        if alias:
+            ptr["out"][alias[0]] = ptr[alias[1]][alias[2]]
+        fr = api.AccumulateFrames(*[ptr["frames"][k] for k in ("rgb32f", "depth", "normal", "hit_id", "cams")], memory.get("frames", 0))
+        hi = api.AccumulateHistory(*[ptr["history"][k] for k in ("rgb32f", "depth", "normal", "length", "hit_id", "cam")], memory.get("history", 0))
+        mo = api.AccumulateMotion(n_prims, *[ptr["motion"][k] for k in ("prim_type", "prim_data", "history_prim_data")], memory.get("motion", 0))
+        o = api.AccumulateMovingOutputs(*[ptr["out"][k] for k in ("rgb32f", "length", "prev_xy")], memory.get("out", 0))
+        p = api.AccumulateParams(*params) if params is not None else None
+        rc = entry(C.byref(p) if p else None, C.byref(fr) if frames else None, C.byref(hi), C.byref(mo) if motion else None, C.byref(o) if out else None)
+        untouched = all((v == 7.25).all() for v in outs.values()) and all(np.array_equal(a, b, equal_nan=True) for a, b in zip(arrays, before))
+        return rc, untouched
+
+    return call
+
+
+@pytest.mark.parametrize("name,status,change", refusal_cases(), ids=[c[0] for c in refusal_cases()])
+def test_every_refusal_by_status_code_without_a_device(name, status, change):
+    L = P.lib()
+    call = make_call(lambda p, fr, hi, mo, o: L.p3d_debug_accumulate_moving(0, p, fr, hi, mo, o))
+    rc, untouched = call(**change)
+    assert rc == status, name
+    assert untouched, "a refused call wrote something"
+    assert L.p3d_last_error(), "every refusal has a text"
+    if status == ERR_LIMIT:
+        assert b"31 bits" in L.p3d_last_error()
+
+
+def test_a_null_scene_is_refused():
+    L = P.lib()
+    call = make_call(lambda p, fr, hi, mo, o: L.p3d_accumulate_moving(None, p, fr, hi, mo, o))
+    rc, untouched = call()
+    assert rc == ERR_ARG and b"scene" in L.p3d_last_error() and untouched

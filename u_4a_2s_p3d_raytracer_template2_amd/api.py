@@ -140,6 +140,17 @@ class AccumulateOutputs(C.Structure):
     _fields_ = [("rgb32f", C.c_void_p), ("length", C.c_void_p), ("memory", C.c_int32)]
 
 
+class AccumulateMotion(C.Structure):
+    """p3d_accumulate_motion: the kinds of n_prims primitives, the [n_frames][n_prims][12] records the frames were rendered with
+    and the [n_prims][12] records the history was rendered with (the form DeviceScene.update takes), host (memory 0) or device (1)."""
+    _fields_ = [("n_prims", C.c_uint32), ("prim_type", C.c_void_p), ("prim_data", C.c_void_p), ("history_prim_data", C.c_void_p),
+                ("memory", C.c_int32)]
+
+
+class AccumulateMovingOutputs(C.Structure):
+    _fields_ = [("rgb32f", C.c_void_p), ("length", C.c_void_p), ("prev_xy", C.c_void_p), ("memory", C.c_int32)]
+
+
 # p3d_accumulate's defaults: conveniences, not measured
 ACCUMULATE_DEPTH_TOLERANCE = 0.05
 ACCUMULATE_NORMAL_MIN = 0.9
@@ -197,9 +208,9 @@ class SceneStats(C.Structure):
 
 # every symbol include/p3d_hip.h declares (tests check that the library exports them all)
 C_ABI_SYMBOLS = ["p3d_abi_version", "p3d_last_error", "p3d_device_count", "p3d_scene_create",
-                 "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_scene_update", "p3d_scene_rebuild", "p3d_scene_rebuild_with", "p3d_scene_last_builder", "p3d_scene_tree_cost", "p3d_scene_build_grid", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_render_aov", "p3d_generate_samples", "p3d_trace_rays", "p3d_occluded", "p3d_denoise", "p3d_accumulate", "p3d_ambient_occlusion", "p3d_sync",
+                 "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_scene_update", "p3d_scene_rebuild", "p3d_scene_rebuild_with", "p3d_scene_last_builder", "p3d_scene_tree_cost", "p3d_scene_build_grid", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_render_aov", "p3d_generate_samples", "p3d_trace_rays", "p3d_occluded", "p3d_denoise", "p3d_accumulate", "p3d_accumulate_moving", "p3d_ambient_occlusion", "p3d_sync",
                  "p3d_get_counters", "p3d_get_profile", "p3d_last_schedule", "p3d_set_tuning", "p3d_set_primary_tiles", "p3d_last_primary_tiles", "p3d_set_sky_tiles", "p3d_last_sky_tiles", "p3d_set_stream", "p3d_timer_begin", "p3d_timer_end", "p3d_deinterleave_frames",
-                 "p3d_deinterleave", "p3d_debug_intersect", "p3d_debug_powf", "p3d_debug_pow", "p3d_debug_schlick_kr", "p3d_debug_check_rcp", "p3d_debug_check_rcp_len", "p3d_debug_lbvh_build", "p3d_debug_ploc_build", "p3d_debug_grid_build", "p3d_debug_rand", "p3d_debug_sample_stream", "p3d_debug_denoise", "p3d_debug_accumulate", "p3d_tune_schedule", "p3d_debug_set_stamps", "p3d_debug_set_stamp_level",
+                 "p3d_deinterleave", "p3d_debug_intersect", "p3d_debug_powf", "p3d_debug_pow", "p3d_debug_schlick_kr", "p3d_debug_check_rcp", "p3d_debug_check_rcp_len", "p3d_debug_lbvh_build", "p3d_debug_ploc_build", "p3d_debug_grid_build", "p3d_debug_rand", "p3d_debug_sample_stream", "p3d_debug_denoise", "p3d_debug_accumulate", "p3d_debug_accumulate_moving", "p3d_tune_schedule", "p3d_debug_set_stamps", "p3d_debug_set_stamp_level",
                  "p3d_comm_unique_id", "p3d_comm_create", "p3d_comm_create_all", "p3d_comm_destroy", "p3d_comm_info",
                  "p3d_gather", "p3d_gather_all", "p3d_device_alloc", "p3d_device_free", "p3d_upload", "p3d_download"]
 
@@ -261,6 +272,11 @@ def lib():
     L.p3d_debug_accumulate.argtypes = [C.c_int] + _acc + [C.POINTER(AccumulateOutputs)]
     L.p3dh_accumulate.argtypes = _acc + [C.c_void_p, C.c_void_p]
     L.p3dh_accumulate.restype = None
+    _mov = _acc + [C.POINTER(AccumulateMotion)]
+    L.p3d_accumulate_moving.argtypes = [C.c_void_p] + _mov + [C.POINTER(AccumulateMovingOutputs)]
+    L.p3d_debug_accumulate_moving.argtypes = [C.c_int] + _mov + [C.POINTER(AccumulateMovingOutputs)]
+    L.p3dh_accumulate_moving.argtypes = _mov + [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.p3dh_accumulate_moving.restype = None
     L.p3d_ambient_occlusion.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.POINTER(RenderParams), C.POINTER(AoParams),
                                         C.POINTER(AoInputs), C.POINTER(AoOutputs)]
     L.p3dh_ao_segments.argtypes = [C.POINTER(AoParams), C.POINTER(Camera), C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 5
@@ -904,6 +920,37 @@ class DeviceScene:
         o = AccumulateOutputs(out_rgb32f_ptr or None, out_length_ptr or None, 1)
         _check(lib().p3d_accumulate(self.h, C.byref(p), C.byref(fr), C.byref(hi) if hi else None, C.byref(o)), "p3d_accumulate")
 
+    def accumulate_moving(self, rgb32f, depth, normal, cams, hit_id, prim_type, prim_data, history=None, prev_xy=True, **kw):
+        """p3d_accumulate_moving on host arrays: DeviceScene.accumulate for a sequence whose primitives moved between the frames.
+        hit_id is needed; prim_type (n_prims,) and prim_data (n, n_prims, 12) or (n_prims, 12) are the geometry every frame was
+        rendered with, as DeviceScene.update takes it; a history also carries prim_data, the (n_prims, 12) records it was
+        rendered with.  Returns {"rgb32f", "length"} and, with prev_xy, "prev_xy" (n, H, W, 2): where each pixel's surface
+        point was in the frame before (NaN where there is none)."""
+        p, fr, hi, mo, out, keep = _accumulate_moving_request(rgb32f, depth, normal, cams, hit_id, prim_type, prim_data, history, prev_xy, **kw)
+        o = AccumulateMovingOutputs(out["rgb32f"].ctypes.data, out["length"].ctypes.data, out["prev_xy"].ctypes.data if prev_xy else None, 0)
+        _check(lib().p3d_accumulate_moving(self.h, C.byref(p), C.byref(fr), C.byref(hi) if hi else None, C.byref(mo), C.byref(o)),
+               "p3d_accumulate_moving")
+        return out
+
+    def accumulate_moving_device(self, res_x, res_y, cams, rgb32f_ptr, depth_ptr, normal_ptr, hit_ptr, n_prims, prim_type_ptr, prim_data_ptr,
+                                 out_rgb32f_ptr=0, out_length_ptr=0, out_prev_xy_ptr=0, history=None,
+                                 depth_tolerance=ACCUMULATE_DEPTH_TOLERANCE, normal_min=ACCUMULATE_NORMAL_MIN, max_history=ACCUMULATE_MAX_HISTORY):
+        """Enqueue p3d_accumulate_moving on caller-owned DEVICE buffers (raw pointers; 0 = no such plane) holding len(cams)
+        frames and their geometry; asynchronous on the scene's stream.  history: None, or a dict of device pointers rgb32f,
+        depth, normal, length, prim_data (optionally hit_id) and the host Camera cam.  out_rgb32f_ptr may equal rgb32f_ptr."""
+        arr, n = _camera_array(cams)
+        p = AccumulateParams(int(res_x), int(res_y), n, depth_tolerance, normal_min, max_history)
+        fr = AccumulateFrames(rgb32f_ptr or None, depth_ptr or None, normal_ptr or None, hit_ptr or None, arr, 1)
+        hi = None
+        if history is not None:
+            hcam = (Camera * 1)(history["cam"])
+            hi = AccumulateHistory(history["rgb32f"] or None, history["depth"] or None, history["normal"] or None, history["length"] or None,
+                                   history.get("hit_id") or None, hcam, 1)
+        mo = AccumulateMotion(int(n_prims), prim_type_ptr or None, prim_data_ptr or None, (history or {}).get("prim_data") or None, 1)
+        o = AccumulateMovingOutputs(out_rgb32f_ptr or None, out_length_ptr or None, out_prev_xy_ptr or None, 1)
+        _check(lib().p3d_accumulate_moving(self.h, C.byref(p), C.byref(fr), C.byref(hi) if hi else None, C.byref(mo), C.byref(o)),
+               "p3d_accumulate_moving")
+
     def ambient_occlusion(self, cam_or_cams, depth, normal, rgb32f=None, samples=AO_SAMPLES, radius=AO_RADIUS, bias=AO_BIAS, seed=0,
                           accel=ACCEL_BVH, no_lds=False, private_walk=False, want=("ao", "rgb32f")):
         """p3d_ambient_occlusion on host arrays: depth (n, H, W) or (H, W) and normal (n, H, W, 3) or (H, W, 3) as render_aov
@@ -1173,6 +1220,47 @@ def debug_accumulate(rgb32f, depth, normal, cams, hit_id=None, history=None, dev
     p, fr, hi, out, keep = _accumulate_request(rgb32f, depth, normal, cams, hit_id, history, **kw)
     o = AccumulateOutputs(out["rgb32f"].ctypes.data, out["length"].ctypes.data, 0)
     _check(lib().p3d_debug_accumulate(int(device), C.byref(p), C.byref(fr), C.byref(hi) if hi else None, C.byref(o)), "p3d_debug_accumulate")
+    return out
+
+
+def _accumulate_moving_request(rgb32f, depth, normal, cams, hit_id, prim_type, prim_data, history=None, prev_xy=True, **kw):
+    """_accumulate_request and the geometry -> (params, frames, history or None, AccumulateMotion, the zeroed outputs {"rgb32f",
+    "length"[, "prev_xy"]}, what must stay alive)."""
+    if hit_id is None:
+        raise ValueError("accumulate_moving needs hit_id: the motion is looked up by it")
+    p, fr, hi, out, keep = _accumulate_request(rgb32f, depth, normal, cams, hit_id, history, **kw)
+    kind = np.ascontiguousarray(prim_type, np.uint32).reshape(-1)
+    n_prims = kind.size
+    data = np.ascontiguousarray(prim_data, np.float32)
+    if data.size != p.n_frames * n_prims * 12:
+        raise ValueError("prim_data must hold 12 floats per primitive and frame: (%d, %d, 12)" % (p.n_frames, n_prims))
+    hdata = None
+    if history is not None:
+        hdata = np.ascontiguousarray(history["prim_data"], np.float32)
+        if hdata.size != n_prims * 12:
+            raise ValueError("the history's prim_data must be (%d, 12)" % n_prims)
+    mo = AccumulateMotion(n_prims, kind.ctypes.data, data.ctypes.data, None if hdata is None else hdata.ctypes.data, 0)
+    if prev_xy:
+        out["prev_xy"] = np.zeros(out["length"].shape + (2,), np.float32)
+    return p, fr, hi, mo, out, keep + [kind, data, hdata]
+
+
+def host_accumulate_moving(rgb32f, depth, normal, cams, hit_id, prim_type, prim_data, history=None, prev_xy=True, **kw):
+    """p3dh_accumulate_moving: the host layer's restatement of p3d_accumulate_moving, every bit of it, on host arrays (no GPU).
+    Arguments and result as DeviceScene.accumulate_moving."""
+    p, fr, hi, mo, out, keep = _accumulate_moving_request(rgb32f, depth, normal, cams, hit_id, prim_type, prim_data, history, prev_xy, **kw)
+    lib().p3dh_accumulate_moving(C.byref(p), C.byref(fr), C.byref(hi) if hi else None, C.byref(mo), out["rgb32f"].ctypes.data,
+                                 out["length"].ctypes.data, out["prev_xy"].ctypes.data if prev_xy else None)
+    return out
+
+
+def debug_accumulate_moving(rgb32f, depth, normal, cams, hit_id, prim_type, prim_data, history=None, prev_xy=True, device=0, **kw):
+    """p3d_debug_accumulate_moving: the launches of p3d_accumulate_moving over host arrays, without a scene.  Arguments and result
+    as DeviceScene.accumulate_moving."""
+    p, fr, hi, mo, out, keep = _accumulate_moving_request(rgb32f, depth, normal, cams, hit_id, prim_type, prim_data, history, prev_xy, **kw)
+    o = AccumulateMovingOutputs(out["rgb32f"].ctypes.data, out["length"].ctypes.data, out["prev_xy"].ctypes.data if prev_xy else None, 0)
+    _check(lib().p3d_debug_accumulate_moving(int(device), C.byref(p), C.byref(fr), C.byref(hi) if hi else None, C.byref(mo), C.byref(o)),
+           "p3d_debug_accumulate_moving")
     return out
 
 

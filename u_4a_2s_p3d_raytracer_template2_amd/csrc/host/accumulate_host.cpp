@@ -1,9 +1,11 @@
-// accumulate_host.cpp -- the reprojection of p3d_accumulate in plain loops on the host: DESIGN "Temporal accumulation" read
-// operation by operation, float arithmetic without contraction (HFLAGS: -ffp-contract=off).  What the device kernel
-// (../accumulate.hip) is compared against, bit for bit; it shares no code with it.
+// accumulate_host.cpp -- the reprojection of p3d_accumulate and of p3d_accumulate_moving in plain loops on the host: DESIGN
+// "Temporal accumulation" and "Accumulation through moved primitives" read operation by operation, float arithmetic without
+// contraction (HFLAGS: -ffp-contract=off).  What the device kernels (../accumulate.hip, ../accumulate_motion.hip) are compared
+// against, bit for bit; it shares no code with them.
 #include "accumulate_host.h"
 
 #include <cmath>
+#include <cstring>
 #include <vector>
 
 namespace p3d_host {
@@ -19,9 +21,64 @@ struct Previous {
     const p3d_camera* cam;
 };
 
-// one frame: C, Z, N, I its planes; prev NULL for a frame with nothing to look back at.  out_c may be C.
+// the geometry of p3d_accumulate_moving for one frame: the records it was rendered with and those of the frame it looks back at
+struct Moved {
+    uint32_t n_prims;
+    const uint32_t* type;
+    const float *cur, *prev;        // [n_prims][12]
+};
+
+inline float dot3(const float* p, const float* q) { return (p[0] * q[0] + p[1] * q[1]) + p[2] * q[2]; }
+inline bool same_words(const float* a, const float* b, int n) { return std::memcmp(a, b, 4 * (size_t)n) == 0; }
+
+// P_prev of p3d_accumulate_moving for the point P on primitive I: written to Q.  false: a changed plane, no history.
+bool previous_point(const Moved& m, int32_t I, const float* P, float* Q) {
+    for (int k = 0; k < 3; k++) Q[k] = P[k];
+    if (I < 0 || (uint32_t)I >= m.n_prims) return true;
+    const float *a = m.cur + 12 * (size_t)I, *b = m.prev + 12 * (size_t)I;
+    switch (m.type[I]) {
+    case P3D_SPHERE: {
+        if (same_words(a, b, 4)) return true;
+        const float s = b[3] / a[3];
+        for (int k = 0; k < 3; k++) { const float t = (P[k] - a[k]) * s; Q[k] = b[k] + t; }
+        return true;
+    }
+    case P3D_TRIANGLE: {
+        if (same_words(a, b, 9)) return true;
+        float e1[3], e2[3], w[3];
+        for (int k = 0; k < 3; k++) { e1[k] = a[3 + k] - a[k]; e2[k] = a[6 + k] - a[k]; w[k] = P[k] - a[k]; }
+        const float d11 = dot3(e1, e1), d12 = dot3(e1, e2), d22 = dot3(e2, e2), w1 = dot3(w, e1), w2 = dot3(w, e2);
+        const float m1 = d11 * d22, m2 = d12 * d12;
+        const float den = m1 - m2;
+        const float b1 = d22 * w1, b2 = d12 * w2, g1 = d11 * w2, g2 = d12 * w1;
+        const float beta = (b1 - b2) / den, gamma = (g1 - g2) / den;
+        for (int k = 0; k < 3; k++) {
+            const float f1 = b[3 + k] - b[k], f2 = b[6 + k] - b[k];
+            const float t1 = f1 * beta, t2 = f2 * gamma;
+            const float u = b[k] + t1;
+            Q[k] = u + t2;
+        }
+        return true;
+    }
+    case P3D_BOX: {
+        if (same_words(a, b, 6)) return true;
+        for (int k = 0; k < 3; k++) {
+            const float e = a[3 + k] - a[k];
+            const float t = e != 0.0f ? (P[k] - a[k]) / e : 0.0f;
+            const float u = (b[3 + k] - b[k]) * t;
+            Q[k] = b[k] + u;
+        }
+        return true;
+    }
+    default:
+        return same_words(a, b, 4);
+    }
+}
+
+// one frame: C, Z, N, I its planes; prev NULL for a frame with nothing to look back at.  out_c may be C.  moved: NULL for
+// p3d_accumulate; else I is not NULL and out_xy (or NULL) receives p3d_accumulate_moving's prev_xy.
 void accumulate_frame(const p3d_accumulate_params& p, const p3d_camera& cam, const float* C, const float* Z, const float* N,
-                      const int32_t* I, const Previous* prev, float* out_c, float* out_l) {
+                      const int32_t* I, const Previous* prev, float* out_c, float* out_l, const Moved* moved = nullptr, float* out_xy = nullptr) {
     const int W = p.res_x, H = p.res_y;
     const float rx = (float)W, ry = (float)H;
     float uw[3], vh[3], vz[3];
@@ -31,6 +88,9 @@ void accumulate_frame(const p3d_accumulate_params& p, const p3d_camera& cam, con
             const size_t pi = (size_t)y * W + x;
             const float c0[3] = {C[3 * pi], C[3 * pi + 1], C[3 * pi + 2]};
             float o[3] = {c0[0], c0[1], c0[2]}, len = 1.0f;
+            float xy[2];
+            const uint32_t quiet_nan[2] = {0x7FC00000u, 0x7FC00000u};
+            std::memcpy(xy, quiet_nan, sizeof xy);
             [&] {
                 if (!prev) return;
                 const float z = Z[pi];
@@ -42,7 +102,10 @@ void accumulate_frame(const p3d_accumulate_params& p, const p3d_camera& cam, con
                 for (int k = 0; k < 3; k++) { const float vx = uw[k] * fx, vy = vh[k] * fy; const float t = vx + vy; D[k] = t + vz[k]; }
                 const float s0 = D[0] * D[0], s1 = D[1] * D[1], s2 = D[2] * D[2];
                 const float l = 1.0f / std::sqrt((s0 + s1) + s2);
-                for (int k = 0; k < 3; k++) { d[k] = D[k] * l; const float t = d[k] * z; P[k] = cam.eye[k] + t; q[k] = P[k] - pc.eye[k]; }
+                for (int k = 0; k < 3; k++) { d[k] = D[k] * l; const float t = d[k] * z; P[k] = cam.eye[k] + t; }
+                float Q[3] = {P[0], P[1], P[2]};
+                if (moved && !previous_point(*moved, I[pi], P, Q)) return;
+                for (int k = 0; k < 3; k++) q[k] = Q[k] - pc.eye[k];
                 // 2. the projection into the previous camera
                 const float a = (q[0] * pc.u[0] + q[1] * pc.u[1]) + q[2] * pc.u[2];
                 const float b = (q[0] * pc.v[0] + q[1] * pc.v[1]) + q[2] * pc.v[2];
@@ -52,6 +115,7 @@ void accumulate_frame(const p3d_accumulate_params& p, const p3d_camera& cam, con
                 const float gx = a / (pc.w * s), gy = b / (pc.h * s);
                 const float px = (gx + 0.5f) * rx - 0.5f, py = (gy + 0.5f) * ry - 0.5f;
                 if (!(px > -1.0f && px < rx && py > -1.0f && py < ry)) return;
+                xy[0] = px; xy[1] = py;
                 const float x0f = std::floor(px), y0f = std::floor(py);
                 const float tx = px - x0f, ty = py - y0f;
                 const long x0 = (long)x0f, y0 = (long)y0f;
@@ -89,14 +153,18 @@ void accumulate_frame(const p3d_accumulate_params& p, const p3d_camera& cam, con
             }();
             if (out_c) { out_c[3 * pi] = o[0]; out_c[3 * pi + 1] = o[1]; out_c[3 * pi + 2] = o[2]; }
             if (out_l) out_l[pi] = len;
+            if (out_xy) { out_xy[2 * pi] = xy[0]; out_xy[2 * pi + 1] = xy[1]; }
         }
     }
 }
 
 }  // namespace
 
-void accumulate(const p3d_accumulate_params& p, const p3d_accumulate_frames& fr, const p3d_accumulate_history* history,
-                float* out_rgb32f, float* out_length) {
+namespace {
+
+// both entries: motion NULL for accumulate()
+void accumulate_sequence(const p3d_accumulate_params& p, const p3d_accumulate_frames& fr, const p3d_accumulate_history* history,
+                         const p3d_accumulate_motion* motion, float* out_rgb32f, float* out_length, float* out_prev_xy) {
     const size_t frame = (size_t)p.res_x * (size_t)p.res_y;
     // an output the caller does not want is still what the next frame looks back at
     std::vector<float> own_c(out_rgb32f ? 0 : 3 * frame * p.n_frames), own_l(out_length ? 0 : frame * p.n_frames);
@@ -112,9 +180,29 @@ void accumulate(const p3d_accumulate_params& p, const p3d_accumulate_frames& fr,
             prev = {history->rgb32f, history->depth, history->normal, history->length, history->hit_id, history->cam};
             pp = &prev;
         }
+        Moved moved, *mp = nullptr;
+        if (motion) {
+            const size_t records = 12 * (size_t)motion->n_prims;
+            moved = {motion->n_prims, motion->prim_type, motion->prim_data + f * records,
+                     f > 0 ? motion->prim_data + (f - 1) * records : motion->history_prim_data};
+            mp = &moved;
+        }
         accumulate_frame(p, fr.cams[f], fr.rgb32f + 3 * f * frame, fr.depth + f * frame, fr.normal + 3 * f * frame,
-                         fr.hit_id ? fr.hit_id + f * frame : nullptr, pp, oc + 3 * f * frame, ol + f * frame);
+                         fr.hit_id ? fr.hit_id + f * frame : nullptr, pp, oc + 3 * f * frame, ol + f * frame, mp,
+                         out_prev_xy ? out_prev_xy + 2 * f * frame : nullptr);
     }
+}
+
+}  // namespace
+
+void accumulate(const p3d_accumulate_params& p, const p3d_accumulate_frames& fr, const p3d_accumulate_history* history,
+                float* out_rgb32f, float* out_length) {
+    accumulate_sequence(p, fr, history, nullptr, out_rgb32f, out_length, nullptr);
+}
+
+void accumulate_moving(const p3d_accumulate_params& p, const p3d_accumulate_frames& fr, const p3d_accumulate_history* history,
+                       const p3d_accumulate_motion& motion, float* out_rgb32f, float* out_length, float* out_prev_xy) {
+    accumulate_sequence(p, fr, history, &motion, out_rgb32f, out_length, out_prev_xy);
 }
 
 }  // namespace p3d_host

@@ -14,5 +14,10 @@ namespace p3d_host {
 void accumulate(const p3d_accumulate_params& p, const p3d_accumulate_frames& frames, const p3d_accumulate_history* history,
                 float* out_rgb32f, float* out_length);
 
+// p3d_accumulate_moving likewise: motion as the entry reads it (host arrays; the caller has checked it, frames.hit_id is
+// not NULL).  out_prev_xy holds n_frames frames of 2 floats per pixel and may be NULL like the other two.
+void accumulate_moving(const p3d_accumulate_params& p, const p3d_accumulate_frames& frames, const p3d_accumulate_history* history,
+                       const p3d_accumulate_motion& motion, float* out_rgb32f, float* out_length, float* out_prev_xy);
+
 }  // namespace p3d_host
 #endif

@@ -128,6 +128,13 @@ void p3dh_accumulate(const p3d_accumulate_params* params, const p3d_accumulate_f
     accumulate(*params, *frames, history, out_rgb32f, out_length);
 }
 
+// accumulate_moving() of the host layer: p3d_accumulate_moving's result on host planes and host geometry, every bit.  history
+// may be NULL; the three outputs may each be NULL.  The caller keeps the arguments inside what p3d_accumulate_moving accepts.
+void p3dh_accumulate_moving(const p3d_accumulate_params* params, const p3d_accumulate_frames* frames, const p3d_accumulate_history* history,
+                            const p3d_accumulate_motion* motion, float* out_rgb32f, float* out_length, float* out_prev_xy) {
+    accumulate_moving(*params, *frames, history, *motion, out_rgb32f, out_length, out_prev_xy);
+}
+
 // tile_coverage() of the host layer (tile_coverage_host.cpp): the level-1 launch's tile coverage mask for cam's frame over a
 // scene description, the statements of csrc/p3d_tile_coverage.h.  active_out [tiles_y][tiles_x] bytes; returns 1 when every
 // tile was marked because a primitive asked for it.

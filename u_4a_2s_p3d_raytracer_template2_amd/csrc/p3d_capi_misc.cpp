@@ -427,4 +427,37 @@ int p3d_debug_accumulate(int device, const p3d_accumulate_params* params, const 
     });
 }
 
+int p3d_debug_accumulate_moving(int device, const p3d_accumulate_params* params, const p3d_accumulate_frames* frames,
+                                const p3d_accumulate_history* history, const p3d_accumulate_motion* motion,
+                                const p3d_accumulate_moving_outputs* out) {
+    const char* why = "";
+    if (const int rc = accumulate_moving_check_request(params, frames, history, motion, out, &why)) return fail(rc, why);
+    if (frames->memory != 0 || (history && history->memory != 0) || motion->memory != 0 || out->memory != 0)
+        return fail(P3D_ERR_ARG, "p3d_debug_accumulate_moving takes host planes: every memory field must be 0");
+    const size_t fr = (size_t)params->res_x * (size_t)params->res_y, px = fr * (size_t)params->n_frames, prims = motion->n_prims;
+    const bool many = params->n_frames > 1;
+    const p3d_accumulate_history none = {};
+    const p3d_accumulate_history& h = history ? *history : none;
+    // a plane that is not there (or a spare that is not needed) is one byte that nothing touches
+    DebugArg a[17] = {{frames->rgb32f, nullptr, px * 12}, {frames->depth, nullptr, px * 4}, {frames->normal, nullptr, px * 12},
+                      {frames->hit_id, nullptr, px * 4},
+                      {h.rgb32f, nullptr, history ? fr * 12 : 1}, {h.depth, nullptr, history ? fr * 4 : 1}, {h.normal, nullptr, history ? fr * 12 : 1},
+                      {h.length, nullptr, history ? fr * 4 : 1}, {h.hit_id, nullptr, h.hit_id ? fr * 4 : 1},
+                      {nullptr, out->rgb32f, out->rgb32f ? px * 12 : 1}, {nullptr, out->length, out->length ? px * 4 : 1},
+                      {nullptr, nullptr, many && !out->rgb32f ? 2 * fr * 12 : 1}, {nullptr, nullptr, many && !out->length ? 2 * fr * 4 : 1},
+                      {motion->prim_type, nullptr, prims * 4}, {motion->prim_data, nullptr, prims * 48 * (size_t)params->n_frames},
+                      {history ? motion->history_prim_data : nullptr, nullptr, history ? prims * 48 : 1},
+                      {nullptr, out->prev_xy, out->prev_xy ? px * 8 : 1}};
+    return debug_run("p3d_debug_accumulate_moving", device, a, [&] {
+        const AccumulatePlanes P = {a[0].as<float>(), a[1].as<float>(), a[2].as<float>(), a[3].as<int32_t>(),
+                                    history ? a[4].as<float>() : nullptr, a[5].as<float>(), a[6].as<float>(), a[7].as<float>(),
+                                    h.hit_id ? a[8].as<int32_t>() : nullptr,
+                                    out->rgb32f ? a[9].as<float>() : nullptr, out->length ? a[10].as<float>() : nullptr,
+                                    a[11].as<float>(), a[12].as<float>()};
+        const AccumulateMotion M = {motion->n_prims, a[13].as<uint32_t>(), a[14].as<float>(), history ? a[15].as<float>() : nullptr,
+                                    out->prev_xy ? a[16].as<float>() : nullptr};
+        return launch_accumulate_moving(*params, P, M, frames->cams, h.cam, nullptr);
+    });
+}
+
 }  // extern "C"

@@ -240,6 +240,7 @@ struct p3d_scene {
         p3d::RawBuf in_rgb32f, in_depth, in_normal, in_hit_id;
         p3d::RawBuf hist_rgb32f, hist_depth, hist_normal, hist_length, hist_hit_id;
         p3d::RawBuf out_rgb32f, out_length, spare_rgb32f, spare_length;
+        p3d::RawBuf motion_type, motion_data, motion_hist, out_prev_xy;      // p3d_accumulate_moving: host geometry and the host prev_xy plane
     } accumulate;
     // p3d_ambient_occlusion: the staging of host planes and the frames' cameras (FrameCam records, written on the stream
     // by every call: launch_frame_cams); all counted in device_bytes as they grow.  Apart from the frames' frame_cams.
