@@ -622,6 +622,46 @@ typedef struct p3d_denoise_inputs { const float *rgb32f, *depth, *normal, *albed
  *    p3d_last_schedule(), p3d_last_primary_tiles() and the ray-stream state are what they were. */
 int p3d_denoise(p3d_scene* scene, const p3d_denoise_params* params, const p3d_denoise_inputs* in, const p3d_outputs* out);
 
+/* p3d_denoise steered by a variance plane (SVGF, Schied et al. 2017): the colour stop of a pixel is as wide as the standard
+ * deviation of its luminance says it is still noisy, and closes where the pixel has converged.  The variance is any
+ * non-negative estimate of the luminance's variance per pixel -- over the frames a pixel has accumulated, or over its
+ * neighbours. */
+typedef struct p3d_denoise_variance_inputs { const float *rgb32f, *depth, *normal, *albedo, *variance; int32_t memory; } p3d_denoise_variance_inputs;
+typedef struct p3d_denoise_variance_outputs { uint8_t* rgb8; float* rgb32f; float* variance; int32_t memory; } p3d_denoise_variance_outputs;
+/* The result is DEFINED, as p3d_denoise's is: float32 IEEE-754 basic operations in a fixed order (no fused multiply-add,
+ * correctly rounded division and square root, no exp and no pow); the device, the host layer (p3dh_denoise_variance) and
+ * tests/denoise_variance_reference.py agree on it in every bit.
+ *  - params: p3d_denoise's, with one difference: sigma_color must be finite and > 0.  It is the width of the colour stop in
+ *    standard deviations of the luminance, not an absolute luminance, and it is NOT halved per pass.
+ *  - planes: p3d_denoise's, and the variance V: [n_frames][res_y][res_x] floats, one per pixel.  in->variance is needed;
+ *    out->rgb8, out->rgb32f and out->variance may each be NULL.
+ *  - the filter: pass i (0 <= i < iterations) has step s = 2^i and reads the colour C and the variance V of the previous
+ *    pass (pass 0 the inputs).  Everything of p3d_denoise's definition holds -- validity, k1, inv_a, inv_z, lum, the 25 taps
+ *    dy outer and dx inner, h, wz, wn, wa -- with these changes for a VALID centre p:
+ *      the prefiltered variance: the taps (x + dx, y + dy), dy = -1..1 (outer), dx = -1..1 (inner), at stride 1 whatever
+ *        s, with k = k2[|dx|] * k2[|dy|], k2 = {0.5, 0.25}; a tap outside the frame or not valid contributes nothing; for
+ *        the others sg += k * V_q (a product, then a sum), sk += k.  g = sg / sk, then g = g > 0 ? g : 0.
+ *      inv_c = 1 / (sigma_color * sqrt(g) + 0x1p-20f): a product, a sum, a division.  It is always finite, and a pixel with
+ *        no variance stops at a luminance difference of 2^-20.
+ *      wc = tc * tc,  tc = max(0, 1 - |lum(C_q) - lum(C_p)| * inv_c), always
+ *      w  = ((h * wz) * wn) * wa, then w = w * wc;  sum += w * C_q per channel;  sw += w;  sv += (w * w) * V_q, in this
+ *        order.
+ *      out_p = sw > 0 ? sum / sw per channel : C_p;  V_out = sw > 0 ? sv / (sw * sw) : V_p.
+ *    A centre that is not valid keeps its colour and its variance.  rgb32f receives the last pass's colour, rgb8 its
+ *    quantisation and variance the last pass's variance; iterations == 0 copies and quantises the colour and copies the
+ *    variance.  NaN or negative variances (and NaN colours) give unspecified results for the pixels that read them.
+ *  - aliasing: out->rgb32f == in->rgb32f and out->variance == in->variance in device memory are allowed, each or both,
+ *    for every iterations (no pass writes a buffer it reads, as in p3d_denoise).  P3D_ERR_ARG when an output plane is any
+ *    other input plane, or two output planes are one plane.
+ *  - handle-owned memory: p3d_denoise's scratch buffers grow to carry the variance beside the colour (16 bytes per pixel
+ *    each, as many as p3d_denoise's pass count needs); they and the staging of host planes (p3d_denoise's, and the two
+ *    variance planes) are counted in p3d_scene_stats::device_bytes as they grow, kept for the next call and freed with
+ *    the handle.
+ *  - memory, ordering, stream capture, the 31-bit limit, shards and "no frame state touched": as p3d_denoise.
+ *  - P3D_ERR_ARG: p3d_denoise's refusals; a NULL in->variance; sigma_color == 0; the aliases above. */
+int p3d_denoise_variance(p3d_scene* scene, const p3d_denoise_params* params, const p3d_denoise_variance_inputs* in,
+                         const p3d_denoise_variance_outputs* out);
+
 /* The temporal half of that pipeline: frames of a SEQUENCE from a moving camera (p3d_render_frames, p3d_render --orbit,
  * the render-again loop after SetEye, RT/main.cpp:740) are blended with what the previous frame accumulated at the same
  * surface point, found by reprojecting the pixel's primary hit into the previous camera. */
@@ -760,6 +800,63 @@ typedef struct p3d_accumulate_moving_outputs { float* rgb32f; float* length; flo
 int p3d_accumulate_moving(p3d_scene* scene, const p3d_accumulate_params* params, const p3d_accumulate_frames* frames,
                           const p3d_accumulate_history* history, const p3d_accumulate_motion* motion,
                           const p3d_accumulate_moving_outputs* out);
+
+/* The temporal half of variance-guided denoising (SVGF, Schied et al. 2017): p3d_accumulate, or with a motion
+ * p3d_accumulate_moving, that also carries the first two moments of every pixel's luminance over the frames it has
+ * accumulated, and the variance they give -- the plane that steers p3d_denoise_variance. */
+typedef struct p3d_accumulate_variance_params {
+    float   min_temporal;        /* finite, >= 1: a pixel whose history is shorter takes the spatial estimate (1: none does) */
+    int32_t radius;              /* 1..3: the spatial estimate looks at (2 radius + 1)^2 pixels */
+    float   sigma_depth;         /* finite, > 0: p3d_denoise's depth stop, for the spatial estimate */
+    int32_t normal_power_log2;   /* 0..8: p3d_denoise's normal stop, for the spatial estimate */
+} p3d_accumulate_variance_params;
+typedef struct p3d_accumulate_variance_outputs {   /* each may be NULL, not all */
+    float* rgb32f; float* length;
+    float* moments;              /* [n_frames][res_y][res_x][2] */
+    float* variance;             /* [n_frames][res_y][res_x] */
+    float* prev_xy;              /* with a motion only */
+    int32_t memory;
+} p3d_accumulate_variance_outputs;
+/* DEFINED like its siblings: float32 IEEE-754 basic operations in the stated order, no fused multiply-add, correctly
+ * rounded division and square root; the device, the host layer (p3dh_accumulate_variance) and
+ * tests/accumulate_variance_reference.py agree on it in every bit.  A pure function of its arguments, as they are.
+ *  - arguments: params, frames and history as p3d_accumulate reads them.  motion NULL: a static world, step 2 of
+ *    p3d_accumulate; else step 2 of p3d_accumulate_moving, with everything that entry asks of motion and frames->hit_id.
+ *    history_moments: one frame of [res_y][res_x][2] floats in history->memory, the `moments` output of the frame the
+ *    history describes; needed exactly when history is given.
+ *  - rgb32f, length and prev_xy are, in every bit, what p3d_accumulate (motion NULL) or p3d_accumulate_moving (motion
+ *    given) returns for the same arguments.  prev_xy without a motion: P3D_ERR_ARG.
+ *  - moments, for a pixel with current colour C: l = lum(C) = (0.2126 C.r + 0.7152 C.g) + 0.0722 C.b, m = (l, l * l).
+ *    In step 3 every tap that contributes also adds, after sl and before sw, sm1 += wgt * M'.x and sm2 += wgt * M'.y, M' the
+ *    moments of the frame looked back at (frame f-1's OUTPUT moments; history_moments for frame 0).  In step 4
+ *    Hm = sm / sw per component and out_m = Hm + (m - Hm) * alpha with the colour's alpha.  "No history" in all its forms:
+ *    out_m = m.
+ *  - variance: vt = out_m.y - out_m.x * out_m.x, then vt = vt > 0 ? vt : 0.  A pixel whose Z is not valid gets 0.  A pixel
+ *    whose Z is valid and whose output length is < min_temporal gets a spatial estimate from the frame's INPUT colour:
+ *      inv_z = 1 / (sigma_depth * Z_p); the taps q = (x + dx, y + dy) run dy = -radius..radius (outer), dx likewise
+ *      (inner); a tap outside the frame or with a Z that is not valid contributes nothing; for the others
+ *        wz = tz * tz,  tz = max(0, 1 - |Z_q - Z_p| * inv_z)
+ *        wn = max(0, (N_p.x N_q.x + N_p.y N_q.y) + N_p.z N_q.z), then wn = wn * wn, normal_power_log2 times
+ *        w = wz * wn,  lq = lum(C_q);  s1 += w * lq;  s2 += w * (lq * lq);  sw += w        (products, then sums)
+ *      sw > 0: a = s1 / sw, b = s2 / sw, variance = max(0, b - a * a).  Else variance = vt.
+ *    Every other pixel gets vt.  Lengths are >= 1, so min_temporal == 1 switches the estimate off.  The estimate is not
+ *    fed back: the next frame looks back at the moments only.
+ *  - an output plane the caller does not want but a later launch reads -- colour, length or moments while n_frames > 1, the
+ *    length the spatial estimate reads -- is kept in spare planes of the handle (counted in device_bytes as they grow).
+ *  - launches: per frame p3d_accumulate[_moving]'s launch with the moments in it, and behind it, when min_temporal > 1
+ *    and out->variance is wanted, the launch of the spatial estimate; cameras by value, in stream order.
+ *  - aliasing: out->rgb32f == frames->rgb32f is allowed (with a spatial estimate the colour is then blended into a spare
+ *    plane of the handle and copied over the frame once the estimate has read it).  P3D_ERR_ARG for everything the
+ *    siblings refuse, and for out->moments or out->variance equal to any plane of the frames or of the history,
+ *    history_moments, an array of the motion or another output plane, and for any output plane equal to history_moments.
+ *  - planes, memory (history_moments lies where history->memory says), stream capture, the 31-bit limit, the shards of
+ *    world > 1 and the handle's untouched frame state: as p3d_accumulate.
+ *  - P3D_ERR_ARG besides: a NULL variance_params; history without history_moments or the reverse; min_temporal not finite
+ *    or below 1; radius outside 1..3; sigma_depth not finite or not positive; normal_power_log2 outside 0..8; every output
+ *    plane NULL. */
+int p3d_accumulate_variance(p3d_scene* scene, const p3d_accumulate_params* params, const p3d_accumulate_variance_params* variance_params,
+                            const p3d_accumulate_frames* frames, const p3d_accumulate_history* history, const float* history_moments,
+                            const p3d_accumulate_motion* motion, const p3d_accumulate_variance_outputs* out);
 
 /* Ambient occlusion over the planes of p3d_render_aov: hemisphere any-hit queries fused per pixel.  What a caller of
  * p3d_occluded would build as res_x * res_y * samples segments, upload and count is made in the lanes of one launch from
@@ -1040,6 +1137,10 @@ int p3d_debug_sample_stream(int device, uint32_t seed, int32_t res_x, int32_t re
  * Synchronous; scratch is allocated for the call and freed.  Refusals as p3d_denoise (in->memory or out->memory other than
  * 0: P3D_ERR_ARG). */
 int p3d_debug_denoise(int device, const p3d_denoise_params* params, const p3d_denoise_inputs* in, const p3d_outputs* out);
+/* Likewise the launches of p3d_denoise_variance (csrc/denoise_variance.hip) over HOST planes, without a scene.  Refusals as
+ * p3d_denoise_variance (in->memory or out->memory other than 0: P3D_ERR_ARG). */
+int p3d_debug_denoise_variance(int device, const p3d_denoise_params* params, const p3d_denoise_variance_inputs* in,
+                               const p3d_denoise_variance_outputs* out);
 
 /* The launches of p3d_accumulate (csrc/accumulate.hip) run by the same function over HOST planes, without a scene: the
  * four structs as p3d_accumulate reads them, every memory field 0.  Synchronous; scratch is allocated for the call and
@@ -1051,6 +1152,11 @@ int p3d_debug_accumulate(int device, const p3d_accumulate_params* params, const 
 int p3d_debug_accumulate_moving(int device, const p3d_accumulate_params* params, const p3d_accumulate_frames* frames,
                                 const p3d_accumulate_history* history, const p3d_accumulate_motion* motion,
                                 const p3d_accumulate_moving_outputs* out);
+/* Likewise the launches of p3d_accumulate_variance (csrc/accumulate_variance.hip) over HOST planes and HOST geometry,
+ * without a scene.  Refusals as p3d_accumulate_variance (a memory field other than 0: P3D_ERR_ARG). */
+int p3d_debug_accumulate_variance(int device, const p3d_accumulate_params* params, const p3d_accumulate_variance_params* variance_params,
+                                  const p3d_accumulate_frames* frames, const p3d_accumulate_history* history, const float* history_moments,
+                                  const p3d_accumulate_motion* motion, const p3d_accumulate_variance_outputs* out);
 
 #ifdef __cplusplus
 }

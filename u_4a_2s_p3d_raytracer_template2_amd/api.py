@@ -107,12 +107,31 @@ class DenoiseInputs(C.Structure):
     _fields_ = [("rgb32f", C.c_void_p), ("depth", C.c_void_p), ("normal", C.c_void_p), ("albedo", C.c_void_p), ("memory", C.c_int32)]
 
 
+class DenoiseVarianceInputs(C.Structure):
+    """p3d_denoise_variance_inputs: p3d_denoise_inputs' planes and the variance plane [n][H][W] that steers the colour stop."""
+    _fields_ = [("rgb32f", C.c_void_p), ("depth", C.c_void_p), ("normal", C.c_void_p), ("albedo", C.c_void_p), ("variance", C.c_void_p),
+                ("memory", C.c_int32)]
+
+
+class DenoiseVarianceOutputs(C.Structure):
+    """p3d_denoise_variance_outputs: each plane may be NULL."""
+    _fields_ = [("rgb8", C.c_void_p), ("rgb32f", C.c_void_p), ("variance", C.c_void_p), ("memory", C.c_int32)]
+
+
 # p3d_denoise's defaults (DESIGN "Denoising" says how they were chosen)
 DENOISE_ITERATIONS = 4
 DENOISE_SIGMA_DEPTH = 0.05
 DENOISE_SIGMA_ALBEDO = 0.25
 DENOISE_SIGMA_COLOR = 0.15
 DENOISE_NORMAL_POWER_LOG2 = 5
+# the defaults of p3d_accumulate_variance and p3d_denoise_variance (DESIGN "Variance-guided denoising" says how they were
+# chosen): the history below which a pixel's variance is estimated from its neighbours, that neighbourhood's radius, and the
+# colour stop's width in standard deviations; sigma_depth and normal_power_log2 are the denoiser's
+VARIANCE_MIN_TEMPORAL = 4.0
+VARIANCE_RADIUS = 3
+VARIANCE_SIGMA_COLOR = 4.0
+VARIANCE_SIGMA_DEPTH = DENOISE_SIGMA_DEPTH
+VARIANCE_NORMAL_POWER_LOG2 = DENOISE_NORMAL_POWER_LOG2
 
 
 class AccumulateParams(C.Structure):
@@ -149,6 +168,17 @@ class AccumulateMotion(C.Structure):
 
 class AccumulateMovingOutputs(C.Structure):
     _fields_ = [("rgb32f", C.c_void_p), ("length", C.c_void_p), ("prev_xy", C.c_void_p), ("memory", C.c_int32)]
+
+
+class AccumulateVarianceParams(C.Structure):
+    """p3d_accumulate_variance_params: pixels with a history shorter than min_temporal take the spatial estimate over
+    (2 radius + 1)^2 neighbours, weighted by the denoiser's depth and normal stops."""
+    _fields_ = [("min_temporal", C.c_float), ("radius", C.c_int32), ("sigma_depth", C.c_float), ("normal_power_log2", C.c_int32)]
+
+
+class AccumulateVarianceOutputs(C.Structure):
+    _fields_ = [("rgb32f", C.c_void_p), ("length", C.c_void_p), ("moments", C.c_void_p), ("variance", C.c_void_p), ("prev_xy", C.c_void_p),
+                ("memory", C.c_int32)]
 
 
 # p3d_accumulate's defaults: conveniences, not measured
@@ -208,9 +238,9 @@ class SceneStats(C.Structure):
 
 # every symbol include/p3d_hip.h declares (tests check that the library exports them all)
 C_ABI_SYMBOLS = ["p3d_abi_version", "p3d_last_error", "p3d_device_count", "p3d_scene_create",
-                 "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_scene_update", "p3d_scene_rebuild", "p3d_scene_rebuild_with", "p3d_scene_last_builder", "p3d_scene_tree_cost", "p3d_scene_build_grid", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_render_aov", "p3d_generate_samples", "p3d_trace_rays", "p3d_occluded", "p3d_denoise", "p3d_accumulate", "p3d_accumulate_moving", "p3d_ambient_occlusion", "p3d_sync",
+                 "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_scene_update", "p3d_scene_rebuild", "p3d_scene_rebuild_with", "p3d_scene_last_builder", "p3d_scene_tree_cost", "p3d_scene_build_grid", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_render_aov", "p3d_generate_samples", "p3d_trace_rays", "p3d_occluded", "p3d_denoise", "p3d_denoise_variance", "p3d_accumulate", "p3d_accumulate_moving", "p3d_accumulate_variance", "p3d_ambient_occlusion", "p3d_sync",
                  "p3d_get_counters", "p3d_get_profile", "p3d_last_schedule", "p3d_set_tuning", "p3d_set_primary_tiles", "p3d_last_primary_tiles", "p3d_set_sky_tiles", "p3d_last_sky_tiles", "p3d_set_stream", "p3d_timer_begin", "p3d_timer_end", "p3d_deinterleave_frames",
-                 "p3d_deinterleave", "p3d_debug_intersect", "p3d_debug_powf", "p3d_debug_pow", "p3d_debug_schlick_kr", "p3d_debug_check_rcp", "p3d_debug_check_rcp_len", "p3d_debug_lbvh_build", "p3d_debug_ploc_build", "p3d_debug_grid_build", "p3d_debug_rand", "p3d_debug_sample_stream", "p3d_debug_denoise", "p3d_debug_accumulate", "p3d_debug_accumulate_moving", "p3d_tune_schedule", "p3d_debug_set_stamps", "p3d_debug_set_stamp_level",
+                 "p3d_deinterleave", "p3d_debug_intersect", "p3d_debug_powf", "p3d_debug_pow", "p3d_debug_schlick_kr", "p3d_debug_check_rcp", "p3d_debug_check_rcp_len", "p3d_debug_lbvh_build", "p3d_debug_ploc_build", "p3d_debug_grid_build", "p3d_debug_rand", "p3d_debug_sample_stream", "p3d_debug_denoise", "p3d_debug_denoise_variance", "p3d_debug_accumulate", "p3d_debug_accumulate_moving", "p3d_debug_accumulate_variance", "p3d_tune_schedule", "p3d_debug_set_stamps", "p3d_debug_set_stamp_level",
                  "p3d_comm_unique_id", "p3d_comm_create", "p3d_comm_create_all", "p3d_comm_destroy", "p3d_comm_info",
                  "p3d_gather", "p3d_gather_all", "p3d_device_alloc", "p3d_device_free", "p3d_upload", "p3d_download"]
 
@@ -267,6 +297,10 @@ def lib():
     L.p3d_denoise.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(DenoiseInputs), C.POINTER(Outputs)]
     L.p3d_debug_denoise.argtypes = [C.c_int, C.POINTER(DenoiseParams), C.POINTER(DenoiseInputs), C.POINTER(Outputs)]
     L.p3dh_denoise.argtypes = [C.POINTER(DenoiseParams)] + [C.c_void_p] * 6
+    L.p3d_denoise_variance.argtypes = [C.c_void_p, C.POINTER(DenoiseParams), C.POINTER(DenoiseVarianceInputs), C.POINTER(DenoiseVarianceOutputs)]
+    L.p3d_debug_denoise_variance.argtypes = [C.c_int, C.POINTER(DenoiseParams), C.POINTER(DenoiseVarianceInputs), C.POINTER(DenoiseVarianceOutputs)]
+    L.p3dh_denoise_variance.argtypes = [C.POINTER(DenoiseParams)] + [C.c_void_p] * 8
+    L.p3dh_denoise_variance.restype = None
     _acc = [C.POINTER(AccumulateParams), C.POINTER(AccumulateFrames), C.POINTER(AccumulateHistory)]
     L.p3d_accumulate.argtypes = [C.c_void_p] + _acc + [C.POINTER(AccumulateOutputs)]
     L.p3d_debug_accumulate.argtypes = [C.c_int] + _acc + [C.POINTER(AccumulateOutputs)]
@@ -275,6 +309,12 @@ def lib():
     _mov = _acc + [C.POINTER(AccumulateMotion)]
     L.p3d_accumulate_moving.argtypes = [C.c_void_p] + _mov + [C.POINTER(AccumulateMovingOutputs)]
     L.p3d_debug_accumulate_moving.argtypes = [C.c_int] + _mov + [C.POINTER(AccumulateMovingOutputs)]
+    _var = [C.POINTER(AccumulateParams), C.POINTER(AccumulateVarianceParams), C.POINTER(AccumulateFrames), C.POINTER(AccumulateHistory),
+            C.c_void_p, C.POINTER(AccumulateMotion)]
+    L.p3d_accumulate_variance.argtypes = [C.c_void_p] + _var + [C.POINTER(AccumulateVarianceOutputs)]
+    L.p3d_debug_accumulate_variance.argtypes = [C.c_int] + _var + [C.POINTER(AccumulateVarianceOutputs)]
+    L.p3dh_accumulate_variance.argtypes = _var + [C.c_void_p] * 5
+    L.p3dh_accumulate_variance.restype = None
     L.p3dh_accumulate_moving.argtypes = _mov + [C.c_void_p, C.c_void_p, C.c_void_p]
     L.p3dh_accumulate_moving.restype = None
     L.p3d_ambient_occlusion.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.POINTER(RenderParams), C.POINTER(AoParams),
@@ -892,6 +932,27 @@ class DeviceScene:
         o = Outputs(out_rgb8_ptr or None, out_rgb32f_ptr or None, None, 1)
         _check(lib().p3d_denoise(self.h, C.byref(p), C.byref(i), C.byref(o)), "p3d_denoise")
 
+    def denoise_variance(self, rgb32f, depth, normal, albedo, variance, **kw):
+        """p3d_denoise_variance on host arrays: DeviceScene.denoise's planes and variance (n, H, W) or (H, W), the variance
+        of each pixel's luminance.  Keywords as denoise(); sigma_color (default VARIANCE_SIGMA_COLOR) is the colour stop's
+        width in standard deviations and must be positive.  Returns {"rgb32f", "rgb8", "variance"}."""
+        p, planes, out = _denoise_variance_request(rgb32f, depth, normal, albedo, variance, **kw)
+        i = DenoiseVarianceInputs(*[a.ctypes.data for a in planes], 0)
+        o = DenoiseVarianceOutputs(out["rgb8"].ctypes.data, out["rgb32f"].ctypes.data, out["variance"].ctypes.data, 0)
+        _check(lib().p3d_denoise_variance(self.h, C.byref(p), C.byref(i), C.byref(o)), "p3d_denoise_variance")
+        return out
+
+    def denoise_variance_device(self, res_x, res_y, rgb32f_ptr, depth_ptr, normal_ptr, albedo_ptr, variance_ptr, out_rgb32f_ptr=0,
+                                out_rgb8_ptr=0, out_variance_ptr=0, n_frames=1, iterations=DENOISE_ITERATIONS,
+                                sigma_depth=DENOISE_SIGMA_DEPTH, sigma_albedo=DENOISE_SIGMA_ALBEDO, sigma_color=VARIANCE_SIGMA_COLOR,
+                                normal_power_log2=DENOISE_NORMAL_POWER_LOG2):
+        """Enqueue p3d_denoise_variance on caller-owned DEVICE buffers (raw pointers; an output of 0 = no such plane);
+        asynchronous on the scene's stream.  out_rgb32f_ptr may equal rgb32f_ptr, out_variance_ptr may equal variance_ptr."""
+        p = DenoiseParams(int(res_x), int(res_y), int(n_frames), int(iterations), sigma_depth, sigma_albedo, sigma_color, int(normal_power_log2))
+        i = DenoiseVarianceInputs(rgb32f_ptr or None, depth_ptr or None, normal_ptr or None, albedo_ptr or None, variance_ptr or None, 1)
+        o = DenoiseVarianceOutputs(out_rgb8_ptr or None, out_rgb32f_ptr or None, out_variance_ptr or None, 1)
+        _check(lib().p3d_denoise_variance(self.h, C.byref(p), C.byref(i), C.byref(o)), "p3d_denoise_variance")
+
     def accumulate(self, rgb32f, depth, normal, cams, hit_id=None, history=None, **kw):
         """p3d_accumulate on host arrays: the frames of a sequence, rgb32f / normal (n, H, W, 3) or (H, W, 3), depth and hit_id
         (n, H, W) or (H, W) as render_aov returns them, cams one Camera per frame.  history: None, or a dict with rgb32f,
@@ -950,6 +1011,46 @@ class DeviceScene:
         o = AccumulateMovingOutputs(out_rgb32f_ptr or None, out_length_ptr or None, out_prev_xy_ptr or None, 1)
         _check(lib().p3d_accumulate_moving(self.h, C.byref(p), C.byref(fr), C.byref(hi) if hi else None, C.byref(mo), C.byref(o)),
                "p3d_accumulate_moving")
+
+    def accumulate_variance(self, rgb32f, depth, normal, cams, hit_id=None, history=None, motion=None, **kw):
+        """p3d_accumulate_variance on host arrays: DeviceScene.accumulate -- or, with motion = dict(prim_type, prim_data),
+        DeviceScene.accumulate_moving -- that also carries the luminance moments.  A history also carries "moments" (H, W, 2),
+        the moments output of the frame it describes (and "prim_data" with a motion).  Keywords: accumulate's, and
+        min_temporal, radius, sigma_depth, normal_power_log2 (defaults: the VARIANCE_* constants).  Returns {"rgb32f",
+        "length", "moments" (n, H, W, 2), "variance" (n, H, W)} and, with a motion, "prev_xy"."""
+        p, vp, fr, hi, hm, mo, out, keep = _accumulate_variance_request(rgb32f, depth, normal, cams, hit_id, history, motion, **kw)
+        o = AccumulateVarianceOutputs(*[out[k].ctypes.data if k in out else None for k in _VARIANCE_PLANES], 0)
+        _check(lib().p3d_accumulate_variance(self.h, C.byref(p), C.byref(vp), C.byref(fr), C.byref(hi) if hi else None, hm,
+                                             C.byref(mo) if mo else None, C.byref(o)), "p3d_accumulate_variance")
+        return out
+
+    def accumulate_variance_device(self, res_x, res_y, cams, rgb32f_ptr, depth_ptr, normal_ptr, hit_ptr=0, out_rgb32f_ptr=0, out_length_ptr=0,
+                                   out_moments_ptr=0, out_variance_ptr=0, out_prev_xy_ptr=0, history=None, motion=None,
+                                   depth_tolerance=ACCUMULATE_DEPTH_TOLERANCE, normal_min=ACCUMULATE_NORMAL_MIN, max_history=ACCUMULATE_MAX_HISTORY,
+                                   min_temporal=VARIANCE_MIN_TEMPORAL, radius=VARIANCE_RADIUS, sigma_depth=VARIANCE_SIGMA_DEPTH,
+                                   normal_power_log2=VARIANCE_NORMAL_POWER_LOG2):
+        """Enqueue p3d_accumulate_variance on caller-owned DEVICE buffers (raw pointers; 0 = no such plane) holding len(cams)
+        frames; asynchronous on the scene's stream.  history: None, or a dict of device pointers rgb32f, depth, normal, length,
+        moments (optionally hit_id; prim_data with a motion) and the host Camera cam.  motion: None, or a dict of n_prims and
+        the device pointers prim_type, prim_data.  out_rgb32f_ptr may equal rgb32f_ptr."""
+        arr, n = _camera_array(cams)
+        p = AccumulateParams(int(res_x), int(res_y), n, depth_tolerance, normal_min, max_history)
+        vp = AccumulateVarianceParams(min_temporal, int(radius), sigma_depth, int(normal_power_log2))
+        fr = AccumulateFrames(rgb32f_ptr or None, depth_ptr or None, normal_ptr or None, hit_ptr or None, arr, 1)
+        hi = None
+        if history is not None:
+            hcam = (Camera * 1)(history["cam"])
+            hi = AccumulateHistory(history["rgb32f"] or None, history["depth"] or None, history["normal"] or None, history["length"] or None,
+                                   history.get("hit_id") or None, hcam, 1)
+        mo = None
+        if motion is not None:
+            mo = AccumulateMotion(int(motion["n_prims"]), motion["prim_type"] or None, motion["prim_data"] or None,
+                                  (history or {}).get("prim_data") or None, 1)
+        o = AccumulateVarianceOutputs(out_rgb32f_ptr or None, out_length_ptr or None, out_moments_ptr or None, out_variance_ptr or None,
+                                      out_prev_xy_ptr or None, 1)
+        _check(lib().p3d_accumulate_variance(self.h, C.byref(p), C.byref(vp), C.byref(fr), C.byref(hi) if hi else None,
+                                             (history or {}).get("moments") or None, C.byref(mo) if mo else None, C.byref(o)),
+               "p3d_accumulate_variance")
 
     def ambient_occlusion(self, cam_or_cams, depth, normal, rgb32f=None, samples=AO_SAMPLES, radius=AO_RADIUS, bias=AO_BIAS, seed=0,
                           accel=ACCEL_BVH, no_lds=False, private_walk=False, want=("ao", "rgb32f")):
@@ -1174,6 +1275,35 @@ def debug_denoise(rgb32f, depth, normal, albedo, device=0, **kw):
     return out
 
 
+def _denoise_variance_request(rgb32f, depth, normal, albedo, variance, sigma_color=VARIANCE_SIGMA_COLOR, **kw):
+    """_denoise_request with the variance plane -> (DenoiseParams, the five contiguous planes, the zeroed outputs)."""
+    p, planes, shape = _denoise_request(rgb32f, depth, normal, albedo, sigma_color=sigma_color, **kw)
+    v = np.ascontiguousarray(variance, np.float32)
+    if v.size != planes[1].size:
+        raise ValueError("variance must match depth")
+    out = {"rgb32f": np.zeros(shape, np.float32), "rgb8": np.zeros(shape, np.uint8), "variance": np.zeros(shape[:-1], np.float32)}
+    return p, planes + (v,), out
+
+
+def host_denoise_variance(rgb32f, depth, normal, albedo, variance, **kw):
+    """p3dh_denoise_variance: the host layer's restatement of p3d_denoise_variance, every bit of it, on host arrays (no GPU).
+    Arguments and result as DeviceScene.denoise_variance."""
+    p, planes, out = _denoise_variance_request(rgb32f, depth, normal, albedo, variance, **kw)
+    lib().p3dh_denoise_variance(C.byref(p), *[a.ctypes.data for a in planes], out["rgb32f"].ctypes.data, out["rgb8"].ctypes.data,
+                                out["variance"].ctypes.data)
+    return out
+
+
+def debug_denoise_variance(rgb32f, depth, normal, albedo, variance, device=0, **kw):
+    """p3d_debug_denoise_variance: the launches of p3d_denoise_variance over host arrays, without a scene.  Arguments and
+    result as DeviceScene.denoise_variance."""
+    p, planes, out = _denoise_variance_request(rgb32f, depth, normal, albedo, variance, **kw)
+    i = DenoiseVarianceInputs(*[a.ctypes.data for a in planes], 0)
+    o = DenoiseVarianceOutputs(out["rgb8"].ctypes.data, out["rgb32f"].ctypes.data, out["variance"].ctypes.data, 0)
+    _check(lib().p3d_debug_denoise_variance(int(device), C.byref(p), C.byref(i), C.byref(o)), "p3d_debug_denoise_variance")
+    return out
+
+
 def _accumulate_request(rgb32f, depth, normal, cams, hit_id=None, history=None, depth_tolerance=ACCUMULATE_DEPTH_TOLERANCE,
                         normal_min=ACCUMULATE_NORMAL_MIN, max_history=ACCUMULATE_MAX_HISTORY):
     """Host planes of one frame (H, W[, 3]) or n frames (n, H, W[, 3]) and their cameras -> (AccumulateParams, AccumulateFrames,
@@ -1261,6 +1391,52 @@ def debug_accumulate_moving(rgb32f, depth, normal, cams, hit_id, prim_type, prim
     o = AccumulateMovingOutputs(out["rgb32f"].ctypes.data, out["length"].ctypes.data, out["prev_xy"].ctypes.data if prev_xy else None, 0)
     _check(lib().p3d_debug_accumulate_moving(int(device), C.byref(p), C.byref(fr), C.byref(hi) if hi else None, C.byref(mo), C.byref(o)),
            "p3d_debug_accumulate_moving")
+    return out
+
+
+_VARIANCE_PLANES = ("rgb32f", "length", "moments", "variance", "prev_xy")
+
+
+def _accumulate_variance_request(rgb32f, depth, normal, cams, hit_id=None, history=None, motion=None, min_temporal=VARIANCE_MIN_TEMPORAL,
+                                 radius=VARIANCE_RADIUS, sigma_depth=VARIANCE_SIGMA_DEPTH, normal_power_log2=VARIANCE_NORMAL_POWER_LOG2, **kw):
+    """_accumulate_request or, with motion = dict(prim_type, prim_data), _accumulate_moving_request, and the moments -> (params,
+    AccumulateVarianceParams, frames, history or None, the history's moments pointer or None, AccumulateMotion or None, the
+    zeroed outputs, what must stay alive)."""
+    if motion is not None:
+        p, fr, hi, mo, out, keep = _accumulate_moving_request(rgb32f, depth, normal, cams, hit_id, motion["prim_type"], motion["prim_data"],
+                                                              history, True, **kw)
+    else:
+        p, fr, hi, out, keep = _accumulate_request(rgb32f, depth, normal, cams, hit_id, history, **kw)
+        mo = None
+    hm = None
+    if history is not None:
+        hmom = np.ascontiguousarray(history["moments"], np.float32)
+        if hmom.size != 2 * p.res_x * p.res_y:
+            raise ValueError("the history's moments are one frame of 2 floats per pixel")
+        hm = hmom.ctypes.data
+        keep = keep + [hmom]
+    out["moments"] = np.zeros(out["length"].shape + (2,), np.float32)
+    out["variance"] = np.zeros(out["length"].shape, np.float32)
+    vp = AccumulateVarianceParams(min_temporal, int(radius), sigma_depth, int(normal_power_log2))
+    return p, vp, fr, hi, hm, mo, out, keep
+
+
+def host_accumulate_variance(rgb32f, depth, normal, cams, hit_id=None, history=None, motion=None, **kw):
+    """p3dh_accumulate_variance: the host layer's restatement of p3d_accumulate_variance, every bit of it, on host arrays (no
+    GPU).  Arguments and result as DeviceScene.accumulate_variance."""
+    p, vp, fr, hi, hm, mo, out, keep = _accumulate_variance_request(rgb32f, depth, normal, cams, hit_id, history, motion, **kw)
+    lib().p3dh_accumulate_variance(C.byref(p), C.byref(vp), C.byref(fr), C.byref(hi) if hi else None, hm, C.byref(mo) if mo else None,
+                                   *[out[k].ctypes.data if k in out else None for k in _VARIANCE_PLANES])
+    return out
+
+
+def debug_accumulate_variance(rgb32f, depth, normal, cams, hit_id=None, history=None, motion=None, device=0, **kw):
+    """p3d_debug_accumulate_variance: the launches of p3d_accumulate_variance over host arrays, without a scene.  Arguments and
+    result as DeviceScene.accumulate_variance."""
+    p, vp, fr, hi, hm, mo, out, keep = _accumulate_variance_request(rgb32f, depth, normal, cams, hit_id, history, motion, **kw)
+    o = AccumulateVarianceOutputs(*[out[k].ctypes.data if k in out else None for k in _VARIANCE_PLANES], 0)
+    _check(lib().p3d_debug_accumulate_variance(int(device), C.byref(p), C.byref(vp), C.byref(fr), C.byref(hi) if hi else None, hm,
+                                               C.byref(mo) if mo else None, C.byref(o)), "p3d_debug_accumulate_variance")
     return out
 
 

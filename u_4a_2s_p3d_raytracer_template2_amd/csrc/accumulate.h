@@ -60,5 +60,54 @@ struct AccumulateMotion {
 hipError_t launch_accumulate_moving(const p3d_accumulate_params& p, const AccumulatePlanes& planes, const AccumulateMotion& motion,
                                     const p3d_camera* cams, const p3d_camera* hist_cam, hipStream_t stream);
 
+// p3d_accumulate_variance (accumulate_variance.hip): what p3d_accumulate_variance (p3d_accumulate.cpp) and the
+// p3d_debug_accumulate_variance probe run.
+constexpr int kAccumulateVarianceMaxRadius = 3;
+
+// Every argument check of p3d_accumulate_variance but the scene's: those of p3d_accumulate (motion NULL) or of
+// p3d_accumulate_moving, and the rules of the new planes and parameters.
+int accumulate_variance_check_request(const p3d_accumulate_params* p, const p3d_accumulate_variance_params* vp,
+                                      const p3d_accumulate_frames* frames, const p3d_accumulate_history* history, const float* history_moments,
+                                      const p3d_accumulate_motion* motion, const p3d_accumulate_variance_outputs* out, const char** why);
+
+// DEVICE planes of launch_accumulate_variance beside AccumulatePlanes: the history's moments (one frame of 2 floats per
+// pixel, read when hist_rgb32f is not NULL), the two new outputs (n_frames frames each, or NULL) and, when out_moments is
+// NULL and n_frames > 1, TWO frames of moments (8 bytes per pixel) used like spare_rgb32f.
+struct AccumulateVariancePlanes {
+    const float* hist_moments;
+    float *out_moments, *out_variance;
+    float* spare_moments;
+};
+
+// Whether the spatial launches run: somebody wants the variance, and a history length can lie below min_temporal.
+inline bool accumulate_variance_spatial(const p3d_accumulate_variance_params& vp, const float* out_variance) {
+    return out_variance && vp.min_temporal > 1.0f;
+}
+// Whether the colour takes a detour through spare_rgb32f: an in-place call whose spatial launch reads the input colour
+// after the temporal launch has blended it.
+inline bool accumulate_variance_colour_detour(const p3d_accumulate_variance_params& vp, const float* rgb32f, const float* out_rgb32f,
+                                              const float* out_variance) {
+    return out_rgb32f == rgb32f && accumulate_variance_spatial(vp, out_variance);
+}
+// Frames (0, 1 or 2) spare_rgb32f and spare_length must hold for launch_accumulate_variance: an output the caller does not
+// want is kept for the next frame (two frames when n_frames > 1), and so is the colour of a detour and the length the
+// spatial launch reads.
+inline int accumulate_variance_spare_colour_frames(const p3d_accumulate_params& p, const float* out_rgb32f, bool detour) {
+    return p.n_frames > 1 ? (!out_rgb32f || detour ? 2 : 0) : (detour ? 1 : 0);
+}
+inline int accumulate_variance_spare_length_frames(const p3d_accumulate_params& p, const p3d_accumulate_variance_params& vp, const float* out_length,
+                                                   const float* out_variance) {
+    if (out_length) return 0;
+    return p.n_frames > 1 ? 2 : (accumulate_variance_spatial(vp, out_variance) ? 1 : 0);
+}
+
+// p3d_accumulate_variance's launches, enqueued as launch_accumulate's are: per frame the temporal launch (motion NULL:
+// accumulate.hip's reprojection, else accumulate_motion.hip's; motion->out_prev_xy as there) and, when
+// accumulate_variance_spatial(), the spatial one behind it.  planes.out_rgb32f == planes.rgb32f is allowed.  The caller has
+// run accumulate_variance_check_request and sized the spare planes as the functions above say.
+hipError_t launch_accumulate_variance(const p3d_accumulate_params& p, const p3d_accumulate_variance_params& vp, const AccumulatePlanes& planes,
+                                      const AccumulateVariancePlanes& variance, const AccumulateMotion* motion, const p3d_camera* cams,
+                                      const p3d_camera* hist_cam, hipStream_t stream);
+
 }  // namespace p3d
 #endif

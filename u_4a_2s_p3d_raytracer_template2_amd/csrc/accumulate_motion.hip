@@ -25,78 +25,6 @@ namespace p3d {
 
 namespace {
 
-// A frame of p3d_accumulate_moving: accumulate.hip's record and the geometry of the two frames.
-struct MovingFrame {
-    AccumulateFrame F;
-    const uint32_t* type;           // [n_prims]
-    const float *cur, *prev;        // [n_prims][12]: what the frame was rendered with, and the frame it looks back at (HISTORY only)
-    float* out_xy;                  // [res_y][res_x][2] or NULL
-    uint32_t n_prims;
-};
-
-// 16 bytes of a record as words; the records and the prev_xy plane are only as aligned as their floats
-typedef uint32_t Words4A __attribute__((ext_vector_type(4)));
-typedef Words4A Words4 __attribute__((aligned(4)));
-typedef float Float2A __attribute__((ext_vector_type(2)));
-typedef Float2A Float2 __attribute__((aligned(4)));
-
-struct Record { Words4A w[3]; };
-
-__device__ __forceinline__ Record load_record(const float* records, uint32_t i) {
-    const Words4* p = (const Words4*)(records + 12 * (size_t)i);
-    return {{p[0], p[1], p[2]}};
-}
-__device__ __forceinline__ float fl(uint32_t w) { return __uint_as_float(w); }
-__device__ __forceinline__ float dot3(V3 p, V3 q) { return (p.x * q.x + p.y * q.y) + p.z * q.z; }
-
-// P_prev of include/p3d_hip.h for the hit point P on primitive I.  false: the primitive has changed and its kind gives no point
-// one frame ago (a plane): no history.
-__device__ __forceinline__ bool previous_point(const MovingFrame& M, int32_t I, V3 P, V3& Q) {
-    Q = P;
-    if (I < 0 || (uint32_t)I >= M.n_prims) return true;
-    const uint32_t k = M.type[I];
-    const Record a = load_record(M.cur, (uint32_t)I), b = load_record(M.prev, (uint32_t)I);
-    const bool same4 = a.w[0].x == b.w[0].x && a.w[0].y == b.w[0].y && a.w[0].z == b.w[0].z && a.w[0].w == b.w[0].w;
-    const bool same6 = same4 && a.w[1].x == b.w[1].x && a.w[1].y == b.w[1].y;
-    const bool same9 = same6 && a.w[1].z == b.w[1].z && a.w[1].w == b.w[1].w && a.w[2].x == b.w[2].x;
-    if (k == P3D_SPHERE) {
-        if (same4) return true;
-        const float s = fdiv(fl(b.w[0].w), fl(a.w[0].w));
-        Q = mk(fl(b.w[0].x) + (P.x - fl(a.w[0].x)) * s, fl(b.w[0].y) + (P.y - fl(a.w[0].y)) * s, fl(b.w[0].z) + (P.z - fl(a.w[0].z)) * s);
-        return true;
-    }
-    if (k == P3D_TRIANGLE) {
-        if (same9) return true;
-        const V3 p0 = mk(fl(a.w[0].x), fl(a.w[0].y), fl(a.w[0].z)), p1 = mk(fl(a.w[0].w), fl(a.w[1].x), fl(a.w[1].y));
-        const V3 p2 = mk(fl(a.w[1].z), fl(a.w[1].w), fl(a.w[2].x));
-        const V3 e1 = mk(p1.x - p0.x, p1.y - p0.y, p1.z - p0.z), e2 = mk(p2.x - p0.x, p2.y - p0.y, p2.z - p0.z);
-        const V3 w = mk(P.x - p0.x, P.y - p0.y, P.z - p0.z);
-        const float d11 = dot3(e1, e1), d12 = dot3(e1, e2), d22 = dot3(e2, e2), w1 = dot3(w, e1), w2 = dot3(w, e2);
-        const float den = d11 * d22 - d12 * d12;
-        const float beta = fdiv(d22 * w1 - d12 * w2, den), gamma = fdiv(d11 * w2 - d12 * w1, den);
-        const V3 q0 = mk(fl(b.w[0].x), fl(b.w[0].y), fl(b.w[0].z)), q1 = mk(fl(b.w[0].w), fl(b.w[1].x), fl(b.w[1].y));
-        const V3 q2 = mk(fl(b.w[1].z), fl(b.w[1].w), fl(b.w[2].x));
-        const V3 f1 = mk(q1.x - q0.x, q1.y - q0.y, q1.z - q0.z), f2 = mk(q2.x - q0.x, q2.y - q0.y, q2.z - q0.z);
-        Q = mk((q0.x + f1.x * beta) + f2.x * gamma, (q0.y + f1.y * beta) + f2.y * gamma, (q0.z + f1.z * beta) + f2.z * gamma);
-        return true;
-    }
-    if (k == P3D_BOX) {
-        if (same6) return true;
-        const float mn[3] = {fl(a.w[0].x), fl(a.w[0].y), fl(a.w[0].z)}, mx[3] = {fl(a.w[0].w), fl(a.w[1].x), fl(a.w[1].y)};
-        const float pmn[3] = {fl(b.w[0].x), fl(b.w[0].y), fl(b.w[0].z)}, pmx[3] = {fl(b.w[0].w), fl(b.w[1].x), fl(b.w[1].y)};
-        const float p[3] = {P.x, P.y, P.z};
-        float r[3];
-        for (int c = 0; c < 3; c++) {
-            const float e = mx[c] - mn[c];
-            const float t = e != 0.0f ? fdiv(p[c] - mn[c], e) : 0.0f;
-            r[c] = pmn[c] + (pmx[c] - pmn[c]) * t;
-        }
-        Q = mk(r[0], r[1], r[2]);
-        return true;
-    }
-    return same4;                    // a plane, or a kind this library does not know: unchanged, or no point to look at
-}
-
 template <bool HISTORY>
 __global__ void __launch_bounds__(kThreads) accumulate_moving_kernel(MovingFrame M) {
     const AccumulateFrame& F = M.F;

@@ -3,7 +3,7 @@
 //   p3d_render <scene.p3f> [--res W H] [--accel 0|1|2] [--depth D] [--spp N] [--seed S]
 //              [--device K | --gpus N] [--out image.png|image.ppm] [--counters] [--soft-shadow] [--fuzzy-reflection]
 //              [--aov PREFIX] [--denoise K [--denoise-sigmas Z A C]] [--accumulate [--accumulate-params TOL NMIN MAXLEN]]
-//              [--ao S RADIUS [--ao-out PREFIX]]
+//              [--variance-guided [--variance-params MIN_TEMPORAL RADIUS SIGMA]] [--ao S RADIUS [--ao-out PREFIX]]
 // --gpus N: devices 0..N-1 each render every N-th block of 16 rows, one RCCL gather to device 0.
 // --orbit N STEP_DEG: N frames of the reference's mouse orbit (alpha advancing by STEP_DEG per frame, RT/main.cpp:339-341,
 // 419-421) in ONE p3d_render_frames call; --out then takes a %d pattern (e.g. frame_%03d.png) for the frame number.
@@ -16,6 +16,11 @@
 // frame before it (p3d_accumulate) before it is written; --accumulate-params TOL NMIN MAXLEN sets depth_tolerance,
 // normal_min and max_history.  With it --denoise K is legal together with --orbit and filters every accumulated frame (one
 // p3d_denoise call over all N).  One GPU; needs --orbit.
+// --orbit N STEP --accumulate --denoise K --variance-guided: the accumulation also carries the luminance moments of every
+// pixel (p3d_accumulate_variance over the sequence) and the filter is steered by their variance (p3d_denoise_variance, one
+// call over all N); --variance-params MIN_TEMPORAL RADIUS SIGMA sets the history below which the variance is estimated from
+// the neighbours, that neighbourhood's radius (1..3) and the colour stop's width in standard deviations.  Needs both
+// --accumulate and --denoise.
 // --ao S RADIUS: the frame is rendered with its planes, p3d_ambient_occlusion runs S (1, 2, 4, .. 64) segments of length RADIUS
 // per pixel over them and the colour is multiplied by the result before it is written.  Combines with --denoise K (the
 // modulated colour is what is filtered), with --aov and with --orbit N STEP [--accumulate]; one GPU: not with --gpus N.
@@ -61,9 +66,11 @@ int main(int argc, char** argv) {
     if (argc < 2) {
         fprintf(stderr, "usage: %s scene.p3f [--res W H] [--accel A] [--depth D] [--spp N] [--seed S] "
                         "[--device K | --gpus N] [--out file.ppm] [--orbit N STEP_DEG] [--counters] [--soft-shadow] [--fuzzy-reflection] [--schlick] [--aov PREFIX] "
-                        "[--denoise K [--denoise-sigmas Z A C]] [--accumulate [--accumulate-params TOL NMIN MAXLEN]] [--ao S RADIUS [--ao-out PREFIX]]\n"
+                        "[--denoise K [--denoise-sigmas Z A C]] [--accumulate [--accumulate-params TOL NMIN MAXLEN]] "
+                        "[--variance-guided [--variance-params MIN_TEMPORAL RADIUS SIGMA]] [--ao S RADIUS [--ao-out PREFIX]]\n"
                         "  --denoise filters one frame on one GPU: not with --orbit, not with --gpus N\n"
                         "  --accumulate blends the frames of --orbit over time on one GPU; with it --denoise filters every accumulated frame\n"
+                        "  --variance-guided steers that filter by the variance of every pixel's luminance over time: needs --accumulate and --denoise\n"
                         "  --ao multiplies the colour by ambient occlusion (S segments of length RADIUS per pixel) on one GPU: not with --gpus N\n", argv[0]);
         return 2;
     }
@@ -93,6 +100,8 @@ int main(int argc, char** argv) {
         else if (a == "--denoise") { need(1); opt.denoise = atoi(argv[++i]); if (opt.denoise < 0 || opt.denoise > 6) { fprintf(stderr, "--denoise needs K in 0..6\n"); return 2; } }
         else if (a == "--denoise-sigmas") { need(3); opt.denoise_sigma_depth = (float)atof(argv[++i]); opt.denoise_sigma_albedo = (float)atof(argv[++i]); opt.denoise_sigma_color = (float)atof(argv[++i]); }
         else if (a == "--accumulate") opt.accumulate = true;
+        else if (a == "--variance-guided") opt.variance_guided = true;
+        else if (a == "--variance-params") { need(3); opt.variance_min_temporal = (float)atof(argv[++i]); opt.variance_radius = atoi(argv[++i]); opt.variance_sigma_color = (float)atof(argv[++i]); }
         else if (a == "--accumulate-params") { need(3); opt.accumulate_depth_tolerance = (float)atof(argv[++i]); opt.accumulate_normal_min = (float)atof(argv[++i]); opt.accumulate_max_history = (float)atof(argv[++i]); }
         else if (a == "--ao") {
             need(2); opt.ambient_occlusion = atoi(argv[++i]); opt.ao_radius = (float)atof(argv[++i]);
@@ -115,6 +124,7 @@ int main(int argc, char** argv) {
     };
     if (orbit_n > 0 && opt.want_aov) { fprintf(stderr, "--aov writes the planes of one frame: not with --orbit\n"); return 2; }
     if (opt.accumulate && (orbit_n < 1 || opt.gpus > 1)) { fprintf(stderr, "--accumulate blends the frames of --orbit N STEP on one GPU: it needs --orbit, not --gpus N\n"); return 2; }
+    if (opt.variance_guided && (!opt.accumulate || opt.denoise < 0)) { fprintf(stderr, "--variance-guided steers the filter of an accumulated sequence: it needs --accumulate and --denoise K\n"); return 2; }
     if (opt.ambient_occlusion > 0 && opt.gpus > 1) { fprintf(stderr, "--ao runs on the planes of whole frames on one GPU: not with --gpus N\n"); return 2; }
     if (!ao_out.empty() && opt.ambient_occlusion < 1) { fprintf(stderr, "--ao-out needs --ao S RADIUS\n"); return 2; }
     if (opt.denoise >= 0 && ((orbit_n > 0 && !opt.accumulate) || opt.gpus > 1)) { fprintf(stderr, "--denoise filters one frame on one GPU: not with --orbit or --gpus N\n"); return 2; }

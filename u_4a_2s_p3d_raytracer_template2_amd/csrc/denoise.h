@@ -33,5 +33,24 @@ hipError_t launch_denoise(const p3d_denoise_params& p, const float* rgb32f, cons
                           const float* albedo, float* scratch0, float* scratch1, float* out_rgb32f, uint8_t* out_rgb8,
                           hipStream_t stream);
 
+// p3d_denoise_variance (denoise_variance.hip): what p3d_denoise_variance (p3d_denoise.cpp) and the
+// p3d_debug_denoise_variance probe run.
+// Every argument check of p3d_denoise_variance but the scene's: denoise_check_request's, and the rules of the new planes.
+int denoise_variance_check_request(const p3d_denoise_params* p, const p3d_denoise_variance_inputs* in,
+                                   const p3d_denoise_variance_outputs* out, const char** why);
+
+// The in_place of denoise_scratch_buffers() for launch_denoise_variance: an output plane is the input plane it filters.
+inline bool denoise_variance_in_place(const float* rgb32f, const float* variance, const float* out_rgb32f, const float* out_variance) {
+    return out_rgb32f == rgb32f || (out_variance && out_variance == variance);
+}
+
+// The variance-guided filter over DEVICE planes, enqueued on `stream`: launch_denoise's launches with the variance plane
+// beside the colour.  out_rgb32f, out_rgb8 and out_variance may each be NULL; out_rgb32f == rgb32f and
+// out_variance == variance are allowed.  scratch0 / scratch1: as denoise_scratch_buffers() says, each
+// n_frames * res_x * res_y * 4 floats (the colour, then the variance).  The caller has run denoise_variance_check_request.
+hipError_t launch_denoise_variance(const p3d_denoise_params& p, const float* rgb32f, const float* depth, const float* normal,
+                                   const float* albedo, const float* variance, float* scratch0, float* scratch1, float* out_rgb32f,
+                                   uint8_t* out_rgb8, float* out_variance, hipStream_t stream);
+
 }  // namespace p3d
 #endif

@@ -110,6 +110,13 @@ void p3dh_denoise(const p3d_denoise_params* params, const float* rgb32f, const f
     denoise(*params, rgb32f, depth, normal, albedo, out_rgb32f, out_rgb8);
 }
 
+// denoise_variance() of the host layer (denoise_host.cpp): p3d_denoise_variance's result on host planes, every bit.
+// out_rgb32f / out_rgb8 / out_variance may each be NULL.  The caller keeps params inside the ranges the entry accepts.
+void p3dh_denoise_variance(const p3d_denoise_params* params, const float* rgb32f, const float* depth, const float* normal,
+                           const float* albedo, const float* variance, float* out_rgb32f, uint8_t* out_rgb8, float* out_variance) {
+    denoise_variance(*params, rgb32f, depth, normal, albedo, variance, out_rgb32f, out_rgb8, out_variance);
+}
+
 // ao_segments() / ao_resolve() of the host layer (ao_host.cpp): steps 1 to 6 and step 8 of p3d_ambient_occlusion's definition
 // on host planes, every bit.  One frame, the frame-th of a batch: origin_out / dir_out [res_y][res_x][samples][3], valid_out
 // [res_y][res_x].  The caller keeps params inside the ranges p3d_ambient_occlusion accepts.
@@ -133,6 +140,17 @@ void p3dh_accumulate(const p3d_accumulate_params* params, const p3d_accumulate_f
 void p3dh_accumulate_moving(const p3d_accumulate_params* params, const p3d_accumulate_frames* frames, const p3d_accumulate_history* history,
                             const p3d_accumulate_motion* motion, float* out_rgb32f, float* out_length, float* out_prev_xy) {
     accumulate_moving(*params, *frames, history, *motion, out_rgb32f, out_length, out_prev_xy);
+}
+
+// accumulate_variance() of the host layer: p3d_accumulate_variance's result on host planes and host geometry, every bit.
+// history (with history_moments) and motion may be NULL; the five outputs may each be NULL; out_rgb32f must not be the
+// frames' colour.  The caller keeps the arguments inside what p3d_accumulate_variance accepts.
+void p3dh_accumulate_variance(const p3d_accumulate_params* params, const p3d_accumulate_variance_params* variance_params,
+                              const p3d_accumulate_frames* frames, const p3d_accumulate_history* history, const float* history_moments,
+                              const p3d_accumulate_motion* motion, float* out_rgb32f, float* out_length, float* out_moments,
+                              float* out_variance, float* out_prev_xy) {
+    accumulate_variance(*params, *variance_params, *frames, history, history_moments, motion, out_rgb32f, out_length, out_moments,
+                        out_variance, out_prev_xy);
 }
 
 // tile_coverage() of the host layer (tile_coverage_host.cpp): the level-1 launch's tile coverage mask for cam's frame over a

@@ -640,13 +640,28 @@ int renderFrames(const Scene& scene, const RenderOptions& opt, const std::vector
                                           opt.accumulate_max_history};
         const p3d_accumulate_frames af = {out.colors.data(), out.depth.data(), out.normal.data(), out.hit_id.data(), cams.data(), 0};
         const p3d_accumulate_outputs ao = {out.colors.data(), nullptr, 0};
-        if (opt.accumulate) rc = p3d_accumulate(dev, &ap, &af, nullptr, &ao);
+        const bool guided = opt.variance_guided && opt.accumulate && opt.denoise >= 0;
+        std::vector<float> variance(guided ? npx * n : 0);
+        if (guided) {                  // the same colour, and the variance of every pixel's luminance beside it
+            const p3d_accumulate_variance_params vp = {opt.variance_min_temporal, opt.variance_radius, opt.denoise_sigma_depth,
+                                                       opt.denoise_normal_power_log2};
+            std::vector<float> blended(npx * 3 * n);        // not in place: the spatial estimate reads the frames' own colour
+            const p3d_accumulate_variance_outputs vo = {blended.data(), nullptr, nullptr, variance.data(), nullptr, 0};
+            rc = p3d_accumulate_variance(dev, &ap, &vp, &af, nullptr, nullptr, nullptr, &vo);
+            out.colors.swap(blended);
+        } else if (opt.accumulate) rc = p3d_accumulate(dev, &ap, &af, nullptr, &ao);
         // one p3d_denoise call over all frames; 0 passes quantise the accumulated colour and filter nothing
         const p3d_denoise_params dp = {cams[0].res_x, cams[0].res_y, n, opt.denoise >= 0 ? opt.denoise : 0, opt.denoise_sigma_depth,
                                        opt.denoise_sigma_albedo, opt.denoise_sigma_color, opt.denoise_normal_power_log2};
         const p3d_denoise_inputs di = {out.colors.data(), out.depth.data(), out.normal.data(), out.albedo.data(), 0};
         const p3d_outputs filtered = {out.img_Data.data(), out.colors.data(), nullptr, 0};
-        if (!rc) rc = p3d_denoise(dev, &dp, &di, &filtered);
+        if (!rc && guided) {
+            p3d_denoise_params gp = dp;
+            gp.sigma_color = opt.variance_sigma_color;
+            const p3d_denoise_variance_inputs gi = {out.colors.data(), out.depth.data(), out.normal.data(), out.albedo.data(), variance.data(), 0};
+            const p3d_denoise_variance_outputs go = {out.img_Data.data(), out.colors.data(), nullptr, 0};
+            rc = p3d_denoise_variance(dev, &gp, &gi, &go);
+        } else if (!rc) rc = p3d_denoise(dev, &dp, &di, &filtered);
         if (!want_colors) out.colors.clear();
         if (!want_hit) out.hit_id.clear();
         out.depth.clear(); out.normal.clear(); out.albedo.clear();

@@ -244,6 +244,13 @@ struct RenderOptions {
     // p3d_denoise call over all of them).  The defaults are those of the Python binding (api.py, ACCUMULATE_*)
     bool accumulate = false;
     float accumulate_depth_tolerance = 0.05f, accumulate_normal_min = 0.9f, accumulate_max_history = 32.0f;
+    // renderFrames() with accumulate and denoise >= 0 both set: the accumulation also carries the luminance moments
+    // (p3d_accumulate_variance) and the filter is steered by the variance they give (p3d_denoise_variance, one call over all
+    // frames, its colour stop variance_sigma_color standard deviations wide instead of denoise_sigma_color).  Without both it
+    // changes nothing.  The defaults are those of the Python binding (api.py, VARIANCE_*)
+    bool variance_guided = false;
+    float variance_min_temporal = 4.0f, variance_sigma_color = 4.0f;
+    int variance_radius = 3;
     // renderScene() and renderFrames() on one GPU: > 0 runs p3d_ambient_occlusion with that many samples per pixel over the
     // frames' planes (accel as the frames', seed as theirs) and multiplies the float colour by it before the accumulator and
     // the filter read it; RenderResult::ao keeps the plane.  The defaults are those of the Python binding (api.py, AO_*)

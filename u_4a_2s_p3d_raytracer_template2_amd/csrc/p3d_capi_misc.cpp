@@ -400,6 +400,26 @@ int p3d_debug_denoise(int device, const p3d_denoise_params* params, const p3d_de
     });
 }
 
+int p3d_debug_denoise_variance(int device, const p3d_denoise_params* params, const p3d_denoise_variance_inputs* in,
+                               const p3d_denoise_variance_outputs* out) {
+    const char* why = "";
+    if (const int rc = denoise_variance_check_request(params, in, out, &why)) return fail(rc, why);
+    if (in->memory != 0 || out->memory != 0) return fail(P3D_ERR_ARG, "p3d_debug_denoise_variance takes host planes: memory must be 0");
+    const size_t px = (size_t)params->n_frames * (size_t)params->res_x * (size_t)params->res_y;
+    const int n_scratch = denoise_scratch_buffers(params->iterations, false);
+    // a plane that is not wanted (or a scratch buffer that is not needed) is one byte that nothing touches
+    DebugArg a[10] = {{in->rgb32f, nullptr, px * 12}, {in->depth, nullptr, px * 4}, {in->normal, nullptr, px * 12}, {in->albedo, nullptr, px * 12},
+                      {in->variance, nullptr, px * 4},
+                      {nullptr, nullptr, n_scratch > 0 ? px * 16 : 1}, {nullptr, nullptr, n_scratch > 1 ? px * 16 : 1},
+                      {nullptr, out->rgb32f, out->rgb32f ? px * 12 : 1}, {nullptr, out->rgb8, out->rgb8 ? px * 3 : 1},
+                      {nullptr, out->variance, out->variance ? px * 4 : 1}};
+    return debug_run("p3d_debug_denoise_variance", device, a, [&] {
+        return launch_denoise_variance(*params, a[0].as<float>(), a[1].as<float>(), a[2].as<float>(), a[3].as<float>(), a[4].as<float>(),
+                                       a[5].as<float>(), a[6].as<float>(), out->rgb32f ? a[7].as<float>() : nullptr,
+                                       out->rgb8 ? a[8].as<uint8_t>() : nullptr, out->variance ? a[9].as<float>() : nullptr, nullptr);
+    });
+}
+
 int p3d_debug_accumulate(int device, const p3d_accumulate_params* params, const p3d_accumulate_frames* frames,
                          const p3d_accumulate_history* history, const p3d_accumulate_outputs* out) {
     const char* why = "";
@@ -457,6 +477,48 @@ int p3d_debug_accumulate_moving(int device, const p3d_accumulate_params* params,
         const AccumulateMotion M = {motion->n_prims, a[13].as<uint32_t>(), a[14].as<float>(), history ? a[15].as<float>() : nullptr,
                                     out->prev_xy ? a[16].as<float>() : nullptr};
         return launch_accumulate_moving(*params, P, M, frames->cams, h.cam, nullptr);
+    });
+}
+
+int p3d_debug_accumulate_variance(int device, const p3d_accumulate_params* params, const p3d_accumulate_variance_params* variance_params,
+                                  const p3d_accumulate_frames* frames, const p3d_accumulate_history* history, const float* history_moments,
+                                  const p3d_accumulate_motion* motion, const p3d_accumulate_variance_outputs* out) {
+    const char* why = "";
+    if (const int rc = accumulate_variance_check_request(params, variance_params, frames, history, history_moments, motion, out, &why)) return fail(rc, why);
+    if (frames->memory != 0 || (history && history->memory != 0) || (motion && motion->memory != 0) || out->memory != 0)
+        return fail(P3D_ERR_ARG, "p3d_debug_accumulate_variance takes host planes: every memory field must be 0");
+    const size_t fr = (size_t)params->res_x * (size_t)params->res_y, px = fr * (size_t)params->n_frames, prims = motion ? motion->n_prims : 0;
+    const bool many = params->n_frames > 1;
+    const p3d_accumulate_history none = {};
+    const p3d_accumulate_history& h = history ? *history : none;
+    // host planes are staged apart, so no colour is blended in place: no detour
+    const size_t spare_c = (size_t)accumulate_variance_spare_colour_frames(*params, out->rgb32f, false);
+    const size_t spare_l = (size_t)accumulate_variance_spare_length_frames(*params, *variance_params, out->length, out->variance);
+    // a plane that is not there (or a spare that is not needed) is one byte that nothing touches
+    DebugArg a[21] = {{frames->rgb32f, nullptr, px * 12}, {frames->depth, nullptr, px * 4}, {frames->normal, nullptr, px * 12},
+                      {frames->hit_id, nullptr, frames->hit_id ? px * 4 : 1},
+                      {h.rgb32f, nullptr, history ? fr * 12 : 1}, {h.depth, nullptr, history ? fr * 4 : 1}, {h.normal, nullptr, history ? fr * 12 : 1},
+                      {h.length, nullptr, history ? fr * 4 : 1}, {h.hit_id, nullptr, h.hit_id ? fr * 4 : 1},
+                      {nullptr, out->rgb32f, out->rgb32f ? px * 12 : 1}, {nullptr, out->length, out->length ? px * 4 : 1},
+                      {nullptr, nullptr, spare_c ? spare_c * fr * 12 : 1}, {nullptr, nullptr, spare_l ? spare_l * fr * 4 : 1},
+                      {motion ? motion->prim_type : nullptr, nullptr, motion ? prims * 4 : 1},
+                      {motion ? motion->prim_data : nullptr, nullptr, motion ? prims * 48 * (size_t)params->n_frames : 1},
+                      {motion && history ? motion->history_prim_data : nullptr, nullptr, motion && history ? prims * 48 : 1},
+                      {nullptr, out->prev_xy, out->prev_xy ? px * 8 : 1},
+                      {history ? history_moments : nullptr, nullptr, history ? fr * 8 : 1},
+                      {nullptr, out->moments, out->moments ? px * 8 : 1}, {nullptr, out->variance, out->variance ? px * 4 : 1},
+                      {nullptr, nullptr, many && !out->moments ? 2 * fr * 8 : 1}};
+    return debug_run("p3d_debug_accumulate_variance", device, a, [&] {
+        const AccumulatePlanes P = {a[0].as<float>(), a[1].as<float>(), a[2].as<float>(), frames->hit_id ? a[3].as<int32_t>() : nullptr,
+                                    history ? a[4].as<float>() : nullptr, a[5].as<float>(), a[6].as<float>(), a[7].as<float>(),
+                                    h.hit_id ? a[8].as<int32_t>() : nullptr,
+                                    out->rgb32f ? a[9].as<float>() : nullptr, out->length ? a[10].as<float>() : nullptr,
+                                    a[11].as<float>(), a[12].as<float>()};
+        const AccumulateVariancePlanes VP = {history ? a[17].as<float>() : nullptr, out->moments ? a[18].as<float>() : nullptr,
+                                             out->variance ? a[19].as<float>() : nullptr, a[20].as<float>()};
+        const AccumulateMotion M = {motion ? motion->n_prims : 0, a[13].as<uint32_t>(), a[14].as<float>(), motion && history ? a[15].as<float>() : nullptr,
+                                    out->prev_xy ? a[16].as<float>() : nullptr};
+        return launch_accumulate_variance(*params, *variance_params, P, VP, motion ? &M : nullptr, frames->cams, h.cam, nullptr);
     });
 }
 

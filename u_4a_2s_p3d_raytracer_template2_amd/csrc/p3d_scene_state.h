@@ -229,10 +229,11 @@ struct p3d_scene {
     // p3d_generate_samples: jump tables and the summaries of the pass in flight (counted in device_bytes as they grow)
     p3d::SampleStreamScratch sample_stream;
     // p3d_denoise: the two colour buffers the passes alternate between, and the staging of host planes (all counted in
-    // device_bytes as they grow)
+    // device_bytes as they grow).  p3d_denoise_variance: the same, the scratch with the variance behind the colour.
     struct Denoise {
         p3d::RawBuf scratch[2];
         p3d::RawBuf in_rgb32f, in_depth, in_normal, in_albedo, out_rgb32f, out_rgb8;
+        p3d::RawBuf in_variance, out_variance;       // p3d_denoise_variance: the host variance planes
     } denoise;
     // p3d_accumulate: the staging of host planes (frames, history, outputs) and the two frames of an output plane the
     // caller does not want but the next frame reads (all counted in device_bytes as they grow).  No history is kept.
@@ -241,6 +242,7 @@ struct p3d_scene {
         p3d::RawBuf hist_rgb32f, hist_depth, hist_normal, hist_length, hist_hit_id;
         p3d::RawBuf out_rgb32f, out_length, spare_rgb32f, spare_length;
         p3d::RawBuf motion_type, motion_data, motion_hist, out_prev_xy;      // p3d_accumulate_moving: host geometry and the host prev_xy plane
+        p3d::RawBuf hist_moments, out_moments, out_variance, spare_moments;  // p3d_accumulate_variance: the host planes it adds, and the moments the caller does not want
     } accumulate;
     // p3d_ambient_occlusion: the staging of host planes and the frames' cameras (FrameCam records, written on the stream
     // by every call: launch_frame_cams); all counted in device_bytes as they grow.  Apart from the frames' frame_cams.
