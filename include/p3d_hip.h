@@ -924,6 +924,66 @@ typedef struct p3d_ao_outputs { float* ao; float* rgb32f; int32_t memory; } p3d_
  *  - on every refusal the outputs are untouched. */
 int p3d_ambient_occlusion(p3d_scene* scene, const p3d_camera* cams, int32_t n, const p3d_render_params* params,
                           const p3d_ao_params* ao, const p3d_ao_inputs* in, const p3d_ao_outputs* out);
+
+/* The edge-aware upsampler of p3d_render_aov's planes: a low-frequency signal (ambient occlusion, a soft shadow, a fuzzy
+ * reflection) computed at 1 / factor of the resolution is brought up to the full frame along the full frame's depth and
+ * normal (joint bilateral upsampling, Kopf et al. 2007). */
+typedef struct p3d_upsample_params {
+    int32_t res_x, res_y;        /* the LOW resolution, >= 1 each */
+    int32_t factor;              /* s = 1, 2, 3 or 4: the output is res_x * s by res_y * s */
+    int32_t n_frames;            /* >= 1, planes back to back as p3d_render_aov writes them */
+    int32_t channels;            /* c = 1 (an ao plane) or 3 (a colour) floats per pixel of `low` and of the output */
+    float   sigma_depth;         /* finite, > 0: the denoiser's relative depth stop */
+    int32_t normal_power_log2;   /* 0..8: the denoiser's */
+} p3d_upsample_params;
+typedef struct p3d_upsample_inputs  { const float *low, *low_depth, *low_normal, *depth, *normal; int32_t memory; } p3d_upsample_inputs;
+typedef struct p3d_upsample_outputs { float* plane; uint8_t* fallback; int32_t memory; } p3d_upsample_outputs;  /* either may be NULL, not both */
+/* The reference has no upsampler; the result is DEFINED here, as p3d_denoise's is: float32 IEEE-754 basic operations in a
+ * fixed order (no fused multiply-add, correctly rounded division, no exp and no pow), and the device, the host layer
+ * (p3dh_upsample) and tests/upsample_reference.py agree on it in every bit.
+ *  - planes: with s = factor, W = res_x * s and H = res_y * s, in->low is [n_frames][res_y][res_x][c], in->low_depth
+ *    [n_frames][res_y][res_x] and in->low_normal [n_frames][res_y][res_x][3]: the signal and the planes it was computed on;
+ *    in->depth [n_frames][H][W] and in->normal [n_frames][H][W][3]: the full frame's.  out->plane is [n_frames][H][W][c]
+ *    and out->fallback [n_frames][H][W] bytes.  Rows bottom row first, frames back to back -- what p3d_render_aov writes
+ *    with world == 1.  The low planes are those of a camera with the full frame's view window and res / s: pinhole_dir
+ *    puts pixel i of a res_x-wide camera at (i + 0.5) / res_x of the window, so low pixel i has its centre at
+ *    s * (i + 0.5) full-resolution pixels, and the full-resolution pixel x has its centre at x + 0.5.
+ *  - the filter, per full-resolution pixel (x, y) of frame f, with its own depth Z_p and normal N_p:
+ *      taps, per axis, in integers:  t = 2 x + 1 - s,  i0 = floor(t / (2 s))  (floor division: i0 = -1 occurs at the near
+ *      border),  r = t - 2 s i0  (in [0, 2 s)),  fx = (float)r / (float)(2 s).  The two taps of the axis are i0 with weight
+ *      bx0 = 1 - fx and i0 + 1 with weight bx1 = fx; y likewise (j0, by0, by1).  The four taps run dy = 0, 1 (outer),
+ *      dx = 0, 1 (inner), q = (i0 + dx, j0 + dy), b = bx * by.  A tap outside the low frame contributes nothing to any sum.
+ *      A depth is VALID when it is finite and > 0 (the denoiser's rule).
+ *      A valid centre: inv_z = 1 / (sigma_depth * Z_p); only taps with a valid Z_q contribute, with
+ *        wz = tz * tz,  tz = max(0, 1 - |Z_q - Z_p| * inv_z)
+ *        wn = max(0, (N_p.x N_q.x + N_p.y N_q.y) + N_p.z N_q.z), then wn = wn * wn, normal_power_log2 times
+ *        w  = (b * wz) * wn
+ *      A centre that is not valid (a miss: +inf; 0; NaN): only taps that are themselves NOT valid contribute, with w = b --
+ *      sky is made of sky.
+ *      sum += w * C_q per channel (a product, then a sum);  sw += w.  max(0, v) is v > 0 ? v : 0.
+ *      If sw > 0: out = sum / sw per channel and fallback = 0.  Otherwise no low sample explains the pixel (a thin feature,
+ *      a silhouette): out is the plain bilinear value -- the same sums over every tap inside the low frame with w = b, in
+ *      the same order, out = sum / sw -- and fallback = 1.  That sw is > 0: at least one tap inside the frame has b > 0.
+ *      Per axis i0 lies in -1 .. res_x - 1; both taps are inside unless i0 = -1, where r >= s + 1 makes bx1 > 0 on tap 0, or
+ *      i0 = res_x - 1, where r <= s - 1 makes bx0 >= 1 / 2 on tap res_x - 1; with both inside, bx0 or bx1 is >= 1 / 2.
+ *    Non-finite values in `low` give unspecified results.  Frames of a batch are independent.
+ *  - the fallback plane tells a caller which pixels to treat otherwise, for example to re-trace them with p3d_trace_rays.
+ *  - memory: in->memory and out->memory are 0 (host) or 1 (device), independently.  Host planes are staged in buffers the
+ *    handle owns (counted in p3d_scene_stats::device_bytes as they grow, kept for the next call, freed with the handle);
+ *    the call copies back and waits.  With everything in device memory the call only enqueues on the scene's stream: ONE
+ *    launch for all n_frames frames.
+ *  - stream capture: a call that has to allocate while the stream is being captured, or that has a plane in host memory,
+ *    is refused with P3D_ERR_STATE; the capture survives.  After a call of the same shape made before the capture, the
+ *    captured call is accepted and the graph replays.
+ *  - P3D_ERR_ARG: a NULL scene, params, in or out; any NULL input plane; both output planes NULL; factor outside 1..4;
+ *    channels not 1 or 3; res_x, res_y or n_frames below 1; sigma_depth not finite or not positive; normal_power_log2
+ *    outside 0..8; a memory field outside 0 and 1; an output plane that is an input plane.  P3D_ERR_LIMIT, before anything
+ *    is allocated, when n_frames * W * H * channels does not fit 31 bits.
+ *  - shards: the compact shards of world > 1 are not frames; stitch them with p3d_deinterleave[_frames] first.
+ *  - handle state: nothing of the handle's frame state changes -- the measured schedule choice, the learned tile orders,
+ *    p3d_last_schedule(), p3d_last_primary_tiles() and the ray-stream state are what they were.
+ *  - on every refusal the outputs are untouched. */
+int p3d_upsample(p3d_scene* scene, const p3d_upsample_params* params, const p3d_upsample_inputs* in, const p3d_upsample_outputs* out);
 int p3d_sync(p3d_scene* scene);
 /* counters of the most recent render made with P3D_FLAG_COUNTERS (waits for it) */
 int p3d_get_counters(p3d_scene* scene, p3d_counters* out);
@@ -1141,6 +1201,9 @@ int p3d_debug_denoise(int device, const p3d_denoise_params* params, const p3d_de
  * p3d_denoise_variance (in->memory or out->memory other than 0: P3D_ERR_ARG). */
 int p3d_debug_denoise_variance(int device, const p3d_denoise_params* params, const p3d_denoise_variance_inputs* in,
                                const p3d_denoise_variance_outputs* out);
+/* Likewise the launch of p3d_upsample (csrc/upsample.hip) over HOST planes, without a scene.  Refusals as p3d_upsample
+ * (in->memory or out->memory other than 0: P3D_ERR_ARG). */
+int p3d_debug_upsample(int device, const p3d_upsample_params* params, const p3d_upsample_inputs* in, const p3d_upsample_outputs* out);
 
 /* The launches of p3d_accumulate (csrc/accumulate.hip) run by the same function over HOST planes, without a scene: the
  * four structs as p3d_accumulate reads them, every memory field 0.  Synchronous; scratch is allocated for the call and

@@ -208,6 +208,30 @@ AO_RADIUS = 0.5
 AO_BIAS = 0.001
 
 
+class UpsampleParams(C.Structure):
+    """p3d_upsample_params: n_frames low frames of res_x x res_y back to back, brought up by factor 1..4; channels 1 or 3 floats
+    per pixel of the signal; the denoiser's depth stop and normal_power_log2 0..8 squarings of the normal weight."""
+    _fields_ = [("res_x", C.c_int32), ("res_y", C.c_int32), ("factor", C.c_int32), ("n_frames", C.c_int32), ("channels", C.c_int32),
+                ("sigma_depth", C.c_float), ("normal_power_log2", C.c_int32)]
+
+
+class UpsampleInputs(C.Structure):
+    """p3d_upsample_inputs: the low signal with the depth and normal it was computed on, and the full frame's depth and normal,
+    on the host (memory 0) or the scene's device (1)."""
+    _fields_ = [("low", C.c_void_p), ("low_depth", C.c_void_p), ("low_normal", C.c_void_p), ("depth", C.c_void_p), ("normal", C.c_void_p),
+                ("memory", C.c_int32)]
+
+
+class UpsampleOutputs(C.Structure):
+    """p3d_upsample_outputs: each plane may be NULL, not both."""
+    _fields_ = [("plane", C.c_void_p), ("fallback", C.c_void_p), ("memory", C.c_int32)]
+
+
+# p3d_upsample's defaults: the denoiser's stops
+UPSAMPLE_SIGMA_DEPTH = DENOISE_SIGMA_DEPTH
+UPSAMPLE_NORMAL_POWER_LOG2 = DENOISE_NORMAL_POWER_LOG2
+
+
 class PrimUpdate(C.Structure):
     """p3d_prim_update: n primitives to replace ([n][12] floats, optionally [n] scene indices) on the host (memory 0) or the
     scene's device (memory 1); lights: NULL or [n_lights][6] on the host."""
@@ -238,9 +262,9 @@ class SceneStats(C.Structure):
 
 # every symbol include/p3d_hip.h declares (tests check that the library exports them all)
 C_ABI_SYMBOLS = ["p3d_abi_version", "p3d_last_error", "p3d_device_count", "p3d_scene_create",
-                 "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_scene_update", "p3d_scene_rebuild", "p3d_scene_rebuild_with", "p3d_scene_last_builder", "p3d_scene_tree_cost", "p3d_scene_build_grid", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_render_aov", "p3d_generate_samples", "p3d_trace_rays", "p3d_occluded", "p3d_denoise", "p3d_denoise_variance", "p3d_accumulate", "p3d_accumulate_moving", "p3d_accumulate_variance", "p3d_ambient_occlusion", "p3d_sync",
+                 "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_scene_update", "p3d_scene_rebuild", "p3d_scene_rebuild_with", "p3d_scene_last_builder", "p3d_scene_tree_cost", "p3d_scene_build_grid", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_render_aov", "p3d_generate_samples", "p3d_trace_rays", "p3d_occluded", "p3d_denoise", "p3d_denoise_variance", "p3d_accumulate", "p3d_accumulate_moving", "p3d_accumulate_variance", "p3d_ambient_occlusion", "p3d_upsample", "p3d_sync",
                  "p3d_get_counters", "p3d_get_profile", "p3d_last_schedule", "p3d_set_tuning", "p3d_set_primary_tiles", "p3d_last_primary_tiles", "p3d_set_sky_tiles", "p3d_last_sky_tiles", "p3d_set_stream", "p3d_timer_begin", "p3d_timer_end", "p3d_deinterleave_frames",
-                 "p3d_deinterleave", "p3d_debug_intersect", "p3d_debug_powf", "p3d_debug_pow", "p3d_debug_schlick_kr", "p3d_debug_check_rcp", "p3d_debug_check_rcp_len", "p3d_debug_lbvh_build", "p3d_debug_ploc_build", "p3d_debug_grid_build", "p3d_debug_rand", "p3d_debug_sample_stream", "p3d_debug_denoise", "p3d_debug_denoise_variance", "p3d_debug_accumulate", "p3d_debug_accumulate_moving", "p3d_debug_accumulate_variance", "p3d_tune_schedule", "p3d_debug_set_stamps", "p3d_debug_set_stamp_level",
+                 "p3d_deinterleave", "p3d_debug_intersect", "p3d_debug_powf", "p3d_debug_pow", "p3d_debug_schlick_kr", "p3d_debug_check_rcp", "p3d_debug_check_rcp_len", "p3d_debug_lbvh_build", "p3d_debug_ploc_build", "p3d_debug_grid_build", "p3d_debug_rand", "p3d_debug_sample_stream", "p3d_debug_denoise", "p3d_debug_denoise_variance", "p3d_debug_accumulate", "p3d_debug_accumulate_moving", "p3d_debug_accumulate_variance", "p3d_debug_upsample", "p3d_tune_schedule", "p3d_debug_set_stamps", "p3d_debug_set_stamp_level",
                  "p3d_comm_unique_id", "p3d_comm_create", "p3d_comm_create_all", "p3d_comm_destroy", "p3d_comm_info",
                  "p3d_gather", "p3d_gather_all", "p3d_device_alloc", "p3d_device_free", "p3d_upload", "p3d_download"]
 
@@ -301,6 +325,11 @@ def lib():
     L.p3d_debug_denoise_variance.argtypes = [C.c_int, C.POINTER(DenoiseParams), C.POINTER(DenoiseVarianceInputs), C.POINTER(DenoiseVarianceOutputs)]
     L.p3dh_denoise_variance.argtypes = [C.POINTER(DenoiseParams)] + [C.c_void_p] * 8
     L.p3dh_denoise_variance.restype = None
+    _ups = [C.POINTER(UpsampleParams), C.POINTER(UpsampleInputs), C.POINTER(UpsampleOutputs)]
+    L.p3d_upsample.argtypes = [C.c_void_p] + _ups
+    L.p3d_debug_upsample.argtypes = [C.c_int] + _ups
+    L.p3dh_upsample.argtypes = [C.POINTER(UpsampleParams)] + [C.c_void_p] * 7
+    L.p3dh_upsample.restype = None
     _acc = [C.POINTER(AccumulateParams), C.POINTER(AccumulateFrames), C.POINTER(AccumulateHistory)]
     L.p3d_accumulate.argtypes = [C.c_void_p] + _acc + [C.POINTER(AccumulateOutputs)]
     L.p3d_debug_accumulate.argtypes = [C.c_int] + _acc + [C.POINTER(AccumulateOutputs)]
@@ -953,6 +982,27 @@ class DeviceScene:
         o = DenoiseVarianceOutputs(out_rgb8_ptr or None, out_rgb32f_ptr or None, out_variance_ptr or None, 1)
         _check(lib().p3d_denoise_variance(self.h, C.byref(p), C.byref(i), C.byref(o)), "p3d_denoise_variance")
 
+    def upsample(self, low, low_depth, low_normal, depth, normal, **kw):
+        """p3d_upsample on host arrays: low (n, h, w[, 3]) or (h, w[, 3]) with low_depth / low_normal, the planes it was
+        computed on, and depth / normal of the full frame, (n, h s, w s[, 3]) -- the factor s is read from the shapes.
+        Keywords: sigma_depth, normal_power_log2 (defaults: the UPSAMPLE_* constants).  Returns {"plane", "fallback"}: the
+        signal at the full resolution in the layout of low, and one byte per pixel, 1 where no low sample explained it."""
+        p, planes, out = _upsample_request(low, low_depth, low_normal, depth, normal, **kw)
+        i = UpsampleInputs(*[a.ctypes.data for a in planes], 0)
+        o = UpsampleOutputs(out["plane"].ctypes.data, out["fallback"].ctypes.data, 0)
+        _check(lib().p3d_upsample(self.h, C.byref(p), C.byref(i), C.byref(o)), "p3d_upsample")
+        return out
+
+    def upsample_device(self, res_x, res_y, factor, low_ptr, low_depth_ptr, low_normal_ptr, depth_ptr, normal_ptr, out_plane_ptr=0,
+                        out_fallback_ptr=0, n_frames=1, channels=1, sigma_depth=UPSAMPLE_SIGMA_DEPTH,
+                        normal_power_log2=UPSAMPLE_NORMAL_POWER_LOG2):
+        """Enqueue p3d_upsample on caller-owned DEVICE buffers (raw pointers; an output of 0 = no such plane); res_x, res_y are
+        the LOW resolution; asynchronous on the scene's stream."""
+        p = UpsampleParams(int(res_x), int(res_y), int(factor), int(n_frames), int(channels), sigma_depth, int(normal_power_log2))
+        i = UpsampleInputs(low_ptr or None, low_depth_ptr or None, low_normal_ptr or None, depth_ptr or None, normal_ptr or None, 1)
+        o = UpsampleOutputs(out_plane_ptr or None, out_fallback_ptr or None, 1)
+        _check(lib().p3d_upsample(self.h, C.byref(p), C.byref(i), C.byref(o)), "p3d_upsample")
+
     def accumulate(self, rgb32f, depth, normal, cams, hit_id=None, history=None, **kw):
         """p3d_accumulate on host arrays: the frames of a sequence, rgb32f / normal (n, H, W, 3) or (H, W, 3), depth and hit_id
         (n, H, W) or (H, W) as render_aov returns them, cams one Camera per frame.  history: None, or a dict with rgb32f,
@@ -1272,6 +1322,46 @@ def debug_denoise(rgb32f, depth, normal, albedo, device=0, **kw):
     i = DenoiseInputs(*[a.ctypes.data for a in planes], 0)
     o = Outputs(out["rgb8"].ctypes.data, out["rgb32f"].ctypes.data, None, 0)
     _check(lib().p3d_debug_denoise(int(device), C.byref(p), C.byref(i), C.byref(o)), "p3d_debug_denoise")
+    return out
+
+
+def _upsample_request(low, low_depth, low_normal, depth, normal, sigma_depth=UPSAMPLE_SIGMA_DEPTH,
+                      normal_power_log2=UPSAMPLE_NORMAL_POWER_LOG2):
+    """Host planes of one frame or n frames -> (UpsampleParams, the five contiguous float32 planes, the zeroed outputs)."""
+    lz = np.ascontiguousarray(low_depth, np.float32)
+    z = np.ascontiguousarray(depth, np.float32)
+    if lz.ndim not in (2, 3) or z.ndim != lz.ndim:
+        raise ValueError("low_depth and depth must both be (h, w) or (n, h, w)")
+    n, (h, w), (H, W) = (1 if lz.ndim == 2 else lz.shape[0]), lz.shape[-2:], z.shape[-2:]
+    s = W // w if w else 0
+    if s < 1 or (W, H) != (w * s, h * s) or (z.ndim == 3 and z.shape[0] != n):
+        raise ValueError("depth must be low_depth's shape times one integer factor")
+    lo = np.ascontiguousarray(low, np.float32)
+    c = 3 if lo.ndim == lz.ndim + 1 else 1
+    ln = np.ascontiguousarray(low_normal, np.float32)
+    nr = np.ascontiguousarray(normal, np.float32)
+    if lo.size != lz.size * c or (c == 3 and lo.shape[-1] != 3) or ln.size != lz.size * 3 or nr.size != z.size * 3:
+        raise ValueError("low must be low_depth's shape (optionally with 3 channels), the normals their depth's shape with 3")
+    p = UpsampleParams(w, h, s, n, c, sigma_depth, int(normal_power_log2))
+    out = {"plane": np.zeros(z.shape + ((3,) if c == 3 else ()), np.float32), "fallback": np.zeros(z.shape, np.uint8)}
+    return p, (lo, lz, ln, z, nr), out
+
+
+def host_upsample(low, low_depth, low_normal, depth, normal, **kw):
+    """p3dh_upsample: the host layer's restatement of p3d_upsample, every bit of it, on host arrays (no GPU).  Arguments and
+    result as DeviceScene.upsample."""
+    p, planes, out = _upsample_request(low, low_depth, low_normal, depth, normal, **kw)
+    lib().p3dh_upsample(C.byref(p), *[a.ctypes.data for a in planes], out["plane"].ctypes.data, out["fallback"].ctypes.data)
+    return out
+
+
+def debug_upsample(low, low_depth, low_normal, depth, normal, device=0, **kw):
+    """p3d_debug_upsample: the launch of p3d_upsample over host arrays, without a scene.  Arguments and result as
+    DeviceScene.upsample."""
+    p, planes, out = _upsample_request(low, low_depth, low_normal, depth, normal, **kw)
+    i = UpsampleInputs(*[a.ctypes.data for a in planes], 0)
+    o = UpsampleOutputs(out["plane"].ctypes.data, out["fallback"].ctypes.data, 0)
+    _check(lib().p3d_debug_upsample(int(device), C.byref(p), C.byref(i), C.byref(o)), "p3d_debug_upsample")
     return out
 
 

@@ -16,6 +16,7 @@
 #include "denoise_host.h"
 #include "p3d_scene.h"
 #include "tile_coverage_host.h"
+#include "upsample_host.h"
 
 using namespace p3d_host;
 
@@ -115,6 +116,13 @@ void p3dh_denoise(const p3d_denoise_params* params, const float* rgb32f, const f
 void p3dh_denoise_variance(const p3d_denoise_params* params, const float* rgb32f, const float* depth, const float* normal,
                            const float* albedo, const float* variance, float* out_rgb32f, uint8_t* out_rgb8, float* out_variance) {
     denoise_variance(*params, rgb32f, depth, normal, albedo, variance, out_rgb32f, out_rgb8, out_variance);
+}
+
+// upsample() of the host layer (upsample_host.cpp): p3d_upsample's result on host planes, every bit.  out_plane / out_fallback
+// may each be NULL.  The caller keeps params inside the ranges p3d_upsample accepts.
+void p3dh_upsample(const p3d_upsample_params* params, const float* low, const float* low_depth, const float* low_normal, const float* depth,
+                   const float* normal, float* out_plane, uint8_t* out_fallback) {
+    upsample(*params, low, low_depth, low_normal, depth, normal, out_plane, out_fallback);
 }
 
 // ao_segments() / ao_resolve() of the host layer (ao_host.cpp): steps 1 to 6 and step 8 of p3d_ambient_occlusion's definition

@@ -481,13 +481,45 @@ int modulate_by_ao(p3d_scene* dev, const RenderOptions& opt, const p3d_camera* c
     memset(&prm, 0, sizeof prm);
     prm.accel = accel; prm.world = 1;
     const p3d_ao_params ap = {opt.ambient_occlusion, opt.ao_radius, opt.ao_bias, opt.seed};
-    std::vector<float> lit(out.colors.size());
     out.ao.assign(out.depth.size(), 1.0f);
+    if (opt.ao_scale > 1) {            // the plane at res / ao_scale, brought up along the frames' own depth and normal
+        const int s = opt.ao_scale;
+        std::vector<p3d_camera> low_cams(cams, cams + n);
+        for (p3d_camera& c : low_cams) { c.res_x /= s; c.res_y /= s; }
+        const size_t low_px = (size_t)low_cams[0].res_x * low_cams[0].res_y * n;
+        std::vector<float> low_depth(low_px), low_normal(low_px * 3), low_ao(low_px);
+        p3d_render_params low_prm = prm;
+        low_prm.max_depth = 1; low_prm.row_block = 16;
+        const p3d_outputs no_colour = {nullptr, nullptr, nullptr, 0};
+        const p3d_aov_outputs planes = {low_depth.data(), low_normal.data(), nullptr};
+        int rc = p3d_render_aov(dev, low_cams.data(), n, &low_prm, &no_colour, &planes);
+        if (rc) return rc;
+        const p3d_ao_inputs in = {low_depth.data(), low_normal.data(), nullptr, 0};
+        const p3d_ao_outputs o = {low_ao.data(), nullptr, 0};
+        if ((rc = p3d_ambient_occlusion(dev, low_cams.data(), n, &prm, &ap, &in, &o)) != 0) return rc;
+        const p3d_upsample_params up = {low_cams[0].res_x, low_cams[0].res_y, s, n, 1, opt.denoise_sigma_depth, opt.denoise_normal_power_log2};
+        const p3d_upsample_inputs ui = {low_ao.data(), low_depth.data(), low_normal.data(), out.depth.data(), out.normal.data(), 0};
+        const p3d_upsample_outputs uo = {out.ao.data(), nullptr, 0};
+        if ((rc = p3d_upsample(dev, &up, &ui, &uo)) != 0) return rc;
+        for (size_t i = 0; i < out.ao.size(); i++)
+            for (int c = 0; c < 3; c++) out.colors[3 * i + c] = out.ao[i] * out.colors[3 * i + c];
+        return P3D_OK;
+    }
+    std::vector<float> lit(out.colors.size());
     const p3d_ao_inputs in = {out.depth.data(), out.normal.data(), out.colors.data(), 0};
     const p3d_ao_outputs o = {out.ao.data(), lit.data(), 0};
     const int rc = p3d_ambient_occlusion(dev, cams, n, &prm, &ap, &in, &o);
     if (!rc) out.colors.swap(lit);
     return rc;
+}
+
+// RenderOptions::ao_scale against the frame: "" or why the call is refused
+const char* ao_scale_refusal(const RenderOptions& opt, int res_x, int res_y) {
+    if (opt.ao_scale == 1) return "";
+    if (opt.ambient_occlusion < 1) return "ao_scale needs ambient_occlusion";
+    if (opt.ao_scale < 1 || opt.ao_scale > 4) return "ao_scale must be in 1..4";
+    if (res_x % opt.ao_scale || res_y % opt.ao_scale) return "ao_scale must divide both resolutions";
+    return "";
 }
 
 }  // namespace
@@ -503,6 +535,7 @@ int renderScene(const Scene& scene, const RenderOptions& opt, bool want_colors, 
     scene.flatten(flat);
     p3d_camera cam;
     scene.GetCamera()->describe(&cam);
+    if (const char* why = ao_scale_refusal(opt, cam.res_x, cam.res_y); *why) { if (err) *err = why; return P3D_ERR_ARG; }
     p3d_render_params prm;
     memset(&prm, 0, sizeof prm);
     prm.max_depth = opt.max_depth;
@@ -594,6 +627,7 @@ int renderFrames(const Scene& scene, const RenderOptions& opt, const std::vector
     std::vector<p3d_camera> cams((size_t)n);
     Camera cam = *scene.GetCamera();
     for (int f = 0; f < n; f++) { cam.SetEye(eyes[f]); cam.describe(&cams[f]); }
+    if (const char* why = ao_scale_refusal(opt, cams[0].res_x, cams[0].res_y); *why) { if (err) *err = why; return P3D_ERR_ARG; }
     Scene::Flat flat;
     scene.flatten(flat);
     p3d_render_params prm;

@@ -256,6 +256,11 @@ struct RenderOptions {
     // the filter read it; RenderResult::ao keeps the plane.  The defaults are those of the Python binding (api.py, AO_*)
     int ambient_occlusion = 0;
     float ao_radius = 0.5f, ao_bias = 0.001f;
+    // ... at 1 / ao_scale of the resolution: 1 is the path above, untouched.  2, 3 or 4 (it must divide both resolutions) renders
+    // the primary hits' depth and normal once more at res / ao_scale (the same view window, max_depth 1), runs
+    // p3d_ambient_occlusion on those and brings the plane up along the frames' own depth and normal with p3d_upsample
+    // (denoise_sigma_depth, denoise_normal_power_log2); the colour is multiplied by the upsampled plane
+    int ao_scale = 1;
 };
 struct RenderResult {
     std::vector<uint8_t> img_Data;   // RGB8, bottom row first (RT/main.cpp:76)

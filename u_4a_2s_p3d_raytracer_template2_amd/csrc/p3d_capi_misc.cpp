@@ -4,6 +4,7 @@
 
 #include "accumulate.h"
 #include "denoise.h"
+#include "upsample.h"
 #include "grid_device.h"
 #include "p3d_scene_state.h"
 
@@ -417,6 +418,22 @@ int p3d_debug_denoise_variance(int device, const p3d_denoise_params* params, con
         return launch_denoise_variance(*params, a[0].as<float>(), a[1].as<float>(), a[2].as<float>(), a[3].as<float>(), a[4].as<float>(),
                                        a[5].as<float>(), a[6].as<float>(), out->rgb32f ? a[7].as<float>() : nullptr,
                                        out->rgb8 ? a[8].as<uint8_t>() : nullptr, out->variance ? a[9].as<float>() : nullptr, nullptr);
+    });
+}
+
+int p3d_debug_upsample(int device, const p3d_upsample_params* params, const p3d_upsample_inputs* in, const p3d_upsample_outputs* out) {
+    const char* why = "";
+    if (const int rc = upsample_check_request(params, in, out, &why)) return fail(rc, why);
+    if (in->memory != 0 || out->memory != 0) return fail(P3D_ERR_ARG, "p3d_debug_upsample takes host planes: memory must be 0");
+    const size_t low_px = (size_t)params->n_frames * (size_t)params->res_x * (size_t)params->res_y;
+    const size_t px = low_px * (size_t)params->factor * (size_t)params->factor, c = (size_t)params->channels;
+    // a plane that is not wanted is one byte that nothing touches
+    DebugArg a[7] = {{in->low, nullptr, low_px * c * 4}, {in->low_depth, nullptr, low_px * 4}, {in->low_normal, nullptr, low_px * 12},
+                     {in->depth, nullptr, px * 4}, {in->normal, nullptr, px * 12},
+                     {nullptr, out->plane, out->plane ? px * c * 4 : 1}, {nullptr, out->fallback, out->fallback ? px : 1}};
+    return debug_run("p3d_debug_upsample", device, a, [&] {
+        return launch_upsample(*params, a[0].as<float>(), a[1].as<float>(), a[2].as<float>(), a[3].as<float>(), a[4].as<float>(),
+                               out->plane ? a[5].as<float>() : nullptr, out->fallback ? a[6].as<uint8_t>() : nullptr, nullptr);
     });
 }
 
