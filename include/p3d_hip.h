@@ -1030,6 +1030,48 @@ int p3d_set_sky_tiles(p3d_scene* scene, int32_t on);
  * and before the first render. */
 int p3d_last_sky_tiles(p3d_scene* scene, int32_t* used, int32_t* empty_tiles);
 
+/* Reflection children that the Fresnel term multiplies by zero, a switch that changes no bit of a frame of a finite scene:
+ * the reference computes KR = 1 / 2 * (R0 + R1) for every material with T != 0 -- an integer division, so KR is +0 (SURVEY
+ * Q5) -- and a node returns color + reflection_color * KR * spec + refraction_color * (1 - KR).  on = 1: a node whose
+ * material has T != 0 spawns no reflection child; the child's closest-hit walk, its shadow queries and its whole subtree are
+ * skipped, and the node adds the zero the reference adds for a child it never traced.  A finite child colour times +0 is a
+ * zero of either sign, and the sum it goes into is added to a colour that is never -0: the node keeps every bit
+ * (finding 5).
+ *  - applies to every entry that shades -- p3d_render, p3d_render_frames, p3d_render_aov, p3d_trace_rays --, on all three
+ *    schedules, with samples and without, with either scene placement.  The kernels read the switch in the scene's
+ *    material records (no launch parameter, no instruction in the kernels that prune): a call that changes the setting
+ *    BLOCKS -- it queues the rewritten records on the scene's stream behind the frames in flight and returns when the
+ *    copy has been made (frames queued on a stream the scene used before a p3d_set_stream are the caller's to wait for)
+ *    --, and a captured frame replays with the setting in force when it is replayed.
+ *  - never applies to frames with P3D_FLAG_COUNTERS (their ray counts stay the reference's) or P3D_FEATURE_SCHLICK
+ *    (SCHLICK_APPROX makes KR non-zero): they trace every ray whatever is set here.
+ *  - the one exception: a skipped subtree that would have returned an infinite or NaN component.  The reference's pixel is
+ *    then NaN (inf * 0) and the pruned frame's is not.  Finite rays meet that only through non-finite or overflowing scene
+ *    data or a degenerate configuration (a zero-radius sphere, a zero-area triangle, a hit point that coincides with a
+ *    light, L + V == 0 under a specular material): results for those are unspecified here as they are after a
+ *    p3d_scene_update with non-finite data.  What p3d_scene_create can see of it -- a material, light or background
+ *    component or a flattened triangle / plane normal that is not finite -- keeps the switch off for the handle's
+ *    lifetime: p3d_get_prune_reflections() reports 0 whatever was set.
+ *  - default: see kDefaultPruneReflections (csrc/p3d_kernel_variant.h) and profiles/prune_reflections.txt;
+ *    P3D_PRUNE_REFLECTIONS=0 / 1 in the environment sets it for every scene created afterwards.
+ * The schedule choice of the handle is measured again after a change.  P3D_ERR_ARG: a NULL scene, on outside 0 and 1.
+ * P3D_ERR_STATE: a change while the scene's stream is being captured. */
+int p3d_set_prune_reflections(p3d_scene* scene, int32_t on);
+/* *on = 1 if frames of this scene prune: the switch is on and the scene was finite when it was created. */
+int p3d_get_prune_reflections(const p3d_scene* scene, int32_t* on);
+/* Closest-hit rays queued per tree level by the most recent wavefront-schedule frame (p3d_render, p3d_render_frames,
+ * p3d_render_aov) or ray stream (p3d_trace_rays) of this scene: counts[l - 1] = rays of level l for l = 1 .. min(n,
+ * max_depth), zero beyond; 1 <= n <= 16.  Level 1 is the frame's camera rays (the stream's rays); a deeper level is the sum
+ * of the shard counters its launch read, which stay on the device until the handle's next wavefront pass.  On the last level
+ * of a frame with max_depth >= 2 a node's two children travel as a pair of slots and the figure counts slots: twice the
+ * nodes of level max_depth - 1 that have a child, an absent sibling included.  Waits for the scene's stream.
+ * P3D_ERR_STATE: while the stream is being captured; before the first such frame; when the most recent p3d_render* call ran
+ * the tile or the tree schedule; when the frame ran more passes than it has sets of counters (one per concurrent pass, four:
+ * a frame of up to four sample passes or bands is summed over them, one of more -- spp >= 3, or a frame cut into many bands
+ * because its queues exceed the workspace budget -- has lost its earlier passes).  P3D_ERR_ARG: a NULL argument, n outside
+ * 1..16. */
+int p3d_last_level_rays(p3d_scene* scene, uint32_t* counts, int32_t n);
+
 /* Elapsed device time of the most recent render made with P3D_FLAG_PROFILE (waits for it):
  * the whole frame (all launches of the call, samples and bands included) and its dominant
  * kernel alone -- wf_primary_kernel, or whitted_tree_kernel with P3D_FLAG_TREE_KERNEL -- for

@@ -263,7 +263,7 @@ class SceneStats(C.Structure):
 # every symbol include/p3d_hip.h declares (tests check that the library exports them all)
 C_ABI_SYMBOLS = ["p3d_abi_version", "p3d_last_error", "p3d_device_count", "p3d_scene_create",
                  "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_scene_update", "p3d_scene_rebuild", "p3d_scene_rebuild_with", "p3d_scene_last_builder", "p3d_scene_tree_cost", "p3d_scene_build_grid", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_render_aov", "p3d_generate_samples", "p3d_trace_rays", "p3d_occluded", "p3d_denoise", "p3d_denoise_variance", "p3d_accumulate", "p3d_accumulate_moving", "p3d_accumulate_variance", "p3d_ambient_occlusion", "p3d_upsample", "p3d_sync",
-                 "p3d_get_counters", "p3d_get_profile", "p3d_last_schedule", "p3d_set_tuning", "p3d_set_primary_tiles", "p3d_last_primary_tiles", "p3d_set_sky_tiles", "p3d_last_sky_tiles", "p3d_set_stream", "p3d_timer_begin", "p3d_timer_end", "p3d_deinterleave_frames",
+                 "p3d_get_counters", "p3d_get_profile", "p3d_last_schedule", "p3d_set_tuning", "p3d_set_primary_tiles", "p3d_last_primary_tiles", "p3d_set_sky_tiles", "p3d_last_sky_tiles", "p3d_set_prune_reflections", "p3d_get_prune_reflections", "p3d_last_level_rays", "p3d_set_stream", "p3d_timer_begin", "p3d_timer_end", "p3d_deinterleave_frames",
                  "p3d_deinterleave", "p3d_debug_intersect", "p3d_debug_powf", "p3d_debug_pow", "p3d_debug_schlick_kr", "p3d_debug_check_rcp", "p3d_debug_check_rcp_len", "p3d_debug_lbvh_build", "p3d_debug_ploc_build", "p3d_debug_grid_build", "p3d_debug_rand", "p3d_debug_sample_stream", "p3d_debug_denoise", "p3d_debug_denoise_variance", "p3d_debug_accumulate", "p3d_debug_accumulate_moving", "p3d_debug_accumulate_variance", "p3d_debug_upsample", "p3d_tune_schedule", "p3d_debug_set_stamps", "p3d_debug_set_stamp_level",
                  "p3d_comm_unique_id", "p3d_comm_create", "p3d_comm_create_all", "p3d_comm_destroy", "p3d_comm_info",
                  "p3d_gather", "p3d_gather_all", "p3d_device_alloc", "p3d_device_free", "p3d_upload", "p3d_download"]
@@ -362,6 +362,9 @@ def lib():
     L.p3d_last_primary_tiles.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     L.p3d_set_sky_tiles.argtypes = [C.c_void_p, C.c_int32]
     L.p3d_last_sky_tiles.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.p3d_set_prune_reflections.argtypes = [C.c_void_p, C.c_int32]
+    L.p3d_get_prune_reflections.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+    L.p3d_last_level_rays.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_int32]
     L.p3dh_tile_coverage.argtypes = [C.POINTER(Camera), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(SceneDesc), C.c_void_p]
     L.p3dh_tile_coverage.restype = C.c_int32
     L.p3d_timer_begin.argtypes = [C.c_void_p]
@@ -750,6 +753,24 @@ class DeviceScene:
         used, empty = C.c_int32(), C.c_int32()
         _check(lib().p3d_last_sky_tiles(self.h, C.byref(used), C.byref(empty)), "p3d_last_sky_tiles")
         return bool(used.value), empty.value
+
+    def set_prune_reflections(self, on):
+        """p3d_set_prune_reflections: transmissive nodes spawn no reflection child (the reference scales it by KR = +0).
+        Never changes a frame of a finite scene; counting and Schlick frames trace every ray whatever is set."""
+        _check(lib().p3d_set_prune_reflections(self.h, 1 if on else 0), "p3d_set_prune_reflections")
+
+    def prune_reflections(self):
+        """Whether frames of this scene prune: the switch is on and the scene was finite when it was created."""
+        v = C.c_int32()
+        _check(lib().p3d_get_prune_reflections(self.h, C.byref(v)), "p3d_get_prune_reflections")
+        return bool(v.value)
+
+    def last_level_rays(self, n=16):
+        """p3d_last_level_rays: closest-hit rays queued per tree level (index 0 = level 1) by the most recent
+        wavefront-schedule frame or ray stream, as a uint32 array of n entries.  Waits for the stream."""
+        v = (C.c_uint32 * int(n))()
+        _check(lib().p3d_last_level_rays(self.h, v, int(n)), "p3d_last_level_rays")
+        return np.array(list(v), np.uint32)
 
     def sync(self):
         _check(lib().p3d_sync(self.h), "p3d_sync")

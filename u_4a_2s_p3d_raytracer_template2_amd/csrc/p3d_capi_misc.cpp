@@ -134,6 +134,33 @@ int p3d_last_sky_tiles(p3d_scene* s, int32_t* used, int32_t* empty_tiles) {
     return P3D_OK;
 }
 
+// The shard counters the level launches of a wavefront pass keep stay on the device until the next pass's level-1 launch
+// clears them (LaunchParams::wf_alt): they are read back here, after the stream has passed, and nowhere on a frame's own path.
+int p3d_last_level_rays(p3d_scene* s, uint32_t* counts, int32_t n) {
+    if (!s || !counts) return fail(P3D_ERR_ARG, "NULL argument");
+    if (n < 1 || n > kMaxDepth) return fail(P3D_ERR_ARG, "n must be in 1..16");
+    if (!s->last_wf.valid) return fail(P3D_ERR_STATE, "the handle's most recent frame did not run the wavefront schedule (or there is none yet)");
+    if (s->last_wf.passes > (size_t)s->last_wf.lanes)
+        return fail(P3D_ERR_STATE, "the frame ran several passes over the same counters (sample passes or bands): only its last pass is on the device");
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(s->stream, &cap);
+    if (cap != hipStreamCaptureStatusNone) return fail(P3D_ERR_STATE, "p3d_last_level_rays waits for the stream: not while it is being captured");
+    HIP_TRY(hipSetDevice(s->device));
+    for (int32_t i = 0; i < n; i++) counts[i] = 0u;
+    std::vector<uint32_t> w(kCountBufferWords);
+    for (size_t ln = 0; ln < s->last_wf.passes; ln++) {          // (the joined lanes' launches are in front of the stream's tail)
+        HIP_TRY(hipMemcpyAsync(w.data(), s->ws[ln].counts.p, w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+        const uint32_t par = w[kCountWords + 4 * kShards + 32] & 1u;     // the set this pass's launches used (wf_ctrl[32])
+        for (int l = 2; l <= s->last_wf.D && l <= n; l++) {
+            const uint32_t* q = l == 2 ? w.data() + kCountWords + (size_t)(par * 2u) * kShards : w.data() + (size_t)l * kShards;
+            for (int sh = 0; sh < kShards; sh++) counts[l - 1] += q[sh];
+        }
+    }
+    counts[0] = (uint32_t)std::min<uint64_t>(s->last_wf.level1, 0xFFFFFFFFull);
+    return P3D_OK;
+}
+
 int p3d_timer_begin(p3d_scene* s) {
     if (!s) return fail(P3D_ERR_ARG, "scene is NULL");
     HIP_TRY(hipSetDevice(s->device));

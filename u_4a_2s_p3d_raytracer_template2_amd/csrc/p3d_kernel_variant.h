@@ -38,6 +38,10 @@ constexpr int kDefaultPrimaryTiles = 2;
 // whether a handle gives the frames of those kernels a tile coverage mask (p3d_tile_coverage.h) until p3d_set_sky_tiles()
 // says otherwise; the measurement behind the value is profiles/sky_tiles.txt
 constexpr bool kDefaultSkyTiles = true;
+// whether a handle leaves out the reflection children that KR = 1 / 2 * (R0 + R1) = +0 scales to nothing (p3d_shade.h:
+// shade_hit) until p3d_set_prune_reflections() says otherwise; the measurement behind the value is
+// profiles/prune_reflections.txt
+constexpr bool kDefaultPruneReflections = true;
 
 // Several tiles per workgroup are built for the level-1 kernel of scenes served from LDS, walked per lane, and there only
 // for the timed builds without features: the variant exists to spread a workgroup's fixed cost (scene copy, launch

@@ -749,6 +749,19 @@ int run_wavefront(p3d_scene* s, const FrameConfig& cfg, FramePlan& plan, size_t 
             if (rc) return rc;
         }
     }
+    {   // what p3d_last_level_rays() needs to read the lanes' counters by (nothing is read back on a frame's own path)
+        uint64_t level1 = plan.rays ? plan.rays->count : 0;
+        if (!plan.rays) {
+            uint64_t rows = 0;                             // rows of the compact buffer that are rows of the image (image_row())
+            for (int r = 0; r < cfg.frame_rows; r++) {
+                const int blk = r / P.row_block;
+                if ((blk * P.world + P.rank) * P.row_block + (r - blk * P.row_block) < P.res_y) rows++;
+            }
+            level1 = rows * (uint64_t)cfg.n_frames * (uint64_t)P.res_x * (uint64_t)P.wf_nsamples;
+        }
+        s->last_wf.valid = true; s->last_wf.D = D; s->last_wf.lanes = lanes; s->last_wf.passes = (size_t)task;
+        s->last_wf.level1 = level1;
+    }
     for (int ln = 1; ln < lanes; ln++) {               // ... and the stream continues after all of them
         HIP_TRY(hipEventRecord(s->ev_join[ln], s->lane_stream[ln]));
         HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_join[ln], 0));
@@ -836,6 +849,7 @@ int render_batch(p3d_scene* s, const p3d_camera* cams, int32_t n_frames, const p
     s->last_schedule = sched;
     s->last_primary_tiles = 1;          // (the wavefront schedule says what its level-1 launch ran with)
     s->last_sky.on = false;             // (... and whether the frame had a tile coverage mask)
+    s->last_wf.valid = false;           // (... and what p3d_last_level_rays() may read: run_wavefront)
     LaunchParams& P = plan.P;
     const size_t lds = sched == SCHED_TREE   ? tree_kernel_lds_bytes(P, plan.lds_scene)
                        : sched == SCHED_TILE ? tile_kernel_lds_bytes(plan.PT, plan.lds_scene)

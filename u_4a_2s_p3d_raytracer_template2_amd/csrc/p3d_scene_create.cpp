@@ -13,6 +13,19 @@
 
 using namespace p3d;
 
+namespace {
+// The materials as the scene blob holds them.  shade_hit() (p3d_shade.h) spawns a reflection child where refl > 0; a
+// material with T != 0 gets its refl negated while the handle prunes (p3d_set_prune_reflections), which the builds that must
+// trace the child anyway -- counting, Schlick -- read as set.  So that a negative refl of such a material can only mean
+// that, one the caller gave (never a reflection, like zero) is stored as zero.
+std::vector<MaterialRec> encoded_materials(const std::vector<MaterialRec>& mats, bool prune) {
+    std::vector<MaterialRec> out = mats;
+    for (MaterialRec& m : out)
+        if (m.T != 0.0f) m.refl = m.refl > 0.0f ? (prune ? -m.refl : m.refl) : 0.0f;
+    return out;
+}
+}  // namespace
+
 extern "C" {
 
 int p3d_scene_create(const p3d_scene_desc* d, const p3d_build_opts* opts, int device, p3d_scene** out) {
@@ -99,6 +112,21 @@ int p3d_scene_create(const p3d_scene_desc* d, const p3d_build_opts* opts, int de
     if (const char* e = getenv("P3D_OCC")) { int v = atoi(e); if (v == 0 || v == 5 || v == 6) s->occupancy = v; }
     if (const char* e = getenv("P3D_PRIMARY_TILES")) { int v = atoi(e); if (v >= 1 && v <= kMaxPrimaryTiles) s->primary_tiles = v; }
     if (const char* e = getenv("P3D_SKY_TILES")) s->sky_tiles = atoi(e) != 0;
+    if (const char* e = getenv("P3D_PRUNE_REFLECTIONS")) s->prune_reflections = atoi(e) != 0;
+    {   // p3d_set_prune_reflections applies to finite scenes only: what the host can see of that, it checks here, once
+        bool finite = std::isfinite(d->background[0]) && std::isfinite(d->background[1]) && std::isfinite(d->background[2]);
+        auto all_finite = [&](const float* p, size_t n) { for (size_t i = 0; i < n; i++) finite = finite && std::isfinite(p[i]); };
+        // (a negative shininess: powf(+0, shine) is +inf where the half vector is at right angles to the normal)
+        for (const MaterialRec& m : mats) { all_finite(reinterpret_cast<const float*>(&m), sizeof(MaterialRec) / sizeof(float)); finite = finite && !(m.shine < 0.0f); }
+        for (const LightRec& l : lights) { all_finite(l.pos, 3); all_finite(l.col, 3); }
+        for (const TriRec& t : tris) all_finite(t.n, 3);                 // (a zero-area triangle's is NaN)
+        for (const PlaneRec& p : planes) {                               // (normalised per hit: a zero normal becomes NaN there)
+            const float n[3] = {p.nx, p.ny, p.nz};
+            all_finite(n, 3);
+            finite = finite && (p.nx != 0.0f || p.ny != 0.0f || p.nz != 0.0f);
+        }
+        s->finite_scene = finite;
+    }
     if (const char* e = getenv("P3D_TRI_STRIDE")) s->tri_quads = atoi(e) == 64 ? 4u : 3u;
     if (const char* e = getenv("P3D_SHARE_MIN_IDLE")) { int v = atoi(e); if (v >= 0 && v <= 65) s->share_min_idle = v; }
     if (const char* e = getenv("P3D_DEBUG_SKIP")) s->dbg_skip = (uint32_t)atoi(e);      // read by -DP3D_DEBUG_SKIP builds only
@@ -151,7 +179,9 @@ int p3d_scene_create(const p3d_scene_desc* d, const p3d_build_opts* opts, int de
             s->off_tri_normals = section(nrm.data(), nrm.size() * 4);
         }
         s->off_boxes = section(boxes.data(), boxes.size() * sizeof(BoxRec));
-        s->off_mats = section(mats.data(), mats.size() * sizeof(MaterialRec));
+        s->host_materials = mats;
+        s->blob_prunes = s->prunes();
+        s->off_mats = section(encoded_materials(mats, s->blob_prunes).data(), mats.size() * sizeof(MaterialRec));
         // the f32 nodes only travel with scenes small enough to be rendered from an LDS copy of the blob
         if (small_scene && blob.size() * 4 + nodes.size() * sizeof(NodePair) <= s->lds_scene_limit) {
             s->off_nodes = section(nodes.data(), nodes.size() * sizeof(NodePair));
@@ -267,6 +297,44 @@ int p3d_set_sky_tiles(p3d_scene* s, int32_t on) {
     if (!s) return fail(P3D_ERR_ARG, "scene is NULL");
     if (on != 0 && on != 1) return fail(P3D_ERR_ARG, "on must be 0 or 1");
     s->sky_tiles = on != 0;
+    return P3D_OK;
+}
+
+int p3d_set_prune_reflections(p3d_scene* s, int32_t on) {
+    if (!s) return fail(P3D_ERR_ARG, "scene is NULL");
+    if (on != 0 && on != 1) return fail(P3D_ERR_ARG, "on must be 0 or 1");
+    const bool was = s->prune_reflections;
+    s->prune_reflections = on != 0;
+    if (s->prunes() == s->blob_prunes) return P3D_OK;
+    // the kernels read the switch in the material records: rewrite them behind whatever the stream still holds
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(s->stream, &cap);
+    if (cap != hipStreamCaptureStatusNone) {
+        s->prune_reflections = was;
+        return fail(P3D_ERR_STATE, "p3d_set_prune_reflections rewrites the scene's materials: not while the stream is being captured");
+    }
+    hipError_t e = hipSetDevice(s->device);
+    // Frames in flight still read the old records: the copy is queued behind them on the scene's stream (no other stream is
+    // touched, so a capture elsewhere in the process is left alone), and the call returns when it has been made -- `enc`
+    // is pageable and dies here.  A stream the handle was given before (p3d_set_stream) is the caller's to have synchronised,
+    // as for every other call; the handle's own stream is waited for when it is not the one in use.
+    if (e == hipSuccess && s->stream != (hipStream_t)s->own_stream) e = hipStreamSynchronize(s->own_stream);
+    const std::vector<MaterialRec> enc = encoded_materials(s->host_materials, s->prunes());
+    if (e == hipSuccess && !enc.empty())
+        e = hipMemcpyAsync((uint32_t*)s->blob.p + 4 * (size_t)s->off_mats, enc.data(), enc.size() * sizeof(MaterialRec), hipMemcpyHostToDevice, s->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+    if (e != hipSuccess) {
+        s->prune_reflections = was;
+        return fail(P3D_ERR_HIP, std::string("p3d_set_prune_reflections: ") + hipGetErrorString(e));
+    }
+    s->blob_prunes = s->prunes();
+    s->pick.invalidate(); s->pick_batch.invalidate();                  // the switch changes what the schedules cost: measure again
+    return P3D_OK;
+}
+
+int p3d_get_prune_reflections(const p3d_scene* s, int32_t* on) {
+    if (!s || !on) return fail(P3D_ERR_ARG, "NULL argument");
+    *on = s->prunes() ? 1 : 0;
     return P3D_OK;
 }
 

@@ -162,6 +162,9 @@ extern "C" int p3d_scene_rebuild_with(p3d_scene* s, uint32_t builder, p3d_rebuil
     HIP_TRY(alloc_devbuf(new_blob, (size_t)quads * 4));
     HIP_TRY(hipMemsetAsync(new_blob.p, 0, (size_t)quads * 16, st));
     HIP_TRY(hipMemcpyAsync(new_blob.p, s->blob.p, (size_t)s->off_leaves * 16, hipMemcpyDeviceToDevice, st));
+    // The material records travel as the blob holds them, that is in the encoding p3d_set_prune_reflections last wrote
+    // (p3d_scene_create.cpp: encoded_materials; refl of a T != 0 material negated while the handle prunes, a caller's
+    // negative refl stored as 0): p3d_scene::host_materials and blob_prunes describe the new blob as they did the old one.
     if (mat_bytes)
         HIP_TRY(hipMemcpyAsync(new_blob.p + 4 * (size_t)N.off_mats, s->blob.p + 4 * (size_t)s->off_mats, mat_bytes, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(new_map.p, s->prim_map.p, (size_t)n_prims * 4, hipMemcpyDeviceToDevice, st));   // the planes keep theirs

@@ -283,6 +283,19 @@ struct p3d_scene {
     bool sky_tiles = p3d::kDefaultSkyTiles;
     p3d::RawBuf sky_mask;
     struct { bool on = false; p3d::CoverTiles tiles{}; uint32_t row_words = 0; } last_sky;
+    // p3d_set_prune_reflections: what the caller asked for, and whether the scene as created lets it apply (finite_scene:
+    // every material, light, background and flattened normal component is finite).  Frames prune when both hold.
+    // The kernels learn it from the material records (p3d_shade.h: shade_hit): host_materials is the caller's materials,
+    // blob_prunes says which encoding of them the scene blob holds (p3d_scene_create.cpp: encoded_materials).
+    bool prune_reflections = p3d::kDefaultPruneReflections;
+    bool finite_scene = true;
+    bool prunes() const { return prune_reflections && finite_scene; }
+    std::vector<p3d::MaterialRec> host_materials;
+    bool blob_prunes = false;
+    // p3d_last_level_rays: the most recent wavefront-schedule frame (or ray stream) of the handle -- its depth, its level-1
+    // rays and how many passes it ran on how many lanes (every lane's counters keep its last pass).  valid = false before the
+    // first one and after a tile or tree frame.
+    struct { bool valid = false; int D = 0, lanes = 0; size_t passes = 0; uint64_t level1 = 0; } last_wf;
     uint32_t tri_quads = 3;    // 16-byte quads per triangle test record (3; 4 = round 2's 64-byte stride, P3D_TRI_STRIDE=64)
     bool verbose = false;      // P3D_VERBOSE=1: launch geometry on stderr (diagnostic)
     int share_min_idle = 16;   // work-sharing walk of scenes read from HBM: idle lanes before a steal round (0 or > 64: private walks)

@@ -280,7 +280,16 @@ __device__ __forceinline__ NodeOut shade_hit(const LaunchParams& P, const SV& sv
     }
     bool inside = false;
     if (dot(ray.d, normal) > 0.0f) { normal = mul(normal, -1.0f); inside = true; }
-    if (M.refl > 0.0f) {                                                 // RT/main.cpp:646-667
+    // A transmissive node's reflection child is scaled by KR = 1 / 2 * (R0 + R1) = +0 below: with
+    // p3d_set_prune_reflections on it is not spawned, and neither is its subtree (finding 5: why the
+    // frame keeps every bit).  The switch lives in the material record: while it is on, the host keeps the refl of every
+    // material with T != 0 NEGATED in the scene blob (p3d_scene_create.cpp: encoded_materials), so the test below -- the one
+    // the kernels always made -- is false for it: no launch parameter, no load, no instruction is added to a plain build.
+    // Counting builds trace the child -- their ray counts are the reference's --, and so do Schlick builds, whose KR is not
+    // zero: they read a negated refl as set.  (A material with T != 0 never holds a negative refl of the caller's.)
+    bool spawns_refl = M.refl > 0.0f;
+    if constexpr (COUNT || SCHLICK) spawns_refl = spawns_refl || (M.refl < 0.0f && M.T != 0.0f);
+    if (spawns_refl) {                                                   // RT/main.cpp:646-667
         V3 rdir = sub(ray.d, mul(mul(normal, dot(ray.d, normal)), 2.0f));
         o.refl.o = precise;
         if (STOCH && (P.features & kFeatFuzzy)) {                        // RT/main.cpp:651-660
