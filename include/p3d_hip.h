@@ -925,6 +925,58 @@ typedef struct p3d_ao_outputs { float* ao; float* rgb32f; int32_t memory; } p3d_
 int p3d_ambient_occlusion(p3d_scene* scene, const p3d_camera* cams, int32_t n, const p3d_render_params* params,
                           const p3d_ao_params* ao, const p3d_ao_inputs* in, const p3d_ao_outputs* out);
 
+/* One bounce of diffuse indirect light over the planes of p3d_render_aov (a final gather, "colour bleeding"): per pixel,
+ * `samples` cosine-weighted rays from the primary hit, each returning the direct-lit colour of what it hits, and their
+ * mean.  What a caller of p3d_trace_rays would build as res_x * res_y * samples rays, upload, trace at max_depth 1 and
+ * reduce is made, traced and summed in the lanes of one launch; neither the rays nor their colours exist in memory. */
+typedef struct p3d_indirect_params {
+    int32_t  samples;    /* 1, 2, 4, 8, 16, 32 or 64 rays per pixel */
+    float    bias;       /* finite, >= 0: the origin is moved this far along the normal that faces the eye */
+    uint32_t seed;       /* frame f keys its random streams with seed + f */
+} p3d_indirect_params;
+typedef struct p3d_indirect_inputs {
+    const float *depth, *normal;      /* needed */
+    const float *albedo, *rgb32f;     /* may be NULL */
+    int32_t memory;                   /* 0 host, 1 device */
+} p3d_indirect_inputs;
+typedef struct p3d_indirect_outputs { float* indirect; float* rgb32f; int32_t memory; } p3d_indirect_outputs;   /* either may be NULL, not both */
+/* The reference has no indirect light (Whitted's recursion has no such term); the result is DEFINED here, in float32
+ * IEEE-754 basic operations in a fixed order (no fused multiply-add), and the device, the host layer (p3dh_ao_segments,
+ * p3dh_indirect_resolve) and tests/indirect_reference.py agree on it in every bit.  One part is anchored to what the
+ * reference pins: a sample's radiance is what p3d_trace_rays returns for its ray.
+ *  - planes: as p3d_ambient_occlusion's: depth 1 float per pixel; normal, albedo, rgb32f and indirect 3.  Frame f is seen
+ *    through cams[f] (HOST array of n cameras); all cameras share res_x / res_y.
+ *  - the definition, for pixel (x, y) of frame f with depth Z and normal N:
+ *      1. - 6. steps 1 to 6 of p3d_ambient_occlusion with radius = 1: validity of Z (otherwise the pixel has no query), the
+ *         hit point P through cams[f], the face-forward normal Ns, the origin O = P + Ns * bias, the keys
+ *         pk = rng_mix(seed + f, y * res_x + x) and k = rng_mix(pk, s), the rejection draw, and D = normalized(w) --
+ *         normalized(w) * 1.0f in every bit.  The ray of sample s is the segment p3dh_ao_segments makes at radius 1, and the
+ *         same ray at every sample count.
+ *      7. radiance: r_s is the rgb32f p3d_trace_rays returns for Ray(O, D) with max_depth = 1, features = 0 and
+ *         params->accel: at a hit the clamped direct lighting of the hit point -- the reference's depth >= MAX_DEPTH return,
+ *         processLight with its shadow queries under the mode's shadow semantics --, at a miss the scene's background.
+ *      8. the sum is a balanced tree in sample order, per channel: t_0[s] = r_s, t_(j+1)[i] = t_j[2 i] + t_j[2 i + 1], and
+ *         m = t_(log2 samples)[0] * (1.0f / samples).
+ *      9. out->indirect = m.  out->rgb32f = c + a * m per channel, a product and then a sum, with a = in->albedo (1 when
+ *         that is NULL) and c = in->rgb32f; without in->rgb32f the value is a * m alone.  A pixel without a query gets
+ *         indirect = 0 and rgb32f = c (0 without in->rgb32f).
+ *    A normal that is not unit length, zero or not finite goes through the same operations; step 7's answer for a ray that
+ *    is not finite is p3d_trace_rays'.
+ *  - params: only accel and flags are read, with p3d_trace_rays' rules: P3D_FLAG_NO_LDS_SCENE and P3D_FLAG_PRIVATE_WALK are
+ *    honoured, P3D_FLAG_WAVEFRONT is accepted and does nothing; every other flag is P3D_ERR_ARG, and so are features != 0,
+ *    spp != 0, samples != NULL, world > 1 and rank != 0.  max_depth is not read.  The GRID-mode lazy build and the
+ *    refusal of a handle built with cull_never_hit (P3D_ERR_STATE, in every accel) are p3d_trace_rays'.
+ *  - P3D_ERR_ARG also for a NULL scene, cams, params, indirect, in or out; n < 1; cameras whose res_x / res_y are below 1 or
+ *    differ; indirect->samples not one of 1, 2, 4, 8, 16, 32, 64; bias not finite or < 0; a NULL depth or normal; both output
+ *    planes NULL; an output plane that is an input plane or the other output plane; a memory field outside 0 and 1.
+ *    P3D_ERR_LIMIT, before anything is allocated, when n * res_y * res_x * samples does not fit 31 bits.
+ *  - memory, staging, stream capture, handle state, scene motion: as p3d_ambient_occlusion, with staging buffers of its
+ *    own.  With everything in device memory the call is the small camera launch and ONE launch for all n frames: no ray
+ *    queues, no workspace.
+ *  - on every refusal the outputs are untouched. */
+int p3d_indirect_diffuse(p3d_scene* scene, const p3d_camera* cams, int32_t n, const p3d_render_params* params,
+                         const p3d_indirect_params* indirect, const p3d_indirect_inputs* in, const p3d_indirect_outputs* out);
+
 /* The edge-aware upsampler of p3d_render_aov's planes: a low-frequency signal (ambient occlusion, a soft shadow, a fuzzy
  * reflection) computed at 1 / factor of the resolution is brought up to the full frame along the full frame's depth and
  * normal (joint bilateral upsampling, Kopf et al. 2007). */

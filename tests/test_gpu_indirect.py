@@ -1,0 +1,541 @@
+"""p3d_indirect_diffuse on the GPU: the fused kernel against the unfused pipeline the definition names -- the NumPy rays
+(tests/ao_reference.py at radius 1) fed to DeviceScene.trace_rays(max_depth = 1) on the same handle, resolved by the NumPy
+restatement (tests/indirect_reference.py) -- and against the reference's own rayTracing() through the oracle.  Every pixel
+comparison is an equality of bits; every output is allocated with PAD elements of sentinel on either side, which must stay
+untouched."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import indirect_reference as R                             # noqa: E402
+import test_gpu_scene_update as SU                         # noqa: E402
+import u_4a_2s_p3d_raytracer_template2_amd as P            # noqa: E402
+from extra_scenes import scene_path                        # noqa: E402
+from oracle import oracle_py as O                          # noqa: E402
+from u_4a_2s_p3d_raytracer_template2_amd import api        # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+ERR_ARG, ERR_LIMIT, ERR_STATE = -1, -4, -5
+F = np.float32
+MODES = {"lds": dict(), "hbm": dict(no_lds=True), "hbm_private": dict(no_lds=True, private_walk=True)}
+RES = (24, 16)
+BIAS, SEED = 0.001, 77
+PAD = 16
+SENTINEL = F(-12345.0)
+PLANES = ("indirect", "rgb32f")
+
+
+def same_bits(got, ref, what):
+    assert got.shape == ref.shape and got.dtype == ref.dtype, what
+    bad = got.view(np.uint32) != ref.view(np.uint32) if got.dtype == np.float32 else got != ref
+    assert not bad.any(), "%s: %d of %d values differ, first at %s" % (what, int(bad.sum()), bad.size, np.argwhere(bad)[0])
+
+
+@pytest.fixture(scope="module")
+def scenes():
+    """scenes(name, res=RES, n=1) -> (handle, cameras, planes): one device handle per scene for the whole module, and the
+    frames of render_aov through n orbit cameras (n == 1: the scene's own) at res, rendered once and never modified."""
+    made, frames = {}, {}
+
+    def get(name, res=RES, n=1):
+        if name not in made:
+            made[name] = P.DeviceScene.from_host(P.HostScene(scene_path(name)))
+        k = (name, res, n)
+        if k not in frames:
+            hs = P.HostScene(scene_path(name))
+            hs.set_resolution(*res)
+            cams = [hs.camera()] if n == 1 else hs.orbit_cameras(n, 7.0)
+            f = made[name].render_aov(cams, max_depth=2, accel=api.ACCEL_BVH)
+            for a in f.values():
+                if isinstance(a, np.ndarray):
+                    a.setflags(write=False)
+            frames[k] = (cams, f)
+        return (made[name],) + frames[k]
+    yield get
+    for ds in made.values():
+        ds.close()
+
+
+def padded(shape):
+    a = np.full(int(np.prod(shape)) + 2 * PAD, SENTINEL, F)
+    return a, a[PAD:-PAD].reshape(shape)
+
+
+def untouched(whole):
+    return bool((whole[:PAD] == SENTINEL).all() and (whole[-PAD:] == SENTINEL).all())
+
+
+def fused(ds, cams, depth, normal, albedo=None, rgb=None, samples=8, seed=SEED, accel=api.ACCEL_BVH, want=PLANES, bias=BIAS,
+          prm_edit=None, ind_edit=None, in_edit=None, out_edit=None, n=None, **mode):
+    """p3d_indirect_diffuse through ctypes on host planes, outputs padded with SENTINEL -> (status, {"indirect", "rgb32f"});
+    the padding is checked here."""
+    arr, n_cams = api._camera_array(cams)
+    H, W = arr[0].res_y, arr[0].res_x
+    depth = np.ascontiguousarray(depth, F).reshape(n_cams, H, W)
+    normal = np.ascontiguousarray(normal, F).reshape(n_cams, H, W, 3)
+    albedo = None if albedo is None else np.ascontiguousarray(albedo, F).reshape(n_cams, H, W, 3)
+    rgb = None if rgb is None else np.ascontiguousarray(rgb, F).reshape(n_cams, H, W, 3)
+    whole_ind, ind = padded((n_cams, H, W, 3))
+    whole_rgb, out_rgb = padded((n_cams, H, W, 3))
+    prm = ds._ray_params(1, accel, mode.get("no_lds", False), mode.get("private_walk", False), False)
+    g = api.IndirectParams(int(samples), bias, int(seed) & 0xFFFFFFFF)
+    i = api.IndirectInputs(depth.ctypes.data, normal.ctypes.data, albedo.ctypes.data if albedo is not None else None,
+                           rgb.ctypes.data if rgb is not None else None, 0)
+    o = api.IndirectOutputs(ind.ctypes.data if "indirect" in want else None, out_rgb.ctypes.data if "rgb32f" in want else None, 0)
+    for edit, x in ((prm_edit, prm), (ind_edit, g), (in_edit, i), (out_edit, o)):
+        if edit:
+            edit(x)
+    rc = P.lib().p3d_indirect_diffuse(ds.h, arr, n_cams if n is None else n, C.byref(prm), C.byref(g), C.byref(i), C.byref(o))
+    assert untouched(whole_ind) and untouched(whole_rgb), "written outside an output plane"
+    return rc, {"indirect": ind, "rgb32f": out_rgb}
+
+
+def fused_ok(*args, **kw):
+    rc, out = fused(*args, **kw)
+    assert rc == 0, P.lib().p3d_last_error()
+    return out
+
+
+def frame_rays(cams, depth, normal, samples, seed, bias=BIAS):
+    """The NumPy rays of every frame: [(origin, dir, valid)] with frame f keyed by seed + f."""
+    return [R.rays(cams[f], depth[f], normal[f], samples, bias, seed, f) for f in range(len(cams))]
+
+
+def device_radiance(ds, accel, **mode):
+    return lambda o, d: ds.trace_rays(o, d, max_depth=1, accel=accel, want=("rgb32f",), **mode)["rgb32f"]
+
+
+def unfused(ds, cams, depth, normal, albedo=None, rgb=None, samples=8, seed=SEED, accel=api.ACCEL_BVH, bias=BIAS, **mode):
+    """(planes, radiances (n, H, W, S, 3), valid (n, H, W)) of the composition p3d_indirect_diffuse fuses."""
+    rays = frame_rays(cams, depth, normal, samples, seed, bias)
+    rad = R.radiance_from(device_radiance(ds, accel, **mode), rays, samples)
+    valid = np.stack([v for _, _, v in rays])
+    return R.resolve(rad, valid, albedo, rgb), rad, valid
+
+
+def same_result(got, ref, what):
+    for k in PLANES:
+        same_bits(got[k], ref[k], "%s %s" % (what, k))
+
+
+# ---- 1. fused equals unfused
+
+@pytest.mark.parametrize("samples", [1, 8, 64])
+@pytest.mark.parametrize("mode", sorted(MODES))
+@pytest.mark.parametrize("accel", [0, 1, 2])
+@pytest.mark.parametrize("name", ["balls_box", "balls_low", "mount_low"])
+def test_fused_equals_unfused(name, accel, mode, samples, scenes):
+    ds, cams, f = scenes(name)
+    ref, rad, valid = unfused(ds, cams, f["depth"], f["normal"], f["albedo"], f["rgb32f"], samples, accel=accel, **MODES[mode])
+    got = fused_ok(ds, cams, f["depth"], f["normal"], f["albedo"], f["rgb32f"], samples, accel=accel, **MODES[mode])
+    same_result(got, ref, "%s accel %d %s S=%d" % (name, accel, mode, samples))
+    q = valid.astype(bool)
+    assert np.array_equal(q, np.isfinite(f["depth"])) and q.any()
+    assert not got["indirect"][~q].any()
+    same_bits(got["rgb32f"][~q], np.ascontiguousarray(f["rgb32f"][~q]), "a pixel without a query keeps its colour")
+
+
+@pytest.mark.parametrize("private_walk", [False, True], ids=["shared", "private"])
+def test_dragon_equals_trace_rays(private_walk, scenes):
+    ds, cams, f = scenes("dragon")
+    assert ds.stats()["n_triangles"] > 2000 and np.isfinite(f["depth"]).any(), "a scene read from HBM natively, with queries"
+    ref, rad, valid = unfused(ds, cams, f["depth"], f["normal"], f["albedo"], f["rgb32f"], 8, private_walk=private_walk)
+    got = fused_ok(ds, cams, f["depth"], f["normal"], f["albedo"], f["rgb32f"], 8, private_walk=private_walk)
+    same_result(got, ref, "dragon private %s" % private_walk)
+
+
+# ---- 2. the anchor to the reference: the oracle's rayTracing() at MAX_DEPTH 1 on the same rays
+
+@pytest.mark.parametrize("accel", [0, 1, 2])
+@pytest.mark.parametrize("name", ["balls_box", "mount_low"])
+def test_planes_equal_the_references_ray_tracing(name, accel, scenes):
+    ds, cams, f = scenes(name)
+    rays = frame_rays(cams, f["depth"], f["normal"], 8, SEED)
+    osc = O.Scene(scene_path(name))
+    rad = R.radiance_from(R.oracle_radiance(osc, accel), rays, 8)
+    ref = R.resolve(rad, np.stack([v for _, _, v in rays]), f["albedo"], f["rgb32f"])
+    got = fused_ok(ds, cams, f["depth"], f["normal"], f["albedo"], f["rgb32f"], 8, accel=accel)
+    same_result(got, ref, "%s accel %d against the oracle" % (name, accel))
+
+
+def test_balls_box_is_not_trivial(scenes):
+    """The conditions of the issue, on the unfused reference alone (the oracle, accel 2, S = 8, the scene's own camera)."""
+    ds, cams, f = scenes("balls_box")
+    o, d, v = frame_rays(cams, f["depth"], f["normal"], 8, SEED)[0]
+    q = v.astype(bool)
+    osc = O.Scene(scene_path("balls_box"))
+    hit, shadowed = R.census(osc, O.lib(), o[q].reshape(-1, 3), d[q].reshape(-1, 3))
+    print("balls_box %dx%d S=8: %.1f%% of the samples of valid pixels hit, %d shadowed" % (RES + (100.0 * hit.mean(), int(shadowed.sum()))))
+    assert (~hit).mean() >= 0.1, "at least 10 % of the samples of valid pixels miss"
+    assert hit.mean() >= 0.1, "at least 10 % hit"
+    assert shadowed.any(), "a shadow query of a hit sample answers occluded: the sample is darker than its unshadowed term"
+    rad = R.radiance_from(R.oracle_radiance(osc, 2), [(o, d, v)], 8)
+    ind = R.resolve(rad, v[None])["indirect"][0]
+    assert len(np.unique(ind[q].view(np.uint32), axis=0)) > 1, "indirect is not constant over the frame"
+
+
+# ---- 3. shapes: res_x below 64 / S, no multiple of it, one row, one pixel and 64 pixels per wave
+
+@pytest.mark.parametrize("samples", [1, 16, 64])
+@pytest.mark.parametrize("res", [(1, 1), (7, 3), (9, 2), (63, 1), (65, 2)], ids=lambda r: "%dx%d" % r)
+def test_shapes(res, samples, scenes):
+    ds, cams, f = scenes("balls_low", res)
+    # every pixel gets a query, so that row tails hold some: where the frame shows the sky, a point 3 units along the
+    # pixel's ray whose normal is the view axis (it points at the eye)
+    sky = ~np.isfinite(f["depth"])
+    depth = np.where(sky, F(3.0), f["depth"]).astype(F)
+    normal = np.where(sky[..., None], np.array(list(cams[0].n), F), f["normal"]).astype(F)
+    for mode in ("lds", "hbm"):
+        ref, _, valid = unfused(ds, cams, depth, normal, f["albedo"], f["rgb32f"], samples, **MODES[mode])
+        assert valid.all()
+        got = fused_ok(ds, cams, depth, normal, f["albedo"], f["rgb32f"], samples, **MODES[mode])
+        same_result(got, ref, "%dx%d S=%d %s" % (res + (samples, mode)))
+
+
+@pytest.mark.parametrize("mode", ["lds", "hbm"])
+def test_a_batch_is_its_frames_with_seed_plus_f(mode, scenes):
+    ds, cams, f = scenes("balls_box", (23, 5), 3)
+    assert (f["depth"][0].view(np.uint32) != f["depth"][2].view(np.uint32)).any(), "the orbit must show"
+    batch = fused_ok(ds, cams, f["depth"], f["normal"], f["albedo"], f["rgb32f"], 16, **MODES[mode])
+    ref, _, _ = unfused(ds, cams, f["depth"], f["normal"], f["albedo"], f["rgb32f"], 16, **MODES[mode])
+    same_result(batch, ref, "batch")
+    for k in range(3):
+        one = fused_ok(ds, [cams[k]], f["depth"][k], f["normal"][k], f["albedo"][k], f["rgb32f"][k], 16, seed=SEED + k, **MODES[mode])
+        for p in PLANES:
+            same_bits(one[p][0], batch[p][k], "frame %d alone: %s" % (k, p))
+    other = fused_ok(ds, [cams[0]], f["depth"][0], f["normal"][0], None, None, 16, seed=SEED + 1)
+    assert (batch["indirect"][0].view(np.uint32) != other["indirect"][0].view(np.uint32)).any(), "the seed must show"
+
+
+def test_sample_s_is_the_same_ray_at_every_sample_count(scenes):
+    ds, cams, f = scenes("balls_box")
+    _, rad8, valid = unfused(ds, cams, f["depth"], f["normal"], None, None, 8)
+    one = fused_ok(ds, cams, f["depth"], f["normal"], None, None, 1)
+    q = valid.astype(bool)
+    same_bits(one["indirect"][q], np.ascontiguousarray(rad8[:, :, :, 0][q]), "S = 1 is the first term of S = 8")
+
+
+# ---- 4. outputs, memory, capture
+
+def test_output_planes_with_and_without_albedo_and_colour(scenes):
+    ds, cams, f = scenes("balls_box")
+    _, rad, valid = unfused(ds, cams, f["depth"], f["normal"], None, None, 8)
+    for albedo in (None, f["albedo"]):
+        for rgb in (None, f["rgb32f"]):
+            ref = R.resolve(rad, valid, albedo, rgb)
+            for want in (("indirect",), ("rgb32f",), PLANES):
+                got = fused_ok(ds, cams, f["depth"], f["normal"], albedo, rgb, 8, want=want)
+                for k in PLANES:
+                    if k in want:
+                        same_bits(got[k], ref[k], "want %s albedo %s colour %s: %s" % (want, albedo is not None, rgb is not None, k))
+                    else:
+                        assert (got[k] == SENTINEL).all(), "a plane that was not asked for was written"
+    plain = R.resolve(rad, valid)
+    same_bits(plain["rgb32f"], plain["indirect"], "without albedo and colour rgb32f is the indirect light")
+    # the pipeline connects: the sum is a colour p3d_denoise takes
+    lit = fused_ok(ds, cams, f["depth"], f["normal"], f["albedo"], f["rgb32f"], 8)["rgb32f"]
+    got = ds.denoise(lit, f["depth"], f["normal"], f["albedo"], iterations=2)
+    ref = api.host_denoise(lit, f["depth"], f["normal"], f["albedo"], iterations=2)
+    same_bits(got["rgb32f"], ref["rgb32f"], "denoised frame with indirect light")
+
+
+def test_host_and_device_memory_give_equal_bits(scenes):
+    import torch
+    ds, cams, f = scenes("balls_box", (23, 5), 3)
+    ref = fused_ok(ds, cams, f["depth"], f["normal"], f["albedo"], f["rgb32f"], 16)
+    arr, n = api._camera_array(cams)
+    host = {k: np.array(f[k], F) for k in ("depth", "normal", "albedo", "rgb32f")}
+    dev = {k: torch.from_numpy(host[k]).cuda() for k in host}
+    prm = ds._ray_params(1, api.ACCEL_BVH, False, False, False)
+    g = api.IndirectParams(16, BIAS, SEED)
+    for im in (0, 1):
+        for om in (0, 1):
+            src = {k: (dev[k].data_ptr() if im else host[k].ctypes.data) for k in host}
+            whole_ind, ind = padded((n, 5, 23, 3))
+            whole_rgb, rgb = padded((n, 5, 23, 3))
+            d_ind, d_rgb = torch.from_numpy(whole_ind.copy()).cuda(), torch.from_numpy(whole_rgb.copy()).cuda()
+            i = api.IndirectInputs(src["depth"], src["normal"], src["albedo"], src["rgb32f"], im)
+            o = api.IndirectOutputs(d_ind.data_ptr() + 4 * PAD if om else ind.ctypes.data, d_rgb.data_ptr() + 4 * PAD if om else rgb.ctypes.data, om)
+            assert P.lib().p3d_indirect_diffuse(ds.h, arr, n, C.byref(prm), C.byref(g), C.byref(i), C.byref(o)) == 0, P.lib().p3d_last_error()
+            ds.sync()
+            if om:
+                whole_ind, whole_rgb = d_ind.cpu().numpy(), d_rgb.cpu().numpy()
+            assert untouched(whole_ind) and untouched(whole_rgb)
+            same_bits(whole_ind[PAD:-PAD].reshape(ref["indirect"].shape), ref["indirect"], "in %d out %d: indirect" % (im, om))
+            same_bits(whole_rgb[PAD:-PAD].reshape(ref["rgb32f"].shape), ref["rgb32f"], "in %d out %d: rgb32f" % (im, om))
+    for k in host:
+        same_bits(dev[k].cpu().numpy(), host[k], "an input plane changed: " + k)
+
+
+def test_staging_is_counted_in_device_bytes():
+    hs = P.HostScene(scene_path("balls_box"))
+    hs.set_resolution(64, 16)
+    ds = P.DeviceScene.from_host(hs)
+    f = ds.render_aov(hs.camera(), max_depth=1)
+    before = ds.stats()["device_bytes"]
+    fused_ok(ds, [hs.camera()], f["depth"], f["normal"], f["albedo"], f["rgb32f"], 4)
+    grown = ds.stats()["device_bytes"] - before
+    assert grown == 64 * 16 * (4 + 12 + 12 + 12 + 12 + 12) + 128, grown          # the planes in and out, one camera record
+    fused_ok(ds, [hs.camera()], f["depth"], f["normal"], f["albedo"], f["rgb32f"], 4)
+    assert ds.stats()["device_bytes"] - before == grown
+    ds.close()
+
+
+def test_stream_capture():
+    import torch
+    hs = P.HostScene(scene_path("balls_box"))
+    hs.set_resolution(*RES)
+    ds = P.DeviceScene.from_host(hs)
+    cams = hs.orbit_cameras(2, 7.0)
+    f = ds.render_aov(cams, max_depth=2)
+    ref = fused_ok(ds, cams[:1], f["depth"][0], f["normal"][0], None, None, 8)       # (one camera: the buffer holds one record)
+    ref2, _, _ = unfused(ds, cams, f["depth"], f["normal"], None, None, 8)
+    dev = {k: torch.from_numpy(np.ascontiguousarray(f[k])).cuda() for k in ("depth", "normal")}
+    out = torch.zeros(2 * RES[0] * RES[1] * 3, dtype=torch.float32, device="cuda:0")
+    run = lambda: ds.indirect_diffuse_device(cams, dev["depth"].data_ptr(), dev["normal"].data_ptr(), out_indirect_ptr=out.data_ptr(),
+                                             samples=8, bias=BIAS, seed=SEED)
+    side = torch.cuda.Stream()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=side, capture_error_mode="thread_local"):
+        ds.set_stream(torch.cuda.current_stream().cuda_stream)
+        with pytest.raises(P.P3DError, match=r"\(%d\).*before the capture" % ERR_STATE):
+            run()                                                               # two cameras: the buffer would have to grow
+        with pytest.raises(P.P3DError, match=r"\(%d\).*host planes" % ERR_STATE):
+            ds.indirect_diffuse(cams, f["depth"], f["normal"], samples=8)
+        ds.indirect_diffuse_device(cams[:1], dev["depth"].data_ptr(), dev["normal"].data_ptr(), out_indirect_ptr=out.data_ptr(),
+                                   samples=8, bias=BIAS, seed=SEED)
+    ds.set_stream(0)
+    assert not out.any(), "a captured call must not run"
+    g.replay()
+    torch.cuda.synchronize()
+    same_bits(out.cpu().numpy()[:RES[0] * RES[1] * 3].reshape(ref["indirect"].shape), ref["indirect"], "the capture survived the refusals")
+    # after a call of the same shape: captured, and the replay gives the same bits
+    run()
+    ds.sync()
+    out.zero_()
+    torch.cuda.synchronize()
+    g2 = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g2, stream=side, capture_error_mode="thread_local"):
+        ds.set_stream(torch.cuda.current_stream().cuda_stream)
+        run()
+    ds.set_stream(0)
+    assert not out.any(), "a captured call must not run"
+    g2.replay()
+    torch.cuda.synchronize()
+    same_bits(out.cpu().numpy().reshape(ref2["indirect"].shape), ref2["indirect"], "replayed graph")
+    del g, g2
+    ds.close()
+
+
+# ---- 5. refusals
+
+def set_(**kw):
+    def edit(x):
+        for k, v in kw.items():
+            setattr(x, k, v)
+    return edit
+
+
+_one_float = (C.c_float * 4)()
+# name -> (status, text p3d_last_error must hold, prm / indirect / in / out edits)
+REFUSED = {
+    "flag_tree": (ERR_ARG, "flags", set_(flags=api.FLAG_TREE_KERNEL), None, None, None),
+    "flag_tile": (ERR_ARG, "flags", set_(flags=api.FLAG_TILE_KERNEL), None, None, None),
+    "flag_counters": (ERR_ARG, "flags", set_(flags=api.FLAG_COUNTERS), None, None, None),
+    "flag_profile": (ERR_ARG, "flags", set_(flags=api.FLAG_PROFILE), None, None, None),
+    "flag_packet": (ERR_ARG, "flags", set_(flags=api.FLAG_PACKET_WALK), None, None, None),
+    "flag_device_samples": (ERR_ARG, "flags", set_(flags=api.FLAG_DEVICE_SAMPLES), None, None, None),
+    "flag_unknown": (ERR_ARG, "flags", set_(flags=1 << 20), None, None, None),
+    "feature_soft_shadow": (ERR_ARG, "features", set_(features=api.FEATURE_SOFT_SHADOW), None, None, None),
+    "feature_schlick": (ERR_ARG, "features", set_(features=api.FEATURE_SCHLICK), None, None, None),
+    "spp": (ERR_ARG, "spp", set_(spp=1), None, None, None),
+    "samples_pointer": (ERR_ARG, "samples", set_(samples=C.cast(_one_float, C.POINTER(C.c_float))), None, None, None),
+    "world": (ERR_ARG, "world", set_(world=2), None, None, None),
+    "rank": (ERR_ARG, "rank", set_(rank=1), None, None, None),
+    "accel_3": (ERR_ARG, "accel", set_(accel=3), None, None, None),
+    "depth_null": (ERR_ARG, "depth", None, None, set_(depth=None), None),
+    "normal_null": (ERR_ARG, "normal", None, None, set_(normal=None), None),
+    "inputs_memory_2": (ERR_ARG, "p3d_indirect_inputs::memory", None, None, set_(memory=2), None),
+    "outputs_memory_negative": (ERR_ARG, "p3d_indirect_outputs::memory", None, None, None, set_(memory=-1)),
+    "both_outputs_null": (ERR_ARG, "indirect and rgb32f", None, None, None, set_(indirect=None, rgb32f=None)),
+}
+for _s in (0, 3, 5, 12, 65, 128, -8):
+    REFUSED["samples_%d" % _s] = (ERR_ARG, "p3d_indirect_params::samples", None, set_(samples=_s), None, None)
+for _k, _v in (("negative", -0.001), ("inf", np.inf), ("nan", np.nan)):
+    REFUSED["bias_" + _k] = (ERR_ARG, "bias", None, set_(bias=_v), None, None)
+
+
+@pytest.mark.parametrize("case", sorted(REFUSED))
+def test_refusals_leave_the_outputs_and_the_handle_alone(case, scenes):
+    ds, cams, f = scenes("balls_box")
+    status, text, prm_edit, ind_edit, in_edit, out_edit = REFUSED[case]
+    before, sched = ds.stats()["device_bytes"], ds.last_schedule()
+    rc, out = fused(ds, cams, f["depth"], f["normal"], f["albedo"], f["rgb32f"], 8, prm_edit=prm_edit, ind_edit=ind_edit, in_edit=in_edit,
+                    out_edit=out_edit)
+    assert rc == status, (case, rc, P.lib().p3d_last_error())
+    assert text in P.lib().p3d_last_error().decode(), P.lib().p3d_last_error()
+    assert (out["indirect"] == SENTINEL).all() and (out["rgb32f"] == SENTINEL).all(), "a refused call wrote"
+    assert ds.stats()["device_bytes"] == before, "a refused call grew the handle"
+    assert ds.last_schedule() == sched, "a refused call changed p3d_last_schedule"
+
+
+def test_a_frame_after_refusals_is_bit_identical(scenes):
+    ds, cams, f = scenes("balls_box")
+    first = ds.render(cams[0], max_depth=4)
+    sched = ds.last_schedule()
+    for case in ("samples_3", "flag_tree", "bias_nan", "both_outputs_null"):
+        status, _, prm_edit, ind_edit, in_edit, out_edit = REFUSED[case]
+        rc, _ = fused(ds, cams, f["depth"], f["normal"], None, None, 8, prm_edit=prm_edit, ind_edit=ind_edit, in_edit=in_edit, out_edit=out_edit)
+        assert rc == status
+    again = ds.render(cams[0], max_depth=4)
+    assert ds.last_schedule() == sched
+    same_bits(again["rgb32f"], first["rgb32f"], "the frame after the refusals")
+    assert np.array_equal(again["hit_id"], first["hit_id"])
+
+
+def test_more_refusals(scenes):
+    import torch
+    ds, cams, f = scenes("balls_box")
+    L = P.lib()
+    # aliases: an output plane that is an input plane, or the other output plane
+    for name in ("depth", "normal", "albedo", "rgb32f"):
+        for which in PLANES:
+            keep = np.ascontiguousarray(f[name]).copy()
+
+            def edit_in(i, keep=keep, name=name):
+                setattr(i, name, keep.ctypes.data)
+
+            def edit_out(o, keep=keep, which=which):
+                setattr(o, which, keep.ctypes.data)
+            rc, out = fused(ds, cams, f["depth"], f["normal"], f["albedo"], f["rgb32f"], 8, in_edit=edit_in, out_edit=edit_out)
+            assert rc == ERR_ARG and b"alias" in L.p3d_last_error(), (name, which)
+            same_bits(keep, np.ascontiguousarray(f[name]), "a refused call wrote")
+    rc, out = fused(ds, cams, f["depth"], f["normal"], None, None, 8, out_edit=lambda o: setattr(o, "rgb32f", o.indirect))
+    assert rc == ERR_ARG and b"alias" in L.p3d_last_error()
+    # n below 1, cameras that differ, NULL structs
+    rc, out = fused(ds, cams, f["depth"], f["normal"], None, None, 8, n=0)
+    assert rc == ERR_ARG and b"n must" in L.p3d_last_error() and (out["indirect"] == SENTINEL).all()
+    other = api.Camera.from_buffer_copy(cams[0])
+    other.res_x += 1
+    prm = ds._ray_params(1, api.ACCEL_BVH, False, False, False)
+    g = api.IndirectParams(8, BIAS, SEED)
+    d2, n2 = np.zeros((2,) + f["depth"].shape[1:], F), np.zeros((2,) + f["normal"].shape[1:], F)
+    o2 = np.full(n2.shape, SENTINEL, F)
+    arr, _ = api._camera_array([cams[0], other])
+    i, o = api.IndirectInputs(d2.ctypes.data, n2.ctypes.data, None, None, 0), api.IndirectOutputs(o2.ctypes.data, None, 0)
+    assert L.p3d_indirect_diffuse(ds.h, arr, 2, C.byref(prm), C.byref(g), C.byref(i), C.byref(o)) == ERR_ARG and b"res_x" in L.p3d_last_error()
+    for args in ((None, C.byref(prm), C.byref(g), C.byref(i), C.byref(o)), (arr, None, C.byref(g), C.byref(i), C.byref(o)),
+                 (arr, C.byref(prm), None, C.byref(i), C.byref(o)), (arr, C.byref(prm), C.byref(g), None, C.byref(o)),
+                 (arr, C.byref(prm), C.byref(g), C.byref(i), None)):
+        assert L.p3d_indirect_diffuse(ds.h, args[0], 1, *args[1:]) == ERR_ARG and L.p3d_last_error()
+    # the limit, before anything is allocated: 32768 x 32768 pixels fit 31 bits, their 2 samples each do not; 46341^2 pixels do not
+    torch.cuda.synchronize()
+    free0, before = torch.cuda.mem_get_info()[0], ds.stats()["device_bytes"]
+    big = api.Camera.from_buffer_copy(cams[0])
+    big.res_x, big.res_y = 32768, 32768
+    arr1, _ = api._camera_array([big])
+    g2 = api.IndirectParams(2, BIAS, SEED)
+    assert L.p3d_indirect_diffuse(ds.h, arr1, 1, C.byref(prm), C.byref(g2), C.byref(i), C.byref(o)) == ERR_LIMIT
+    assert b"31 bits" in L.p3d_last_error() and torch.cuda.mem_get_info()[0] == free0 and ds.stats()["device_bytes"] == before
+    g1 = api.IndirectParams(1, BIAS, SEED)
+    big.res_x, big.res_y = 46341, 46341
+    arr1, _ = api._camera_array([big])
+    assert L.p3d_indirect_diffuse(ds.h, arr1, 1, C.byref(prm), C.byref(g1), C.byref(i), C.byref(o)) == ERR_LIMIT
+    assert (o2 == SENTINEL).all()
+    # accepted: P3D_FLAG_WAVEFRONT does nothing, max_depth is not read
+    ref = fused_ok(ds, cams, f["depth"], f["normal"], None, None, 8)
+    for depth in (0, 7):
+        got = fused_ok(ds, cams, f["depth"], f["normal"], None, None, 8, prm_edit=set_(flags=api.FLAG_WAVEFRONT, max_depth=depth))
+        same_result(got, ref, "P3D_FLAG_WAVEFRONT, max_depth %d" % depth)
+
+
+def test_a_cull_never_hit_scene_is_refused(scenes):
+    _, cams, f = scenes("balls_box")
+    ds = P.DeviceScene.from_host(P.HostScene(scene_path("balls_box")), cull_never_hit=True)
+    for accel in (api.ACCEL_NONE, api.ACCEL_GRID, api.ACCEL_BVH):
+        rc, out = fused(ds, cams, f["depth"], f["normal"], None, None, 8, accel=accel)
+        assert rc == ERR_STATE and b"cull_never_hit" in P.lib().p3d_last_error() and (out["indirect"] == SENTINEL).all()
+    ds.close()
+
+
+# ---- 6. scene motion, handle state
+
+def test_queries_follow_an_update_and_a_rebuild(tmp_path):
+    m = SU.lattice(tmp_path)
+    hs = P.HostScene(m.path["B"])
+    hs.set_resolution(*RES)
+    cams = [hs.camera()]
+    fresh = m.fresh("B")
+    f = fresh.render_aov(cams, max_depth=1)
+    assert np.isfinite(f["depth"]).mean() > 0.3
+    ds = m.fresh("A")
+    stale = fused_ok(ds, cams, f["depth"], f["normal"], None, None, 8)
+    ds.update(m.data["B"])
+    moved = fused_ok(ds, cams, f["depth"], f["normal"], None, None, 8)
+    assert (stale["indirect"].view(np.uint32) != moved["indirect"].view(np.uint32)).any(), "the update must show"
+    for accel in (0, 1, 2):
+        ref, _, _ = unfused(ds, cams, f["depth"], f["normal"], None, None, 8, accel=accel)
+        same_result(fused_ok(ds, cams, f["depth"], f["normal"], None, None, 8, accel=accel), ref, "after the update, accel %d" % accel)
+        same_result(fused_ok(fresh, cams, f["depth"], f["normal"], None, None, 8, accel=accel), ref, "a fresh handle on the moved scene, accel %d" % accel)
+    assert ds.rebuild()["rebuilt"] == 1
+    for accel in (0, 1, 2):
+        for private_walk in (False, True):
+            ref, _, _ = unfused(ds, cams, f["depth"], f["normal"], None, None, 8, accel=accel, private_walk=private_walk)
+            same_result(fused_ok(ds, cams, f["depth"], f["normal"], None, None, 8, accel=accel, private_walk=private_walk), ref,
+                        "after the rebuild, accel %d private %s" % (accel, private_walk))
+    ds.close(); fresh.close()
+
+
+def test_handle_state_is_left_alone():
+    hs = P.HostScene(scene_path("balls_box"))
+    hs.set_resolution(64, 48)
+    ds = P.DeviceScene.from_host(hs)
+    cam = hs.camera()
+    f = ds.render_aov(cam, max_depth=2)
+    a = ds.render(cam, max_depth=4)
+    sched, tiles = ds.last_schedule(), ds.last_primary_tiles()
+    ds.indirect_diffuse(cam, f["depth"], f["normal"], f["albedo"], f["rgb32f"], samples=8, seed=SEED)
+    ds.indirect_diffuse(cam, f["depth"], f["normal"], f["albedo"], f["rgb32f"], samples=8, seed=SEED, accel=api.ACCEL_NONE, no_lds=True)
+    assert ds.last_schedule() == sched and ds.last_primary_tiles() == tiles
+    b = ds.render(cam, max_depth=4)
+    assert ds.last_schedule() == sched and ds.last_primary_tiles() == tiles
+    same_bits(a["rgb32f"], b["rgb32f"], "the frame after the gather")
+    assert np.array_equal(a["hit_id"], b["hit_id"])
+    ds.close()
+
+
+# ---- 7. the command line
+
+def test_cli_gi_denoise(tmp_path, scenes):
+    import subprocess
+    ds, cams, f = scenes("balls_box", (64, 48))
+    exe = os.path.join(os.path.dirname(P.__file__), "p3d_render")
+    out, plain = tmp_path / "gi.ppm", tmp_path / "plain.ppm"
+    common = [exe, scene_path("balls_box"), "--res", "64", "48", "--seed", str(SEED)]
+    r = subprocess.run(common + ["--gi", "8", "--denoise", "2", "--out", str(out)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run(common + ["--out", str(plain)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    hs = P.HostScene(scene_path("balls_box"))
+    frame = ds.render_aov(cams, max_depth=4, accel=hs.accel)
+    lit = fused_ok(ds, cams, frame["depth"], frame["normal"], frame["albedo"], frame["rgb32f"], 8, accel=hs.accel)
+    ref = api.host_denoise(lit["rgb32f"], frame["depth"], frame["normal"], frame["albedo"], iterations=2)
+    head = b"P6\n64 48\n255\n"
+    data = out.read_bytes()
+    assert data.startswith(head)
+    got = np.frombuffer(data[len(head):], np.uint8).reshape(48, 64, 3)[::-1]                  # the file is top row first
+    same_bits(np.ascontiguousarray(got), ref["rgb8"][0], "p3d_render --gi 8 --denoise 2")
+    assert data != plain.read_bytes(), "the gather must show in the file"
+    png = tmp_path / "gi.png"
+    r = subprocess.run(common + ["--gi", "8", "--denoise", "2", "--out", str(png)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and png.read_bytes().startswith(b"\x89PNG"), r.stderr
+    assert (lit["indirect"] > 0).any()
+    r = subprocess.run(common + ["--gi", "8", "--gpus", "2"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--gi" in r.stderr
+    r = subprocess.run(common + ["--gi", "6"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--gi" in r.stderr

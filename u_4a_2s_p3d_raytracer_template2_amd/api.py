@@ -208,6 +208,28 @@ AO_RADIUS = 0.5
 AO_BIAS = 0.001
 
 
+class IndirectParams(C.Structure):
+    """p3d_indirect_params: samples (1, 2, 4, .. 64) cosine-weighted rays per pixel, their origin moved bias along the normal
+    that faces the eye; frame f keys its random streams with seed + f."""
+    _fields_ = [("samples", C.c_int32), ("bias", C.c_float), ("seed", C.c_uint32)]
+
+
+class IndirectInputs(C.Structure):
+    """p3d_indirect_inputs: depth, normal and (optionally) albedo and colour planes as p3d_render_aov writes them, host
+    (memory 0) or device (1)."""
+    _fields_ = [("depth", C.c_void_p), ("normal", C.c_void_p), ("albedo", C.c_void_p), ("rgb32f", C.c_void_p), ("memory", C.c_int32)]
+
+
+class IndirectOutputs(C.Structure):
+    """p3d_indirect_outputs: each plane may be NULL, not both."""
+    _fields_ = [("indirect", C.c_void_p), ("rgb32f", C.c_void_p), ("memory", C.c_int32)]
+
+
+# p3d_indirect_diffuse's defaults: conveniences, not measured (bias: the reference's EPSILON, RT/macros.h:1)
+INDIRECT_SAMPLES = 8
+INDIRECT_BIAS = 0.001
+
+
 class UpsampleParams(C.Structure):
     """p3d_upsample_params: n_frames low frames of res_x x res_y back to back, brought up by factor 1..4; channels 1 or 3 floats
     per pixel of the signal; the denoiser's depth stop and normal_power_log2 0..8 squarings of the normal weight."""
@@ -262,7 +284,7 @@ class SceneStats(C.Structure):
 
 # every symbol include/p3d_hip.h declares (tests check that the library exports them all)
 C_ABI_SYMBOLS = ["p3d_abi_version", "p3d_last_error", "p3d_device_count", "p3d_scene_create",
-                 "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_scene_update", "p3d_scene_rebuild", "p3d_scene_rebuild_with", "p3d_scene_last_builder", "p3d_scene_tree_cost", "p3d_scene_build_grid", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_render_aov", "p3d_generate_samples", "p3d_trace_rays", "p3d_occluded", "p3d_denoise", "p3d_denoise_variance", "p3d_accumulate", "p3d_accumulate_moving", "p3d_accumulate_variance", "p3d_ambient_occlusion", "p3d_upsample", "p3d_sync",
+                 "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_scene_update", "p3d_scene_rebuild", "p3d_scene_rebuild_with", "p3d_scene_last_builder", "p3d_scene_tree_cost", "p3d_scene_build_grid", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_render_aov", "p3d_generate_samples", "p3d_trace_rays", "p3d_occluded", "p3d_denoise", "p3d_denoise_variance", "p3d_accumulate", "p3d_accumulate_moving", "p3d_accumulate_variance", "p3d_ambient_occlusion", "p3d_indirect_diffuse", "p3d_upsample", "p3d_sync",
                  "p3d_get_counters", "p3d_get_profile", "p3d_last_schedule", "p3d_set_tuning", "p3d_set_primary_tiles", "p3d_last_primary_tiles", "p3d_set_sky_tiles", "p3d_last_sky_tiles", "p3d_set_prune_reflections", "p3d_get_prune_reflections", "p3d_last_level_rays", "p3d_set_stream", "p3d_timer_begin", "p3d_timer_end", "p3d_deinterleave_frames",
                  "p3d_deinterleave", "p3d_debug_intersect", "p3d_debug_powf", "p3d_debug_pow", "p3d_debug_schlick_kr", "p3d_debug_check_rcp", "p3d_debug_check_rcp_len", "p3d_debug_lbvh_build", "p3d_debug_ploc_build", "p3d_debug_grid_build", "p3d_debug_rand", "p3d_debug_sample_stream", "p3d_debug_denoise", "p3d_debug_denoise_variance", "p3d_debug_accumulate", "p3d_debug_accumulate_moving", "p3d_debug_accumulate_variance", "p3d_debug_upsample", "p3d_tune_schedule", "p3d_debug_set_stamps", "p3d_debug_set_stamp_level",
                  "p3d_comm_unique_id", "p3d_comm_create", "p3d_comm_create_all", "p3d_comm_destroy", "p3d_comm_info",
@@ -352,6 +374,10 @@ def lib():
     L.p3dh_ao_segments.restype = None
     L.p3dh_ao_resolve.argtypes = [C.c_int32, C.c_uint64] + [C.c_void_p] * 4
     L.p3dh_ao_resolve.restype = None
+    L.p3d_indirect_diffuse.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.POINTER(RenderParams), C.POINTER(IndirectParams),
+                                       C.POINTER(IndirectInputs), C.POINTER(IndirectOutputs)]
+    L.p3dh_indirect_resolve.argtypes = [C.c_int32, C.c_uint64] + [C.c_void_p] * 6
+    L.p3dh_indirect_resolve.restype = None
     L.p3d_sync.argtypes = [C.c_void_p]
     L.p3d_get_counters.argtypes = [C.c_void_p, C.POINTER(Counters)]
     L.p3d_set_stream.argtypes = [C.c_void_p, C.c_void_p]
@@ -1157,6 +1183,40 @@ class DeviceScene:
         o = AoOutputs(out_ao_ptr or None, out_rgb32f_ptr or None, 1)
         _check(lib().p3d_ambient_occlusion(self.h, arr, n, C.byref(p), C.byref(a), C.byref(i), C.byref(o)), "p3d_ambient_occlusion")
 
+    def indirect_diffuse(self, cam_or_cams, depth, normal, albedo=None, rgb32f=None, samples=INDIRECT_SAMPLES, bias=INDIRECT_BIAS, seed=0,
+                         accel=ACCEL_BVH, no_lds=False, private_walk=False, want=("indirect", "rgb32f")):
+        """p3d_indirect_diffuse on host arrays: depth (n, H, W) or (H, W) and normal (n, H, W, 3) or (H, W, 3) as render_aov
+        returns them, seen through one Camera or a sequence of n; albedo and rgb32f (both optional) are the planes the
+        gathered light is multiplied by and added to.  Returns the planes named in `want`: indirect (n, H, W, 3), the mean
+        radiance of the samples, and rgb32f (n, H, W, 3) = rgb32f + albedo * indirect."""
+        arr, n = _camera_array([cam_or_cams] if isinstance(cam_or_cams, Camera) else cam_or_cams)
+        H, W = arr[0].res_y, arr[0].res_x
+        depth = np.ascontiguousarray(depth, np.float32).reshape(n, H, W)
+        normal = np.ascontiguousarray(normal, np.float32).reshape(n, H, W, 3)
+        if albedo is not None:
+            albedo = np.ascontiguousarray(albedo, np.float32).reshape(n, H, W, 3)
+        if rgb32f is not None:
+            rgb32f = np.ascontiguousarray(rgb32f, np.float32).reshape(n, H, W, 3)
+        out = {k: np.zeros((n, H, W, 3), np.float32) for k in ("indirect", "rgb32f") if k in want}
+        p = self._ray_params(1, accel, no_lds, private_walk, False)
+        g = IndirectParams(int(samples), bias, int(seed) & 0xFFFFFFFF)
+        i = IndirectInputs(depth.ctypes.data, normal.ctypes.data, albedo.ctypes.data if albedo is not None else None,
+                           rgb32f.ctypes.data if rgb32f is not None else None, 0)
+        o = IndirectOutputs(out["indirect"].ctypes.data if "indirect" in out else None, out["rgb32f"].ctypes.data if "rgb32f" in out else None, 0)
+        _check(lib().p3d_indirect_diffuse(self.h, arr, n, C.byref(p), C.byref(g), C.byref(i), C.byref(o)), "p3d_indirect_diffuse")
+        return out
+
+    def indirect_diffuse_device(self, cam_or_cams, depth_ptr, normal_ptr, albedo_ptr=0, rgb32f_ptr=0, out_indirect_ptr=0, out_rgb32f_ptr=0,
+                                samples=INDIRECT_SAMPLES, bias=INDIRECT_BIAS, seed=0, accel=ACCEL_BVH, no_lds=False, private_walk=False):
+        """Enqueue p3d_indirect_diffuse on caller-owned DEVICE buffers (raw pointers; 0 = no such plane) holding one frame per
+        camera; asynchronous on the scene's stream."""
+        arr, n = _camera_array([cam_or_cams] if isinstance(cam_or_cams, Camera) else cam_or_cams)
+        p = self._ray_params(1, accel, no_lds, private_walk, False)
+        g = IndirectParams(int(samples), bias, int(seed) & 0xFFFFFFFF)
+        i = IndirectInputs(depth_ptr or None, normal_ptr or None, albedo_ptr or None, rgb32f_ptr or None, 1)
+        o = IndirectOutputs(out_indirect_ptr or None, out_rgb32f_ptr or None, 1)
+        _check(lib().p3d_indirect_diffuse(self.h, arr, n, C.byref(p), C.byref(g), C.byref(i), C.byref(o)), "p3d_indirect_diffuse")
+
     def deinterleave_frames(self, gathered_ptr, frames_ptr, res_x, res_y, row_block, world, bpp, n_frames,
                             rank_stride_bytes=0, tile_stride_bytes=0, frame_stride_bytes=0):
         L = lib()
@@ -1576,6 +1636,23 @@ def host_ao_resolve(occluded, samples, rgb32f=None):
     out = {"ao": np.zeros(occluded.shape, np.float32), "rgb32f": np.zeros(occluded.shape + (3,), np.float32)}
     lib().p3dh_ao_resolve(int(samples), occluded.size, occluded.ctypes.data, rgb32f.ctypes.data if rgb32f is not None else None,
                           out["ao"].ctypes.data, out["rgb32f"].ctypes.data)
+    return out
+
+
+def host_indirect_resolve(radiance, valid, albedo=None, rgb32f=None):
+    """p3dh_indirect_resolve: steps 8 and 9 of p3d_indirect_diffuse's definition on the host (no GPU) -- radiance
+    (..., samples, 3), the colour of every sample's ray, and valid (...) uint8, 1 where the pixel has a query ->
+    {"indirect" (..., 3), "rgb32f" (..., 3)}.  albedo and rgb32f (..., 3) are optional."""
+    radiance = np.ascontiguousarray(radiance, np.float32)
+    shape, S = radiance.shape[:-2], radiance.shape[-2]
+    valid = np.ascontiguousarray(valid, np.uint8).reshape(shape)
+    if albedo is not None:
+        albedo = np.ascontiguousarray(albedo, np.float32).reshape(shape + (3,))
+    if rgb32f is not None:
+        rgb32f = np.ascontiguousarray(rgb32f, np.float32).reshape(shape + (3,))
+    out = {"indirect": np.zeros(shape + (3,), np.float32), "rgb32f": np.zeros(shape + (3,), np.float32)}
+    lib().p3dh_indirect_resolve(int(S), valid.size, radiance.ctypes.data, valid.ctypes.data, albedo.ctypes.data if albedo is not None else None,
+                                rgb32f.ctypes.data if rgb32f is not None else None, out["indirect"].ctypes.data, out["rgb32f"].ctypes.data)
     return out
 
 

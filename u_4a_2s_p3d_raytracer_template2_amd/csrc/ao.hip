@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "p3d_ao_segment.h"
 #include "p3d_launch.h"
 #include "p3d_pinhole.h"
 #include "p3d_scene_view.h"
@@ -28,30 +29,6 @@ namespace {
 #define P3D_AO_LANE_PER_PIXEL 0          // 1: a lane is a pixel and loops over its samples.  Measured: DESIGN "Ambient occlusion"
 #endif
 constexpr bool kLanePerPixel = P3D_AO_LANE_PER_PIXEL != 0;
-constexpr uint32_t kTries = 32u;         // rejection draws of step 5
-constexpr float kTiny = 0x1p-20f;        // least squared length steps 5 and 6 normalise
-
-// Steps 4 (the sample's key) to 6 for sample s of the pixel with key pk: L, the segment's direction times its length.
-// `live`: the lane has a query; the loop ends when no live lane of the wave is still drawing.
-__device__ __forceinline__ V3 ao_segment(V3 Ns, uint32_t pk, uint32_t s, float radius, bool live) {
-    const uint32_t k = rng_mix(pk, s);
-    V3 c = mk(0.0f, 0.0f, 0.0f);
-    bool accepted = false;
-#pragma nounroll
-    for (uint32_t j = 0; j < kTries; j++) {
-        if (__ballot(live && !accepted) == 0) break;
-        const float c0 = 2.0f * rng_u01(k, 3u * j) - 1.0f, c1 = 2.0f * rng_u01(k, 3u * j + 1u) - 1.0f, c2 = 2.0f * rng_u01(k, 3u * j + 2u) - 1.0f;
-        const float q = (c0 * c0 + c1 * c1) + c2 * c2;
-        const bool take = !accepted && q <= 1.0f && q >= kTiny;
-        if (take) c = mk(c0, c1, c2);
-        accepted = accepted || take;
-    }
-    V3 v = Ns;
-    if (accepted) v = normalized(c);
-    V3 w = add(Ns, v);
-    if (!((w.x * w.x + w.y * w.y) + w.z * w.z >= kTiny)) w = Ns;
-    return mul(normalized(w), radius);
-}
 
 template <bool LDS, int WALK, int OCC>
 __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void wf_ao_kernel(const LaunchParams P, const AoIO A) {

@@ -4,6 +4,7 @@
 //              [--device K | --gpus N] [--out image.png|image.ppm] [--counters] [--soft-shadow] [--fuzzy-reflection]
 //              [--aov PREFIX] [--denoise K [--denoise-sigmas Z A C]] [--accumulate [--accumulate-params TOL NMIN MAXLEN]]
 //              [--variance-guided [--variance-params MIN_TEMPORAL RADIUS SIGMA]] [--ao S RADIUS [--ao-scale F] [--ao-out PREFIX]]
+//              [--gi S [--gi-bias B]]
 // --gpus N: devices 0..N-1 each render every N-th block of 16 rows, one RCCL gather to device 0.
 // --orbit N STEP_DEG: N frames of the reference's mouse orbit (alpha advancing by STEP_DEG per frame, RT/main.cpp:339-341,
 // 419-421) in ONE p3d_render_frames call; --out then takes a %d pattern (e.g. frame_%03d.png) for the frame number.
@@ -28,6 +29,10 @@
 // --ao S RADIUS --ao-scale F: the occlusion is computed at 1 / F of the resolution (F in 1..4, dividing W and H; 1: as without)
 // on planes rendered at that resolution and brought up along the frame's own depth and normal by p3d_upsample; everything
 // after it (the modulation, --ao-out, --denoise, --accumulate) sees the upsampled plane.
+// --gi S [--gi-bias B]: the frame is rendered with its planes, p3d_indirect_diffuse gathers one bounce of diffuse indirect
+// light with S (1, 2, 4, .. 64) rays per pixel over them (origins moved B along the normal, default 0.001) and
+// albedo * indirect is added to the colour before it is written.  Combines with --denoise K (the sum is what is filtered),
+// with --ao (applied first) and with --aov; one frame on one GPU: not with --orbit, not with --gpus N.
 // Defaults are the reference's: resolution / accel / spp from the file, MAX_DEPTH 4.
 #include <chrono>
 #include <cstdio>
@@ -70,12 +75,13 @@ int main(int argc, char** argv) {
         fprintf(stderr, "usage: %s scene.p3f [--res W H] [--accel A] [--depth D] [--spp N] [--seed S] "
                         "[--device K | --gpus N] [--out file.ppm] [--orbit N STEP_DEG] [--counters] [--soft-shadow] [--fuzzy-reflection] [--schlick] [--aov PREFIX] "
                         "[--denoise K [--denoise-sigmas Z A C]] [--accumulate [--accumulate-params TOL NMIN MAXLEN]] "
-                        "[--variance-guided [--variance-params MIN_TEMPORAL RADIUS SIGMA]] [--ao S RADIUS [--ao-scale F] [--ao-out PREFIX]]\n"
+                        "[--variance-guided [--variance-params MIN_TEMPORAL RADIUS SIGMA]] [--ao S RADIUS [--ao-scale F] [--ao-out PREFIX]] [--gi S [--gi-bias B]]\n"
                         "  --denoise filters one frame on one GPU: not with --orbit, not with --gpus N\n"
                         "  --accumulate blends the frames of --orbit over time on one GPU; with it --denoise filters every accumulated frame\n"
                         "  --variance-guided steers that filter by the variance of every pixel's luminance over time: needs --accumulate and --denoise\n"
                         "  --ao multiplies the colour by ambient occlusion (S segments of length RADIUS per pixel) on one GPU: not with --gpus N\n"
-                        "  --ao-scale computes it at 1 / F of the resolution (F in 1..4, dividing W and H) and upsamples it along the frame's depth and normal: needs --ao\n", argv[0]);
+                        "  --ao-scale computes it at 1 / F of the resolution (F in 1..4, dividing W and H) and upsamples it along the frame's depth and normal: needs --ao\n"
+                        "  --gi adds one bounce of diffuse indirect light (S rays per pixel) to one frame on one GPU: not with --orbit, not with --gpus N\n", argv[0]);
         return 2;
     }
     RenderOptions opt;
@@ -114,6 +120,12 @@ int main(int argc, char** argv) {
         }
         else if (a == "--ao-out") { need(1); ao_out = argv[++i]; }
         else if (a == "--ao-scale") { need(1); opt.ao_scale = atoi(argv[++i]); if (opt.ao_scale < 1 || opt.ao_scale > 4) { fprintf(stderr, "--ao-scale needs F in 1..4\n"); return 2; } }
+        else if (a == "--gi") {
+            need(1); opt.indirect_diffuse = atoi(argv[++i]);
+            const int S = opt.indirect_diffuse;
+            if (S < 1 || S > 64 || (S & (S - 1))) { fprintf(stderr, "--gi needs S in 1, 2, 4, .. 64\n"); return 2; }
+        }
+        else if (a == "--gi-bias") { need(1); opt.indirect_bias = (float)atof(argv[++i]); if (!(opt.indirect_bias >= 0.0f)) { fprintf(stderr, "--gi-bias needs B >= 0\n"); return 2; } }
         else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     Scene scene;
@@ -131,6 +143,7 @@ int main(int argc, char** argv) {
     if (opt.accumulate && (orbit_n < 1 || opt.gpus > 1)) { fprintf(stderr, "--accumulate blends the frames of --orbit N STEP on one GPU: it needs --orbit, not --gpus N\n"); return 2; }
     if (opt.variance_guided && (!opt.accumulate || opt.denoise < 0)) { fprintf(stderr, "--variance-guided steers the filter of an accumulated sequence: it needs --accumulate and --denoise K\n"); return 2; }
     if (opt.ambient_occlusion > 0 && opt.gpus > 1) { fprintf(stderr, "--ao runs on the planes of whole frames on one GPU: not with --gpus N\n"); return 2; }
+    if (opt.indirect_diffuse > 0 && (opt.gpus > 1 || orbit_n > 0)) { fprintf(stderr, "--gi gathers over the planes of one whole frame on one GPU: not with --gpus N or --orbit\n"); return 2; }
     if (opt.ao_scale != 1 && opt.ambient_occlusion < 1) { fprintf(stderr, "--ao-scale needs --ao S RADIUS\n"); return 2; }
     if (W % opt.ao_scale || H % opt.ao_scale) { fprintf(stderr, "--ao-scale F must divide both resolutions (%d x %d)\n", W, H); return 2; }
     if (!ao_out.empty() && opt.ambient_occlusion < 1) { fprintf(stderr, "--ao-out needs --ao S RADIUS\n"); return 2; }

@@ -13,6 +13,7 @@
 #include "../grid_builder.h"
 #include "accumulate_host.h"
 #include "ao_host.h"
+#include "indirect_host.h"
 #include "denoise_host.h"
 #include "p3d_scene.h"
 #include "tile_coverage_host.h"
@@ -134,6 +135,14 @@ void p3dh_ao_segments(const p3d_ao_params* params, const p3d_camera* cam, int32_
 }
 void p3dh_ao_resolve(int32_t samples, uint64_t n_pixels, const int32_t* occluded, const float* rgb32f_in, float* ao_out, float* rgb32f_out) {
     ao_resolve(samples, (size_t)n_pixels, occluded, rgb32f_in, ao_out, rgb32f_out);
+}
+
+// indirect_resolve() of the host layer (indirect_host.cpp): steps 8 and 9 of p3d_indirect_diffuse's definition on host planes,
+// every bit.  radiance [n_pixels][samples][3], valid [n_pixels]; albedo, rgb32f_in, indirect_out and rgb32f_out may each be
+// NULL.  The rays are p3dh_ao_segments' at radius 1.  The caller keeps samples inside what p3d_indirect_diffuse accepts.
+void p3dh_indirect_resolve(int32_t samples, uint64_t n_pixels, const float* radiance, const uint8_t* valid, const float* albedo,
+                           const float* rgb32f_in, float* indirect_out, float* rgb32f_out) {
+    indirect_resolve(samples, (size_t)n_pixels, radiance, valid, albedo, rgb32f_in, indirect_out, rgb32f_out);
 }
 
 // accumulate() of the host layer (accumulate_host.cpp): p3d_accumulate's result on host planes, every bit.  history may be

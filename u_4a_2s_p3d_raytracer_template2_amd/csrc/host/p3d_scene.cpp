@@ -513,6 +513,20 @@ int modulate_by_ao(p3d_scene* dev, const RenderOptions& opt, const p3d_camera* c
     return rc;
 }
 
+// RenderOptions::indirect_diffuse over n frames in host memory: out.colors becomes colour + albedo * indirect.
+int add_indirect_diffuse(p3d_scene* dev, const RenderOptions& opt, const p3d_camera* cams, int n, int accel, RenderResult& out) {
+    p3d_render_params prm;
+    memset(&prm, 0, sizeof prm);
+    prm.accel = accel; prm.world = 1;
+    const p3d_indirect_params ip = {opt.indirect_diffuse, opt.indirect_bias, opt.seed};
+    std::vector<float> lit(out.colors.size());
+    const p3d_indirect_inputs in = {out.depth.data(), out.normal.data(), out.albedo.data(), out.colors.data(), 0};
+    const p3d_indirect_outputs o = {nullptr, lit.data(), 0};
+    const int rc = p3d_indirect_diffuse(dev, cams, n, &prm, &ip, &in, &o);
+    if (!rc) out.colors.swap(lit);
+    return rc;
+}
+
 // RenderOptions::ao_scale against the frame: "" or why the call is refused
 const char* ao_scale_refusal(const RenderOptions& opt, int res_x, int res_y) {
     if (opt.ao_scale == 1) return "";
@@ -531,6 +545,7 @@ int renderScene(const Scene& scene, const RenderOptions& opt, bool want_colors, 
     if (opt.gpus < 1 || opt.gpus > 64) { if (err) *err = "gpus must be in 1..64"; return P3D_ERR_ARG; }
     if (opt.denoise >= 0 && opt.gpus > 1) { if (err) *err = "the denoiser is served on one GPU (shards are not frames)"; return P3D_ERR_ARG; }
     if (opt.ambient_occlusion > 0 && opt.gpus > 1) { if (err) *err = "ambient occlusion is served on one GPU (shards are not frames)"; return P3D_ERR_ARG; }
+    if (opt.indirect_diffuse > 0 && opt.gpus > 1) { if (err) *err = "indirect diffuse is served on one GPU (shards are not frames)"; return P3D_ERR_ARG; }
     Scene::Flat flat;
     scene.flatten(flat);
     p3d_camera cam;
@@ -569,9 +584,9 @@ int renderScene(const Scene& scene, const RenderOptions& opt, bool want_colors, 
     auto done = [&](int code) { if (code) bad(code); if (sample_buf) p3d_device_free(dev, sample_buf); p3d_scene_destroy(dev); return code; };
     if (prm.spp > 0 && (rc = device_samples(dev, opt.seed, &cam, 1, prm, &sample_buf)) != 0) return done(rc);
     size_t npx = (size_t)cam.res_x * cam.res_y;
-    const bool with_ao = opt.ambient_occlusion > 0;
-    // the filter reads the float colour and the planes, and so does ambient occlusion: 0 passes then quantise its colour
-    const bool denoised = opt.denoise >= 0 || with_ao, planes = opt.want_aov || denoised;
+    const bool with_ao = opt.ambient_occlusion > 0, with_gi = opt.indirect_diffuse > 0;
+    // the filter reads the float colour and the planes, and so do ambient occlusion and the gather: 0 passes then quantise their colour
+    const bool denoised = opt.denoise >= 0 || with_ao || with_gi, planes = opt.want_aov || denoised;
     out.img_Data.assign(npx * 3, 0);
     if (want_colors || denoised) out.colors.assign(npx * 3, 0.0f);
     if (want_hit) out.hit_id.assign(npx, -1);
@@ -586,6 +601,7 @@ int renderScene(const Scene& scene, const RenderOptions& opt, bool want_colors, 
     rc = p3d_timer_begin(dev);
     if (!rc) rc = planes ? p3d_render_aov(dev, &cam, 1, &prm, &o, &a) : p3d_render(dev, &cam, &prm, &o);
     if (!rc && with_ao) rc = modulate_by_ao(dev, opt, &cam, 1, prm.accel, out);
+    if (!rc && with_gi) rc = add_indirect_diffuse(dev, opt, &cam, 1, prm.accel, out);
     if (!rc && denoised) {             // img_Data and colors become the filtered frame
         const p3d_denoise_params dp = {cam.res_x, cam.res_y, 1, opt.denoise >= 0 ? opt.denoise : 0, opt.denoise_sigma_depth, opt.denoise_sigma_albedo,
                                        opt.denoise_sigma_color, opt.denoise_normal_power_log2};
@@ -623,6 +639,7 @@ int renderFrames(const Scene& scene, const RenderOptions& opt, const std::vector
     if (!scene.GetCamera()) { if (err) *err = "scene has no camera"; return P3D_ERR_ARG; }
     if (opt.gpus != 1) { if (err) *err = "renderFrames renders on one device (gpus must be 1)"; return P3D_ERR_ARG; }
     if (eyes.empty()) { if (err) *err = "no eyes"; return P3D_ERR_ARG; }
+    if (opt.indirect_diffuse > 0) { if (err) *err = "indirect diffuse is served by renderScene (one frame)"; return P3D_ERR_ARG; }
     const int n = (int)eyes.size();
     std::vector<p3d_camera> cams((size_t)n);
     Camera cam = *scene.GetCamera();

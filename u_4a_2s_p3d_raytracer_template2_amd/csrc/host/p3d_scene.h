@@ -261,6 +261,11 @@ struct RenderOptions {
     // p3d_ambient_occlusion on those and brings the plane up along the frames' own depth and normal with p3d_upsample
     // (denoise_sigma_depth, denoise_normal_power_log2); the colour is multiplied by the upsampled plane
     int ao_scale = 1;
+    // renderScene() on one GPU: > 0 runs p3d_indirect_diffuse with that many rays per pixel over the frame's planes (accel as
+    // the frame's, seed as its) and adds albedo * indirect to the float colour -- after ambient occlusion, before the filter
+    // reads it.  The default bias is that of the Python binding (api.py, INDIRECT_BIAS)
+    int indirect_diffuse = 0;
+    float indirect_bias = 0.001f;
 };
 struct RenderResult {
     std::vector<uint8_t> img_Data;   // RGB8, bottom row first (RT/main.cpp:76)

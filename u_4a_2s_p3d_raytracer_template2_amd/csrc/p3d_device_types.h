@@ -237,6 +237,19 @@ struct AoIO {
     uint32_t seed;
 };
 
+// The planes of p3d_indirect_diffuse (wf_indirect_kernel), laid out and mapped to lanes like AoIO's.  depth and normal are
+// needed; albedo and color may each be nullptr; indirect and rgb (3 floats per pixel both) may each be nullptr, not both.
+struct IndirectIO {
+    const float* depth; const float* normal; const float* albedo; const float* color;
+    float* indirect; float* rgb;
+    const FrameCam* cams;
+    int32_t res_x, res_y, n_frames;
+    int32_t log2_samples;
+    uint32_t row_waves, row_groups;
+    float bias;
+    uint32_t seed;
+};
+
 // Every level of a pass for the fused resolve launch (small frames / shards, wf_resolve_fused_kernel): level l's
 // parked nodes (shard s at nodes[l] + s * cap[l]) and their per-shard counts; levels top .. 1 are combined.
 struct ResolveLevels { NodeRec* nodes[18]; const uint32_t* ncount[18]; uint32_t cap[18]; int32_t top; };

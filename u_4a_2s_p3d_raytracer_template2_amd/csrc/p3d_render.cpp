@@ -1,6 +1,6 @@
-// p3d_render.cpp -- p3d_render, p3d_render_frames, p3d_render_aov, p3d_trace_rays, p3d_occluded, p3d_ambient_occlusion and p3d_tune_schedule of include/p3d_hip.h: a frame (or a
-// batch of frames, or a stream of the caller's rays, or their shadow queries, or those of ambient occlusion) as a sequence of steps -- validate the request, fill the launch
-// parameters, size the workspaces, choose the schedule, enqueue it.  The kernels are those of p3d_kernels.hip and ao.hip (p3d_launch.h).
+// p3d_render.cpp -- p3d_render, p3d_render_frames, p3d_render_aov, p3d_trace_rays, p3d_occluded, p3d_ambient_occlusion, p3d_indirect_diffuse and p3d_tune_schedule of include/p3d_hip.h: a frame (or a
+// batch of frames, or a stream of the caller's rays, or their shadow queries, or those of ambient occlusion, or a gather of indirect light) as a sequence of steps -- validate the request, fill the launch
+// parameters, size the workspaces, choose the schedule, enqueue it.  The kernels are those of p3d_kernels.hip, ao.hip and indirect.hip (p3d_launch.h).
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -1129,9 +1129,133 @@ int ambient_occlusion(p3d_scene* s, const p3d_camera* cams, int32_t n, const p3d
     return P3D_OK;
 }
 
+// All argument checks of p3d_indirect_diffuse, in the order include/p3d_hip.h lists them: p3d_trace_rays' rules for params
+// (max_depth is not read: the request is normalised to depth 1 without features), then p3d_ambient_occlusion's for the rest.
+int validate_indirect_request(const p3d_scene* s, const p3d_camera* cams, int32_t n, const p3d_render_params* prm,
+                              const p3d_indirect_params* ind, const p3d_indirect_inputs* in, const p3d_indirect_outputs* out, FrameConfig& cfg) {
+    if (!s || !cams || !prm || !ind || !in || !out) return fail(P3D_ERR_ARG, "NULL argument");
+    if (n < 1) return fail(P3D_ERR_ARG, "n must be at least 1");
+    if (prm->accel < 0 || prm->accel > 2) return fail(P3D_ERR_ARG, "accel must be 0, 1 or 2");
+    if (prm->flags & ~kRayStreamFlags)
+        return fail(P3D_ERR_ARG, "flags: indirect diffuse accepts P3D_FLAG_NO_LDS_SCENE, _PRIVATE_WALK and _WAVEFRONT only");
+    if (prm->features != 0) return fail(P3D_ERR_ARG, "features: the bounce is lit without features, features must be 0");
+    if (prm->spp != 0) return fail(P3D_ERR_ARG, "spp: indirect diffuse has no pixel samples, spp must be 0");
+    if (prm->samples) return fail(P3D_ERR_ARG, "samples: indirect diffuse has no pixel samples, p3d_render_params::samples must be NULL");
+    if (prm->world > 1 || prm->rank != 0) return fail(P3D_ERR_ARG, "world / rank: indirect diffuse is not sharded, world must be 0 or 1 and rank 0 (stitch the planes first)");
+    const int32_t S = ind->samples;
+    if (S < 1 || S > 64 || (S & (S - 1)) != 0) return fail(P3D_ERR_ARG, "p3d_indirect_params::samples must be 1, 2, 4, 8, 16, 32 or 64");
+    if (!std::isfinite(ind->bias) || !(ind->bias >= 0.0f)) return fail(P3D_ERR_ARG, "p3d_indirect_params::bias must be finite and not negative");
+    if (!in->depth || !in->normal) return fail(P3D_ERR_ARG, "p3d_indirect_inputs::depth / normal is NULL");
+    if (!out->indirect && !out->rgb32f) return fail(P3D_ERR_ARG, "p3d_indirect_outputs: both indirect and rgb32f are NULL");
+    if (in->memory != 0 && in->memory != 1) return fail(P3D_ERR_ARG, "p3d_indirect_inputs::memory must be 0 (host) or 1 (device)");
+    if (out->memory != 0 && out->memory != 1) return fail(P3D_ERR_ARG, "p3d_indirect_outputs::memory must be 0 (host) or 1 (device)");
+    const void* const outs[2] = {out->indirect, out->rgb32f};
+    for (const void* o : outs)
+        if (o && (o == in->depth || o == in->normal || o == in->albedo || o == in->rgb32f)) return fail(P3D_ERR_ARG, "an output plane aliases an input plane");
+    if (out->indirect && out->indirect == out->rgb32f) return fail(P3D_ERR_ARG, "p3d_indirect_outputs::indirect and rgb32f alias each other");
+    if (cams[0].res_x < 1 || cams[0].res_y < 1) return fail(P3D_ERR_ARG, "res_x and res_y of the cameras must be at least 1");
+    for (int f = 1; f < n; f++)
+        if (cams[f].res_x != cams[0].res_x || cams[f].res_y != cams[0].res_y) return fail(P3D_ERR_ARG, "the cameras differ in res_x / res_y");
+    // 64-bit products of 31-bit factors, compared step by step so that none of them wraps
+    const uint64_t rows = (uint64_t)n * (uint64_t)cams[0].res_y;
+    if (rows > kMaxStackedPixels || rows * (uint64_t)cams[0].res_x > kMaxStackedPixels ||
+        rows * (uint64_t)cams[0].res_x * (uint64_t)S > kMaxStackedPixels)
+        return fail(P3D_ERR_LIMIT, "n * res_y * res_x * samples does not fit 31 bits");
+    if (s->cull_never_hit) return fail(P3D_ERR_STATE, "scene was built with cull_never_hit: it serves frames only, not rays of any length");
+    cfg.max_depth = 1; cfg.accel = prm->accel; cfg.spp = 0;
+    cfg.flags = prm->flags & kConfigFlags; cfg.features = 0;
+    return P3D_OK;
+}
+
+// Level 1 of p3d_trace_rays at max_depth 1 on rays made in lanes from the planes, summed per pixel: the scene into the launch
+// parameters as for any entry, the cameras into the handle's buffer by a launch of the stream, then ONE launch of
+// wf_indirect_kernel (indirect.hip) for all frames.  No queues, no workspace, no schedule: of the handle it touches the
+// staging of s->indirect and the grid of the first GRID call.
+int indirect_diffuse(p3d_scene* s, const p3d_camera* cams, int32_t n, const p3d_render_params* prm, const p3d_indirect_params* ind,
+                     const p3d_indirect_inputs* in, const p3d_indirect_outputs* out) {
+    FrameConfig cfg;
+    int rc = validate_indirect_request(s, cams, n, prm, ind, in, out, cfg);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(s->device));
+    const size_t pixels = (size_t)n * (size_t)cams[0].res_y * (size_t)cams[0].res_x;
+    const bool host_in = in->memory == 0, host_out = out->memory == 0;
+    p3d_scene::IndirectDiffuse& B = s->indirect;
+
+    // everything the call needs of the handle, sized before anything is allocated
+    struct Need { RawBuf* buf; size_t bytes; } needs[7];
+    int n_needs = 0;
+    needs[n_needs++] = {&B.cams, (size_t)n * sizeof(FrameCam)};
+    if (host_in) {
+        needs[n_needs++] = {&B.in_depth, pixels * 4}; needs[n_needs++] = {&B.in_normal, pixels * 12};
+        if (in->albedo) needs[n_needs++] = {&B.in_albedo, pixels * 12};
+        if (in->rgb32f) needs[n_needs++] = {&B.in_rgb32f, pixels * 12};
+    }
+    if (host_out && out->indirect) needs[n_needs++] = {&B.out_indirect, pixels * 12};
+    if (host_out && out->rgb32f) needs[n_needs++] = {&B.out_rgb32f, pixels * 12};
+    if (capturing(s->stream)) {
+        if (host_in || host_out)
+            return fail(P3D_ERR_STATE, "p3d_indirect_diffuse copies host planes and waits for them: not while the stream is being captured");
+        for (int i = 0; i < n_needs; i++)
+            if (needs[i].bytes > needs[i].buf->cap)
+                return fail(P3D_ERR_STATE, "p3d_indirect_diffuse has to allocate its camera buffer: make a call of this shape before the capture");
+    }
+
+    FramePlan plan;
+    plan.s = s;
+    if ((rc = fill_scene_params(s, cfg, prm, plan)) != P3D_OK) return rc;
+    const LaunchParams& P = plan.P;
+    if (wavefront_lds_bytes(P, plan.lds_scene) > kMaxLdsBytes) return fail(P3D_ERR_LIMIT, "BVH depth needs more LDS than a CU has");
+    for (int i = 0; i < n_needs; i++) HIP_TRY(ensure_counted(s, *needs[i].buf, needs[i].bytes));
+
+    IndirectIO io;
+    memset(&io, 0, sizeof io);
+    io.depth = in->depth; io.normal = in->normal; io.albedo = in->albedo; io.color = in->rgb32f;
+    io.indirect = out->indirect; io.rgb = out->rgb32f;
+    io.res_x = cams[0].res_x; io.res_y = cams[0].res_y; io.n_frames = n;
+    for (io.log2_samples = 0; (1 << io.log2_samples) < ind->samples; io.log2_samples++) {}
+    io.bias = ind->bias; io.seed = ind->seed;
+    {   // the cameras travel in the arguments of a launch of this stream: a captured call replays with its own
+        std::vector<FrameCam> fc((size_t)n);
+        for (int f = 0; f < n; f++) fc[f] = camera_record(cams[f]);
+        HIP_TRY(launch_frame_cams((FrameCam*)B.cams.p, fc.data(), n, s->stream));
+        io.cams = (const FrameCam*)B.cams.p;
+    }
+    if (host_in) {
+        HIP_TRY(hipMemcpyAsync(B.in_depth.p, in->depth, pixels * 4, hipMemcpyHostToDevice, s->stream));
+        HIP_TRY(hipMemcpyAsync(B.in_normal.p, in->normal, pixels * 12, hipMemcpyHostToDevice, s->stream));
+        io.depth = (const float*)B.in_depth.p; io.normal = (const float*)B.in_normal.p;
+        if (in->albedo) {
+            HIP_TRY(hipMemcpyAsync(B.in_albedo.p, in->albedo, pixels * 12, hipMemcpyHostToDevice, s->stream));
+            io.albedo = (const float*)B.in_albedo.p;
+        }
+        if (in->rgb32f) {
+            HIP_TRY(hipMemcpyAsync(B.in_rgb32f.p, in->rgb32f, pixels * 12, hipMemcpyHostToDevice, s->stream));
+            io.color = (const float*)B.in_rgb32f.p;
+        }
+    }
+    if (host_out) {
+        if (out->indirect) io.indirect = (float*)B.out_indirect.p;
+        if (out->rgb32f) io.rgb = (float*)B.out_rgb32f.p;
+    }
+    HIP_TRY(launch_wf_indirect(P, io, plan.kv, s->stream));
+    if (host_out) {
+        if (out->indirect) HIP_TRY(hipMemcpyAsync(out->indirect, io.indirect, pixels * 12, hipMemcpyDeviceToHost, s->stream));
+        if (out->rgb32f) HIP_TRY(hipMemcpyAsync(out->rgb32f, io.rgb, pixels * 12, hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+    } else if (host_in) {
+        HIP_TRY(hipStreamSynchronize(s->stream));        // the caller's host planes have been read when the call returns
+    }
+    return P3D_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int p3d_indirect_diffuse(p3d_scene* s, const p3d_camera* cams, int32_t n, const p3d_render_params* prm, const p3d_indirect_params* ind,
+                         const p3d_indirect_inputs* in, const p3d_indirect_outputs* out) {
+    return indirect_diffuse(s, cams, n, prm, ind, in, out);
+}
 
 int p3d_ambient_occlusion(p3d_scene* s, const p3d_camera* cams, int32_t n, const p3d_render_params* prm, const p3d_ao_params* ao,
                           const p3d_ao_inputs* in, const p3d_ao_outputs* out) {

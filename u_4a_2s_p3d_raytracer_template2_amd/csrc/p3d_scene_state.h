@@ -1,5 +1,5 @@
 // p3d_scene_state.h -- the scene handle behind the C-ABI of include/p3d_hip.h, shared by the files that implement it
-// (p3d_scene_create.cpp, p3d_scene_update.cpp, p3d_scene_rebuild.cpp, p3d_scene_build_grid.cpp, p3d_render.cpp, p3d_generate_samples.cpp, p3d_denoise.cpp, p3d_accumulate.cpp, p3d_upsample.cpp, p3d_capi_misc.cpp; p3d_ambient_occlusion lives in p3d_render.cpp).  Internal: not installed with include/.
+// (p3d_scene_create.cpp, p3d_scene_update.cpp, p3d_scene_rebuild.cpp, p3d_scene_build_grid.cpp, p3d_render.cpp, p3d_generate_samples.cpp, p3d_denoise.cpp, p3d_accumulate.cpp, p3d_upsample.cpp, p3d_capi_misc.cpp; p3d_ambient_occlusion and p3d_indirect_diffuse live in p3d_render.cpp).  Internal: not installed with include/.
 // Every device resource in it is owned by a member that frees it: deleting a p3d_scene releases all of them.
 #ifndef P3D_SCENE_STATE_H
 #define P3D_SCENE_STATE_H
@@ -249,6 +249,10 @@ struct p3d_scene {
     struct AmbientOcclusion {
         p3d::RawBuf in_depth, in_normal, in_rgb32f, out_ao, out_rgb32f, cams;
     } ao;
+    // p3d_indirect_diffuse: the same for its planes; all counted in device_bytes as they grow.
+    struct IndirectDiffuse {
+        p3d::RawBuf in_depth, in_normal, in_albedo, in_rgb32f, out_indirect, out_rgb32f, cams;
+    } indirect;
     // p3d_upsample: the staging of host planes (counted in device_bytes as they grow).  The filter itself needs no scratch.
     struct Upsample {
         p3d::RawBuf in_low, in_low_depth, in_low_normal, in_depth, in_normal, out_plane, out_fallback;

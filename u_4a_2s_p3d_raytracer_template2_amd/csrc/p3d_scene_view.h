@@ -1,6 +1,6 @@
 // p3d_scene_view.h -- what every ray kernel does before it walks: the scene view of its launch (the blob where it lies, or
 // an LDS copy of it), its wave's traversal stack behind that copy, and the register budget attribute.  Shared by the kernel
-// files that walk the scene (p3d_kernels.hip, ao.hip).
+// files that walk the scene (p3d_kernels.hip, ao.hip, indirect.hip).
 #ifndef P3D_SCENE_VIEW_H
 #define P3D_SCENE_VIEW_H
 
