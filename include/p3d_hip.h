@@ -603,7 +603,9 @@ typedef struct p3d_denoise_inputs { const float *rgb32f, *depth, *normal, *albed
  *    out->hit_id must be NULL.  in->memory and out->memory are 0 (host) or 1 (device), independently; host planes are
  *    staged in buffers the handle owns and copied back before the call returns, as in p3d_trace_rays.
  *  - ordering: with all planes in device memory the call only enqueues on the scene's stream: one launch per pass, all
- *    frames in it (iterations == 0: one copy-and-quantise launch).
+ *    frames in it (iterations == 0: one copy-and-quantise launch).  With a plane in host memory on EITHER side the call
+ *    waits for the stream before it returns -- host inputs with device outputs too, so the caller's host planes have
+ *    been read (pinned ones included) when it returns, as in p3d_accumulate and p3d_ambient_occlusion.
  *  - aliasing: out->rgb32f == in->rgb32f in device memory is allowed for every iterations.  No pass writes a buffer it
  *    reads: the colour alternates between two scratch buffers of the handle and the last pass writes the destination (a
  *    single in-place pass reads a copy).  Partial overlap is unspecified.
@@ -657,7 +659,8 @@ typedef struct p3d_denoise_variance_outputs { uint8_t* rgb8; float* rgb32f; floa
  *    each, as many as p3d_denoise's pass count needs); they and the staging of host planes (p3d_denoise's, and the two
  *    variance planes) are counted in p3d_scene_stats::device_bytes as they grow, kept for the next call and freed with
  *    the handle.
- *  - memory, ordering, stream capture, the 31-bit limit, shards and "no frame state touched": as p3d_denoise.
+ *  - memory, ordering (the wait with a host plane on either side included), stream capture, the 31-bit limit, shards and
+ *    "no frame state touched": as p3d_denoise.
  *  - P3D_ERR_ARG: p3d_denoise's refusals; a NULL in->variance; sigma_color == 0; the aliases above. */
 int p3d_denoise_variance(p3d_scene* scene, const p3d_denoise_params* params, const p3d_denoise_variance_inputs* in,
                          const p3d_denoise_variance_outputs* out);
@@ -1022,8 +1025,9 @@ typedef struct p3d_upsample_outputs { float* plane; uint8_t* fallback; int32_t m
  *  - the fallback plane tells a caller which pixels to treat otherwise, for example to re-trace them with p3d_trace_rays.
  *  - memory: in->memory and out->memory are 0 (host) or 1 (device), independently.  Host planes are staged in buffers the
  *    handle owns (counted in p3d_scene_stats::device_bytes as they grow, kept for the next call, freed with the handle);
- *    the call copies back and waits.  With everything in device memory the call only enqueues on the scene's stream: ONE
- *    launch for all n_frames frames.
+ *    the call copies back and waits -- with host inputs and device outputs too, so the caller's host planes have been read
+ *    (pinned ones included) when it returns.  With everything in device memory the call only enqueues on the scene's
+ *    stream: ONE launch for all n_frames frames.
  *  - stream capture: a call that has to allocate while the stream is being captured, or that has a plane in host memory,
  *    is refused with P3D_ERR_STATE; the capture survives.  After a call of the same shape made before the capture, the
  *    captured call is accepted and the graph replays.

@@ -11,6 +11,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import accumulate_reference as R                           # noqa: E402
 import u_4a_2s_p3d_raytracer_template2_amd as P            # noqa: E402
 from conftest import scene_path                            # noqa: E402
+from plane_memory import check_host_device_split          # noqa: E402
 from test_accumulate_host import make_call, refusal_cases  # noqa: E402
 from u_4a_2s_p3d_raytracer_template2_amd import api        # noqa: E402
 
@@ -208,6 +209,32 @@ def test_mixed_memory(handle):
         ds.sync()
         got = dict(rgb32f=o32d.cpu().numpy(), length=old.cpu().numpy()) if om else dict(rgb32f=o32h, length=olh)
         same_result(got, ref, "frames %d history %d out %d" % (fm, hm, om))
+
+
+
+def test_host_or_device_memory_on_either_side(handle):
+    """Host inputs (frames and history) with device outputs, device inputs with host outputs: the all-device bits.  Two frames
+    of 70 x 5 with a history: more than one tile across with a tail."""
+    import ctypes as C
+    _, ds = handle
+    w, h, n = 70, 5, 2
+    seq = R.make_sequence(w, h, n, seed=8, history=True)
+    planes = {k: seq[k] for k in PLANES + ("hit_id",)}
+    planes.update({"h_" + k: seq["history"][k] for k in PLANES + ("length", "hit_id")})
+
+    cams, _ = api._camera_array(seq["cams"])
+    hcam = (api.Camera * 1)(seq["history"]["cam"])
+    p = api.AccumulateParams(w, h, n, KW["depth_tolerance"], KW["normal_min"], KW["max_history"])
+    frames_of = lambda i, m: api.AccumulateFrames(i["rgb32f"], i["depth"], i["normal"], i["hit_id"], cams, m)
+    history_of = lambda i, m: api.AccumulateHistory(i["h_rgb32f"], i["h_depth"], i["h_normal"], i["h_length"], i["h_hit_id"], hcam, m)
+
+    def call(i, in_memory, o, out_memory):
+        fr, hi = frames_of(i, in_memory), history_of(i, in_memory)
+        out = api.AccumulateOutputs(o["rgb32f"], o["length"], out_memory)
+        assert P.lib().p3d_accumulate(ds.h, C.byref(p), C.byref(fr), C.byref(hi), C.byref(out)) == 0, P.lib().p3d_last_error()
+
+    ref = check_host_device_split(ds, planes, dict(rgb32f=np.zeros((n, h, w, 3), F), length=np.zeros((n, h, w), F)), call)
+    assert (ref["length"] > 1).any() and (ref["length"] == 1).any()
 
 
 @pytest.mark.parametrize("name,status,change", refusal_cases(), ids=[c[0] for c in refusal_cases()])

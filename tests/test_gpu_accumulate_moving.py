@@ -13,6 +13,7 @@ import accumulate_moving_reference as M                    # noqa: E402
 import scene_motion as SM                                  # noqa: E402
 import u_4a_2s_p3d_raytracer_template2_amd as P            # noqa: E402
 from conftest import scene_path                            # noqa: E402
+from plane_memory import check_host_device_split          # noqa: E402
 from u_4a_2s_p3d_raytracer_template2_amd import api        # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -241,6 +242,33 @@ def test_mixed_memory(handle):
         ds.sync()
         got = {k: devo[k].cpu().numpy() for k in OUT} if om else host
         same_result(got, ref, "frames %d history %d motion %d out %d" % (fm, hm, mm, om))
+
+
+
+def test_host_or_device_memory_on_either_side(handle):
+    """Host inputs (frames, history and geometry) with device outputs, device inputs with host outputs: the all-device bits.
+    Two frames of 70 x 5 with a history: more than one tile across with a tail."""
+    _, ds = handle
+    w, h, n = 70, 5, 2
+    seq = M.make_sequence(w, h, n, seed=8, history=True)
+    planes = {k: seq[k] for k in PLANES + ("hit_id", "prim_type", "prim_data")}
+    planes.update({"h_" + k: seq["history"][k] for k in PLANES + ("length", "hit_id", "prim_data")})
+
+    cams, _ = api._camera_array(seq["cams"])
+    hcam = (api.Camera * 1)(seq["history"]["cam"])
+    p = api.AccumulateParams(w, h, n, KW["depth_tolerance"], KW["normal_min"], KW["max_history"])
+    frames_of = lambda i, m: api.AccumulateFrames(i["rgb32f"], i["depth"], i["normal"], i["hit_id"], cams, m)
+    history_of = lambda i, m: api.AccumulateHistory(i["h_rgb32f"], i["h_depth"], i["h_normal"], i["h_length"], i["h_hit_id"], hcam, m)
+
+    def call(i, in_memory, o, out_memory):
+        fr, hi = frames_of(i, in_memory), history_of(i, in_memory)
+        mo = api.AccumulateMotion(4, i["prim_type"], i["prim_data"], i["h_prim_data"], in_memory)
+        out = api.AccumulateMovingOutputs(*[o[k] for k in OUT], out_memory)
+        assert P.lib().p3d_accumulate_moving(ds.h, C.byref(p), C.byref(fr), C.byref(hi), C.byref(mo), C.byref(out)) == 0, P.lib().p3d_last_error()
+
+    outs = dict(rgb32f=np.zeros((n, h, w, 3), F), length=np.zeros((n, h, w), F), prev_xy=np.zeros((n, h, w, 2), F))
+    ref = check_host_device_split(ds, planes, outs, call)
+    assert (ref["length"] > 1).any() and (ref["length"] == 1).any()
 
 
 def test_stream_capture():

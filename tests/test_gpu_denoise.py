@@ -12,6 +12,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import denoise_reference as R                              # noqa: E402
 import u_4a_2s_p3d_raytracer_template2_amd as P            # noqa: E402
 from conftest import scene_path                            # noqa: E402
+from plane_memory import check_host_device_split          # noqa: E402
 from u_4a_2s_p3d_raytracer_template2_amd import api        # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -118,6 +119,24 @@ def test_device_memory_sentinels_and_in_place(handle):
     ds.denoise_device(w, h, *[t.data_ptr() for t in dev], out_rgb8_ptr=o8.data_ptr(), n_frames=n, **kw)
     ds.sync()
     same_bits(o8.cpu().numpy().reshape(ref["rgb8"].shape), ref["rgb8"], "rgb8 alone")
+
+
+
+def test_host_or_device_memory_on_either_side(handle):
+    """Host inputs with device outputs (and the stream idle on return), device inputs with host outputs: the all-device bits.
+    Two frames of 70 x 5: more than one tile across with a tail, fewer rows than a tile."""
+    _, ds = handle
+    w, h, n = 70, 5, 2
+    planes = dict(zip(("rgb32f", "depth", "normal", "albedo"), R.random_planes(w, h, n=n, seed=31)))
+    p = api.DenoiseParams(w, h, n, 3, SIGMAS["sigma_depth"], SIGMAS["sigma_albedo"], 0.3, 5)
+
+    def call(i, in_memory, o, out_memory):
+        di = api.DenoiseInputs(i["rgb32f"], i["depth"], i["normal"], i["albedo"], in_memory)
+        do = api.Outputs(o["rgb8"], o["rgb32f"], None, out_memory)
+        assert P.lib().p3d_denoise(ds.h, C.byref(p), C.byref(di), C.byref(do)) == 0, P.lib().p3d_last_error()
+
+    ref = check_host_device_split(ds, planes, dict(rgb32f=np.zeros((n, h, w, 3), np.float32), rgb8=np.zeros((n, h, w, 3), np.uint8)), call)
+    assert not np.array_equal(ref["rgb32f"], planes["rgb32f"])
 
 
 def test_refusals(handle):

@@ -12,6 +12,7 @@ import denoise_reference as R                              # noqa: E402
 import denoise_variance_reference as RV                    # noqa: E402
 import u_4a_2s_p3d_raytracer_template2_amd as P            # noqa: E402
 from conftest import scene_path                            # noqa: E402
+from plane_memory import check_host_device_split          # noqa: E402
 from test_denoise_variance_host import make_call, refusal_cases      # noqa: E402
 from u_4a_2s_p3d_raytracer_template2_amd import api        # noqa: E402
 
@@ -108,6 +109,26 @@ def test_device_memory_sentinels_and_in_place(handle):
     assert P.lib().p3d_denoise_variance(ds.h, C.byref(p), C.byref(i), C.byref(o)) == 0
     ds.sync()
     same_bits(ov.cpu().numpy().reshape(v.shape), ref["variance"], "host in, device out: the variance alone")
+
+
+
+def test_host_or_device_memory_on_either_side(handle):
+    """Host inputs with device outputs (and the stream idle on return), device inputs with host outputs: the all-device bits.
+    Two frames of 70 x 5: more than one tile across with a tail, fewer rows than a tile."""
+    _, ds = handle
+    w, h, n = 70, 5, 2
+    planes = dict(zip(("rgb32f", "depth", "normal", "albedo"), R.random_planes(w, h, n=n, seed=31)))
+    planes["variance"] = RV.random_variance(planes["depth"], seed=32)
+    p = api.DenoiseParams(w, h, n, 3, SIGMAS["sigma_depth"], SIGMAS["sigma_albedo"], 0.5, 5)
+
+    def call(i, in_memory, o, out_memory):
+        di = api.DenoiseVarianceInputs(i["rgb32f"], i["depth"], i["normal"], i["albedo"], i["variance"], in_memory)
+        do = api.DenoiseVarianceOutputs(o["rgb8"], o["rgb32f"], o["variance"], out_memory)
+        assert P.lib().p3d_denoise_variance(ds.h, C.byref(p), C.byref(di), C.byref(do)) == 0, P.lib().p3d_last_error()
+
+    outs = dict(rgb32f=np.zeros((n, h, w, 3), np.float32), rgb8=np.zeros((n, h, w, 3), np.uint8), variance=np.zeros((n, h, w), np.float32))
+    ref = check_host_device_split(ds, planes, outs, call)
+    assert not np.array_equal(ref["rgb32f"], planes["rgb32f"])
 
 
 @pytest.mark.parametrize("name,status,change", refusal_cases(), ids=[c[0] for c in refusal_cases()])

@@ -15,6 +15,7 @@ import indirect_reference as R                             # noqa: E402
 import test_gpu_scene_update as SU                         # noqa: E402
 import u_4a_2s_p3d_raytracer_template2_amd as P            # noqa: E402
 from extra_scenes import scene_path                        # noqa: E402
+from plane_memory import check_host_device_split          # noqa: E402
 from oracle import oracle_py as O                          # noqa: E402
 from u_4a_2s_p3d_raytracer_template2_amd import api        # noqa: E402
 
@@ -270,6 +271,26 @@ def test_host_and_device_memory_give_equal_bits(scenes):
             same_bits(whole_rgb[PAD:-PAD].reshape(ref["rgb32f"].shape), ref["rgb32f"], "in %d out %d: rgb32f" % (im, om))
     for k in host:
         same_bits(dev[k].cpu().numpy(), host[k], "an input plane changed: " + k)
+
+
+
+def test_host_or_device_memory_on_either_side(scenes):
+    """Host inputs with device outputs, device inputs with host outputs: the all-device bits.  Two frames of 70 x 5 at 4
+    samples: 16 pixels a wave, so a row is more than one workgroup of an LDS scene and ends in a tail."""
+    ds, cams, f = scenes("balls_box", (70, 5), 2)
+    arr, n = api._camera_array(cams)
+    planes = {k: np.array(f[k], F) for k in ("depth", "normal", "albedo", "rgb32f")}
+    prm = ds._ray_params(1, api.ACCEL_BVH, False, False, False)
+    g = api.IndirectParams(4, BIAS, SEED)
+
+    def call(i, in_memory, o, out_memory):
+        ii = api.IndirectInputs(i["depth"], i["normal"], i["albedo"], i["rgb32f"], in_memory)
+        io = api.IndirectOutputs(o["indirect"], o["rgb32f"], out_memory)
+        assert P.lib().p3d_indirect_diffuse(ds.h, arr, n, C.byref(prm), C.byref(g), C.byref(ii), C.byref(io)) == 0, P.lib().p3d_last_error()
+
+    ref = check_host_device_split(ds, planes, dict(indirect=np.zeros((n, 5, 70, 3), F), rgb32f=np.zeros((n, 5, 70, 3), F)), call)
+    same_result(ref, fused_ok(ds, cams, f["depth"], f["normal"], f["albedo"], f["rgb32f"], 4), "the all-device call and the host call")
+    assert (ref["indirect"] > 0).any()
 
 
 def test_staging_is_counted_in_device_bytes():

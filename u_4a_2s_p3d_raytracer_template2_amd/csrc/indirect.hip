@@ -5,7 +5,7 @@
 // included, or the background -- and the pixel's indirect light is their mean.  The rays are p3d_ambient_occlusion's segments
 // at radius 1 (p3d_ao_segment.h) and never exist in memory, and neither do their colours: no queues, no workspace.  The
 // definition, operation by operation: include/p3d_hip.h; the host restatement of the sum: host/indirect_host.cpp.
-//   Lane mapping: wf_ao_kernel's (ao.hip).  A lane is one (pixel, sample); the S lanes of a pixel are consecutive and a wave
+//   Lane mapping: wf_ao_kernel's (p3d_pixel_gather.h).  A lane is one (pixel, sample); the S lanes of a pixel are consecutive and a wave
 //   covers 64 / S consecutive pixels of one row.  The sum over a pixel's samples is log2 S xor-shuffle steps among its lanes:
 //   lanes l and l ^ m add the same two values, so every lane of the group holds the balanced tree's sum in the same bits,
 //   and lane 0 of the group -- whose operands are (lower half) + (upper half) at every step -- writes.  No LDS and no atomics
@@ -16,9 +16,7 @@
 #include <stdint.h>
 
 #include "p3d_ao_segment.h"
-#include "p3d_launch.h"
-#include "p3d_pinhole.h"
-#include "p3d_scene_view.h"
+#include "p3d_pixel_gather.h"
 
 namespace p3d {
 
@@ -28,36 +26,20 @@ template <bool LDS, int WALK, int OCC>
 __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void wf_indirect_kernel(const LaunchParams P, const IndirectIO A) {
     using SV = typename View<LDS>::type;
     const SV sv = View<LDS>::make_shading(P);
-    // workgroup -> (frame, row, group of the row); all wave-uniform
-    const uint32_t group = blockIdx.x % A.row_groups, fy = blockIdx.x / A.row_groups;
-    const uint32_t y = fy % (uint32_t)A.res_y, f = fy / (uint32_t)A.res_y;
-    const uint32_t lane = threadIdx.x & 63u, wave = group * (LDS ? 4u : 1u) + (threadIdx.x >> 6);
-    const uint32_t S = 1u << A.log2_samples;
-    // (x < res_x + 64 <= 2^31 + 63: the host keeps n * res_y * res_x * samples below 2^31)
-    const uint32_t x = wave * (64u >> A.log2_samples) + (lane >> A.log2_samples);
-    const bool in_row = x < (uint32_t)A.res_x;
+    PixelGather g;
+    const bool in_row = gather_lane<LDS, false>(A, g);
     if (__ballot(in_row) == 0) return;                           // past the row's end; no barrier follows the scene copy's
-    const size_t pixel = ((size_t)f * (size_t)A.res_y + y) * (size_t)A.res_x + x;
-    float Z = 0.0f;
-    V3 N = mk(0.0f, 0.0f, 0.0f);
-    if (in_row) {                                                // row tails neither read nor write
-        Z = A.depth[pixel];
-        const float* n = A.normal + 3 * pixel;
-        N = mk(n[0], n[1], n[2]);
-    }
-    const bool need = in_row && valid_depth(Z);                  // 1. an invalid depth: no query, indirect = 0
+    gather_surface(A, in_row, g);
+    const bool need = in_row && valid_depth(g.Z);                // 1. an invalid depth: no query, indirect = 0
+    const uint32_t lane = g.lane, S = g.S;
+    const size_t pixel = g.pixel;
     V3 r = mk(0.0f, 0.0f, 0.0f);
     if (__ballot(need) != 0) {                                   // a wave without a query skips the walk
-        const FrameCam& C = A.cams[f];
-        // 2. the hit point, 3. the normal facing the eye and the origin
-        const V3 d = pinhole_dir(C.uw, C.vh, C.vz, (int32_t)x, (int32_t)y, A.res_x, A.res_y);
-        const V3 Pt = pinhole_point(C.eye, d, Z);
-        const bool away = (N.x * d.x + N.y * d.y) + N.z * d.z > 0.0f;
-        const V3 Ns = away ? mk(-N.x, -N.y, -N.z) : N;
+        gather_origin(A, g);                                     // 2., 3.
         Ray ray;
-        ray.o = mk(Pt.x + Ns.x * A.bias, Pt.y + Ns.y * A.bias, Pt.z + Ns.z * A.bias);
-        const uint32_t pk = rng_mix(A.seed + f, y * (uint32_t)A.res_x + x);      // 4.
-        ray.d = ao_segment(Ns, pk, lane & (S - 1u), 1.0f, need);                  // 5., 6.: the segment at radius 1
+        ray.o = g.O;
+        const uint32_t pk = gather_key(A, g);                    // 4.
+        ray.d = ao_segment(g.Ns, pk, lane & (S - 1u), 1.0f, need);              // 5., 6.: the segment at radius 1
         if (!need) {                                             // lanes without a query stay for the wave-wide walk steps
             ray.o = mk(0.0f, 0.0f, 0.0f); ray.d = mk(1.0f, 0.0f, 0.0f);
         }
@@ -95,39 +77,18 @@ __global__ __launch_bounds__(LDS ? 256 : 64) P3D_OCC(OCC) void wf_indirect_kerne
     }
 }
 
-using IndirectKernelFn = void (*)(const LaunchParams, const IndirectIO);
-template <bool LDS, int WALK> constexpr IndirectKernelFn indirect_kernel() { return wf_indirect_kernel<LDS, WALK, WALK == WALK_GRID ? 1 : kRaysOcc>; }
-
-// the five builds: LDS x {lane, grid}, HBM x {lane, shared, grid}
-const void* indirect_kernel_for(const KernelVariant& request) {
-    const KernelVariant v = canonical_level(request, Level::IndirectDiffuse);
-    IndirectKernelFn fn = nullptr;
-    if (v.lds) fn = v.walk == WALK_GRID ? indirect_kernel<true, WALK_GRID>() : v.walk == WALK_LANE ? indirect_kernel<true, WALK_LANE>() : nullptr;
-    else fn = v.walk == WALK_GRID ? indirect_kernel<false, WALK_GRID>() : v.walk == WALK_SHARED ? indirect_kernel<false, WALK_SHARED>()
-              : v.walk == WALK_LANE ? indirect_kernel<false, WALK_LANE>() : nullptr;
-    return reinterpret_cast<const void*>(fn);
-}
+template <bool LDS, int WALK> struct IndirectKernel {
+    static const void* fn() { return reinterpret_cast<const void*>(&wf_indirect_kernel<LDS, WALK, kGatherOcc<WALK>>); }
+};
 
 }  // namespace
 
-// p3d_indirect_diffuse: one workgroup per wg_waves waves of a row, all frames in one launch (A.row_waves and A.row_groups
-// are set here).  The launch parameters go with max_depth = 1, whatever the caller's: a sample's ray is a ray of depth 1
-// that returns its direct lighting.
+// p3d_indirect_diffuse: p3d_pixel_gather.h's launch of wf_indirect_kernel.  The launch parameters go with max_depth = 1,
+// whatever the caller's: a sample's ray is a ray of depth 1 that returns its direct lighting.
 hipError_t launch_wf_indirect(const LaunchParams& P, const IndirectIO& A, const KernelVariant& v, hipStream_t stream) {
-    const void* fn = indirect_kernel_for(v);
-    if (!fn) return hipErrorInvalidDeviceFunction;
-    const size_t shmem = wavefront_lds_bytes(P, v.lds);
-    hipError_t e = allow_lds(fn, shmem);
-    if (e != hipSuccess) return e;
     LaunchParams Pc = P;
     Pc.max_depth = 1;
-    IndirectIO Ac = A;
-    const uint32_t per_wave = 64u >> A.log2_samples;
-    Ac.row_waves = (uint32_t)(((uint64_t)A.res_x + per_wave - 1) / per_wave);
-    Ac.row_groups = (Ac.row_waves + (uint32_t)P.wg_waves - 1) / (uint32_t)P.wg_waves;
-    void* args[] = {&Pc, &Ac};
-    const uint64_t blocks = (uint64_t)A.n_frames * (uint64_t)A.res_y * Ac.row_groups;      // at most the pixel count
-    return hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(64u * (unsigned)P.wg_waves), args, shmem, stream);
+    return launch_pixel_gather<IndirectKernel, Level::IndirectDiffuse>(Pc, A, v, 64u >> A.log2_samples, stream);
 }
 
 }  // namespace p3d

@@ -1,12 +1,10 @@
 // p3d_capi_misc.cpp -- the small entries of include/p3d_hip.h: errors, device queries, synchronisation, counters,
-// profile and timers, de-interleaving, device memory for callers, and the debug entries that run one device function.
+// profile and timers, de-interleaving, device memory for callers, and the debug entries that run one device function
+// (those of the image-space entries: p3d_debug_planes.cpp).
 #include <cstring>
 
-#include "accumulate.h"
-#include "denoise.h"
-#include "upsample.h"
 #include "grid_device.h"
-#include "p3d_scene_state.h"
+#include "p3d_debug_run.h"
 
 using namespace p3d;
 
@@ -115,9 +113,7 @@ int p3d_last_sky_tiles(p3d_scene* s, int32_t* used, int32_t* empty_tiles) {
     if (s->last_schedule < 0) return fail(P3D_ERR_STATE, "no render yet");
     *used = 0; *empty_tiles = 0;
     if (!s->last_sky.on) return P3D_OK;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(s->stream, &cap);
-    if (cap != hipStreamCaptureStatusNone) return fail(P3D_ERR_STATE, "p3d_last_sky_tiles waits for the stream: not while it is being captured");
+    if (stream_capturing(s->stream)) return fail(P3D_ERR_STATE, "p3d_last_sky_tiles waits for the stream: not while it is being captured");
     HIP_TRY(hipSetDevice(s->device));
     const CoverTiles& g = s->last_sky.tiles;
     std::vector<uint32_t> status((size_t)g.tiles_y);
@@ -142,9 +138,7 @@ int p3d_last_level_rays(p3d_scene* s, uint32_t* counts, int32_t n) {
     if (!s->last_wf.valid) return fail(P3D_ERR_STATE, "the handle's most recent frame did not run the wavefront schedule (or there is none yet)");
     if (s->last_wf.passes > (size_t)s->last_wf.lanes)
         return fail(P3D_ERR_STATE, "the frame ran several passes over the same counters (sample passes or bands): only its last pass is on the device");
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(s->stream, &cap);
-    if (cap != hipStreamCaptureStatusNone) return fail(P3D_ERR_STATE, "p3d_last_level_rays waits for the stream: not while it is being captured");
+    if (stream_capturing(s->stream)) return fail(P3D_ERR_STATE, "p3d_last_level_rays waits for the stream: not while it is being captured");
     HIP_TRY(hipSetDevice(s->device));
     for (int32_t i = 0; i < n; i++) counts[i] = 0u;
     std::vector<uint32_t> w(kCountBufferWords);
@@ -232,31 +226,6 @@ int p3d_download(p3d_scene* s, void* host_dst, const void* device_src, uint64_t 
 }  // extern "C"
 
 namespace {
-
-// One argument of a debug entry on the device: `bytes` of scratch, filled from `in` before the launch (if any) and copied
-// to `out` after it (if any).
-struct DebugArg {
-    const void* in; void* out; size_t bytes;
-    void* d = nullptr;
-    template <typename T> T* as() const { return (T*)d; }
-};
-
-// Runs one debug launch on `device`: scratch for the arguments, inputs up, launch, wait, outputs back.  The scratch is freed on
-// every path; a HIP error is reported as "<entry>: <error>".
-template <size_t N, typename Launch>
-int debug_run(const char* entry, int device, DebugArg (&args)[N], Launch launch) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(P3D_ERR_NO_DEVICE, "no HIP device visible");
-    hipError_t e = hipSetDevice(device);
-    for (DebugArg& a : args) if (e == hipSuccess) e = hipMalloc(&a.d, a.bytes);
-    for (DebugArg& a : args) if (e == hipSuccess && a.in) e = hipMemcpy(a.d, a.in, a.bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = launch();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    for (DebugArg& a : args) if (e == hipSuccess && a.out) e = hipMemcpy(a.out, a.d, a.bytes, hipMemcpyDeviceToHost);
-    for (DebugArg& a : args) (void)hipFree(a.d);
-    if (e != hipSuccess) return fail(P3D_ERR_HIP, std::string(entry) + ": " + hipGetErrorString(e));
-    return P3D_OK;
-}
 
 typedef hipError_t (*RcpCheckLaunch)(uint32_t, uint64_t, unsigned long long*, uint32_t*, hipStream_t);
 int debug_check_reciprocal(const char* entry, RcpCheckLaunch launch, int device, uint32_t first_bits, uint64_t count,
@@ -409,160 +378,6 @@ int p3d_debug_sample_stream(int device, uint32_t seed, int32_t res_x, int32_t re
     DebugArg a[1] = {{nullptr, out, (size_t)(pixels * per_pixel) * 4 * sizeof(float)}};
     return debug_run("p3d_debug_sample_stream", device, a, [&] {
         return generate_sample_stream(scratch, seed, res_x, res_y, spp, aperture, a[0].as<float>(), pairs_per_pass, passes, nullptr);
-    });
-}
-
-int p3d_debug_denoise(int device, const p3d_denoise_params* params, const p3d_denoise_inputs* in, const p3d_outputs* out) {
-    const char* why = "";
-    if (const int rc = denoise_check_request(params, in, out, &why)) return fail(rc, why);
-    if (in->memory != 0 || out->memory != 0) return fail(P3D_ERR_ARG, "p3d_debug_denoise takes host planes: memory must be 0");
-    const size_t px = (size_t)params->n_frames * (size_t)params->res_x * (size_t)params->res_y;
-    const int n_scratch = denoise_scratch_buffers(params->iterations, false);
-    // a plane that is not wanted (or a scratch buffer that is not needed) is one byte that nothing touches
-    DebugArg a[8] = {{in->rgb32f, nullptr, px * 12}, {in->depth, nullptr, px * 4}, {in->normal, nullptr, px * 12}, {in->albedo, nullptr, px * 12},
-                     {nullptr, nullptr, n_scratch > 0 ? px * 12 : 1}, {nullptr, nullptr, n_scratch > 1 ? px * 12 : 1},
-                     {nullptr, out->rgb32f, out->rgb32f ? px * 12 : 1}, {nullptr, out->rgb8, out->rgb8 ? px * 3 : 1}};
-    return debug_run("p3d_debug_denoise", device, a, [&] {
-        return launch_denoise(*params, a[0].as<float>(), a[1].as<float>(), a[2].as<float>(), a[3].as<float>(), a[4].as<float>(), a[5].as<float>(),
-                              out->rgb32f ? a[6].as<float>() : nullptr, out->rgb8 ? a[7].as<uint8_t>() : nullptr, nullptr);
-    });
-}
-
-int p3d_debug_denoise_variance(int device, const p3d_denoise_params* params, const p3d_denoise_variance_inputs* in,
-                               const p3d_denoise_variance_outputs* out) {
-    const char* why = "";
-    if (const int rc = denoise_variance_check_request(params, in, out, &why)) return fail(rc, why);
-    if (in->memory != 0 || out->memory != 0) return fail(P3D_ERR_ARG, "p3d_debug_denoise_variance takes host planes: memory must be 0");
-    const size_t px = (size_t)params->n_frames * (size_t)params->res_x * (size_t)params->res_y;
-    const int n_scratch = denoise_scratch_buffers(params->iterations, false);
-    // a plane that is not wanted (or a scratch buffer that is not needed) is one byte that nothing touches
-    DebugArg a[10] = {{in->rgb32f, nullptr, px * 12}, {in->depth, nullptr, px * 4}, {in->normal, nullptr, px * 12}, {in->albedo, nullptr, px * 12},
-                      {in->variance, nullptr, px * 4},
-                      {nullptr, nullptr, n_scratch > 0 ? px * 16 : 1}, {nullptr, nullptr, n_scratch > 1 ? px * 16 : 1},
-                      {nullptr, out->rgb32f, out->rgb32f ? px * 12 : 1}, {nullptr, out->rgb8, out->rgb8 ? px * 3 : 1},
-                      {nullptr, out->variance, out->variance ? px * 4 : 1}};
-    return debug_run("p3d_debug_denoise_variance", device, a, [&] {
-        return launch_denoise_variance(*params, a[0].as<float>(), a[1].as<float>(), a[2].as<float>(), a[3].as<float>(), a[4].as<float>(),
-                                       a[5].as<float>(), a[6].as<float>(), out->rgb32f ? a[7].as<float>() : nullptr,
-                                       out->rgb8 ? a[8].as<uint8_t>() : nullptr, out->variance ? a[9].as<float>() : nullptr, nullptr);
-    });
-}
-
-int p3d_debug_upsample(int device, const p3d_upsample_params* params, const p3d_upsample_inputs* in, const p3d_upsample_outputs* out) {
-    const char* why = "";
-    if (const int rc = upsample_check_request(params, in, out, &why)) return fail(rc, why);
-    if (in->memory != 0 || out->memory != 0) return fail(P3D_ERR_ARG, "p3d_debug_upsample takes host planes: memory must be 0");
-    const size_t low_px = (size_t)params->n_frames * (size_t)params->res_x * (size_t)params->res_y;
-    const size_t px = low_px * (size_t)params->factor * (size_t)params->factor, c = (size_t)params->channels;
-    // a plane that is not wanted is one byte that nothing touches
-    DebugArg a[7] = {{in->low, nullptr, low_px * c * 4}, {in->low_depth, nullptr, low_px * 4}, {in->low_normal, nullptr, low_px * 12},
-                     {in->depth, nullptr, px * 4}, {in->normal, nullptr, px * 12},
-                     {nullptr, out->plane, out->plane ? px * c * 4 : 1}, {nullptr, out->fallback, out->fallback ? px : 1}};
-    return debug_run("p3d_debug_upsample", device, a, [&] {
-        return launch_upsample(*params, a[0].as<float>(), a[1].as<float>(), a[2].as<float>(), a[3].as<float>(), a[4].as<float>(),
-                               out->plane ? a[5].as<float>() : nullptr, out->fallback ? a[6].as<uint8_t>() : nullptr, nullptr);
-    });
-}
-
-int p3d_debug_accumulate(int device, const p3d_accumulate_params* params, const p3d_accumulate_frames* frames,
-                         const p3d_accumulate_history* history, const p3d_accumulate_outputs* out) {
-    const char* why = "";
-    if (const int rc = accumulate_check_request(params, frames, history, out, &why)) return fail(rc, why);
-    if (frames->memory != 0 || (history && history->memory != 0) || out->memory != 0)
-        return fail(P3D_ERR_ARG, "p3d_debug_accumulate takes host planes: every memory field must be 0");
-    const size_t fr = (size_t)params->res_x * (size_t)params->res_y, px = fr * (size_t)params->n_frames;
-    const bool many = params->n_frames > 1;
-    const p3d_accumulate_history none = {};
-    const p3d_accumulate_history& h = history ? *history : none;
-    // a plane that is not there (or a spare that is not needed) is one byte that nothing touches
-    DebugArg a[13] = {{frames->rgb32f, nullptr, px * 12}, {frames->depth, nullptr, px * 4}, {frames->normal, nullptr, px * 12},
-                      {frames->hit_id, nullptr, frames->hit_id ? px * 4 : 1},
-                      {h.rgb32f, nullptr, history ? fr * 12 : 1}, {h.depth, nullptr, history ? fr * 4 : 1}, {h.normal, nullptr, history ? fr * 12 : 1},
-                      {h.length, nullptr, history ? fr * 4 : 1}, {h.hit_id, nullptr, h.hit_id ? fr * 4 : 1},
-                      {nullptr, out->rgb32f, out->rgb32f ? px * 12 : 1}, {nullptr, out->length, out->length ? px * 4 : 1},
-                      {nullptr, nullptr, many && !out->rgb32f ? 2 * fr * 12 : 1}, {nullptr, nullptr, many && !out->length ? 2 * fr * 4 : 1}};
-    return debug_run("p3d_debug_accumulate", device, a, [&] {
-        const AccumulatePlanes P = {a[0].as<float>(), a[1].as<float>(), a[2].as<float>(), frames->hit_id ? a[3].as<int32_t>() : nullptr,
-                                    history ? a[4].as<float>() : nullptr, a[5].as<float>(), a[6].as<float>(), a[7].as<float>(),
-                                    h.hit_id ? a[8].as<int32_t>() : nullptr,
-                                    out->rgb32f ? a[9].as<float>() : nullptr, out->length ? a[10].as<float>() : nullptr,
-                                    a[11].as<float>(), a[12].as<float>()};
-        return launch_accumulate(*params, P, frames->cams, h.cam, nullptr);
-    });
-}
-
-int p3d_debug_accumulate_moving(int device, const p3d_accumulate_params* params, const p3d_accumulate_frames* frames,
-                                const p3d_accumulate_history* history, const p3d_accumulate_motion* motion,
-                                const p3d_accumulate_moving_outputs* out) {
-    const char* why = "";
-    if (const int rc = accumulate_moving_check_request(params, frames, history, motion, out, &why)) return fail(rc, why);
-    if (frames->memory != 0 || (history && history->memory != 0) || motion->memory != 0 || out->memory != 0)
-        return fail(P3D_ERR_ARG, "p3d_debug_accumulate_moving takes host planes: every memory field must be 0");
-    const size_t fr = (size_t)params->res_x * (size_t)params->res_y, px = fr * (size_t)params->n_frames, prims = motion->n_prims;
-    const bool many = params->n_frames > 1;
-    const p3d_accumulate_history none = {};
-    const p3d_accumulate_history& h = history ? *history : none;
-    // a plane that is not there (or a spare that is not needed) is one byte that nothing touches
-    DebugArg a[17] = {{frames->rgb32f, nullptr, px * 12}, {frames->depth, nullptr, px * 4}, {frames->normal, nullptr, px * 12},
-                      {frames->hit_id, nullptr, px * 4},
-                      {h.rgb32f, nullptr, history ? fr * 12 : 1}, {h.depth, nullptr, history ? fr * 4 : 1}, {h.normal, nullptr, history ? fr * 12 : 1},
-                      {h.length, nullptr, history ? fr * 4 : 1}, {h.hit_id, nullptr, h.hit_id ? fr * 4 : 1},
-                      {nullptr, out->rgb32f, out->rgb32f ? px * 12 : 1}, {nullptr, out->length, out->length ? px * 4 : 1},
-                      {nullptr, nullptr, many && !out->rgb32f ? 2 * fr * 12 : 1}, {nullptr, nullptr, many && !out->length ? 2 * fr * 4 : 1},
-                      {motion->prim_type, nullptr, prims * 4}, {motion->prim_data, nullptr, prims * 48 * (size_t)params->n_frames},
-                      {history ? motion->history_prim_data : nullptr, nullptr, history ? prims * 48 : 1},
-                      {nullptr, out->prev_xy, out->prev_xy ? px * 8 : 1}};
-    return debug_run("p3d_debug_accumulate_moving", device, a, [&] {
-        const AccumulatePlanes P = {a[0].as<float>(), a[1].as<float>(), a[2].as<float>(), a[3].as<int32_t>(),
-                                    history ? a[4].as<float>() : nullptr, a[5].as<float>(), a[6].as<float>(), a[7].as<float>(),
-                                    h.hit_id ? a[8].as<int32_t>() : nullptr,
-                                    out->rgb32f ? a[9].as<float>() : nullptr, out->length ? a[10].as<float>() : nullptr,
-                                    a[11].as<float>(), a[12].as<float>()};
-        const AccumulateMotion M = {motion->n_prims, a[13].as<uint32_t>(), a[14].as<float>(), history ? a[15].as<float>() : nullptr,
-                                    out->prev_xy ? a[16].as<float>() : nullptr};
-        return launch_accumulate_moving(*params, P, M, frames->cams, h.cam, nullptr);
-    });
-}
-
-int p3d_debug_accumulate_variance(int device, const p3d_accumulate_params* params, const p3d_accumulate_variance_params* variance_params,
-                                  const p3d_accumulate_frames* frames, const p3d_accumulate_history* history, const float* history_moments,
-                                  const p3d_accumulate_motion* motion, const p3d_accumulate_variance_outputs* out) {
-    const char* why = "";
-    if (const int rc = accumulate_variance_check_request(params, variance_params, frames, history, history_moments, motion, out, &why)) return fail(rc, why);
-    if (frames->memory != 0 || (history && history->memory != 0) || (motion && motion->memory != 0) || out->memory != 0)
-        return fail(P3D_ERR_ARG, "p3d_debug_accumulate_variance takes host planes: every memory field must be 0");
-    const size_t fr = (size_t)params->res_x * (size_t)params->res_y, px = fr * (size_t)params->n_frames, prims = motion ? motion->n_prims : 0;
-    const bool many = params->n_frames > 1;
-    const p3d_accumulate_history none = {};
-    const p3d_accumulate_history& h = history ? *history : none;
-    // host planes are staged apart, so no colour is blended in place: no detour
-    const size_t spare_c = (size_t)accumulate_variance_spare_colour_frames(*params, out->rgb32f, false);
-    const size_t spare_l = (size_t)accumulate_variance_spare_length_frames(*params, *variance_params, out->length, out->variance);
-    // a plane that is not there (or a spare that is not needed) is one byte that nothing touches
-    DebugArg a[21] = {{frames->rgb32f, nullptr, px * 12}, {frames->depth, nullptr, px * 4}, {frames->normal, nullptr, px * 12},
-                      {frames->hit_id, nullptr, frames->hit_id ? px * 4 : 1},
-                      {h.rgb32f, nullptr, history ? fr * 12 : 1}, {h.depth, nullptr, history ? fr * 4 : 1}, {h.normal, nullptr, history ? fr * 12 : 1},
-                      {h.length, nullptr, history ? fr * 4 : 1}, {h.hit_id, nullptr, h.hit_id ? fr * 4 : 1},
-                      {nullptr, out->rgb32f, out->rgb32f ? px * 12 : 1}, {nullptr, out->length, out->length ? px * 4 : 1},
-                      {nullptr, nullptr, spare_c ? spare_c * fr * 12 : 1}, {nullptr, nullptr, spare_l ? spare_l * fr * 4 : 1},
-                      {motion ? motion->prim_type : nullptr, nullptr, motion ? prims * 4 : 1},
-                      {motion ? motion->prim_data : nullptr, nullptr, motion ? prims * 48 * (size_t)params->n_frames : 1},
-                      {motion && history ? motion->history_prim_data : nullptr, nullptr, motion && history ? prims * 48 : 1},
-                      {nullptr, out->prev_xy, out->prev_xy ? px * 8 : 1},
-                      {history ? history_moments : nullptr, nullptr, history ? fr * 8 : 1},
-                      {nullptr, out->moments, out->moments ? px * 8 : 1}, {nullptr, out->variance, out->variance ? px * 4 : 1},
-                      {nullptr, nullptr, many && !out->moments ? 2 * fr * 8 : 1}};
-    return debug_run("p3d_debug_accumulate_variance", device, a, [&] {
-        const AccumulatePlanes P = {a[0].as<float>(), a[1].as<float>(), a[2].as<float>(), frames->hit_id ? a[3].as<int32_t>() : nullptr,
-                                    history ? a[4].as<float>() : nullptr, a[5].as<float>(), a[6].as<float>(), a[7].as<float>(),
-                                    h.hit_id ? a[8].as<int32_t>() : nullptr,
-                                    out->rgb32f ? a[9].as<float>() : nullptr, out->length ? a[10].as<float>() : nullptr,
-                                    a[11].as<float>(), a[12].as<float>()};
-        const AccumulateVariancePlanes VP = {history ? a[17].as<float>() : nullptr, out->moments ? a[18].as<float>() : nullptr,
-                                             out->variance ? a[19].as<float>() : nullptr, a[20].as<float>()};
-        const AccumulateMotion M = {motion ? motion->n_prims : 0, a[13].as<uint32_t>(), a[14].as<float>(), motion && history ? a[15].as<float>() : nullptr,
-                                    out->prev_xy ? a[16].as<float>() : nullptr};
-        return launch_accumulate_variance(*params, *variance_params, P, VP, motion ? &M : nullptr, frames->cams, h.cam, nullptr);
     });
 }
 

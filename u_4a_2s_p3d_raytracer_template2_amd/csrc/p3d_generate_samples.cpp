@@ -16,12 +16,8 @@ extern "C" int p3d_generate_samples(p3d_scene* s, uint32_t seed, int32_t res_x, 
     if (pixels > kMaxStackedPixels || per_pixel > kMaxStackedPixels || pixels * per_pixel > kMaxStackedPixels)
         return fail(P3D_ERR_LIMIT, "res_x * res_y * spp * spp does not fit 31 bits");
     HIP_TRY(hipSetDevice(s->device));
-    {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        (void)hipStreamIsCapturing(s->stream, &cap);
-        if (cap != hipStreamCaptureStatusNone)
-            return fail(P3D_ERR_STATE, "p3d_generate_samples waits on the device for the sample count: not while the stream is being captured");
-    }
+    if (stream_capturing(s->stream))
+        return fail(P3D_ERR_STATE, "p3d_generate_samples waits on the device for the sample count: not while the stream is being captured");
     const size_t bytes = (size_t)(pixels * per_pixel) * 4 * sizeof(float);
     float* d_out = out;
     if (memory == 0) {       // staged where p3d_render stages a host sample array

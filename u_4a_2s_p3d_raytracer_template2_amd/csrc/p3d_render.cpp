@@ -6,7 +6,7 @@
 #include <cstdio>
 #include <cstring>
 
-#include "p3d_scene_state.h"
+#include "p3d_plane_stage.h"
 
 using namespace p3d;
 
@@ -20,12 +20,6 @@ size_t wavefront_bytes_per_pixel(int D) {
     for (int l = 2; l <= D; l++) b += ((size_t)1 << (l - 1)) * sizeof(RayRec);
     for (int l = 1; l <= D - 1; l++) b += ((size_t)1 << (l - 1)) * sizeof(NodeRec);
     return b;
-}
-
-bool capturing(hipStream_t stream) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(stream, &cap);
-    return cap != hipStreamCaptureStatusNone;
 }
 
 // ---- the request
@@ -117,7 +111,7 @@ int ensure_grid(p3d_scene* s) {
     if (s->grid_ready) return P3D_OK;
     // built on the first GRID frame of a scene, with synchronous allocations and copies: not something a
     // stream capture can hold.  Render one GRID frame before capturing.
-    if (capturing(s->stream))
+    if (stream_capturing(s->stream))
         return fail(P3D_ERR_STATE, "the first GRID-mode frame of a scene builds and uploads the grid: render one before capturing the stream");
     if (s->grid_stale_count)
         return fail(P3D_ERR_STATE, "primitives were updated from device memory: GRID mode needs their points on the host, update them from host memory");
@@ -412,7 +406,7 @@ int choose_schedule(p3d_scene* s, const FrameConfig& cfg, const p3d_render_param
         // Scenes whose lanes can share their walks measure every schedule both ways (candidates 0-2 shared, 3-5 private).
         const int NC = plan.can_share ? 2 * kSchedules : kSchedules;
         const bool avail[kSchedules] = {plan.wavefront_ok, !plan.stochastic, plan.tile_ok};
-        const bool cap = capturing(s->stream);
+        const bool cap = stream_capturing(s->stream);
         SchedulePick& pk = cfg.batch() ? s->pick_batch : s->pick;
         const PickKey key = pick_key(cfg);
         int cand = -1;
@@ -472,7 +466,7 @@ int tile_order_begin(p3d_scene* s, const FrameConfig& cfg, int sched, LaunchPara
     p3d_scene::TileOrder& L = sched == SCHED_TILE ? (cfg.batch() ? s->tile_lpt_batch : s->tile_lpt) : (cfg.batch() ? s->wave_lpt_batch : s->wave_lpt);
     const uint32_t n_tiles = (uint32_t)Q.n_tiles;
     const TileOrderKey key = tile_order_key(cfg, sched, Q.n_tiles);
-    const bool cap = capturing(s->stream);
+    const bool cap = stream_capturing(s->stream);
     if (!L.key.matches(key)) {
         L.valid = false;
         if (cap) { L.key.invalidate(); return P3D_OK; }      // (allocations: not while a capture is open)
@@ -684,7 +678,7 @@ int sky_tiles_begin(p3d_scene* s, const FrameConfig& cfg, const FramePlan& plan,
     J.row_words = cover_row_words(P.tiles_x);
     const size_t words = (size_t)P.tiles_y * J.row_words + (size_t)P.tiles_y;
     if (s->sky_mask.cap < words * sizeof(uint32_t)) {
-        if (capturing(s->stream)) return P3D_OK;
+        if (stream_capturing(s->stream)) return P3D_OK;
         HIP_TRY(s->sky_mask.ensure(words * sizeof(uint32_t)));
     }
     J.blob = P.blob; J.off_spheres = P.off_spheres; J.off_tris = P.off_tris; J.off_boxes = P.off_boxes; J.tri_quads = P.tri_quads;
@@ -888,16 +882,6 @@ int render_batch(p3d_scene* s, const p3d_camera* cams, int32_t n_frames, const p
     return P3D_OK;
 }
 
-// A staging buffer of the ray-stream state (p3d_scene::rays), counted in p3d_scene_stats::device_bytes at whatever size it
-// has after the call: p3d_trace_rays and p3d_occluded share origin / dir, so both grow them here and the count does not
-// depend on which came first (a failed allocation leaves the buffer empty and counted as such).
-hipError_t ensure_counted(p3d_scene* s, RawBuf& b, size_t bytes) {
-    s->stats.device_bytes -= b.cap;
-    const hipError_t e = b.ensure(bytes);
-    s->stats.device_bytes += b.cap;
-    return e;
-}
-
 // rayTracing(ray, 1, 1.0) on n rays of the caller's: the wavefront schedule with wf_rays_kernel as its level 1.  The same
 // steps as render_batch -- the scene into the launch parameters, a workspace plan, run_wavefront -- without a camera, a
 // schedule choice, a tile order or anything else a frame remembers: what a stream keeps between calls is in s->rays.
@@ -1015,31 +999,38 @@ int occluded(p3d_scene* s, const p3d_rays* seg, const p3d_render_params* prm, co
     return P3D_OK;
 }
 
-// All argument checks of p3d_ambient_occlusion, in the order include/p3d_hip.h lists them: p3d_occluded's rules for params
-// (the same normalised request), then the entry's own.
-int validate_ao_request(const p3d_scene* s, const p3d_camera* cams, int32_t n, const p3d_render_params* prm, const p3d_ao_params* ao,
-                        const p3d_ao_inputs* in, const p3d_ao_outputs* out, FrameConfig& cfg) {
-    if (!s || !cams || !prm || !ao || !in || !out) return fail(P3D_ERR_ARG, "NULL argument");
+// What p3d_ambient_occlusion and p3d_indirect_diffuse ask alike, with what their messages call the entry and its structs.
+struct GatherRequest {
+    const char *noun, *features, *params, *inputs, *outputs, *plane;     // features: the whole message
+    int32_t samples; const float* radius; float bias;                      // radius: nullptr = the entry has none
+    const float *depth, *normal, *albedo, *rgb32f; int32_t in_memory;      // albedo: nullptr = the entry has none (or it is not there)
+    const float *out_plane, *out_rgb32f; int32_t out_memory;
+};
+
+// The argument checks the two entries share, in the order include/p3d_hip.h lists them: p3d_occluded's rules for params (the
+// same normalised request: cfg), then the planes and the cameras.  An entry checks for NULL arguments before, and what a
+// culled scene serves after.
+int validate_gather_request(const p3d_camera* cams, int32_t n, const p3d_render_params* prm, const GatherRequest& q, FrameConfig& cfg) {
+    const std::string noun = q.noun, params = q.params, inputs = q.inputs, outputs = q.outputs;
     if (n < 1) return fail(P3D_ERR_ARG, "n must be at least 1");
     if (prm->accel < 0 || prm->accel > 2) return fail(P3D_ERR_ARG, "accel must be 0, 1 or 2");
-    if (prm->flags & ~kRayStreamFlags)
-        return fail(P3D_ERR_ARG, "flags: ambient occlusion accepts P3D_FLAG_NO_LDS_SCENE, _PRIVATE_WALK and _WAVEFRONT only");
-    if (prm->features != 0) return fail(P3D_ERR_ARG, "features: ambient occlusion has none, features must be 0");
-    if (prm->spp != 0) return fail(P3D_ERR_ARG, "spp: ambient occlusion has no pixel samples, spp must be 0");
-    if (prm->samples) return fail(P3D_ERR_ARG, "samples: ambient occlusion has no pixel samples, p3d_render_params::samples must be NULL");
-    if (prm->world > 1 || prm->rank != 0) return fail(P3D_ERR_ARG, "world / rank: ambient occlusion is not sharded, world must be 0 or 1 and rank 0 (stitch the planes first)");
-    const int32_t S = ao->samples;
-    if (S < 1 || S > 64 || (S & (S - 1)) != 0) return fail(P3D_ERR_ARG, "p3d_ao_params::samples must be 1, 2, 4, 8, 16, 32 or 64");
-    if (!std::isfinite(ao->radius) || !(ao->radius > 0.0f)) return fail(P3D_ERR_ARG, "p3d_ao_params::radius must be finite and positive");
-    if (!std::isfinite(ao->bias) || !(ao->bias >= 0.0f)) return fail(P3D_ERR_ARG, "p3d_ao_params::bias must be finite and not negative");
-    if (!in->depth || !in->normal) return fail(P3D_ERR_ARG, "p3d_ao_inputs::depth / normal is NULL");
-    if (!out->ao && !out->rgb32f) return fail(P3D_ERR_ARG, "p3d_ao_outputs: both ao and rgb32f are NULL");
-    if (in->memory != 0 && in->memory != 1) return fail(P3D_ERR_ARG, "p3d_ao_inputs::memory must be 0 (host) or 1 (device)");
-    if (out->memory != 0 && out->memory != 1) return fail(P3D_ERR_ARG, "p3d_ao_outputs::memory must be 0 (host) or 1 (device)");
-    const void* const outs[2] = {out->ao, out->rgb32f};
-    for (const void* o : outs)
-        if (o && (o == in->depth || o == in->normal || o == in->rgb32f)) return fail(P3D_ERR_ARG, "an output plane aliases an input plane");
-    if (out->ao && (const void*)out->ao == (const void*)out->rgb32f) return fail(P3D_ERR_ARG, "p3d_ao_outputs::ao and rgb32f alias each other");
+    if (prm->flags & ~kRayStreamFlags) return fail(P3D_ERR_ARG, "flags: " + noun + " accepts P3D_FLAG_NO_LDS_SCENE, _PRIVATE_WALK and _WAVEFRONT only");
+    if (prm->features != 0) return fail(P3D_ERR_ARG, q.features);
+    if (prm->spp != 0) return fail(P3D_ERR_ARG, "spp: " + noun + " has no pixel samples, spp must be 0");
+    if (prm->samples) return fail(P3D_ERR_ARG, "samples: " + noun + " has no pixel samples, p3d_render_params::samples must be NULL");
+    if (prm->world > 1 || prm->rank != 0) return fail(P3D_ERR_ARG, "world / rank: " + noun + " is not sharded, world must be 0 or 1 and rank 0 (stitch the planes first)");
+    const int32_t S = q.samples;
+    if (S < 1 || S > 64 || (S & (S - 1)) != 0) return fail(P3D_ERR_ARG, params + "::samples must be 1, 2, 4, 8, 16, 32 or 64");
+    if (q.radius && (!std::isfinite(*q.radius) || !(*q.radius > 0.0f))) return fail(P3D_ERR_ARG, params + "::radius must be finite and positive");
+    if (!std::isfinite(q.bias) || !(q.bias >= 0.0f)) return fail(P3D_ERR_ARG, params + "::bias must be finite and not negative");
+    if (!q.depth || !q.normal) return fail(P3D_ERR_ARG, inputs + "::depth / normal is NULL");
+    if (!q.out_plane && !q.out_rgb32f) return fail(P3D_ERR_ARG, outputs + ": both " + q.plane + " and rgb32f are NULL");
+    if (q.in_memory != 0 && q.in_memory != 1) return fail(P3D_ERR_ARG, inputs + "::memory must be 0 (host) or 1 (device)");
+    if (q.out_memory != 0 && q.out_memory != 1) return fail(P3D_ERR_ARG, outputs + "::memory must be 0 (host) or 1 (device)");
+    const float* const outs[2] = {q.out_plane, q.out_rgb32f};
+    for (const float* o : outs)
+        if (o && (o == q.depth || o == q.normal || o == q.albedo || o == q.rgb32f)) return fail(P3D_ERR_ARG, "an output plane aliases an input plane");
+    if (q.out_plane && q.out_plane == q.out_rgb32f) return fail(P3D_ERR_ARG, outputs + "::" + q.plane + " and rgb32f alias each other");
     if (cams[0].res_x < 1 || cams[0].res_y < 1) return fail(P3D_ERR_ARG, "res_x and res_y of the cameras must be at least 1");
     for (int f = 1; f < n; f++)
         if (cams[f].res_x != cams[0].res_x || cams[f].res_y != cams[0].res_y) return fail(P3D_ERR_ARG, "the cameras differ in res_x / res_y");
@@ -1048,10 +1039,22 @@ int validate_ao_request(const p3d_scene* s, const p3d_camera* cams, int32_t n, c
     if (rows > kMaxStackedPixels || rows * (uint64_t)cams[0].res_x > kMaxStackedPixels ||
         rows * (uint64_t)cams[0].res_x * (uint64_t)S > kMaxStackedPixels)
         return fail(P3D_ERR_LIMIT, "n * res_y * res_x * samples does not fit 31 bits");
-    if (s->cull_never_hit && prm->accel != P3D_ACCEL_BVH)
-        return fail(P3D_ERR_STATE, "scene was built with cull_never_hit: occlusion queries are served in accel BVH only (unit-length rays)");
     cfg.max_depth = 1; cfg.accel = prm->accel; cfg.spp = 0;
     cfg.flags = prm->flags & kConfigFlags; cfg.features = 0;
+    return P3D_OK;
+}
+
+// What AoIO and IndirectIO (all zero so far) say alike of a call, and the cameras into cam_buf: they travel in the arguments
+// of a launch of this stream, so a captured call replays with its own.
+template <typename IO>
+int fill_gather_io(p3d_scene* s, FrameCam* cam_buf, const p3d_camera* cams, int32_t n, int32_t samples, float bias, uint32_t seed, IO& io) {
+    io.res_x = cams[0].res_x; io.res_y = cams[0].res_y; io.n_frames = n;
+    for (io.log2_samples = 0; (1 << io.log2_samples) < samples; io.log2_samples++) {}
+    io.bias = bias; io.seed = seed;
+    std::vector<FrameCam> fc((size_t)n);
+    for (int f = 0; f < n; f++) fc[f] = camera_record(cams[f]);
+    HIP_TRY(launch_frame_cams(cam_buf, fc.data(), n, s->stream));
+    io.cams = cam_buf;
     return P3D_OK;
 }
 
@@ -1060,192 +1063,85 @@ int validate_ao_request(const p3d_scene* s, const p3d_camera* cams, int32_t n, c
 // frames.  Of the handle it touches the staging of s->ao and the grid of the first GRID call.
 int ambient_occlusion(p3d_scene* s, const p3d_camera* cams, int32_t n, const p3d_render_params* prm, const p3d_ao_params* ao,
                       const p3d_ao_inputs* in, const p3d_ao_outputs* out) {
+    if (!s || !cams || !prm || !ao || !in || !out) return fail(P3D_ERR_ARG, "NULL argument");
+    const GatherRequest q = {"ambient occlusion", "features: ambient occlusion has none, features must be 0", "p3d_ao_params", "p3d_ao_inputs",
+                             "p3d_ao_outputs", "ao", ao->samples, &ao->radius, ao->bias,
+                             in->depth, in->normal, nullptr, in->rgb32f, in->memory, out->ao, out->rgb32f, out->memory};
     FrameConfig cfg;
-    int rc = validate_ao_request(s, cams, n, prm, ao, in, out, cfg);
+    int rc = validate_gather_request(cams, n, prm, q, cfg);
     if (rc) return rc;
+    if (s->cull_never_hit && prm->accel != P3D_ACCEL_BVH)
+        return fail(P3D_ERR_STATE, "scene was built with cull_never_hit: occlusion queries are served in accel BVH only (unit-length rays)");
     HIP_TRY(hipSetDevice(s->device));
     const size_t pixels = (size_t)n * (size_t)cams[0].res_y * (size_t)cams[0].res_x;
     const bool host_in = in->memory == 0, host_out = out->memory == 0;
     p3d_scene::AmbientOcclusion& B = s->ao;
 
-    // everything the call needs of the handle, sized before anything is allocated
-    struct Need { RawBuf* buf; size_t bytes; } needs[6];
-    int n_needs = 0;
-    needs[n_needs++] = {&B.cams, (size_t)n * sizeof(FrameCam)};
-    if (host_in) {
-        needs[n_needs++] = {&B.in_depth, pixels * 4}; needs[n_needs++] = {&B.in_normal, pixels * 12};
-        if (in->rgb32f) needs[n_needs++] = {&B.in_rgb32f, pixels * 12};
-    }
-    if (host_out && out->ao) needs[n_needs++] = {&B.out_ao, pixels * 4};
-    if (host_out && out->rgb32f) needs[n_needs++] = {&B.out_rgb32f, pixels * 12};
-    if (capturing(s->stream)) {
-        if (host_in || host_out)
-            return fail(P3D_ERR_STATE, "p3d_ambient_occlusion copies host planes and waits for them: not while the stream is being captured");
-        for (int i = 0; i < n_needs; i++)
-            if (needs[i].bytes > needs[i].buf->cap)
-                return fail(P3D_ERR_STATE, "p3d_ambient_occlusion has to allocate its camera buffer: make a call of this shape before the capture");
-    }
+    PlaneStage st(s, "p3d_ambient_occlusion", "its camera buffer");
+    const PlaneStage::Plane cam_buf = st.scratch(B.cams, (size_t)n * sizeof(FrameCam));
+    const PlaneStage::Plane depth = st.in(B.in_depth, in->depth, pixels * 4, host_in), normal = st.in(B.in_normal, in->normal, pixels * 12, host_in),
+                            color = st.in(B.in_rgb32f, in->rgb32f, pixels * 12, host_in);
+    const PlaneStage::Plane o_ao = st.out(B.out_ao, out->ao, pixels * 4, host_out), o_rgb = st.out(B.out_rgb32f, out->rgb32f, pixels * 12, host_out);
+    if ((rc = st.refuse_in_capture()) != P3D_OK) return rc;
 
     FramePlan plan;
     plan.s = s;
     if ((rc = fill_scene_params(s, cfg, prm, plan)) != P3D_OK) return rc;
     const LaunchParams& P = plan.P;
     if (wavefront_lds_bytes(P, plan.lds_scene) > kMaxLdsBytes) return fail(P3D_ERR_LIMIT, "BVH depth needs more LDS than a CU has");
-    for (int i = 0; i < n_needs; i++) HIP_TRY(ensure_counted(s, *needs[i].buf, needs[i].bytes));
+    if ((rc = st.allocate()) != P3D_OK) return rc;
 
     AoIO io;
     memset(&io, 0, sizeof io);
-    io.depth = in->depth; io.normal = in->normal; io.color = in->rgb32f; io.ao = out->ao; io.rgb = out->rgb32f;
-    io.res_x = cams[0].res_x; io.res_y = cams[0].res_y; io.n_frames = n;
-    for (io.log2_samples = 0; (1 << io.log2_samples) < ao->samples; io.log2_samples++) {}
-    io.radius = ao->radius; io.bias = ao->bias; io.seed = ao->seed;
-    {   // the cameras travel in the arguments of a launch of this stream: a captured call replays with its own
-        std::vector<FrameCam> fc((size_t)n);
-        for (int f = 0; f < n; f++) fc[f] = camera_record(cams[f]);
-        HIP_TRY(launch_frame_cams((FrameCam*)B.cams.p, fc.data(), n, s->stream));
-        io.cams = (const FrameCam*)B.cams.p;
-    }
-    if (host_in) {
-        HIP_TRY(hipMemcpyAsync(B.in_depth.p, in->depth, pixels * 4, hipMemcpyHostToDevice, s->stream));
-        HIP_TRY(hipMemcpyAsync(B.in_normal.p, in->normal, pixels * 12, hipMemcpyHostToDevice, s->stream));
-        io.depth = (const float*)B.in_depth.p; io.normal = (const float*)B.in_normal.p;
-        if (in->rgb32f) {
-            HIP_TRY(hipMemcpyAsync(B.in_rgb32f.p, in->rgb32f, pixels * 12, hipMemcpyHostToDevice, s->stream));
-            io.color = (const float*)B.in_rgb32f.p;
-        }
-    }
-    if (host_out) {
-        if (out->ao) io.ao = (float*)B.out_ao.p;
-        if (out->rgb32f) io.rgb = (float*)B.out_rgb32f.p;
-    }
+    if ((rc = fill_gather_io(s, cam_buf, cams, n, ao->samples, ao->bias, ao->seed, io)) != P3D_OK) return rc;
+    io.radius = ao->radius;
+    if ((rc = st.upload()) != P3D_OK) return rc;
+    io.depth = depth; io.normal = normal; io.color = color; io.ao = o_ao; io.rgb = o_rgb;
     HIP_TRY(launch_wf_ao(P, io, plan.kv, s->stream));
-    if (host_out) {
-        if (out->ao) HIP_TRY(hipMemcpyAsync(out->ao, io.ao, pixels * 4, hipMemcpyDeviceToHost, s->stream));
-        if (out->rgb32f) HIP_TRY(hipMemcpyAsync(out->rgb32f, io.rgb, pixels * 12, hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipStreamSynchronize(s->stream));
-    } else if (host_in) {
-        HIP_TRY(hipStreamSynchronize(s->stream));        // the caller's host planes have been read when the call returns
-    }
-    return P3D_OK;
-}
-
-// All argument checks of p3d_indirect_diffuse, in the order include/p3d_hip.h lists them: p3d_trace_rays' rules for params
-// (max_depth is not read: the request is normalised to depth 1 without features), then p3d_ambient_occlusion's for the rest.
-int validate_indirect_request(const p3d_scene* s, const p3d_camera* cams, int32_t n, const p3d_render_params* prm,
-                              const p3d_indirect_params* ind, const p3d_indirect_inputs* in, const p3d_indirect_outputs* out, FrameConfig& cfg) {
-    if (!s || !cams || !prm || !ind || !in || !out) return fail(P3D_ERR_ARG, "NULL argument");
-    if (n < 1) return fail(P3D_ERR_ARG, "n must be at least 1");
-    if (prm->accel < 0 || prm->accel > 2) return fail(P3D_ERR_ARG, "accel must be 0, 1 or 2");
-    if (prm->flags & ~kRayStreamFlags)
-        return fail(P3D_ERR_ARG, "flags: indirect diffuse accepts P3D_FLAG_NO_LDS_SCENE, _PRIVATE_WALK and _WAVEFRONT only");
-    if (prm->features != 0) return fail(P3D_ERR_ARG, "features: the bounce is lit without features, features must be 0");
-    if (prm->spp != 0) return fail(P3D_ERR_ARG, "spp: indirect diffuse has no pixel samples, spp must be 0");
-    if (prm->samples) return fail(P3D_ERR_ARG, "samples: indirect diffuse has no pixel samples, p3d_render_params::samples must be NULL");
-    if (prm->world > 1 || prm->rank != 0) return fail(P3D_ERR_ARG, "world / rank: indirect diffuse is not sharded, world must be 0 or 1 and rank 0 (stitch the planes first)");
-    const int32_t S = ind->samples;
-    if (S < 1 || S > 64 || (S & (S - 1)) != 0) return fail(P3D_ERR_ARG, "p3d_indirect_params::samples must be 1, 2, 4, 8, 16, 32 or 64");
-    if (!std::isfinite(ind->bias) || !(ind->bias >= 0.0f)) return fail(P3D_ERR_ARG, "p3d_indirect_params::bias must be finite and not negative");
-    if (!in->depth || !in->normal) return fail(P3D_ERR_ARG, "p3d_indirect_inputs::depth / normal is NULL");
-    if (!out->indirect && !out->rgb32f) return fail(P3D_ERR_ARG, "p3d_indirect_outputs: both indirect and rgb32f are NULL");
-    if (in->memory != 0 && in->memory != 1) return fail(P3D_ERR_ARG, "p3d_indirect_inputs::memory must be 0 (host) or 1 (device)");
-    if (out->memory != 0 && out->memory != 1) return fail(P3D_ERR_ARG, "p3d_indirect_outputs::memory must be 0 (host) or 1 (device)");
-    const void* const outs[2] = {out->indirect, out->rgb32f};
-    for (const void* o : outs)
-        if (o && (o == in->depth || o == in->normal || o == in->albedo || o == in->rgb32f)) return fail(P3D_ERR_ARG, "an output plane aliases an input plane");
-    if (out->indirect && out->indirect == out->rgb32f) return fail(P3D_ERR_ARG, "p3d_indirect_outputs::indirect and rgb32f alias each other");
-    if (cams[0].res_x < 1 || cams[0].res_y < 1) return fail(P3D_ERR_ARG, "res_x and res_y of the cameras must be at least 1");
-    for (int f = 1; f < n; f++)
-        if (cams[f].res_x != cams[0].res_x || cams[f].res_y != cams[0].res_y) return fail(P3D_ERR_ARG, "the cameras differ in res_x / res_y");
-    // 64-bit products of 31-bit factors, compared step by step so that none of them wraps
-    const uint64_t rows = (uint64_t)n * (uint64_t)cams[0].res_y;
-    if (rows > kMaxStackedPixels || rows * (uint64_t)cams[0].res_x > kMaxStackedPixels ||
-        rows * (uint64_t)cams[0].res_x * (uint64_t)S > kMaxStackedPixels)
-        return fail(P3D_ERR_LIMIT, "n * res_y * res_x * samples does not fit 31 bits");
-    if (s->cull_never_hit) return fail(P3D_ERR_STATE, "scene was built with cull_never_hit: it serves frames only, not rays of any length");
-    cfg.max_depth = 1; cfg.accel = prm->accel; cfg.spp = 0;
-    cfg.flags = prm->flags & kConfigFlags; cfg.features = 0;
-    return P3D_OK;
+    return st.finish();
 }
 
 // Level 1 of p3d_trace_rays at max_depth 1 on rays made in lanes from the planes, summed per pixel: the scene into the launch
 // parameters as for any entry, the cameras into the handle's buffer by a launch of the stream, then ONE launch of
 // wf_indirect_kernel (indirect.hip) for all frames.  No queues, no workspace, no schedule: of the handle it touches the
-// staging of s->indirect and the grid of the first GRID call.
+// staging of s->indirect and the grid of the first GRID call.  (Its rules for params are p3d_trace_rays': max_depth is not
+// read, the request is normalised to depth 1 without features.)
 int indirect_diffuse(p3d_scene* s, const p3d_camera* cams, int32_t n, const p3d_render_params* prm, const p3d_indirect_params* ind,
                      const p3d_indirect_inputs* in, const p3d_indirect_outputs* out) {
+    if (!s || !cams || !prm || !ind || !in || !out) return fail(P3D_ERR_ARG, "NULL argument");
+    const GatherRequest q = {"indirect diffuse", "features: the bounce is lit without features, features must be 0", "p3d_indirect_params",
+                             "p3d_indirect_inputs", "p3d_indirect_outputs", "indirect", ind->samples, nullptr, ind->bias,
+                             in->depth, in->normal, in->albedo, in->rgb32f, in->memory, out->indirect, out->rgb32f, out->memory};
     FrameConfig cfg;
-    int rc = validate_indirect_request(s, cams, n, prm, ind, in, out, cfg);
+    int rc = validate_gather_request(cams, n, prm, q, cfg);
     if (rc) return rc;
+    if (s->cull_never_hit) return fail(P3D_ERR_STATE, "scene was built with cull_never_hit: it serves frames only, not rays of any length");
     HIP_TRY(hipSetDevice(s->device));
     const size_t pixels = (size_t)n * (size_t)cams[0].res_y * (size_t)cams[0].res_x;
     const bool host_in = in->memory == 0, host_out = out->memory == 0;
     p3d_scene::IndirectDiffuse& B = s->indirect;
 
-    // everything the call needs of the handle, sized before anything is allocated
-    struct Need { RawBuf* buf; size_t bytes; } needs[7];
-    int n_needs = 0;
-    needs[n_needs++] = {&B.cams, (size_t)n * sizeof(FrameCam)};
-    if (host_in) {
-        needs[n_needs++] = {&B.in_depth, pixels * 4}; needs[n_needs++] = {&B.in_normal, pixels * 12};
-        if (in->albedo) needs[n_needs++] = {&B.in_albedo, pixels * 12};
-        if (in->rgb32f) needs[n_needs++] = {&B.in_rgb32f, pixels * 12};
-    }
-    if (host_out && out->indirect) needs[n_needs++] = {&B.out_indirect, pixels * 12};
-    if (host_out && out->rgb32f) needs[n_needs++] = {&B.out_rgb32f, pixels * 12};
-    if (capturing(s->stream)) {
-        if (host_in || host_out)
-            return fail(P3D_ERR_STATE, "p3d_indirect_diffuse copies host planes and waits for them: not while the stream is being captured");
-        for (int i = 0; i < n_needs; i++)
-            if (needs[i].bytes > needs[i].buf->cap)
-                return fail(P3D_ERR_STATE, "p3d_indirect_diffuse has to allocate its camera buffer: make a call of this shape before the capture");
-    }
+    PlaneStage st(s, "p3d_indirect_diffuse", "its camera buffer");
+    const PlaneStage::Plane cam_buf = st.scratch(B.cams, (size_t)n * sizeof(FrameCam));
+    const PlaneStage::Plane depth = st.in(B.in_depth, in->depth, pixels * 4, host_in), normal = st.in(B.in_normal, in->normal, pixels * 12, host_in),
+                            albedo = st.in(B.in_albedo, in->albedo, pixels * 12, host_in), color = st.in(B.in_rgb32f, in->rgb32f, pixels * 12, host_in);
+    const PlaneStage::Plane o_indirect = st.out(B.out_indirect, out->indirect, pixels * 12, host_out), o_rgb = st.out(B.out_rgb32f, out->rgb32f, pixels * 12, host_out);
+    if ((rc = st.refuse_in_capture()) != P3D_OK) return rc;
 
     FramePlan plan;
     plan.s = s;
     if ((rc = fill_scene_params(s, cfg, prm, plan)) != P3D_OK) return rc;
     const LaunchParams& P = plan.P;
     if (wavefront_lds_bytes(P, plan.lds_scene) > kMaxLdsBytes) return fail(P3D_ERR_LIMIT, "BVH depth needs more LDS than a CU has");
-    for (int i = 0; i < n_needs; i++) HIP_TRY(ensure_counted(s, *needs[i].buf, needs[i].bytes));
+    if ((rc = st.allocate()) != P3D_OK) return rc;
 
     IndirectIO io;
     memset(&io, 0, sizeof io);
-    io.depth = in->depth; io.normal = in->normal; io.albedo = in->albedo; io.color = in->rgb32f;
-    io.indirect = out->indirect; io.rgb = out->rgb32f;
-    io.res_x = cams[0].res_x; io.res_y = cams[0].res_y; io.n_frames = n;
-    for (io.log2_samples = 0; (1 << io.log2_samples) < ind->samples; io.log2_samples++) {}
-    io.bias = ind->bias; io.seed = ind->seed;
-    {   // the cameras travel in the arguments of a launch of this stream: a captured call replays with its own
-        std::vector<FrameCam> fc((size_t)n);
-        for (int f = 0; f < n; f++) fc[f] = camera_record(cams[f]);
-        HIP_TRY(launch_frame_cams((FrameCam*)B.cams.p, fc.data(), n, s->stream));
-        io.cams = (const FrameCam*)B.cams.p;
-    }
-    if (host_in) {
-        HIP_TRY(hipMemcpyAsync(B.in_depth.p, in->depth, pixels * 4, hipMemcpyHostToDevice, s->stream));
-        HIP_TRY(hipMemcpyAsync(B.in_normal.p, in->normal, pixels * 12, hipMemcpyHostToDevice, s->stream));
-        io.depth = (const float*)B.in_depth.p; io.normal = (const float*)B.in_normal.p;
-        if (in->albedo) {
-            HIP_TRY(hipMemcpyAsync(B.in_albedo.p, in->albedo, pixels * 12, hipMemcpyHostToDevice, s->stream));
-            io.albedo = (const float*)B.in_albedo.p;
-        }
-        if (in->rgb32f) {
-            HIP_TRY(hipMemcpyAsync(B.in_rgb32f.p, in->rgb32f, pixels * 12, hipMemcpyHostToDevice, s->stream));
-            io.color = (const float*)B.in_rgb32f.p;
-        }
-    }
-    if (host_out) {
-        if (out->indirect) io.indirect = (float*)B.out_indirect.p;
-        if (out->rgb32f) io.rgb = (float*)B.out_rgb32f.p;
-    }
+    if ((rc = fill_gather_io(s, cam_buf, cams, n, ind->samples, ind->bias, ind->seed, io)) != P3D_OK) return rc;
+    if ((rc = st.upload()) != P3D_OK) return rc;
+    io.depth = depth; io.normal = normal; io.albedo = albedo; io.color = color; io.indirect = o_indirect; io.rgb = o_rgb;
     HIP_TRY(launch_wf_indirect(P, io, plan.kv, s->stream));
-    if (host_out) {
-        if (out->indirect) HIP_TRY(hipMemcpyAsync(out->indirect, io.indirect, pixels * 12, hipMemcpyDeviceToHost, s->stream));
-        if (out->rgb32f) HIP_TRY(hipMemcpyAsync(out->rgb32f, io.rgb, pixels * 12, hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipStreamSynchronize(s->stream));
-    } else if (host_in) {
-        HIP_TRY(hipStreamSynchronize(s->stream));        // the caller's host planes have been read when the call returns
-    }
-    return P3D_OK;
+    return st.finish();
 }
 
 }  // namespace

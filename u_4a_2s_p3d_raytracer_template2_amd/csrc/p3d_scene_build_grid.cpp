@@ -28,12 +28,8 @@ extern "C" int p3d_scene_build_grid(p3d_scene* s, p3d_grid_info* info) {
     if (s->cull_never_hit)
         return fail(P3D_ERR_STATE, "scene was built with cull_never_hit: GRID mode walks the reference's grid over ALL primitives; use accel BVH");
     HIP_TRY(hipSetDevice(s->device));
-    {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        (void)hipStreamIsCapturing(s->stream, &cap);
-        if (cap != hipStreamCaptureStatusNone)
-            return fail(P3D_ERR_STATE, "p3d_scene_build_grid allocates and waits on the device: not while the stream is being captured");
-    }
+    if (stream_capturing(s->stream))
+        return fail(P3D_ERR_STATE, "p3d_scene_build_grid allocates and waits on the device: not while the stream is being captured");
     auto report = [&](uint32_t built) {
         if (!info) return;
         info->built = built;

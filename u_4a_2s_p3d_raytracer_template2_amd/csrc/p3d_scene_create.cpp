@@ -307,9 +307,7 @@ int p3d_set_prune_reflections(p3d_scene* s, int32_t on) {
     s->prune_reflections = on != 0;
     if (s->prunes() == s->blob_prunes) return P3D_OK;
     // the kernels read the switch in the material records: rewrite them behind whatever the stream still holds
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(s->stream, &cap);
-    if (cap != hipStreamCaptureStatusNone) {
+    if (stream_capturing(s->stream)) {
         s->prune_reflections = was;
         return fail(P3D_ERR_STATE, "p3d_set_prune_reflections rewrites the scene's materials: not while the stream is being captured");
     }

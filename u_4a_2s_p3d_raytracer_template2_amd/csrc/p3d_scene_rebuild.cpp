@@ -17,12 +17,6 @@ using namespace p3d;
 
 namespace {
 
-bool stream_capturing(hipStream_t stream) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(stream, &cap);
-    return cap != hipStreamCaptureStatusNone;
-}
-
 // the f32 node pairs of the tree the handle walks, or nullptr: a handle read from HBM has none before its first update
 const NodePair* f32_nodes(const p3d_scene* s) {
     if (s->lds_capable) return (const NodePair*)(s->blob.p + 4 * (size_t)s->off_nodes);

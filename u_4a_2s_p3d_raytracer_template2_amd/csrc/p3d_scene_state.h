@@ -1,5 +1,5 @@
 // p3d_scene_state.h -- the scene handle behind the C-ABI of include/p3d_hip.h, shared by the files that implement it
-// (p3d_scene_create.cpp, p3d_scene_update.cpp, p3d_scene_rebuild.cpp, p3d_scene_build_grid.cpp, p3d_render.cpp, p3d_generate_samples.cpp, p3d_denoise.cpp, p3d_accumulate.cpp, p3d_upsample.cpp, p3d_capi_misc.cpp; p3d_ambient_occlusion and p3d_indirect_diffuse live in p3d_render.cpp).  Internal: not installed with include/.
+// (p3d_scene_create.cpp, p3d_scene_update.cpp, p3d_scene_rebuild.cpp, p3d_scene_build_grid.cpp, p3d_render.cpp, p3d_generate_samples.cpp, p3d_denoise.cpp, p3d_accumulate.cpp, p3d_upsample.cpp, p3d_capi_misc.cpp, p3d_debug_planes.cpp; p3d_ambient_occlusion and p3d_indirect_diffuse live in p3d_render.cpp).  Internal: not installed with include/.
 // Every device resource in it is owned by a member that frees it: deleting a p3d_scene releases all of them.
 #ifndef P3D_SCENE_STATE_H
 #define P3D_SCENE_STATE_H
@@ -119,6 +119,13 @@ struct OwnedEvent {
 using LaneStream = OwnedStream<hipStreamNonBlocking>;
 using TimingEvent = OwnedEvent<hipEventDefault>;
 using OrderEvent = OwnedEvent<hipEventDisableTiming>;
+
+// Whether `stream` is being captured into a graph: what waits for the stream or allocates is refused then.
+inline bool stream_capturing(hipStream_t stream) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing(stream, &cap);
+    return cap != hipStreamCaptureStatusNone;
+}
 
 }  // namespace p3d
 

@@ -52,12 +52,8 @@ extern "C" int p3d_scene_update(p3d_scene* s, const p3d_prim_update* u) {
             if (u->index[i] >= n_prims) return fail(P3D_ERR_ARG, "primitive index out of range");
     }
     HIP_TRY(hipSetDevice(s->device));
-    {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        (void)hipStreamIsCapturing(s->stream, &cap);
-        if (cap != hipStreamCaptureStatusNone)
-            return fail(P3D_ERR_STATE, "p3d_scene_update waits on the device and changes launch parameters: not while the stream is being captured");
-    }
+    if (stream_capturing(s->stream))
+        return fail(P3D_ERR_STATE, "p3d_scene_update waits on the device and changes launch parameters: not while the stream is being captured");
     const uint32_t n_nodes = (uint32_t)s->qnodes.n;
     uint32_t bad_indices = 0;
     if (u->n > 0) {

@@ -6,7 +6,7 @@
 #include <cmath>
 
 #include "denoise.h"
-#include "p3d_scene_state.h"
+#include "p3d_plane_stage.h"
 
 using namespace p3d;
 
@@ -47,55 +47,15 @@ extern "C" int p3d_upsample(p3d_scene* s, const p3d_upsample_params* params, con
     const bool host_in = in->memory == 0, host_out = out->memory == 0;
     p3d_scene::Upsample& U = s->upsample;
 
-    // everything the call needs of the handle, sized before anything is allocated
-    struct Need { RawBuf* buf; size_t bytes; } needs[7];
-    int n_needs = 0;
-    if (host_in) {
-        needs[n_needs++] = {&U.in_low, low_px * c * 4}; needs[n_needs++] = {&U.in_low_depth, low_px * 4};
-        needs[n_needs++] = {&U.in_low_normal, low_px * 12};
-        needs[n_needs++] = {&U.in_depth, px * 4}; needs[n_needs++] = {&U.in_normal, px * 12};
-    }
-    if (host_out && out->plane) needs[n_needs++] = {&U.out_plane, px * c * 4};
-    if (host_out && out->fallback) needs[n_needs++] = {&U.out_fallback, px};
-    {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        (void)hipStreamIsCapturing(s->stream, &cap);
-        if (cap != hipStreamCaptureStatusNone) {
-            if (host_in || host_out)
-                return fail(P3D_ERR_STATE, "p3d_upsample copies host planes and waits for them: not while the stream is being captured");
-            for (int i = 0; i < n_needs; i++)
-                if (needs[i].bytes > needs[i].buf->cap)
-                    return fail(P3D_ERR_STATE, "p3d_upsample has to allocate its staging: make a call of this shape before the capture");
-        }
-    }
-    for (int i = 0; i < n_needs; i++) {
-        s->stats.device_bytes -= needs[i].buf->cap;
-        const hipError_t e = needs[i].buf->ensure(needs[i].bytes);
-        s->stats.device_bytes += needs[i].buf->cap;
-        HIP_TRY(e);
-    }
+    PlaneStage st(s, "p3d_upsample", "its staging");
+    const PlaneStage::Plane low = st.in(U.in_low, in->low, low_px * c * 4, host_in), low_depth = st.in(U.in_low_depth, in->low_depth, low_px * 4, host_in),
+                            low_normal = st.in(U.in_low_normal, in->low_normal, low_px * 12, host_in),
+                            depth = st.in(U.in_depth, in->depth, px * 4, host_in), normal = st.in(U.in_normal, in->normal, px * 12, host_in);
+    const PlaneStage::Plane plane = st.out(U.out_plane, out->plane, px * c * 4, host_out), fallback = st.out(U.out_fallback, out->fallback, px, host_out);
+    if (const int rc = st.refuse_in_capture()) return rc;
+    if (const int rc = st.allocate()) return rc;
 
-    const float *low = in->low, *low_depth = in->low_depth, *low_normal = in->low_normal, *depth = in->depth, *normal = in->normal;
-    if (host_in) {
-        HIP_TRY(hipMemcpyAsync(U.in_low.p, in->low, low_px * c * 4, hipMemcpyHostToDevice, s->stream));
-        HIP_TRY(hipMemcpyAsync(U.in_low_depth.p, in->low_depth, low_px * 4, hipMemcpyHostToDevice, s->stream));
-        HIP_TRY(hipMemcpyAsync(U.in_low_normal.p, in->low_normal, low_px * 12, hipMemcpyHostToDevice, s->stream));
-        HIP_TRY(hipMemcpyAsync(U.in_depth.p, in->depth, px * 4, hipMemcpyHostToDevice, s->stream));
-        HIP_TRY(hipMemcpyAsync(U.in_normal.p, in->normal, px * 12, hipMemcpyHostToDevice, s->stream));
-        low = (const float*)U.in_low.p; low_depth = (const float*)U.in_low_depth.p; low_normal = (const float*)U.in_low_normal.p;
-        depth = (const float*)U.in_depth.p; normal = (const float*)U.in_normal.p;
-    }
-    float* d_plane = out->plane;
-    uint8_t* d_fallback = out->fallback;
-    if (host_out) {
-        if (out->plane) d_plane = (float*)U.out_plane.p;
-        if (out->fallback) d_fallback = (uint8_t*)U.out_fallback.p;
-    }
-    HIP_TRY(launch_upsample(*params, low, low_depth, low_normal, depth, normal, d_plane, d_fallback, s->stream));
-    if (host_out) {
-        if (out->plane) HIP_TRY(hipMemcpyAsync(out->plane, d_plane, px * c * 4, hipMemcpyDeviceToHost, s->stream));
-        if (out->fallback) HIP_TRY(hipMemcpyAsync(out->fallback, d_fallback, px, hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipStreamSynchronize(s->stream));
-    }
-    return P3D_OK;
+    if (const int rc = st.upload()) return rc;
+    HIP_TRY(launch_upsample(*params, low, low_depth, low_normal, depth, normal, plane, fallback, s->stream));
+    return st.finish();
 }
