@@ -980,6 +980,54 @@ typedef struct p3d_indirect_outputs { float* indirect; float* rgb32f; int32_t me
 int p3d_indirect_diffuse(p3d_scene* scene, const p3d_camera* cams, int32_t n, const p3d_render_params* params,
                          const p3d_indirect_params* indirect, const p3d_indirect_inputs* in, const p3d_indirect_outputs* out);
 
+/* Several bounces of diffuse indirect light over the same planes: per pixel `samples` paths of at most `bounces` rays, a path
+ * per lane.  Ray 0 of a path is the ray p3d_indirect_diffuse traces for that sample; at every hit the path goes on in a
+ * cosine-weighted direction, its throughput multiplied by the albedo of what it hit, and every ray adds the direct-lit
+ * colour of what it hits times the throughput.  What a caller would build as `bounces` rounds of p3d_trace_rays with kernels
+ * of their own in between -- 24 bytes of ray and 12 of colour per sample per round -- is a loop in the lanes of one launch. */
+typedef struct p3d_path_params {
+    int32_t  samples;   /* 1, 2, 4, 8, 16, 32 or 64 paths per pixel */
+    int32_t  bounces;   /* 1 .. 8: rays per path at most */
+    float    bias;      /* finite, >= 0: every vertex's origin is moved this far along the normal that faces the incoming ray */
+    uint32_t seed;      /* frame f keys its random streams with seed + f */
+} p3d_path_params;
+/* The result is DEFINED here like p3d_indirect_diffuse's, in float32 IEEE-754 basic operations in the stated order (no fused
+ * multiply-add), and the device, the host layer (p3dh_ao_segments, p3dh_path_next, p3dh_path_add, p3dh_indirect_resolve) and
+ * tests/path_reference.py agree on it in every bit.  Every ray's answer is anchored to what p3d_trace_rays returns for it.
+ *  - planes, cameras, inputs and outputs: p3d_indirect_diffuse's.
+ *  - the definition, for pixel (x, y) of frame f and sample s = 0 .. samples - 1:
+ *      1. vertex 0: steps 1 to 6 of p3d_indirect_diffuse give the pixel's validity (an invalid depth: no path), O_0, Ns_0,
+ *         pk_0 = rng_mix(seed + f, y * res_x + x) and D_0: ray 0 of the path is the ray p3d_indirect_diffuse traces for
+ *         sample s.
+ *      2. trace: for b = 0 .. bounces - 1 while the path is alive, (r_b, hit_b, t_b, N_b) is what p3d_trace_rays answers as
+ *         rgb32f, hit_id, t and normal for Ray(O_b, D_b) with max_depth = 1, features = 0 and params->accel: r_b is the
+ *         clamped direct lighting of the hit with its shadow queries, or the background on a miss; N_b is
+ *         getNormal(O_b + D_b * t_b).normalize().
+ *      3. sum: R = r_0; for b >= 1, per channel, R = R + T_b * r_b, a product and then a sum.  A path that misses at
+ *         bounce b (hit_b < 0) ends after adding that term.
+ *      4. next vertex, when hit_b >= 0 and b + 1 < bounces:
+ *           P = O_b + D_b * t_b, per component a product and then a sum;
+ *           a = floats 0..2 of the hit's material record: the albedo p3d_render_aov defines, not multiplied by Kd;
+ *           T_(b+1) = a for b = 0, else T_b * a per channel;
+ *           Ns = -N_b if (N_b.x D_b.x + N_b.y D_b.y) + N_b.z D_b.z > 0, else N_b;
+ *           O_(b+1) = P + Ns * bias, per component a product and then a sum;
+ *           pk_(b+1) = rng_mix(pk_0, 0x80000000 + (b + 1));
+ *           D_(b+1) = steps 5 and 6 of p3d_ambient_occlusion at radius 1 from Ns with the key rng_mix(pk_(b+1), s).
+ *         The keys do not depend on `samples` or `bounces`: sample s is the same path at every sample count, and a path of
+ *         fewer bounces is a prefix of a path of more.
+ *      5. resolve: steps 8 and 9 of p3d_indirect_diffuse on the per-sample R: the balanced tree in sample order, times
+ *         1.0f / samples, out->indirect = m and out->rgb32f = c + a * m.  A pixel without a path gets what it gets there.
+ *    Normals that are not unit length, zero or not finite, and glass or mirror materials, go through the same operations.
+ *    There is no Russian roulette and no specular path segment.  With bounces == 1 every output bit is
+ *    p3d_indirect_diffuse's.
+ *  - params, P3D_ERR_ARG, P3D_ERR_LIMIT (still on n * res_y * res_x * samples), P3D_ERR_STATE, memory, stream capture,
+ *    handle state, scene motion and refusals: as p3d_indirect_diffuse, with `paths` in the place of `indirect`; in addition
+ *    paths->bounces outside 1 .. 8 is P3D_ERR_ARG.  The staging buffers and the camera buffer are p3d_indirect_diffuse's:
+ *    calls of the two entries on planes of one size share them.  With everything in device memory the call is the small
+ *    camera launch and ONE launch for all n frames and all bounces. */
+int p3d_indirect_paths(p3d_scene* scene, const p3d_camera* cams, int32_t n, const p3d_render_params* params,
+                       const p3d_path_params* paths, const p3d_indirect_inputs* in, const p3d_indirect_outputs* out);
+
 /* The edge-aware upsampler of p3d_render_aov's planes: a low-frequency signal (ambient occlusion, a soft shadow, a fuzzy
  * reflection) computed at 1 / factor of the resolution is brought up to the full frame along the full frame's depth and
  * normal (joint bilateral upsampling, Kopf et al. 2007). */

@@ -230,6 +230,16 @@ INDIRECT_SAMPLES = 8
 INDIRECT_BIAS = 0.001
 
 
+class PathParams(C.Structure):
+    """p3d_path_params: samples (1, 2, 4, .. 64) paths per pixel of at most bounces (1 .. 8) rays each, every vertex's origin
+    moved bias along the normal that faces the incoming ray; frame f keys its random streams with seed + f."""
+    _fields_ = [("samples", C.c_int32), ("bounces", C.c_int32), ("bias", C.c_float), ("seed", C.c_uint32)]
+
+
+# p3d_indirect_paths' default: a convenience, not measured
+PATH_BOUNCES = 3
+
+
 class UpsampleParams(C.Structure):
     """p3d_upsample_params: n_frames low frames of res_x x res_y back to back, brought up by factor 1..4; channels 1 or 3 floats
     per pixel of the signal; the denoiser's depth stop and normal_power_log2 0..8 squarings of the normal weight."""
@@ -284,7 +294,7 @@ class SceneStats(C.Structure):
 
 # every symbol include/p3d_hip.h declares (tests check that the library exports them all)
 C_ABI_SYMBOLS = ["p3d_abi_version", "p3d_last_error", "p3d_device_count", "p3d_scene_create",
-                 "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_scene_update", "p3d_scene_rebuild", "p3d_scene_rebuild_with", "p3d_scene_last_builder", "p3d_scene_tree_cost", "p3d_scene_build_grid", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_render_aov", "p3d_generate_samples", "p3d_trace_rays", "p3d_occluded", "p3d_denoise", "p3d_denoise_variance", "p3d_accumulate", "p3d_accumulate_moving", "p3d_accumulate_variance", "p3d_ambient_occlusion", "p3d_indirect_diffuse", "p3d_upsample", "p3d_sync",
+                 "p3d_scene_destroy", "p3d_scene_set_skybox", "p3d_scene_get_stats", "p3d_scene_update", "p3d_scene_rebuild", "p3d_scene_rebuild_with", "p3d_scene_last_builder", "p3d_scene_tree_cost", "p3d_scene_build_grid", "p3d_local_rows", "p3d_render", "p3d_render_frames", "p3d_render_aov", "p3d_generate_samples", "p3d_trace_rays", "p3d_occluded", "p3d_denoise", "p3d_denoise_variance", "p3d_accumulate", "p3d_accumulate_moving", "p3d_accumulate_variance", "p3d_ambient_occlusion", "p3d_indirect_diffuse", "p3d_indirect_paths", "p3d_upsample", "p3d_sync",
                  "p3d_get_counters", "p3d_get_profile", "p3d_last_schedule", "p3d_set_tuning", "p3d_set_primary_tiles", "p3d_last_primary_tiles", "p3d_set_sky_tiles", "p3d_last_sky_tiles", "p3d_set_prune_reflections", "p3d_get_prune_reflections", "p3d_last_level_rays", "p3d_set_stream", "p3d_timer_begin", "p3d_timer_end", "p3d_deinterleave_frames",
                  "p3d_deinterleave", "p3d_debug_intersect", "p3d_debug_powf", "p3d_debug_pow", "p3d_debug_schlick_kr", "p3d_debug_check_rcp", "p3d_debug_check_rcp_len", "p3d_debug_lbvh_build", "p3d_debug_ploc_build", "p3d_debug_grid_build", "p3d_debug_rand", "p3d_debug_sample_stream", "p3d_debug_denoise", "p3d_debug_denoise_variance", "p3d_debug_accumulate", "p3d_debug_accumulate_moving", "p3d_debug_accumulate_variance", "p3d_debug_upsample", "p3d_tune_schedule", "p3d_debug_set_stamps", "p3d_debug_set_stamp_level",
                  "p3d_comm_unique_id", "p3d_comm_create", "p3d_comm_create_all", "p3d_comm_destroy", "p3d_comm_info",
@@ -378,6 +388,12 @@ def lib():
                                        C.POINTER(IndirectInputs), C.POINTER(IndirectOutputs)]
     L.p3dh_indirect_resolve.argtypes = [C.c_int32, C.c_uint64] + [C.c_void_p] * 6
     L.p3dh_indirect_resolve.restype = None
+    L.p3d_indirect_paths.argtypes = [C.c_void_p, C.POINTER(Camera), C.c_int32, C.POINTER(RenderParams), C.POINTER(PathParams),
+                                     C.POINTER(IndirectInputs), C.POINTER(IndirectOutputs)]
+    L.p3dh_path_next.argtypes = [C.c_uint64, C.c_int32, C.c_float] + [C.c_void_p] * 13
+    L.p3dh_path_next.restype = None
+    L.p3dh_path_add.argtypes = [C.c_uint64, C.c_int32] + [C.c_void_p] * 4
+    L.p3dh_path_add.restype = None
     L.p3d_sync.argtypes = [C.c_void_p]
     L.p3d_get_counters.argtypes = [C.c_void_p, C.POINTER(Counters)]
     L.p3d_set_stream.argtypes = [C.c_void_p, C.c_void_p]
@@ -1184,8 +1200,8 @@ class DeviceScene:
         _check(lib().p3d_ambient_occlusion(self.h, arr, n, C.byref(p), C.byref(a), C.byref(i), C.byref(o)), "p3d_ambient_occlusion")
 
     def indirect_diffuse(self, cam_or_cams, depth, normal, albedo=None, rgb32f=None, samples=INDIRECT_SAMPLES, bias=INDIRECT_BIAS, seed=0,
-                         accel=ACCEL_BVH, no_lds=False, private_walk=False, want=("indirect", "rgb32f")):
-        """p3d_indirect_diffuse on host arrays: depth (n, H, W) or (H, W) and normal (n, H, W, 3) or (H, W, 3) as render_aov
+                         accel=ACCEL_BVH, no_lds=False, private_walk=False, want=("indirect", "rgb32f"), bounces=None):
+        """p3d_indirect_diffuse on host arrays (bounces: see indirect_paths): depth (n, H, W) or (H, W) and normal (n, H, W, 3) or (H, W, 3) as render_aov
         returns them, seen through one Camera or a sequence of n; albedo and rgb32f (both optional) are the planes the
         gathered light is multiplied by and added to.  Returns the planes named in `want`: indirect (n, H, W, 3), the mean
         radiance of the samples, and rgb32f (n, H, W, 3) = rgb32f + albedo * indirect."""
@@ -1199,23 +1215,45 @@ class DeviceScene:
             rgb32f = np.ascontiguousarray(rgb32f, np.float32).reshape(n, H, W, 3)
         out = {k: np.zeros((n, H, W, 3), np.float32) for k in ("indirect", "rgb32f") if k in want}
         p = self._ray_params(1, accel, no_lds, private_walk, False)
-        g = IndirectParams(int(samples), bias, int(seed) & 0xFFFFFFFF)
         i = IndirectInputs(depth.ctypes.data, normal.ctypes.data, albedo.ctypes.data if albedo is not None else None,
                            rgb32f.ctypes.data if rgb32f is not None else None, 0)
         o = IndirectOutputs(out["indirect"].ctypes.data if "indirect" in out else None, out["rgb32f"].ctypes.data if "rgb32f" in out else None, 0)
-        _check(lib().p3d_indirect_diffuse(self.h, arr, n, C.byref(p), C.byref(g), C.byref(i), C.byref(o)), "p3d_indirect_diffuse")
+        self._indirect_call(arr, n, p, samples, bias, seed, bounces, i, o)
         return out
 
+    def _indirect_call(self, arr, n, p, samples, bias, seed, bounces, i, o):
+        """p3d_indirect_diffuse (bounces None) or p3d_indirect_paths on filled input and output structs."""
+        if bounces is None:
+            g = IndirectParams(int(samples), bias, int(seed) & 0xFFFFFFFF)
+            _check(lib().p3d_indirect_diffuse(self.h, arr, n, C.byref(p), C.byref(g), C.byref(i), C.byref(o)), "p3d_indirect_diffuse")
+        else:
+            g = PathParams(int(samples), int(bounces), bias, int(seed) & 0xFFFFFFFF)
+            _check(lib().p3d_indirect_paths(self.h, arr, n, C.byref(p), C.byref(g), C.byref(i), C.byref(o)), "p3d_indirect_paths")
+
     def indirect_diffuse_device(self, cam_or_cams, depth_ptr, normal_ptr, albedo_ptr=0, rgb32f_ptr=0, out_indirect_ptr=0, out_rgb32f_ptr=0,
-                                samples=INDIRECT_SAMPLES, bias=INDIRECT_BIAS, seed=0, accel=ACCEL_BVH, no_lds=False, private_walk=False):
+                                samples=INDIRECT_SAMPLES, bias=INDIRECT_BIAS, seed=0, accel=ACCEL_BVH, no_lds=False, private_walk=False,
+                                bounces=None):
         """Enqueue p3d_indirect_diffuse on caller-owned DEVICE buffers (raw pointers; 0 = no such plane) holding one frame per
-        camera; asynchronous on the scene's stream."""
+        camera; asynchronous on the scene's stream.  (bounces: see indirect_paths_device.)"""
         arr, n = _camera_array([cam_or_cams] if isinstance(cam_or_cams, Camera) else cam_or_cams)
         p = self._ray_params(1, accel, no_lds, private_walk, False)
-        g = IndirectParams(int(samples), bias, int(seed) & 0xFFFFFFFF)
         i = IndirectInputs(depth_ptr or None, normal_ptr or None, albedo_ptr or None, rgb32f_ptr or None, 1)
         o = IndirectOutputs(out_indirect_ptr or None, out_rgb32f_ptr or None, 1)
-        _check(lib().p3d_indirect_diffuse(self.h, arr, n, C.byref(p), C.byref(g), C.byref(i), C.byref(o)), "p3d_indirect_diffuse")
+        self._indirect_call(arr, n, p, samples, bias, seed, bounces, i, o)
+
+    def indirect_paths(self, cam_or_cams, depth, normal, albedo=None, rgb32f=None, samples=INDIRECT_SAMPLES, bounces=PATH_BOUNCES,
+                       bias=INDIRECT_BIAS, seed=0, accel=ACCEL_BVH, no_lds=False, private_walk=False, want=("indirect", "rgb32f")):
+        """p3d_indirect_paths on host arrays: indirect_diffuse's arguments and result, with `samples` paths per pixel of at most
+        `bounces` (1 .. 8) rays each; bounces = 1 gives indirect_diffuse's bits."""
+        return self.indirect_diffuse(cam_or_cams, depth, normal, albedo, rgb32f, samples, bias, seed, accel, no_lds, private_walk, want,
+                                     bounces=int(bounces))
+
+    def indirect_paths_device(self, cam_or_cams, depth_ptr, normal_ptr, albedo_ptr=0, rgb32f_ptr=0, out_indirect_ptr=0, out_rgb32f_ptr=0,
+                              samples=INDIRECT_SAMPLES, bounces=PATH_BOUNCES, bias=INDIRECT_BIAS, seed=0, accel=ACCEL_BVH, no_lds=False,
+                              private_walk=False):
+        """Enqueue p3d_indirect_paths on caller-owned DEVICE buffers: indirect_diffuse_device's arguments, plus bounces."""
+        self.indirect_diffuse_device(cam_or_cams, depth_ptr, normal_ptr, albedo_ptr, rgb32f_ptr, out_indirect_ptr, out_rgb32f_ptr, samples, bias,
+                                     seed, accel, no_lds, private_walk, bounces=int(bounces))
 
     def deinterleave_frames(self, gathered_ptr, frames_ptr, res_x, res_y, row_block, world, bpp, n_frames,
                             rank_stride_bytes=0, tile_stride_bytes=0, frame_stride_bytes=0):
@@ -1653,6 +1691,41 @@ def host_indirect_resolve(radiance, valid, albedo=None, rgb32f=None):
     out = {"indirect": np.zeros(shape + (3,), np.float32), "rgb32f": np.zeros(shape + (3,), np.float32)}
     lib().p3dh_indirect_resolve(int(S), valid.size, radiance.ctypes.data, valid.ctypes.data, albedo.ctypes.data if albedo is not None else None,
                                 rgb32f.ctypes.data if rgb32f is not None else None, out["indirect"].ctypes.data, out["rgb32f"].ctypes.data)
+    return out
+
+
+def host_path_next(b, bias, origin, direction, t, normal, hit_id, prim_material, materials12, pk0, sample, throughput=None):
+    """p3dh_path_next: step 4 of p3d_indirect_paths' definition on the host (no GPU) for m paths that just traced ray b --
+    origin, direction (m, 3), and t (m,), normal (m, 3), hit_id (m,) as p3d_trace_rays answered; prim_material and materials12
+    of HostScene.arrays(); pk0 (m,) the pixels' keys, sample (m,) the paths' samples; throughput (m, 3) T_b (not read when
+    b == 0).  Returns the next origin, direction (m, 3), T_(b+1) (m, 3) and alive (m,) uint8."""
+    origin = np.ascontiguousarray(origin, np.float32).reshape(-1, 3)
+    m = len(origin)
+    direction = np.ascontiguousarray(direction, np.float32).reshape(m, 3)
+    t = np.ascontiguousarray(t, np.float32).reshape(m)
+    normal = np.ascontiguousarray(normal, np.float32).reshape(m, 3)
+    hit_id = np.ascontiguousarray(hit_id, np.int32).reshape(m)
+    prim_material = np.ascontiguousarray(prim_material, np.uint32)
+    materials12 = np.ascontiguousarray(materials12, np.float32).reshape(-1, 12)
+    pk0 = np.ascontiguousarray(pk0, np.uint32).reshape(m)
+    sample = np.ascontiguousarray(sample, np.uint32).reshape(m)
+    T = np.zeros((m, 3), np.float32) if throughput is None else np.array(throughput, np.float32).reshape(m, 3)
+    o2, d2, alive = np.zeros((m, 3), np.float32), np.zeros((m, 3), np.float32), np.zeros(m, np.uint8)
+    lib().p3dh_path_next(m, int(b), float(bias), origin.ctypes.data, direction.ctypes.data, t.ctypes.data, normal.ctypes.data, hit_id.ctypes.data,
+                         prim_material.ctypes.data, materials12.ctypes.data, pk0.ctypes.data, sample.ctypes.data, T.ctypes.data,
+                         o2.ctypes.data, d2.ctypes.data, alive.ctypes.data)
+    return o2, d2, T, alive
+
+
+def host_path_add(b, throughput, radiance, alive, total):
+    """p3dh_path_add: step 3 on the host -- total (m, 3) with r_b (radiance (m, 3)) added under T_b (throughput (m, 3)) where
+    alive (m,) is set: R = r_0 when b == 0, else R + T_b * r_b.  Returns the new sums; `total` is not modified."""
+    radiance = np.ascontiguousarray(radiance, np.float32).reshape(-1, 3)
+    m = len(radiance)
+    throughput = np.ascontiguousarray(throughput, np.float32).reshape(m, 3)
+    alive = np.ascontiguousarray(alive, np.uint8).reshape(m)
+    out = np.array(total, np.float32).reshape(m, 3)
+    lib().p3dh_path_add(m, int(b), throughput.ctypes.data, radiance.ctypes.data, alive.ctypes.data, out.ctypes.data)
     return out
 
 

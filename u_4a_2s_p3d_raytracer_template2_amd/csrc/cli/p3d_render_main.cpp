@@ -4,7 +4,7 @@
 //              [--device K | --gpus N] [--out image.png|image.ppm] [--counters] [--soft-shadow] [--fuzzy-reflection]
 //              [--aov PREFIX] [--denoise K [--denoise-sigmas Z A C]] [--accumulate [--accumulate-params TOL NMIN MAXLEN]]
 //              [--variance-guided [--variance-params MIN_TEMPORAL RADIUS SIGMA]] [--ao S RADIUS [--ao-scale F] [--ao-out PREFIX]]
-//              [--gi S [--gi-bias B]]
+//              [--gi S [--gi-bias B] [--gi-bounces B]]
 // --gpus N: devices 0..N-1 each render every N-th block of 16 rows, one RCCL gather to device 0.
 // --orbit N STEP_DEG: N frames of the reference's mouse orbit (alpha advancing by STEP_DEG per frame, RT/main.cpp:339-341,
 // 419-421) in ONE p3d_render_frames call; --out then takes a %d pattern (e.g. frame_%03d.png) for the frame number.
@@ -33,6 +33,7 @@
 // light with S (1, 2, 4, .. 64) rays per pixel over them (origins moved B along the normal, default 0.001) and
 // albedo * indirect is added to the colour before it is written.  Combines with --denoise K (the sum is what is filtered),
 // with --ao (applied first) and with --aov; one frame on one GPU: not with --orbit, not with --gpus N.
+// --gi S --gi-bounces B: p3d_indirect_paths in its place, S paths per pixel of at most B (1 .. 8) rays each; needs --gi.
 // Defaults are the reference's: resolution / accel / spp from the file, MAX_DEPTH 4.
 #include <chrono>
 #include <cstdio>
@@ -75,13 +76,14 @@ int main(int argc, char** argv) {
         fprintf(stderr, "usage: %s scene.p3f [--res W H] [--accel A] [--depth D] [--spp N] [--seed S] "
                         "[--device K | --gpus N] [--out file.ppm] [--orbit N STEP_DEG] [--counters] [--soft-shadow] [--fuzzy-reflection] [--schlick] [--aov PREFIX] "
                         "[--denoise K [--denoise-sigmas Z A C]] [--accumulate [--accumulate-params TOL NMIN MAXLEN]] "
-                        "[--variance-guided [--variance-params MIN_TEMPORAL RADIUS SIGMA]] [--ao S RADIUS [--ao-scale F] [--ao-out PREFIX]] [--gi S [--gi-bias B]]\n"
+                        "[--variance-guided [--variance-params MIN_TEMPORAL RADIUS SIGMA]] [--ao S RADIUS [--ao-scale F] [--ao-out PREFIX]] [--gi S [--gi-bias B] [--gi-bounces B]]\n"
                         "  --denoise filters one frame on one GPU: not with --orbit, not with --gpus N\n"
                         "  --accumulate blends the frames of --orbit over time on one GPU; with it --denoise filters every accumulated frame\n"
                         "  --variance-guided steers that filter by the variance of every pixel's luminance over time: needs --accumulate and --denoise\n"
                         "  --ao multiplies the colour by ambient occlusion (S segments of length RADIUS per pixel) on one GPU: not with --gpus N\n"
                         "  --ao-scale computes it at 1 / F of the resolution (F in 1..4, dividing W and H) and upsamples it along the frame's depth and normal: needs --ao\n"
-                        "  --gi adds one bounce of diffuse indirect light (S rays per pixel) to one frame on one GPU: not with --orbit, not with --gpus N\n", argv[0]);
+                        "  --gi adds one bounce of diffuse indirect light (S rays per pixel) to one frame on one GPU: not with --orbit, not with --gpus N\n"
+                        "  --gi-bounces follows every ray of --gi over up to B (1..8) diffuse bounces: needs --gi\n", argv[0]);
         return 2;
     }
     RenderOptions opt;
@@ -126,6 +128,7 @@ int main(int argc, char** argv) {
             if (S < 1 || S > 64 || (S & (S - 1))) { fprintf(stderr, "--gi needs S in 1, 2, 4, .. 64\n"); return 2; }
         }
         else if (a == "--gi-bias") { need(1); opt.indirect_bias = (float)atof(argv[++i]); if (!(opt.indirect_bias >= 0.0f)) { fprintf(stderr, "--gi-bias needs B >= 0\n"); return 2; } }
+        else if (a == "--gi-bounces") { need(1); opt.indirect_bounces = atoi(argv[++i]); if (opt.indirect_bounces < 1 || opt.indirect_bounces > 8) { fprintf(stderr, "--gi-bounces needs B in 1..8\n"); return 2; } }
         else { fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
     }
     Scene scene;
@@ -144,6 +147,7 @@ int main(int argc, char** argv) {
     if (opt.variance_guided && (!opt.accumulate || opt.denoise < 0)) { fprintf(stderr, "--variance-guided steers the filter of an accumulated sequence: it needs --accumulate and --denoise K\n"); return 2; }
     if (opt.ambient_occlusion > 0 && opt.gpus > 1) { fprintf(stderr, "--ao runs on the planes of whole frames on one GPU: not with --gpus N\n"); return 2; }
     if (opt.indirect_diffuse > 0 && (opt.gpus > 1 || orbit_n > 0)) { fprintf(stderr, "--gi gathers over the planes of one whole frame on one GPU: not with --gpus N or --orbit\n"); return 2; }
+    if (opt.indirect_bounces > 0 && opt.indirect_diffuse < 1) { fprintf(stderr, "--gi-bounces needs --gi S\n"); return 2; }
     if (opt.ao_scale != 1 && opt.ambient_occlusion < 1) { fprintf(stderr, "--ao-scale needs --ao S RADIUS\n"); return 2; }
     if (W % opt.ao_scale || H % opt.ao_scale) { fprintf(stderr, "--ao-scale F must divide both resolutions (%d x %d)\n", W, H); return 2; }
     if (!ao_out.empty() && opt.ambient_occlusion < 1) { fprintf(stderr, "--ao-out needs --ao S RADIUS\n"); return 2; }

@@ -14,6 +14,7 @@
 #include "accumulate_host.h"
 #include "ao_host.h"
 #include "indirect_host.h"
+#include "indirect_paths_host.h"
 #include "denoise_host.h"
 #include "p3d_scene.h"
 #include "tile_coverage_host.h"
@@ -143,6 +144,18 @@ void p3dh_ao_resolve(int32_t samples, uint64_t n_pixels, const int32_t* occluded
 void p3dh_indirect_resolve(int32_t samples, uint64_t n_pixels, const float* radiance, const uint8_t* valid, const float* albedo,
                            const float* rgb32f_in, float* indirect_out, float* rgb32f_out) {
     indirect_resolve(samples, (size_t)n_pixels, radiance, valid, albedo, rgb32f_in, indirect_out, rgb32f_out);
+}
+
+// path_next() / path_add() of the host layer (indirect_paths_host.cpp): steps 4 and 3 of p3d_indirect_paths' definition for m
+// paths that just traced ray b, every bit.  The arrays are indirect_paths_host.h's; vertex 0 is p3dh_ao_segments' at radius 1
+// and step 5 is p3dh_indirect_resolve.  The caller keeps b in 0 .. 6 and hit_id inside the scene.
+void p3dh_path_next(uint64_t m, int32_t b, float bias, const float* origin, const float* dir, const float* t, const float* normal,
+                    const int32_t* hit_id, const uint32_t* prim_material, const float* materials, const uint32_t* pk0, const uint32_t* sample,
+                    float* throughput, float* origin_out, float* dir_out, uint8_t* alive_out) {
+    path_next((size_t)m, b, bias, origin, dir, t, normal, hit_id, prim_material, materials, pk0, sample, throughput, origin_out, dir_out, alive_out);
+}
+void p3dh_path_add(uint64_t m, int32_t b, const float* throughput, const float* radiance, const uint8_t* alive, float* sum) {
+    path_add((size_t)m, b, throughput, radiance, alive, sum);
 }
 
 // accumulate() of the host layer (accumulate_host.cpp): p3d_accumulate's result on host planes, every bit.  history may be

@@ -522,7 +522,8 @@ int add_indirect_diffuse(p3d_scene* dev, const RenderOptions& opt, const p3d_cam
     std::vector<float> lit(out.colors.size());
     const p3d_indirect_inputs in = {out.depth.data(), out.normal.data(), out.albedo.data(), out.colors.data(), 0};
     const p3d_indirect_outputs o = {nullptr, lit.data(), 0};
-    const int rc = p3d_indirect_diffuse(dev, cams, n, &prm, &ip, &in, &o);
+    const p3d_path_params pp = {opt.indirect_diffuse, opt.indirect_bounces, opt.indirect_bias, opt.seed};
+    const int rc = opt.indirect_bounces > 0 ? p3d_indirect_paths(dev, cams, n, &prm, &pp, &in, &o) : p3d_indirect_diffuse(dev, cams, n, &prm, &ip, &in, &o);
     if (!rc) out.colors.swap(lit);
     return rc;
 }

@@ -266,6 +266,8 @@ struct RenderOptions {
     // reads it.  The default bias is that of the Python binding (api.py, INDIRECT_BIAS)
     int indirect_diffuse = 0;
     float indirect_bias = 0.001f;
+    // ... > 0: p3d_indirect_paths with that many rays per path at most (1 .. 8) in p3d_indirect_diffuse's place; 0: as without
+    int indirect_bounces = 0;
 };
 struct RenderResult {
     std::vector<uint8_t> img_Data;   // RGB8, bottom row first (RT/main.cpp:76)

@@ -1,7 +1,7 @@
 // p3d_ao_segment.h -- steps 4 to 6 of p3d_ambient_occlusion's definition (include/p3d_hip.h) in a lane: the cosine-weighted
 // segment of one sample of a pixel, from the counter-based random streams of p3d_shade.h.  Said once for the two kernels
 // that make their rays in lanes: wf_ao_kernel (ao.hip) and wf_indirect_kernel (indirect.hip), whose ray of sample s is this
-// segment at radius 1.
+// segment at radius 1, and wf_indirect_paths_kernel (indirect_paths.hip), every vertex of whose paths draws one.
 #ifndef P3D_AO_SEGMENT_H
 #define P3D_AO_SEGMENT_H
 

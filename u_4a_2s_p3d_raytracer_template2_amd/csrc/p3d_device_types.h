@@ -250,6 +250,9 @@ struct IndirectIO {
     uint32_t seed;
 };
 
+// ... and of p3d_indirect_paths (wf_indirect_paths_kernel): the same planes, and the rays a path traces at most (1 .. 8).
+struct PathIO : IndirectIO { int32_t bounces; };
+
 // Every level of a pass for the fused resolve launch (small frames / shards, wf_resolve_fused_kernel): level l's
 // parked nodes (shard s at nodes[l] + s * cap[l]) and their per-shard counts; levels top .. 1 are combined.
 struct ResolveLevels { NodeRec* nodes[18]; const uint32_t* ncount[18]; uint32_t cap[18]; int32_t top; };

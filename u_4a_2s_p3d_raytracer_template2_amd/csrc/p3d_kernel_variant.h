@@ -30,8 +30,9 @@ struct KernelVariant {
 // The level kernels: wf_primary_kernel, wf_secondary_kernel (no BATCH: the deeper levels are shared), wf_tile_kernel,
 // wf_rays_kernel: level 1 of a ray stream (p3d_trace_rays), wf_occlusion_kernel: the shadow query on the caller's
 // segments (p3d_occluded), wf_ao_kernel (ao.hip): the same query on segments made in lanes (p3d_ambient_occlusion), and
-// wf_indirect_kernel (indirect.hip): a ray stream's level 1 on rays made in lanes (p3d_indirect_diffuse).
-enum class Level { Primary, Secondary, Tile, Rays, Occlusion, AmbientOcclusion, IndirectDiffuse };
+// wf_indirect_kernel (indirect.hip): a ray stream's level 1 on rays made in lanes (p3d_indirect_diffuse), and
+// wf_indirect_paths_kernel (indirect_paths.hip): that level 1 in a loop, a path per lane (p3d_indirect_paths).
+enum class Level { Primary, Secondary, Tile, Rays, Occlusion, AmbientOcclusion, IndirectDiffuse, IndirectPaths };
 constexpr int kMaxPrimaryTiles = 3;
 // what a handle asks for until p3d_set_primary_tiles() says otherwise: 2 measured 2.4 % faster than 1 on the 1080p frame of
 // mount_low with four frames in flight, 3 measured 1.6 % (profiles/r06_primary_tiles.txt)
@@ -58,10 +59,10 @@ constexpr bool has_aov(Level k) { return k == Level::Primary || k == Level::Tile
 // The ray-stream level-1 kernel is built per scene placement and walk and nothing else: the per-lane, grid and shared walks
 // (a packet request gets the per-lane walk), at the register budget frames run their level kernels at by default.
 constexpr int kRaysOcc = 6;
-// The occlusion kernel, the ambient-occlusion kernel and the indirect-diffuse kernel are built by the same rule: five builds
-// each, LDS x {lane, grid} and HBM x {lane, shared, grid}.
+// The occlusion kernel, the ambient-occlusion kernel, the indirect-diffuse kernel and the indirect-paths kernel are built by
+// the same rule: five builds each, LDS x {lane, grid} and HBM x {lane, shared, grid}.
 constexpr bool caller_rays(Level k) {
-    return k == Level::Rays || k == Level::Occlusion || k == Level::AmbientOcclusion || k == Level::IndirectDiffuse;
+    return k == Level::Rays || k == Level::Occlusion || k == Level::AmbientOcclusion || k == Level::IndirectDiffuse || k == Level::IndirectPaths;
 }
 // the build of level kernel k that serves request v
 constexpr KernelVariant canonical_level(KernelVariant v, Level k) {

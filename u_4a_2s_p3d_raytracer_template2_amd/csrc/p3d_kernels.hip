@@ -1301,6 +1301,7 @@ constexpr bool variants_are_consistent(int first, int last) {
             if (!built_level(canonical_level(v, Level::Occlusion), Level::Occlusion)) return false;
             if (!built_level(canonical_level(v, Level::AmbientOcclusion), Level::AmbientOcclusion)) return false;
             if (!built_level(canonical_level(v, Level::IndirectDiffuse), Level::IndirectDiffuse)) return false;
+            if (!built_level(canonical_level(v, Level::IndirectPaths), Level::IndirectPaths)) return false;
             for (int tiles = 0; tiles <= kMaxPrimaryTiles + 1; tiles++) {
                 v.tiles = tiles;
                 if (!built_level(canonical_level(v, Level::Primary), Level::Primary)) return false;
@@ -1311,7 +1312,7 @@ constexpr bool variants_are_consistent(int first, int last) {
         }
         KernelVariant v = variant_at(i);
         for (v.tiles = kMaxPrimaryTiles; v.tiles >= 1; v.tiles--)
-            for (Level k : {Level::Primary, Level::Secondary, Level::Tile, Level::Rays, Level::Occlusion, Level::AmbientOcclusion, Level::IndirectDiffuse})
+            for (Level k : {Level::Primary, Level::Secondary, Level::Tile, Level::Rays, Level::Occlusion, Level::AmbientOcclusion, Level::IndirectDiffuse, Level::IndirectPaths})
                 if (built_level(v, k) && !(canonical_level(v, k) == v)) return false;
         v.tiles = 1;
         for (int priv : kPrivs)

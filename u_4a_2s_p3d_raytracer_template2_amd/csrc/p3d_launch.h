@@ -51,6 +51,9 @@ hipError_t launch_wf_ao(const LaunchParams& P, const AoIO& A, const KernelVarian
 // ---- indirect.hip
 hipError_t launch_wf_indirect(const LaunchParams& P, const IndirectIO& A, const KernelVariant& v, hipStream_t stream);
 
+// ---- indirect_paths.hip
+hipError_t launch_wf_indirect_paths(const LaunchParams& P, const PathIO& A, const KernelVariant& v, hipStream_t stream);
+
 // ---- p3d_debug_kernels.hip: unit probes of the device arithmetic (p3d_debug_* of include/p3d_hip.h)
 hipError_t launch_debug_check_rcp(uint32_t first, uint64_t count, unsigned long long* n_bad, uint32_t* first_bad, hipStream_t stream);
 hipError_t launch_debug_check_rcp_len(uint32_t first, uint64_t count, unsigned long long* n_bad, uint32_t* first_bad, hipStream_t stream);

@@ -1,6 +1,7 @@
-// p3d_pixel_gather.h -- what the per-pixel gather kernels (wf_ao_kernel of ao.hip, wf_indirect_kernel of indirect.hip) do
-// alike: the lane mapping and the origin of a pixel's rays on the device, the choice among a kernel's five builds and the
-// launch on the host.  IO is AoIO or IndirectIO (p3d_device_types.h): of it the code reads what the two have in common.
+// p3d_pixel_gather.h -- what the per-pixel gather kernels (wf_ao_kernel of ao.hip, wf_indirect_kernel of indirect.hip,
+// wf_indirect_paths_kernel of indirect_paths.hip) do alike: the lane mapping and the origin of a pixel's rays on the device,
+// the choice among a kernel's five builds and the launch on the host.  IO is AoIO, IndirectIO or PathIO
+// (p3d_device_types.h): of it the code reads what they have in common.
 //   Lane mapping: a lane is one (pixel, sample); the S lanes of a pixel are consecutive and a wave covers 64 / S consecutive
 //   pixels of one row.  The workgroup of a scene served from LDS is 4 such waves of one row.  All frames of a call go in ONE
 //   launch; workgroup index = (frame, row, group of the row), the frame slowest.  (LANE_PER_PIXEL: the mapping ao.hip

@@ -1,6 +1,6 @@
-// p3d_render.cpp -- p3d_render, p3d_render_frames, p3d_render_aov, p3d_trace_rays, p3d_occluded, p3d_ambient_occlusion, p3d_indirect_diffuse and p3d_tune_schedule of include/p3d_hip.h: a frame (or a
+// p3d_render.cpp -- p3d_render, p3d_render_frames, p3d_render_aov, p3d_trace_rays, p3d_occluded, p3d_ambient_occlusion, p3d_indirect_diffuse, p3d_indirect_paths and p3d_tune_schedule of include/p3d_hip.h: a frame (or a
 // batch of frames, or a stream of the caller's rays, or their shadow queries, or those of ambient occlusion, or a gather of indirect light) as a sequence of steps -- validate the request, fill the launch
-// parameters, size the workspaces, choose the schedule, enqueue it.  The kernels are those of p3d_kernels.hip, ao.hip and indirect.hip (p3d_launch.h).
+// parameters, size the workspaces, choose the schedule, enqueue it.  The kernels are those of p3d_kernels.hip, ao.hip, indirect.hip and indirect_paths.hip (p3d_launch.h).
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -1106,22 +1106,30 @@ int ambient_occlusion(p3d_scene* s, const p3d_camera* cams, int32_t n, const p3d
 // wf_indirect_kernel (indirect.hip) for all frames.  No queues, no workspace, no schedule: of the handle it touches the
 // staging of s->indirect and the grid of the first GRID call.  (Its rules for params are p3d_trace_rays': max_depth is not
 // read, the request is normalised to depth 1 without features.)
-int indirect_diffuse(p3d_scene* s, const p3d_camera* cams, int32_t n, const p3d_render_params* prm, const p3d_indirect_params* ind,
-                     const p3d_indirect_inputs* in, const p3d_indirect_outputs* out) {
+// p3d_indirect_paths is the same call with wf_indirect_paths_kernel (indirect_paths.hip) in the kernel's place -- the loop
+// over the bounces is in the lanes -- and one more parameter to check: `paths` is its parameter struct, NULL for
+// p3d_indirect_diffuse.  Both entries stage in s->indirect.
+int indirect_gather(p3d_scene* s, const p3d_camera* cams, int32_t n, const p3d_render_params* prm, const p3d_indirect_params* ind,
+                    const p3d_path_params* paths, const p3d_indirect_inputs* in, const p3d_indirect_outputs* out) {
     if (!s || !cams || !prm || !ind || !in || !out) return fail(P3D_ERR_ARG, "NULL argument");
-    const GatherRequest q = {"indirect diffuse", "features: the bounce is lit without features, features must be 0", "p3d_indirect_params",
+    const char* const entry = paths ? "p3d_indirect_paths" : "p3d_indirect_diffuse";
+    const GatherRequest q = {paths ? "indirect paths" : "indirect diffuse",
+                             paths ? "features: the bounces are lit without features, features must be 0"
+                                   : "features: the bounce is lit without features, features must be 0",
+                             paths ? "p3d_path_params" : "p3d_indirect_params",
                              "p3d_indirect_inputs", "p3d_indirect_outputs", "indirect", ind->samples, nullptr, ind->bias,
                              in->depth, in->normal, in->albedo, in->rgb32f, in->memory, out->indirect, out->rgb32f, out->memory};
     FrameConfig cfg;
     int rc = validate_gather_request(cams, n, prm, q, cfg);
     if (rc) return rc;
+    if (paths && (paths->bounces < 1 || paths->bounces > 8)) return fail(P3D_ERR_ARG, "p3d_path_params::bounces must be 1 .. 8");
     if (s->cull_never_hit) return fail(P3D_ERR_STATE, "scene was built with cull_never_hit: it serves frames only, not rays of any length");
     HIP_TRY(hipSetDevice(s->device));
     const size_t pixels = (size_t)n * (size_t)cams[0].res_y * (size_t)cams[0].res_x;
     const bool host_in = in->memory == 0, host_out = out->memory == 0;
     p3d_scene::IndirectDiffuse& B = s->indirect;
 
-    PlaneStage st(s, "p3d_indirect_diffuse", "its camera buffer");
+    PlaneStage st(s, entry, "its camera buffer");
     const PlaneStage::Plane cam_buf = st.scratch(B.cams, (size_t)n * sizeof(FrameCam));
     const PlaneStage::Plane depth = st.in(B.in_depth, in->depth, pixels * 4, host_in), normal = st.in(B.in_normal, in->normal, pixels * 12, host_in),
                             albedo = st.in(B.in_albedo, in->albedo, pixels * 12, host_in), color = st.in(B.in_rgb32f, in->rgb32f, pixels * 12, host_in);
@@ -1135,12 +1143,17 @@ int indirect_diffuse(p3d_scene* s, const p3d_camera* cams, int32_t n, const p3d_
     if (wavefront_lds_bytes(P, plan.lds_scene) > kMaxLdsBytes) return fail(P3D_ERR_LIMIT, "BVH depth needs more LDS than a CU has");
     if ((rc = st.allocate()) != P3D_OK) return rc;
 
-    IndirectIO io;
+    PathIO io;
     memset(&io, 0, sizeof io);
     if ((rc = fill_gather_io(s, cam_buf, cams, n, ind->samples, ind->bias, ind->seed, io)) != P3D_OK) return rc;
     if ((rc = st.upload()) != P3D_OK) return rc;
     io.depth = depth; io.normal = normal; io.albedo = albedo; io.color = color; io.indirect = o_indirect; io.rgb = o_rgb;
-    HIP_TRY(launch_wf_indirect(P, io, plan.kv, s->stream));
+    if (paths) {
+        io.bounces = paths->bounces;
+        HIP_TRY(launch_wf_indirect_paths(P, io, plan.kv, s->stream));
+    } else {
+        HIP_TRY(launch_wf_indirect(P, io, plan.kv, s->stream));
+    }
     return st.finish();
 }
 
@@ -1150,7 +1163,14 @@ extern "C" {
 
 int p3d_indirect_diffuse(p3d_scene* s, const p3d_camera* cams, int32_t n, const p3d_render_params* prm, const p3d_indirect_params* ind,
                          const p3d_indirect_inputs* in, const p3d_indirect_outputs* out) {
-    return indirect_diffuse(s, cams, n, prm, ind, in, out);
+    return indirect_gather(s, cams, n, prm, ind, nullptr, in, out);
+}
+
+int p3d_indirect_paths(p3d_scene* s, const p3d_camera* cams, int32_t n, const p3d_render_params* prm, const p3d_path_params* paths,
+                       const p3d_indirect_inputs* in, const p3d_indirect_outputs* out) {
+    if (!paths) return fail(P3D_ERR_ARG, "NULL argument");
+    const p3d_indirect_params ind = {paths->samples, paths->bias, paths->seed};
+    return indirect_gather(s, cams, n, prm, &ind, paths, in, out);
 }
 
 int p3d_ambient_occlusion(p3d_scene* s, const p3d_camera* cams, int32_t n, const p3d_render_params* prm, const p3d_ao_params* ao,
