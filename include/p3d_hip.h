@@ -1356,12 +1356,12 @@ int p3d_debug_upsample(int device, const p3d_upsample_params* params, const p3d_
  * freed.  Refusals as p3d_accumulate (a memory field other than 0: P3D_ERR_ARG). */
 int p3d_debug_accumulate(int device, const p3d_accumulate_params* params, const p3d_accumulate_frames* frames,
                          const p3d_accumulate_history* history, const p3d_accumulate_outputs* out);
-/* Likewise the launches of p3d_accumulate_moving (csrc/accumulate_motion.hip) over HOST planes and HOST geometry, without a
+/* Likewise the launches of p3d_accumulate_moving (csrc/accumulate.hip) over HOST planes and HOST geometry, without a
  * scene.  Refusals as p3d_accumulate_moving (a memory field other than 0: P3D_ERR_ARG). */
 int p3d_debug_accumulate_moving(int device, const p3d_accumulate_params* params, const p3d_accumulate_frames* frames,
                                 const p3d_accumulate_history* history, const p3d_accumulate_motion* motion,
                                 const p3d_accumulate_moving_outputs* out);
-/* Likewise the launches of p3d_accumulate_variance (csrc/accumulate_variance.hip) over HOST planes and HOST geometry,
+/* Likewise the launches of p3d_accumulate_variance (csrc/accumulate.hip) over HOST planes and HOST geometry,
  * without a scene.  Refusals as p3d_accumulate_variance (a memory field other than 0: P3D_ERR_ARG). */
 int p3d_debug_accumulate_variance(int device, const p3d_accumulate_params* params, const p3d_accumulate_variance_params* variance_params,
                                   const p3d_accumulate_frames* frames, const p3d_accumulate_history* history, const float* history_moments,

@@ -2,6 +2,7 @@
 (tests/accumulate_reference.py), bit for bit, every rejection path of the definition by a constructed case, and the
 properties a temporal accumulation must have."""
 import ctypes as C
+import json
 import os
 import re
 import subprocess
@@ -320,7 +321,18 @@ def refusal_cases():
     cases.append(("out->rgb32f == out->length", ERR_ARG, dict(alias=("length", "out", "rgb32f"))))
     cases.append(("46341 x 46341", ERR_LIMIT, dict(params=(46341, 46341, 1) + good[3:])))
     cases.append(("2 x 2 x 2^30", ERR_LIMIT, dict(params=(2, 2, 1 << 30) + good[3:])))
+    # two defects in one request: the recorded text says which check comes first
+    cases.append(("frames->depth NULL, out->memory = 2", ERR_ARG, dict(frames_null="depth", memory={"out": 2})))
+    cases.append(("history->length NULL, res_x = 0", ERR_ARG, dict(history_null="length", params=(0,) + good[1:])))
+    cases.append(("depth_tolerance = -1, out->length == frames->rgb32f", ERR_ARG, dict(params=good[:3] + (-1.0,) + good[4:], alias=("length", "frames", "rgb32f"))))
     return cases
+
+
+def recorded_refusals(entry):
+    """{case name: (status, p3d_last_error() text)} of the probe `entry`, as tests/golden/make_accumulate_refusals.py recorded
+    them while each of the three accumulate entries still had a check function of its own."""
+    with open(os.path.join(REPO, "tests", "golden", "accumulate_refusals.json")) as f:
+        return {r["case"]: (r["status"], r["text"]) for r in json.load(f) if r["entry"] == entry}
 
 
 def make_call(entry):
@@ -364,6 +376,7 @@ def test_every_refusal_by_status_code_without_a_device(name, status, change):
     assert L.p3d_last_error(), "every refusal has a text"
     if status == ERR_LIMIT:
         assert b"31 bits" in L.p3d_last_error()
+    assert (status, L.p3d_last_error().decode()) == recorded_refusals("p3d_debug_accumulate")[name]
 
 
 def test_a_null_scene_is_refused():

@@ -15,6 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import accumulate_reference as R                           # noqa: E402
 import accumulate_moving_reference as M                    # noqa: E402
 import u_4a_2s_p3d_raytracer_template2_amd as P            # noqa: E402
+from test_accumulate_host import recorded_refusals         # noqa: E402
 from u_4a_2s_p3d_raytracer_template2_amd import api        # noqa: E402
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -284,6 +285,10 @@ def refusal_cases():
     cases.append(("out->rgb32f == out->length", ERR_ARG, dict(alias=("length", "out", "rgb32f"))))
     cases.append(("46341 x 46341", ERR_LIMIT, dict(params=(46341, 46341, 1) + good[3:])))
     cases.append(("2 x 2 x 2^30", ERR_LIMIT, dict(params=(2, 2, 1 << 30) + good[3:])))
+    # two defects in one request: the recorded text says which check comes first
+    cases.append(("frames->depth NULL, out->memory = 2", ERR_ARG, dict(frames_null="depth", memory={"out": 2})))
+    cases.append(("history->length NULL, res_x = 0", ERR_ARG, dict(history_null="length", params=(0,) + good[1:])))
+    cases.append(("depth_tolerance = -1, out->length == frames->rgb32f", ERR_ARG, dict(params=good[:3] + (-1.0,) + good[4:], alias=("length", "frames", "rgb32f"))))
     return cases
 
 
@@ -338,6 +343,7 @@ def test_every_refusal_by_status_code_without_a_device(name, status, change):
     assert L.p3d_last_error(), "every refusal has a text"
     if status == ERR_LIMIT:
         assert b"31 bits" in L.p3d_last_error()
+    assert (status, L.p3d_last_error().decode()) == recorded_refusals("p3d_debug_accumulate_moving")[name]
 
 
 def test_a_null_scene_is_refused():

@@ -16,7 +16,7 @@ import accumulate_reference as R                           # noqa: E402
 import accumulate_variance_reference as RV                 # noqa: E402
 import u_4a_2s_p3d_raytracer_template2_amd as P            # noqa: E402
 from denoise_reference import _lum                         # noqa: E402
-from test_accumulate_host import exact_camera              # noqa: E402
+from test_accumulate_host import exact_camera, recorded_refusals     # noqa: E402
 from u_4a_2s_p3d_raytracer_template2_amd import api        # noqa: E402
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -265,7 +265,23 @@ def refusal_cases():
     cases.append(("out->length == frames->rgb32f", ERR_ARG, dict(alias=("length", "frames", "rgb32f"))))
     cases.append(("46341 x 46341", ERR_LIMIT, dict(params=(46341, 46341, 1) + good[3:])))
     cases.append(("2 x 2 x 2^30", ERR_LIMIT, dict(params=(2, 2, 1 << 30) + good[3:])))
+    # two defects in one request: the recorded text says which check comes first
+    cases.append(("frames->depth NULL, out->memory = 2", ERR_ARG, dict(frames_null="depth", memory={"out": 2})))
+    cases.append(("history->length NULL, res_x = 0", ERR_ARG, dict(history_null="length", params=(0,) + good[1:])))
+    cases.append(("depth_tolerance = -1, out->length == frames->rgb32f", ERR_ARG, dict(params=good[:3] + (-1.0,) + good[4:], alias=("length", "frames", "rgb32f"))))
+    cases.append(("radius = 9, out->moments == frames->depth", ERR_ARG, dict(vparams=(3.0, 9, 0.5, 2), alias=("moments", "frames", "depth"))))
+    cases.append(("history without history_moments, min_temporal = 0.5", ERR_ARG, dict(moments=False, vparams=(0.5,) + vgood[1:])))
+    # a new plane wanted alone is also held to the rules of colour, length and prev_xy, before the variance params are looked at
+    cases.append(("only out->moments, == frames->depth, radius = 9", ERR_ARG, dict(out_planes=("moments",), vparams=(3.0, 9, 0.5, 2), alias=("moments", "frames", "depth"))))
+    cases.append(("only out->variance, == frames->rgb32f", ERR_ARG, dict(out_planes=("variance",), alias=("variance", "frames", "rgb32f"))))
     return cases
+
+
+def accepted_cases():
+    """(name, keyword changes of call()): requests for one of the new planes and nothing else, which pass every check although
+    the siblings' rule "every output plane is NULL" would refuse the planes they know."""
+    return [("only out->%s%s" % (k, ", with a motion" if motion else ""), dict(out_planes=(k,), motion=motion, prev_xy=False))
+            for k in ("moments", "variance") for motion in (False, True)]
 
 
 def make_call(entry):
@@ -278,13 +294,13 @@ def make_call(entry):
 
     def call(params=(5, 3, 1, 0.1, 0.8, 4.0), vparams=(3.0, 3, 0.5, 2), frames=True, out=True, history=True, moments=True, motion=False,
              frames_null=None, history_null=None, motion_null=None, out_planes=("rgb32f", "length", "moments", "variance"), memory={},
-             alias=None):
+             alias=None, prev_xy=None):
         cam, hcam = (api.Camera * 1)(seq["cams"][0]), (api.Camera * 1)(hist["cam"])
         ptr = dict(frames={k: seq[k].ctypes.data for k in ("rgb32f", "depth", "normal", "hit_id")},
                    history={k: hist[k].ctypes.data for k in ("rgb32f", "depth", "normal", "length", "hit_id", "moments")},
                    motion=dict(prim_type=seq["prim_type"].ctypes.data, prim_data=seq["prim_data"].ctypes.data,
                                history_prim_data=hist["prim_data"].ctypes.data),
-                   out={k: outs[k].ctypes.data if k in out_planes or (motion and k == "prev_xy") else None for k in api._VARIANCE_PLANES})
+                   out={k: outs[k].ctypes.data if k in out_planes or (k == "prev_xy" and (motion if prev_xy is None else prev_xy)) else None for k in api._VARIANCE_PLANES})
         ptr["frames"]["cams"], ptr["history"]["cam"] = cam, hcam
         for group, name in (("frames", frames_null), ("history", history_null), ("motion", motion_null)):
             if name:
@@ -311,6 +327,20 @@ def test_every_refusal_by_status_code_without_a_device(name, status, change):
     assert L.p3d_last_error(), "every refusal has a text"
     if status == ERR_LIMIT:
         assert b"31 bits" in L.p3d_last_error()
+    assert (status, L.p3d_last_error().decode()) == recorded_refusals("p3d_debug_accumulate_variance")[name]
+
+
+@pytest.mark.parametrize("name,change", accepted_cases(), ids=[c[0] for c in accepted_cases()])
+def test_a_request_for_a_new_plane_alone_is_accepted(name, change):
+    """Accepted means that the probe goes on to look for a device: P3D_OK where one is visible, P3D_ERR_NO_DEVICE where none
+    is -- a refused request returns its own status and text before that."""
+    L = P.lib()
+    call = make_call(lambda *a: L.p3d_debug_accumulate_variance(0, *a))
+    rc, text = call(**change), L.p3d_last_error().decode()
+    if P.device_count() > 0:
+        assert rc == 0, (name, text)
+    else:
+        assert (rc, text) == (-3, "no HIP device visible") == recorded_refusals("p3d_debug_accumulate_variance")[name]
 
 
 def test_a_null_scene_is_refused():

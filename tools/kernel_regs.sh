@@ -1,7 +1,7 @@
 #!/bin/bash
 # Register / spill / scratch use of every kernel of p3d_kernels.hip (CPU-only: device-only compile + readelf notes).
 # usage: tools/kernel_regs.sh [name filter regex] [extra hipcc flags...]
-# P3D_KERNEL_SRC=denoise.hip, denoise_variance.hip, accumulate.hip, accumulate_motion.hip, accumulate_variance.hip, ao.hip, indirect.hip, indirect_paths.hip or upsample.hip (any kernel
+# P3D_KERNEL_SRC=denoise.hip, denoise_variance.hip, accumulate.hip, ao.hip, indirect.hip, indirect_paths.hip or upsample.hip (any kernel
 # file of csrc/) reads that file instead.
 set -e
 src=${P3D_KERNEL_SRC:-p3d_kernels.hip}

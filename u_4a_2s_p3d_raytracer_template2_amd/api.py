@@ -1083,14 +1083,8 @@ class DeviceScene:
         """Enqueue p3d_accumulate on caller-owned DEVICE buffers (raw pointers; 0 = no such plane) holding len(cams) frames;
         asynchronous on the scene's stream.  history: None, or a dict of device pointers rgb32f, depth, normal, length
         (optionally hit_id) and the host Camera cam.  out_rgb32f_ptr may equal rgb32f_ptr."""
-        arr, n = _camera_array(cams)
-        p = AccumulateParams(int(res_x), int(res_y), n, depth_tolerance, normal_min, max_history)
-        fr = AccumulateFrames(rgb32f_ptr or None, depth_ptr or None, normal_ptr or None, hit_ptr or None, arr, 1)
-        hi = None
-        if history is not None:
-            hcam = (Camera * 1)(history["cam"])
-            hi = AccumulateHistory(history["rgb32f"] or None, history["depth"] or None, history["normal"] or None, history["length"] or None,
-                                   history.get("hit_id") or None, hcam, 1)
+        p, fr, hi, mo, keep = _accumulate_device_structs(res_x, res_y, cams, rgb32f_ptr, depth_ptr, normal_ptr, hit_ptr, history, None,
+                                                         depth_tolerance, normal_min, max_history)
         o = AccumulateOutputs(out_rgb32f_ptr or None, out_length_ptr or None, 1)
         _check(lib().p3d_accumulate(self.h, C.byref(p), C.byref(fr), C.byref(hi) if hi else None, C.byref(o)), "p3d_accumulate")
 
@@ -1112,15 +1106,9 @@ class DeviceScene:
         """Enqueue p3d_accumulate_moving on caller-owned DEVICE buffers (raw pointers; 0 = no such plane) holding len(cams)
         frames and their geometry; asynchronous on the scene's stream.  history: None, or a dict of device pointers rgb32f,
         depth, normal, length, prim_data (optionally hit_id) and the host Camera cam.  out_rgb32f_ptr may equal rgb32f_ptr."""
-        arr, n = _camera_array(cams)
-        p = AccumulateParams(int(res_x), int(res_y), n, depth_tolerance, normal_min, max_history)
-        fr = AccumulateFrames(rgb32f_ptr or None, depth_ptr or None, normal_ptr or None, hit_ptr or None, arr, 1)
-        hi = None
-        if history is not None:
-            hcam = (Camera * 1)(history["cam"])
-            hi = AccumulateHistory(history["rgb32f"] or None, history["depth"] or None, history["normal"] or None, history["length"] or None,
-                                   history.get("hit_id") or None, hcam, 1)
-        mo = AccumulateMotion(int(n_prims), prim_type_ptr or None, prim_data_ptr or None, (history or {}).get("prim_data") or None, 1)
+        motion = dict(n_prims=n_prims, prim_type=prim_type_ptr, prim_data=prim_data_ptr)
+        p, fr, hi, mo, keep = _accumulate_device_structs(res_x, res_y, cams, rgb32f_ptr, depth_ptr, normal_ptr, hit_ptr, history, motion,
+                                                         depth_tolerance, normal_min, max_history)
         o = AccumulateMovingOutputs(out_rgb32f_ptr or None, out_length_ptr or None, out_prev_xy_ptr or None, 1)
         _check(lib().p3d_accumulate_moving(self.h, C.byref(p), C.byref(fr), C.byref(hi) if hi else None, C.byref(mo), C.byref(o)),
                "p3d_accumulate_moving")
@@ -1146,19 +1134,9 @@ class DeviceScene:
         frames; asynchronous on the scene's stream.  history: None, or a dict of device pointers rgb32f, depth, normal, length,
         moments (optionally hit_id; prim_data with a motion) and the host Camera cam.  motion: None, or a dict of n_prims and
         the device pointers prim_type, prim_data.  out_rgb32f_ptr may equal rgb32f_ptr."""
-        arr, n = _camera_array(cams)
-        p = AccumulateParams(int(res_x), int(res_y), n, depth_tolerance, normal_min, max_history)
+        p, fr, hi, mo, keep = _accumulate_device_structs(res_x, res_y, cams, rgb32f_ptr, depth_ptr, normal_ptr, hit_ptr, history, motion,
+                                                         depth_tolerance, normal_min, max_history)
         vp = AccumulateVarianceParams(min_temporal, int(radius), sigma_depth, int(normal_power_log2))
-        fr = AccumulateFrames(rgb32f_ptr or None, depth_ptr or None, normal_ptr or None, hit_ptr or None, arr, 1)
-        hi = None
-        if history is not None:
-            hcam = (Camera * 1)(history["cam"])
-            hi = AccumulateHistory(history["rgb32f"] or None, history["depth"] or None, history["normal"] or None, history["length"] or None,
-                                   history.get("hit_id") or None, hcam, 1)
-        mo = None
-        if motion is not None:
-            mo = AccumulateMotion(int(motion["n_prims"]), motion["prim_type"] or None, motion["prim_data"] or None,
-                                  (history or {}).get("prim_data") or None, 1)
         o = AccumulateVarianceOutputs(out_rgb32f_ptr or None, out_length_ptr or None, out_moments_ptr or None, out_variance_ptr or None,
                                       out_prev_xy_ptr or None, 1)
         _check(lib().p3d_accumulate_variance(self.h, C.byref(p), C.byref(vp), C.byref(fr), C.byref(hi) if hi else None,
@@ -1511,6 +1489,26 @@ def debug_denoise_variance(rgb32f, depth, normal, albedo, variance, device=0, **
     o = DenoiseVarianceOutputs(out["rgb8"].ctypes.data, out["rgb32f"].ctypes.data, out["variance"].ctypes.data, 0)
     _check(lib().p3d_debug_denoise_variance(int(device), C.byref(p), C.byref(i), C.byref(o)), "p3d_debug_denoise_variance")
     return out
+
+
+def _accumulate_device_structs(res_x, res_y, cams, rgb32f_ptr, depth_ptr, normal_ptr, hit_ptr, history, motion, depth_tolerance, normal_min,
+                               max_history):
+    """The structs the three accumulate_*_device methods share, over DEVICE pointers (0 = no such plane) -> (AccumulateParams,
+    AccumulateFrames, AccumulateHistory or None, AccumulateMotion or None, what must stay alive during the call).  history
+    and motion: the dicts of those methods, or None."""
+    arr, n = _camera_array(cams)
+    p = AccumulateParams(int(res_x), int(res_y), n, depth_tolerance, normal_min, max_history)
+    fr = AccumulateFrames(rgb32f_ptr or None, depth_ptr or None, normal_ptr or None, hit_ptr or None, arr, 1)
+    hi = hcam = None
+    if history is not None:
+        hcam = (Camera * 1)(history["cam"])
+        hi = AccumulateHistory(history["rgb32f"] or None, history["depth"] or None, history["normal"] or None, history["length"] or None,
+                               history.get("hit_id") or None, hcam, 1)
+    mo = None
+    if motion is not None:
+        mo = AccumulateMotion(int(motion["n_prims"]), motion["prim_type"] or None, motion["prim_data"] or None,
+                              (history or {}).get("prim_data") or None, 1)
+    return p, fr, hi, mo, (arr, hcam)
 
 
 def _accumulate_request(rgb32f, depth, normal, cams, hit_id=None, history=None, depth_tolerance=ACCUMULATE_DEPTH_TOLERANCE,

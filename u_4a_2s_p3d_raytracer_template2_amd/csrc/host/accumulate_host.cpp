@@ -1,8 +1,7 @@
 // accumulate_host.cpp -- the reprojection of p3d_accumulate, of p3d_accumulate_moving and of p3d_accumulate_variance in plain
 // loops on the host: DESIGN "Temporal accumulation", "Accumulation through moved primitives" and "Variance-guided denoising"
 // read operation by operation, float arithmetic without contraction (HFLAGS: -ffp-contract=off).  What the device kernels
-// (../accumulate.hip, ../accumulate_motion.hip, ../accumulate_variance.hip) are compared against, bit for bit; it shares no
-// code with them.
+// (../accumulate.hip) are compared against, bit for bit; it shares no code with them.
 #include "accumulate_host.h"
 
 #include <cmath>

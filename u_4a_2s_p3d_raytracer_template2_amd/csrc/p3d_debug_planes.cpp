@@ -11,30 +11,55 @@ using namespace p3d;
 
 namespace {
 
-// The three accumulate probes: the 13 planes they share (spare_rgb32f / spare_length: their bytes, 0 = not needed), then
-// the probe's `own` rows, and launch(P, own rows on the device) on them.
-template <typename Launch>
-int debug_accumulate_run(const char* entry, int device, const p3d_accumulate_params* params, const p3d_accumulate_frames* frames,
-                         const p3d_accumulate_history* history, float* out_rgb32f, float* out_length, size_t spare_rgb32f, size_t spare_length,
-                         std::initializer_list<DebugArg> own, Launch launch) {
+// The three accumulate probes: the argument checks, then the 13 planes every request has, the 4 rows of a motion and the 4
+// of the moments where the request has them, and launch_accumulate on them.
+int debug_accumulate(const char* entry, int device, const AccumulateRequest& r) {
+    const char* why = "";
+    if (const int rc = accumulate_check_request(r, &why)) return fail(rc, why);
+    const p3d_accumulate_params* params = r.params;
+    const p3d_accumulate_frames* frames = r.frames;
+    const p3d_accumulate_history* history = r.history;
+    const p3d_accumulate_motion* motion = r.motion;
+    if (frames->memory != 0 || (history && history->memory != 0) || (motion && motion->memory != 0) || r.out_memory != 0)
+        return fail(P3D_ERR_ARG, std::string(entry) + " takes host planes: every memory field must be 0");
+    const bool var = r.entry == kAccumulateVariance, many = params->n_frames > 1;
     const size_t fr = (size_t)params->res_x * (size_t)params->res_y, px = fr * (size_t)params->n_frames;
+    // host planes are staged apart, so no colour is blended in place: no detour
+    const size_t spare_c = (size_t)accumulate_variance_spare_colour_frames(*params, r.out_rgb32f, false) * fr * 12;
+    const size_t spare_l = (size_t)(var ? accumulate_variance_spare_length_frames(*params, *r.variance_params, r.out_length, r.out_variance)
+                                        : many && !r.out_length ? 2 : 0) * fr * 4;
     const p3d_accumulate_history none = {};
     const p3d_accumulate_history& h = history ? *history : none;
     std::vector<DebugArg> a = {{frames->rgb32f, nullptr, px * 12}, {frames->depth, nullptr, px * 4}, {frames->normal, nullptr, px * 12},
                                {frames->hit_id, nullptr, frames->hit_id ? px * 4 : 1},
                                {h.rgb32f, nullptr, history ? fr * 12 : 1}, {h.depth, nullptr, history ? fr * 4 : 1}, {h.normal, nullptr, history ? fr * 12 : 1},
                                {h.length, nullptr, history ? fr * 4 : 1}, {h.hit_id, nullptr, h.hit_id ? fr * 4 : 1},
-                               {nullptr, out_rgb32f, out_rgb32f ? px * 12 : 1}, {nullptr, out_length, out_length ? px * 4 : 1},
-                               {nullptr, nullptr, spare_rgb32f ? spare_rgb32f : 1}, {nullptr, nullptr, spare_length ? spare_length : 1}};
-    const size_t shared = a.size();
-    a.insert(a.end(), own);
+                               {nullptr, r.out_rgb32f, r.out_rgb32f ? px * 12 : 1}, {nullptr, r.out_length, r.out_length ? px * 4 : 1},
+                               {nullptr, nullptr, spare_c ? spare_c : 1}, {nullptr, nullptr, spare_l ? spare_l : 1}};
+    const size_t m0 = a.size();
+    if (motion) {
+        const size_t prims = motion->n_prims;
+        a.insert(a.end(), {{motion->prim_type, nullptr, prims * 4}, {motion->prim_data, nullptr, prims * 48 * (size_t)params->n_frames},
+                           {history ? motion->history_prim_data : nullptr, nullptr, history ? prims * 48 : 1},
+                           {nullptr, r.out_prev_xy, r.out_prev_xy ? px * 8 : 1}});
+    }
+    const size_t v0 = a.size();
+    if (var)
+        a.insert(a.end(), {{history ? r.history_moments : nullptr, nullptr, history ? fr * 8 : 1}, {nullptr, r.out_moments, r.out_moments ? px * 8 : 1},
+                           {nullptr, r.out_variance, r.out_variance ? px * 4 : 1}, {nullptr, nullptr, many && !r.out_moments ? 2 * fr * 8 : 1}});
     return debug_run(entry, device, a, [&] {
         const AccumulatePlanes P = {a[0].as<float>(), a[1].as<float>(), a[2].as<float>(), frames->hit_id ? a[3].as<int32_t>() : nullptr,
                                     history ? a[4].as<float>() : nullptr, a[5].as<float>(), a[6].as<float>(), a[7].as<float>(),
                                     h.hit_id ? a[8].as<int32_t>() : nullptr,
-                                    out_rgb32f ? a[9].as<float>() : nullptr, out_length ? a[10].as<float>() : nullptr,
+                                    r.out_rgb32f ? a[9].as<float>() : nullptr, r.out_length ? a[10].as<float>() : nullptr,
                                     a[11].as<float>(), a[12].as<float>()};
-        return launch(P, a.data() + shared);
+        AccumulateMotion M = {};
+        if (motion) M = {motion->n_prims, a[m0].as<uint32_t>(), a[m0 + 1].as<float>(), history ? a[m0 + 2].as<float>() : nullptr,
+                         r.out_prev_xy ? a[m0 + 3].as<float>() : nullptr};
+        AccumulateVariance V = {};
+        if (var) V = {*r.variance_params, {history ? a[v0].as<float>() : nullptr, r.out_moments ? a[v0 + 1].as<float>() : nullptr,
+                                           r.out_variance ? a[v0 + 2].as<float>() : nullptr, a[v0 + 3].as<float>()}};
+        return launch_accumulate(*params, P, motion ? &M : nullptr, var ? &V : nullptr, frames->cams, history ? history->cam : nullptr, nullptr);
     });
 }
 
@@ -93,68 +118,20 @@ int p3d_debug_upsample(int device, const p3d_upsample_params* params, const p3d_
 
 int p3d_debug_accumulate(int device, const p3d_accumulate_params* params, const p3d_accumulate_frames* frames,
                          const p3d_accumulate_history* history, const p3d_accumulate_outputs* out) {
-    const char* why = "";
-    if (const int rc = accumulate_check_request(params, frames, history, out, &why)) return fail(rc, why);
-    if (frames->memory != 0 || (history && history->memory != 0) || out->memory != 0)
-        return fail(P3D_ERR_ARG, "p3d_debug_accumulate takes host planes: every memory field must be 0");
-    const size_t fr = (size_t)params->res_x * (size_t)params->res_y;
-    const bool many = params->n_frames > 1;
-    return debug_accumulate_run("p3d_debug_accumulate", device, params, frames, history, out->rgb32f, out->length,
-                                many && !out->rgb32f ? 2 * fr * 12 : 0, many && !out->length ? 2 * fr * 4 : 0, {},
-                                [&](const AccumulatePlanes& P, const DebugArg*) {
-        return launch_accumulate(*params, P, frames->cams, history ? history->cam : nullptr, nullptr);
-    });
+    return debug_accumulate("p3d_debug_accumulate", device, accumulate_request(params, frames, history, out));
 }
 
 int p3d_debug_accumulate_moving(int device, const p3d_accumulate_params* params, const p3d_accumulate_frames* frames,
                                 const p3d_accumulate_history* history, const p3d_accumulate_motion* motion,
                                 const p3d_accumulate_moving_outputs* out) {
-    const char* why = "";
-    if (const int rc = accumulate_moving_check_request(params, frames, history, motion, out, &why)) return fail(rc, why);
-    if (frames->memory != 0 || (history && history->memory != 0) || motion->memory != 0 || out->memory != 0)
-        return fail(P3D_ERR_ARG, "p3d_debug_accumulate_moving takes host planes: every memory field must be 0");
-    const size_t fr = (size_t)params->res_x * (size_t)params->res_y, px = fr * (size_t)params->n_frames, prims = motion->n_prims;
-    const bool many = params->n_frames > 1;
-    return debug_accumulate_run("p3d_debug_accumulate_moving", device, params, frames, history, out->rgb32f, out->length,
-                                many && !out->rgb32f ? 2 * fr * 12 : 0, many && !out->length ? 2 * fr * 4 : 0,
-                                {{motion->prim_type, nullptr, prims * 4}, {motion->prim_data, nullptr, prims * 48 * (size_t)params->n_frames},
-                                 {history ? motion->history_prim_data : nullptr, nullptr, history ? prims * 48 : 1},
-                                 {nullptr, out->prev_xy, out->prev_xy ? px * 8 : 1}},
-                                [&](const AccumulatePlanes& P, const DebugArg* a) {
-        const AccumulateMotion M = {motion->n_prims, a[0].as<uint32_t>(), a[1].as<float>(), history ? a[2].as<float>() : nullptr,
-                                    out->prev_xy ? a[3].as<float>() : nullptr};
-        return launch_accumulate_moving(*params, P, M, frames->cams, history ? history->cam : nullptr, nullptr);
-    });
+    return debug_accumulate("p3d_debug_accumulate_moving", device, accumulate_request(params, frames, history, motion, out));
 }
 
 int p3d_debug_accumulate_variance(int device, const p3d_accumulate_params* params, const p3d_accumulate_variance_params* variance_params,
                                   const p3d_accumulate_frames* frames, const p3d_accumulate_history* history, const float* history_moments,
                                   const p3d_accumulate_motion* motion, const p3d_accumulate_variance_outputs* out) {
-    const char* why = "";
-    if (const int rc = accumulate_variance_check_request(params, variance_params, frames, history, history_moments, motion, out, &why)) return fail(rc, why);
-    if (frames->memory != 0 || (history && history->memory != 0) || (motion && motion->memory != 0) || out->memory != 0)
-        return fail(P3D_ERR_ARG, "p3d_debug_accumulate_variance takes host planes: every memory field must be 0");
-    const size_t fr = (size_t)params->res_x * (size_t)params->res_y, px = fr * (size_t)params->n_frames, prims = motion ? motion->n_prims : 0;
-    const bool many = params->n_frames > 1;
-    // host planes are staged apart, so no colour is blended in place: no detour
-    const size_t spare_c = (size_t)accumulate_variance_spare_colour_frames(*params, out->rgb32f, false);
-    const size_t spare_l = (size_t)accumulate_variance_spare_length_frames(*params, *variance_params, out->length, out->variance);
-    return debug_accumulate_run("p3d_debug_accumulate_variance", device, params, frames, history, out->rgb32f, out->length,
-                                spare_c * fr * 12, spare_l * fr * 4,
-                                {{motion ? motion->prim_type : nullptr, nullptr, motion ? prims * 4 : 1},
-                                 {motion ? motion->prim_data : nullptr, nullptr, motion ? prims * 48 * (size_t)params->n_frames : 1},
-                                 {motion && history ? motion->history_prim_data : nullptr, nullptr, motion && history ? prims * 48 : 1},
-                                 {nullptr, out->prev_xy, out->prev_xy ? px * 8 : 1},
-                                 {history ? history_moments : nullptr, nullptr, history ? fr * 8 : 1},
-                                 {nullptr, out->moments, out->moments ? px * 8 : 1}, {nullptr, out->variance, out->variance ? px * 4 : 1},
-                                 {nullptr, nullptr, many && !out->moments ? 2 * fr * 8 : 1}},
-                                [&](const AccumulatePlanes& P, const DebugArg* a) {
-        const AccumulateMotion M = {motion ? motion->n_prims : 0, a[0].as<uint32_t>(), a[1].as<float>(), motion && history ? a[2].as<float>() : nullptr,
-                                    out->prev_xy ? a[3].as<float>() : nullptr};
-        const AccumulateVariancePlanes VP = {history ? a[4].as<float>() : nullptr, out->moments ? a[5].as<float>() : nullptr,
-                                             out->variance ? a[6].as<float>() : nullptr, a[7].as<float>()};
-        return launch_accumulate_variance(*params, *variance_params, P, VP, motion ? &M : nullptr, frames->cams, history ? history->cam : nullptr, nullptr);
-    });
+    return debug_accumulate("p3d_debug_accumulate_variance", device,
+                            accumulate_request(params, variance_params, frames, history, history_moments, motion, out));
 }
 
 }  // extern "C"
